@@ -15,7 +15,12 @@ constant -> weak scaling.  `--gpus N` without a torch.distributed.run environmen
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process (before this
 process touches the GPU) and exits with its return code.
 
-One JSON line on rank 0.  `roofline` is for the dominant kernel class (the 16-bit MFMA GEMM):
+One JSON line on rank 0.  A plain run sets up, warms up, times the K steps (`value` in tiles/s, `ms_per_step`), writes the
+last timed step's outputs if `--dump-outputs DIR` is given (inputs and weights are seeded: the same arguments give the same
+inputs in every run) and prints the line; `roofline`, `kernel_classes`, `cpu_baseline` and `map_vs_cpu_ref` are null there.
+Everything below needs `--full` (the `--no-*` switches then drop single parts of it).
+
+`roofline` is for the dominant kernel class (the 16-bit MFMA GEMM):
 algorithmic FLOPs of its launches / their summed duration, measured with HIP events on the
 launch stream in a second pass of the same steps (so the headline timing carries no event overhead).
 `cpu_baseline` times the CPU oracle (fp32 torch port of the reference) on ONE ViT-H tile: warm-up, 3 timed forwards, median,
@@ -79,15 +84,57 @@ FLOPS_ENC = {"vit_h": 5794.3e9, "vit_b": 1115.96e9}
 PEAK_TFLOPS = {"bf16": 2500.0, "fp16": 2500.0, "fp8": 5000.0}      # MI355X dense MFMA peaks (MI355X_MICROARCH.md)
 
 
+def _state_dict(model_type: str) -> dict:
+    """synth.make_state_dict(model_type) with the tensors filled on a thread pool: every tensor is its own counter stream, so
+    the values are bit-identical; numpy's integer ufuncs run without the GIL, so ViT-H takes seconds instead of ~20 s."""
+    from concurrent.futures import ThreadPoolExecutor
+    shapes = synth.weight_shapes(model_type)
+    try:
+        cpus = len(os.sched_getaffinity(0))
+    except AttributeError:
+        cpus = os.cpu_count() or 1
+    with ThreadPoolExecutor(max(1, min(16, cpus))) as ex:
+        vals = list(ex.map(lambda kv: synth.make_weight(kv[0], kv[1]), shapes.items()))
+    return {k: torch.from_numpy(v) for k, v in zip(shapes, vals)}
+
+
 def build_model(model_type: str, precision: str, device: torch.device):
     from wildlifemapper_amd.segment_anything import sam_model_registry
     from wildlifemapper_amd.segment_anything.network import MedSAM
     sam, _, post = sam_model_registry[model_type](None, None)
     model = MedSAM(sam.image_encoder, sam.mask_decoder, sam.prompt_encoder).eval()
-    sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(model_type).items()}
+    sd = _state_dict(model_type)
     model.load_state_dict(sd, strict=True)
     model._hub.set_precision(precision)
     return model, sd
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d: str, outs: dict) -> None:
+    """--dump-outputs: what the last timed step returned, one DIR/<name>.npy per array.  Box records are split into their
+    fields (the int fields as float64, exact).  An output larger than its share of the 64 MB budget is written as a fixed
+    sample (numpy seed 0, sorted flat indices) next to DIR/<name>_index.npy holding those indices (float64, exact); the two
+    files together stay within the share."""
+    import numpy as np
+    from wildlifemapper_amd.engine import split_records
+    arrays = {}
+    for k, v in outs.items():
+        if k == "records":
+            for f, t in split_records(v).items():
+                arrays[f"records_{f}"] = t.numpy().astype(np.float32 if t.is_floating_point() else np.float64)
+        else:
+            arrays[k] = v.float().numpy()
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // len(arrays) - 4096          # room for the .npy headers
+    for k, v in arrays.items():
+        if v.nbytes > share:
+            n = share // (v.itemsize + 8)
+            idx = np.sort(np.random.default_rng(0).choice(v.size, size=n, replace=False))
+            np.save(os.path.join(d, f"{k}_index.npy"), idx.astype(np.float64))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(d, f"{k}.npy"), np.ascontiguousarray(v))
 
 
 def _host_cpu() -> tuple:
@@ -421,9 +468,14 @@ def main() -> None:
                          "bf16 (the type BASELINE.json configs[1] names; same MFMA rate, +3.9 %% tiles/s, logits 0.7e-3 .. 2.0e-3 depending on "
                          "the weights) | fp8 (configs[4]; tolerance re-stated, see config.tolerance)")
     ap.add_argument("--workload", default="full", choices=["full", "encoder"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short timed runs of the other BASELINE.json configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the HIP-event pass (roofline, kernel_classes), parity_vs_reference, other_configs, "
+                         "frontend_configs and the CPU baseline; a plain run times the steps and prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the HIP-event pass")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short timed runs of the other BASELINE.json configurations")
     ap.add_argument("--backend", default="nccl", help="nccl (RCCL, default) | gloo (single-GPU rehearsal of the N>1 path)")
     ap.add_argument("--same-device", action="store_true", help="rehearsal: every rank uses cuda:0")
     a = ap.parse_args()
@@ -449,12 +501,13 @@ def main() -> None:
     hfc = model.fft(x) if a.workload == "encoder" else None
 
     def step():
+        """The timed path; returns what its caller receives (a dict of tensors)."""
         if a.workload == "encoder":
-            return model.image_encoder(x, hfc)
+            return {"image_embeddings": model.image_encoder(x, hfc)}
         out = model.detect(x, ts)
         if world > 1:
-            return wdist.all_gather_records(out["records"], n_tiles, rank, world)
-        return out["records"]
+            out["records"] = wdist.all_gather_records(out["records"], n_tiles, rank, world)
+        return out
 
     def sync():
         torch.cuda.synchronize(device)
@@ -462,15 +515,19 @@ def main() -> None:
             dist.barrier()
         torch.cuda.synchronize(device)
 
+    last = None
     with torch.no_grad():
         for _ in range(a.warmup):
             step()
         sync()
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            step()
+            last = step()
         sync()
         elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(a.dump_outputs, {k: v.cpu() for k, v in last.items()})
+    del last
     tmax = torch.tensor([elapsed], device=device if a.backend == "nccl" else "cpu", dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -479,7 +536,7 @@ def main() -> None:
 
     roofline = None
     classes = None
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         # second pass of the same steps with per-kernel HIP events on rank 0; every rank runs the steps because
         # a step of the N > 1 path contains the all-gather
         if rank == 0:
@@ -562,53 +619,62 @@ def main() -> None:
             "frac_of_mfma_peak_whole_path": round(tiles_per_s * flops_tile / 1e12 / (PEAK_TFLOPS.get(a.precision, 2500.0) * world), 4) if flops_tile else None,
             "roofline": roofline, "kernel_classes": classes,
         }
-        out_batch = None
-        if world == 1 and a.workload == "full":
-            with torch.no_grad():
-                out_batch = model.detect(x, ts)                       # one more pass over the timed, resident batch
-            torch.cuda.synchronize(device)
-            line["parity_vs_reference"] = parity_vs_reference_fixtures(a.model, out_batch, first)
-        # The other BASELINE.json configurations, timed in this process so that the driver's one command covers them:
-        # configs[1] literally (ViT-H encoder, bf16, B = 4), bf16 at the headline batch, configs[4] (fp8, all GEMMs) and the
-        # fp8 mix that keeps the reference's detections.  Short runs (5 steps): indicative, the headline is `value`.
-        if world == 1 and a.model == "vit_h" and not a.no_other_configs and B >= 4:
-            others = []
-            fold_default = hub.fold_ln
-            try:
-                others.append(dict(time_config(model, x, ts, "bf16", "encoder", 4, 5, 2, device), config="BASELINE.json configs[1]: ViT-H encoder bf16, batch=4"))
-                if B >= 16:
-                    others.append(dict(time_config(model, x, ts, "bf16", "full", 16, 5, 2, device, fold_ln=fold_default, gemm_rate=True),
-                                       config="configs[2] with bf16 operands (bf16 default: LayerNorm as its own kernel, fp32 residual stream)"))
-                    others.append(dict(time_config(model, x, ts, "bf16", "full", 16, 5, 2, device, fold_ln="all", gemm_rate=True),
-                                       config="configs[2] with bf16 operands, LayerNorm folded + split residual stream (WM_LN_FOLD=2, opt-in: another draw of bf16's "
-                                              "~1e-3 logits error, include/wm_hip.h WM_CFG_FOLD_LN)"))
-                    others.append(dict(time_config(model, x, ts, "fp16", "full", 16, 5, 2, device, fold_ln=False, gemm_rate=True),
-                                       config="configs[2], fp16 operands, LayerNorm as its own kernel (WM_LN_FOLD=0): the GEMM class without the folded "
-                                              "LayerNorm's statistics / 16-bit-copy / normalisation work in its epilogues"))
-                    others.append(dict(time_config(model, x, ts, "fp8", "full", 16, 5, 2, device, fold_ln=fold_default, gemm_rate=True),
-                                       config="BASELINE.json configs[4]: fp8, all four GEMMs of every block"))
-                    others.append(dict(time_config(model, x, ts, "fp8", "full", 16, 5, 2, device, fp8_gemms=N_.FP8_MLP, fp8_bf16_head_tail=(8, 8)),
-                                       config="configs[4] variant closest to the reference's detections in the sweep (profiles/r3_fp8_gemm_mask_sweep.txt): fp8 MLP "
-                                              "pair only, first / last 8 blocks bf16"))
-            finally:
-                os.environ["WM_FP8_BF16_HEAD"], os.environ["WM_FP8_BF16_TAIL"] = "0", "0"
-                hub.set_fp8_gemms(0)
-                hub.set_precision(a.precision)
-                if hub.fold_ln != fold_default:
-                    hub.fold_ln = fold_default
-                    hub.close()
-            line["other_configs"] = others
-        # the rows either side of the path (N1 input pipeline, N3 large-frame tiling), measured
-        if world == 1 and a.model == "vit_h" and a.workload == "full" and not a.no_other_configs and B >= 4:
-            line["frontend_configs"] = frontend_configs(model, device, B, tiles_per_s)
-        if not a.no_cpu_baseline and world == 1 and a.workload == "full":
-            line["cpu_baseline"], line["map_vs_cpu_ref"] = cpu_baseline(a.model, sd, model, device, x, ts, first, {k: v.cpu() for k, v in out_batch.items()})
+        if a.full:
+            full_extras(a, line, model, sd, hub, x, ts, B, first, world, device, tiles_per_s)
         else:
             line["cpu_baseline"], line["map_vs_cpu_ref"] = None, None
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def full_extras(a, line: dict, model, sd, hub, x, ts, B: int, first: int, world: int, device, tiles_per_s: float) -> None:
+    """--full, rank 0, after the headline: parity of the timed batch against the reference fixtures, the other BASELINE.json
+    configurations, the frontend rows and the CPU baseline, each written into `line`."""
+    out_batch = None
+    if world == 1 and a.workload == "full":
+        with torch.no_grad():
+            out_batch = model.detect(x, ts)                       # one more pass over the timed, resident batch
+        torch.cuda.synchronize(device)
+        line["parity_vs_reference"] = parity_vs_reference_fixtures(a.model, out_batch, first)
+    # The other BASELINE.json configurations, timed in this process so that the driver's one command covers them:
+    # configs[1] literally (ViT-H encoder, bf16, B = 4), bf16 at the headline batch, configs[4] (fp8, all GEMMs) and the
+    # fp8 mix that keeps the reference's detections (DESIGN.md section 3).  Short runs (5 steps): indicative, the headline is `value`.
+    if world == 1 and a.model == "vit_h" and not a.no_other_configs and B >= 4:
+        others = []
+        fold_default = hub.fold_ln
+        try:
+            others.append(dict(time_config(model, x, ts, "bf16", "encoder", 4, 5, 2, device), config="BASELINE.json configs[1]: ViT-H encoder bf16, batch=4"))
+            if B >= 16:
+                others.append(dict(time_config(model, x, ts, "bf16", "full", 16, 5, 2, device, fold_ln=fold_default, gemm_rate=True),
+                                   config="configs[2] with bf16 operands (bf16 default: LayerNorm as its own kernel, fp32 residual stream)"))
+                others.append(dict(time_config(model, x, ts, "bf16", "full", 16, 5, 2, device, fold_ln="all", gemm_rate=True),
+                                   config="configs[2] with bf16 operands, LayerNorm folded + split residual stream (WM_LN_FOLD=2, opt-in: another draw of bf16's "
+                                          "~1e-3 logits error, include/wm_hip.h WM_CFG_FOLD_LN)"))
+                others.append(dict(time_config(model, x, ts, "fp16", "full", 16, 5, 2, device, fold_ln=False, gemm_rate=True),
+                                   config="configs[2], fp16 operands, LayerNorm as its own kernel (WM_LN_FOLD=0): the GEMM class without the folded "
+                                          "LayerNorm's statistics / 16-bit-copy / normalisation work in its epilogues"))
+                others.append(dict(time_config(model, x, ts, "fp8", "full", 16, 5, 2, device, fold_ln=fold_default, gemm_rate=True),
+                                   config="BASELINE.json configs[4]: fp8, all four GEMMs of every block"))
+                others.append(dict(time_config(model, x, ts, "fp8", "full", 16, 5, 2, device, fp8_gemms=N_.FP8_MLP, fp8_bf16_head_tail=(8, 8)),
+                                   config="configs[4] variant closest to the reference's detections in the sweep (profiles/r3_fp8_gemm_mask_sweep.txt): fp8 MLP "
+                                          "pair only, first / last 8 blocks bf16"))
+        finally:
+            os.environ["WM_FP8_BF16_HEAD"], os.environ["WM_FP8_BF16_TAIL"] = "0", "0"
+            hub.set_fp8_gemms(0)
+            hub.set_precision(a.precision)
+            if hub.fold_ln != fold_default:
+                hub.fold_ln = fold_default
+                hub.close()
+        line["other_configs"] = others
+    # SURVEY.md section 8(f): the rows either side of the path (N1 input pipeline, N3 large-frame tiling), measured
+    if world == 1 and a.model == "vit_h" and a.workload == "full" and not a.no_other_configs and B >= 4:
+        line["frontend_configs"] = frontend_configs(model, device, B, tiles_per_s)
+    if not a.no_cpu_baseline and world == 1 and a.workload == "full":
+        line["cpu_baseline"], line["map_vs_cpu_ref"] = cpu_baseline(a.model, sd, model, device, x, ts, first, {k: v.cpu() for k, v in out_batch.items()})
+    else:
+        line["cpu_baseline"], line["map_vs_cpu_ref"] = None, None
 
 
 if __name__ == "__main__":

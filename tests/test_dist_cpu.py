@@ -73,6 +73,34 @@ def test_bench_gpus_n_self_launches_child_ranks():
     assert '"n_gpus"' not in r.stdout
 
 
+def test_bench_dump_outputs_format(tmp_path):
+    """bench.py --dump-outputs writer: records split into float fields (int fields exact in float64), float32 / float64
+    only, and an output larger than the 64 MB budget (the ViT-H encoder's B = 16 embeddings) written as a fixed seeded sample
+    with its indices, inside the budget."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(0)
+    rec = torch.randn(3, 51, 8, generator=g)
+    rec.view(torch.int32)[..., 5:] = torch.randint(0, 1 << 20, (3, 51, 3), dtype=torch.int32, generator=g)
+    bench.dump_outputs(str(tmp_path / "full"), {"pred_logits": torch.randn(3, 51, 8, generator=g), "records": rec})
+    got = {f.name[:-4]: np.load(f) for f in (tmp_path / "full").iterdir()}
+    assert set(got) == {"pred_logits", "records_boxes", "records_scores", "records_labels", "records_flags", "records_nms_rank"}
+    assert got["records_boxes"].dtype == np.float32 and got["records_flags"].dtype == np.float64
+    assert np.array_equal(got["records_nms_rank"], rec.view(torch.int32)[..., 7].numpy().astype(np.float64))
+    emb = torch.randn(16, 256, 64, 64, generator=g)
+    idxs = []
+    for _ in range(2):                                       # the sample is the same in every run
+        bench.dump_outputs(str(tmp_path / "enc"), {"image_embeddings": emb})
+        files = sorted((tmp_path / "enc").iterdir())
+        assert [f.name for f in files] == ["image_embeddings.npy", "image_embeddings_index.npy"]
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        v, idx = np.load(files[0]), np.load(files[1])
+        assert v.dtype == np.float32 and idx.dtype == np.float64 and v.size > 1 << 20
+        assert np.array_equal(v, emb.numpy().reshape(-1)[idx.astype(np.int64)])
+        idxs.append(idx)
+    assert np.array_equal(idxs[0], idxs[1])
+
+
 # ---------------------------------------------------------------------------
 # evaluate() itself over 2 ranks (inference.py:30-89 + the rank merge of :240-259), model and PostProcess stubbed
 # ---------------------------------------------------------------------------

@@ -928,7 +928,7 @@ def test_bench_two_ranks_on_one_gpu_rehearsal():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device", "--model", "vit_b",
-           "--batch", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--batch", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -938,3 +938,40 @@ def test_bench_two_ranks_on_one_gpu_rehearsal():
     assert line["value"] > 0 and line["steps"] == 2 and line["warmup"] == 1
     assert "all-gather of box records" in line["config"]["parallelism"]
     assert line["roofline"]["achieved"] > 0 and line["cpu_baseline"] is None
+
+
+def test_bench_plain_run_times_steps_and_dumps_last_step(tmp_path):
+    """A plain bench.py run (no --full): the headline line with --steps timed steps and no event pass, and --dump-outputs
+    writes what the last timed step returned -- here equal, bit for bit, to a forward of the same seeded batch in this
+    process.  Two GPU processes in total (this one + the bench)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    d = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--model", "vit_b", "--precision", "fp16",
+           "--batch", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)]
+    r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["unit"] == "tiles/s" and line["higher_is_better"] is True and line["dtype"] == "fp16"
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] / 1e3 / line["config"]["tiles_per_step"] - 1) < 1e-2
+    assert line["roofline"] is None and line["kernel_classes"] is None and line["cpu_baseline"] is None
+    assert "other_configs" not in line and "parity_vs_reference" not in line
+    files = {f.name: np.load(f) for f in d.iterdir()}
+    assert set(files) == {"pred_logits.npy", "pred_boxes.npy", "records_boxes.npy", "records_scores.npy",
+                          "records_labels.npy", "records_flags.npy", "records_nms_rank.npy"}, sorted(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+    m, _ = _model("vit_b", "fp16")
+    with torch.no_grad():
+        out = m.detect(torch.from_numpy(synth.make_batch(0, 2)).to(G.dev()), torch.full((2, 2), 1024.0, device=G.dev()))
+    rec = split_records(out["records"].cpu())
+    assert np.array_equal(files["pred_logits.npy"], out["pred_logits"].cpu().numpy())
+    assert np.array_equal(files["pred_boxes.npy"], out["pred_boxes"].cpu().numpy())
+    assert np.array_equal(files["records_flags.npy"], rec["flags"].numpy().astype(np.float64))
+    assert np.array_equal(files["records_scores.npy"], rec["scores"].numpy())

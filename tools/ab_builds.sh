@@ -8,7 +8,7 @@ for round in 1 2; do
   for spec in "$@"; do
     label=${spec%%=*}; envs=${spec#*=}
     [ "$envs" = "-" ] && envs=""
-    env $(echo $envs | tr ',' ' ') python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-other-configs $WM_AB_BENCH_ARGS > $O/${label}_$round.json 2>> $O/err.txt || { tail -5 $O/err.txt; exit 1; }
+    env $(echo $envs | tr ',' ' ') python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-other-configs $WM_AB_BENCH_ARGS > $O/${label}_$round.json 2>> $O/err.txt || { tail -5 $O/err.txt; exit 1; }
     python - $O/${label}_$round.json $label $round <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

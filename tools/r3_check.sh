@@ -6,7 +6,7 @@ python -m pytest tests -m gpu -x -q 2>&1 | tail -30 > $O/gputests.txt
 rc=$?
 cat $O/gputests.txt
 [ $rc -ne 0 ] && exit $rc
-python bench.py --steps 10 --warmup 3 --no-cpu-baseline ${2:-} > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline ${2:-} > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python - $O/bench.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

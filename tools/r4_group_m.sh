@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 export WM_HIP_LIB=build/ab/libwm_dev.so
 for round in 1 2; do
   for g in 8 4 2; do
-    WM_GEMM_GROUP_M=$g python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-other-configs > $O/bench_g${g}_$round.json 2>> $O/err.txt || { tail -5 $O/err.txt; exit 1; }
+    WM_GEMM_GROUP_M=$g python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-other-configs > $O/bench_g${g}_$round.json 2>> $O/err.txt || { tail -5 $O/err.txt; exit 1; }
     python - $O/bench_g${g}_$round.json $g $round <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
