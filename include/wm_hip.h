@@ -29,12 +29,14 @@
 extern "C" {
 #endif
 
-/* 3 (round 3, second half): wm_op_encoder_attention_qkv added; nothing else changed.
+/* 5: wm_frame_desc, wm_tile_frames_u8, wm_merge_frames_scratch_bytes, wm_merge_frames_nms (many frames of any size);
+ *    nothing else changed.
+ * 3 (round 3, second half): wm_op_encoder_attention_qkv added; nothing else changed.
  * 2 (round 3): wm_config.fp8_gemms; wm_debug_saturation_*; wm_op_layernorm rejects WM_PREC_FP8 with an fp32 output;
  * wm_profile_read no longer reports the fused-LayerNorm time-out (wm_forward / wm_encoder_forward do); precision value 2
  * (fp8), WM_FLAG_MERGED and a NULL handle in wm_postprocess_nms date from round 2.  The Python binding refuses a library
  * whose wm_abi_version() differs from the value it was written for. */
-#define WM_ABI_VERSION 4
+#define WM_ABI_VERSION 5
 
 /* operand type of the transformer blocks' MFMA GEMMs / attention (accumulation, residual stream, LayerNorm
  * statistics, softmax and the whole decoder are fp32; the stem, the HFC adaptor and the neck -- 2.9 % of the
@@ -190,6 +192,30 @@ int wm_tile_frame_u8(const uint8_t* frame_dev, const int32_t* origins_dev, float
                      void* stream);
 int wm_merge_tiles_nms(const wm_box_record* records_dev, const int32_t* origins_dev, int n_tiles, float iou_thr,
                        wm_box_record* merged_dev, void* stream);
+
+/* ---- survey front end: many frames of any size per launch ----------------------------------------------------------
+ * wm_tile_frames_u8: one model batch cut from several frames.  frames_dev[n_frames] (device) gives each frame's uint8 HWC
+ * base pointer and size; tiles_dev[n_tiles][3] = (frame index, y0, x0) (int32, device).  Output [n_tiles,3,1024,1024]
+ * fp32 with wm_tile_frame_u8's arithmetic, each tile bit-identical to cutting it from its own frame alone.
+ * wm_merge_frames_nms: wm_merge_tiles_nms applied to each frame independently, with no limit on tiles per frame.  Frame
+ * f is the tiles [frame_tile_offsets[f], frame_tile_offsets[f+1]) of records_dev / origins_dev; frame_tile_offsets is
+ * HOST memory, n_frames + 1 entries, starting at 0 and strictly increasing.  merged_dev[n_slots] (n_slots = total tiles
+ * * WM_NUM_QUERIES): every slot with its box in frame coordinates, WM_FLAG_MERGED and nms_rank exactly as
+ * wm_merge_tiles_nms would give for that frame alone.  The compacted detection list: frame f's survivors in merged order
+ * are det_dev / det_tile_dev [frame_tile_offsets[f] * WM_NUM_QUERIES + k], k < det_count_dev[f] (det_tile = tile within
+ * the frame).  scratch_dev (16-byte aligned, device) holds at least wm_merge_frames_scratch_bytes(total tiles) bytes;
+ * nothing is allocated.  Boxes must be finite; iou_thr in [0, 1).  Frame coordinates are fp32: below 0.01 px of
+ * fractional resolution up to 65536 px. */
+typedef struct wm_frame_desc {
+    const uint8_t* data;      /* [height, width, 3] uint8, device */
+    int32_t height, width;
+} wm_frame_desc;
+int wm_tile_frames_u8(const wm_frame_desc* frames_dev, int n_frames, const int32_t* tiles_dev, float* out_dev, int n_tiles,
+                      void* stream);
+int64_t wm_merge_frames_scratch_bytes(int n_tiles);    /* <0 on error */
+int wm_merge_frames_nms(const wm_box_record* records_dev, const int32_t* origins_dev, const int32_t* frame_tile_offsets,
+                        int n_frames, float iou_thr, void* scratch_dev, int64_t scratch_bytes, wm_box_record* merged_dev,
+                        wm_box_record* det_dev, int32_t* det_tile_dev, int32_t* det_count_dev, void* stream);
 
 /* ---- intermediate taps (parity tests) -------------------------------------
  * Copies the fp32 token stream (B,64,64,embed_dim) as it stood after the patch embed + pos_embed

@@ -1,0 +1,132 @@
+"""Survey throughput and merge timing (tiling.detect_frames, wm_merge_frames_nms).
+
+  python tools/survey_time.py rate  [--model vit_h] [--batch 16]
+      tiles/s of detect_frames over a mixed survey (8 x 6000x4000, 8 x 3648x5472, 1 x 20000x15000) with device-resident
+      frames and with host frames, against model.detect on resident tiles at the same batch, in one process.
+  python tools/survey_time.py merge [--reps 20]
+      synthetic per-tile records, old (wm_merge_tiles_nms) and new (wm_merge_frames_nms) merge at 35 tiles, new at 391;
+      run under `rocprofv3 --kernel-trace --stats` for the per-kernel times (wall times printed here include the launch).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from wildlifemapper_amd import _native as N, synth, tiling  # noqa: E402
+
+SURVEY = [(4000, 6000)] * 8 + [(3648, 5472)] * 8 + [(15000, 20000)]
+
+
+def make_model(model_type, prec):
+    from wildlifemapper_amd.segment_anything import sam_model_registry
+    from wildlifemapper_amd.segment_anything.network import MedSAM
+    sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(model_type).items()}
+    sam, _, _ = sam_model_registry[model_type](None, None)
+    m = MedSAM(sam.image_encoder, sam.mask_decoder, sam.prompt_encoder).eval()
+    m.load_state_dict(sd, strict=True)
+    m._hub.set_precision(prec)
+    return m
+
+
+def rate(args):
+    dev = torch.device("cuda:0")
+    m = make_model(args.model, args.prec)
+    g = torch.Generator(device=dev).manual_seed(0)
+    dframes = [torch.randint(0, 256, (h, w, 3), dtype=torch.uint8, device=dev, generator=g) for h, w in SURVEY]
+    hframes = [f.cpu().numpy() for f in dframes]
+    n_tiles = sum(len(tiling.tile_origins(h, w)) for h, w in SURVEY)
+    x = tiling.frame_to_tiles(dframes[0], torch.tensor(tiling.tile_origins(4000, 6000)[:args.batch], dtype=torch.int32))
+    n_batches = -(-n_tiles // args.batch)
+
+    def resident():
+        for _ in range(n_batches):
+            m.detect(x)
+
+    def survey(frames):
+        def run():
+            for _ in tiling.detect_frames(m, frames, batch=args.batch):
+                pass
+        return run
+
+    res = {}
+    for name, fn in [("resident_tiles", resident), ("device_frames", survey(dframes)), ("host_frames", survey(hframes))]:
+        fn()                                     # warm-up (handle, pinned buffer, allocator)
+        torch.cuda.synchronize()
+        best = None
+        for _ in range(args.reps):
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t
+            best = dt if best is None else min(best, dt)
+        res[name] = n_batches * args.batch / best if name == "resident_tiles" else n_tiles / best
+        print(f"{name}: {res[name]:.2f} tiles/s (best of {args.reps}, {best:.3f} s)", flush=True)
+    res["device_over_resident"] = res["device_frames"] / res["resident_tiles"]
+    res["host_over_resident"] = res["host_frames"] / res["resident_tiles"]
+    print(json.dumps({"survey_tiles": n_tiles, "frames": len(SURVEY), "model": args.model, "precision": args.prec, "batch": args.batch,
+                      **{k: round(v, 4) for k, v in res.items()}}))
+
+
+def synth_records(H, W, rng, p_cand=0.1):
+    """Per-tile records: a few candidates per tile, objects seen by two horizontally neighbouring tiles duplicated."""
+    org = tiling.tile_origins(H, W)
+    n = len(org)
+    c = rng.random((n, 51, 2)) * 1000 + 12
+    wh = rng.random((n, 51, 2)) * 80 + 10
+    boxes = np.concatenate([c - wh / 2, c + wh / 2], axis=-1).astype(np.float32)
+    scores = rng.random((n, 51)).astype(np.float32)
+    cand = rng.random((n, 51)) < p_cand
+    for t in range(n - 1):
+        if org[t][0] == org[t + 1][0]:
+            dx = org[t + 1][1] - org[t][1]
+            boxes[t + 1, 0] = boxes[t, 0] - np.array([dx, 0, dx, 0], np.float32)
+            cand[t, 0] = cand[t + 1, 0] = True
+    rec = torch.zeros((n, 51, 8), dtype=torch.float32)
+    rec[..., 0:4] = torch.from_numpy(boxes)
+    rec[..., 4] = torch.from_numpy(scores)
+    rec.view(torch.int32)[..., 6] = torch.from_numpy(np.where(cand, N.FLAG_NMS | N.FLAG_SCORE | N.FLAG_CONF, N.FLAG_CONF).astype(np.int32))
+    rec.view(torch.int32)[..., 7] = -1
+    return rec, torch.tensor(org, dtype=torch.int32), int(cand.sum())
+
+
+def merge(args):
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(0)
+    out = {}
+    for label, (H, W) in [("35_tiles", (4000, 6000)), ("391_tiles", (15000, 20000))]:
+        rec, org, ncand = synth_records(H, W, rng)
+        rec, org = rec.to(dev), org.to(dev)
+        n = rec.shape[0]
+        runs = [("new", lambda: tiling.merge_frames(rec, org, [0, n], 0.4))]
+        if n <= tiling.MERGE_ONE_WORKGROUP_MAX_TILES:
+            runs.insert(0, ("old", lambda: tiling.merge_tile_records(rec, org, 0.4)))
+        for name, fn in runs:
+            fn()
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(args.reps):
+                fn()
+            torch.cuda.synchronize()
+            out[f"{name}_{label}_ms_wall"] = round((time.perf_counter() - t) / args.reps * 1e3, 4)
+        out[f"candidates_{label}"] = ncand
+    print(json.dumps(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("mode", choices=("rate", "merge"))
+    ap.add_argument("--model", default="vit_h")
+    ap.add_argument("--prec", default="fp16")
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--reps", type=int, default=3)
+    args = ap.parse_args()
+    rate(args) if args.mode == "rate" else merge(args)
+
+
+if __name__ == "__main__":
+    main()

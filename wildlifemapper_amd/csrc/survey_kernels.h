@@ -1,0 +1,285 @@
+// Survey front end: the large-frame tile cut and cross-tile merge (dec_kernels.h) generalised to many frames of any
+// size per launch.
+//   * tile_frames_u8_kernel: one model batch cut from several frames (per-tile frame index), arithmetic of
+//     tile_frame_u8_kernel.
+//   * merge_frames_nms_kernel: the greedy NMS of merge_tiles_nms_kernel applied to each frame (a segment of tiles)
+//     independently, without a slot limit.
+#pragma once
+
+#include "wm_common.h"
+
+namespace wm {
+
+// Mirrors wm_frame_desc of include/wm_hip.h (16 bytes).
+struct frame_desc {
+    const unsigned char* data;
+    int height, width;
+};
+
+// tiles[n][3] = (frame index, y0, x0).  A tile whose frame index is out of range is written as zeros.
+__global__ __launch_bounds__(256) void tile_frames_u8_kernel(const frame_desc* __restrict__ frames, int n_frames,
+                                                             const int* __restrict__ tiles, float* __restrict__ out, int n) {
+#pragma clang fp contract(off)
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+    const int64_t total = (int64_t)n * 1024 * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int x4 = (int)(i & 255) * 4;
+        const int y = (int)((i >> 8) & 1023);
+        const int64_t t = i >> 18;
+        const int f = tiles[3 * t];
+        f32x4 v[3] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+        if (f >= 0 && f < n_frames) {
+            const frame_desc fd = frames[f];
+            const int H = fd.height, W = fd.width;
+            const int fy = tiles[3 * t + 1] + y, fx0 = tiles[3 * t + 2] + x4;
+            if (fy >= 0 && fy < H) {
+                const unsigned char* row = fd.data + (int64_t)fy * W * 3;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int fx = fx0 + j;
+                    if (fx >= 0 && fx < W) {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) v[c][j] = ((float)row[(int64_t)fx * 3 + c] / 255.0f - mean[c]) / stdv[c];
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *(f32x4*)(out + ((t * 3 + c) * 1024 + y) * (int64_t)1024 + x4) = v[c];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Segmented cross-tile merge.  One workgroup per frame, every step in that workgroup (workgroups meet only at kernel
+// boundaries; no inter-workgroup hand-off):
+//   1. compact the frame's candidates (WM_FLAG_NMS) as 64-bit priority keys (~score order << 32 | slot), write every
+//      slot's output record (frame-coordinate box, WM_FLAG_MERGED clear, nms_rank -1);
+//   2. bitonic-sort the keys: candidate c of the frame = its position in (score desc, slot asc) order;
+//   3. frame-coordinate boxes per candidate; the largest box width / height of the frame;
+//   4. bitonic-sort the candidates by (row, x0) -- rows of the largest box height -- so the boxes a box can intersect
+//      lie in <= a few rows, each a contiguous x0 range found by binary search (no storage beyond O(candidates));
+//   5. resolve greedy NMS by rounds: a candidate is kept when every higher-priority box that would suppress it is
+//      decided and none is kept, suppressed as soon as one of them is kept.  The fixed point is sequential greedy NMS;
+//      the rounds number the longest dependency chain;
+//   6. survivors' nms_rank = prefix count of kept in priority order; records and the compacted detection list.
+// The IoU test is merge_tiles_nms_kernel's: un-contracted, the higher-priority box as `a`.  Pairs with inter == 0 can
+// never suppress (iou_thr >= 0), so only boxes whose interiors meet are compared.  Boxes must be finite.
+// ---------------------------------------------------------------------------
+constexpr int MF_THREADS = 1024, MF_MAX_FRAMES = 64, MF_LDS_SORT = 4096;
+constexpr int MF_UNDECIDED = 0, MF_KEPT = 1, MF_SUPPRESSED = 2;
+constexpr int MF_SCRATCH_PER_SLOT = 16 + 8 + 4 + 4 + 4;      // cbox, skey, sval, cslot, state
+
+struct mf_offsets {
+    int tile[MF_MAX_FRAMES + 1];       // absolute tile offsets of this launch's frames
+};
+
+__device__ __forceinline__ unsigned mf_ord(float f) {       // order-preserving float -> u32
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// Ascending bitonic sort of (key, val) pairs, any n: the comparator of the first step of every merge stage pairs
+// mirrored positions, so all comparators point the same way and the virtual +inf padding past n never moves.
+__device__ void mf_bitonic(uint64_t* key, int* val, int n) {
+    int np2 = 1;
+    while (np2 < n) np2 <<= 1;
+    const int half = np2 >> 1;
+    for (int k = 2; k <= np2; k <<= 1) {
+        for (int j = k >> 1; j >= 1; j >>= 1) {
+            for (int t = threadIdx.x; t < half; t += blockDim.x) {
+                const int blk = t / j, p = t - blk * j;
+                int a, b;
+                if (j == (k >> 1)) { a = blk * k + p; b = blk * k + k - 1 - p; }
+                else { a = blk * 2 * j + p; b = a + j; }
+                if (b < n) {
+                    const uint64_t ka = key[a], kb = key[b];
+                    if (kb < ka) {
+                        key[a] = kb; key[b] = ka;
+                        const int va = val[a]; val[a] = val[b]; val[b] = va;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__device__ __forceinline__ int mf_lower_bound(const uint64_t* key, int n, uint64_t x) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (key[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ int mf_row(float y, float y_min, float row_h) {
+#pragma clang fp contract(off)
+    const float r = floorf((y - y_min) / row_h);
+    return r <= 0.f ? 0 : (r >= 1073741824.f ? 1073741824 : (int)r);
+}
+
+__device__ __forceinline__ int mf_load_state(const int* s) {
+    return __hip_atomic_load(s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// Block-wide exclusive prefix sum of one int per thread (1024 threads = 16 waves of 64); returns the block total too.
+__device__ __forceinline__ int mf_scan(int v, int* s_wave, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += o;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int before = 0, all = 0;
+    for (int w = 0; w < MF_THREADS / 64; ++w) {
+        const int c = s_wave[w];
+        if (w < wave) before += c;
+        all += c;
+    }
+    __syncthreads();
+    total = all;
+    return before + incl - v;
+}
+
+__global__ __launch_bounds__(MF_THREADS) void merge_frames_nms_kernel(
+        const wm_box_record* __restrict__ rec, const int* __restrict__ origins, mf_offsets offs, float iou_thr,
+        char* __restrict__ scratch, int n_slots_total, wm_box_record* __restrict__ out, wm_box_record* __restrict__ det,
+        int* __restrict__ det_tile, int* __restrict__ det_count, int frame_base) {
+#pragma clang fp contract(off)
+    __shared__ uint64_t l_key[MF_LDS_SORT];
+    __shared__ int l_val[MF_LDS_SORT];
+    __shared__ int s_n, s_wave[MF_THREADS / 64];
+    __shared__ unsigned s_wmax, s_hmax, s_ymin;
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const int t0 = offs.tile[f], t1 = offs.tile[f + 1];
+    const int s0 = t0 * WM_NUM_QUERIES, ns = (t1 - t0) * WM_NUM_QUERIES;
+    float4* cbox = (float4*)scratch + s0;
+    uint64_t* g_key = (uint64_t*)(scratch + (size_t)n_slots_total * 16) + s0;
+    int* g_val = (int*)(scratch + (size_t)n_slots_total * 24) + s0;
+    int* cslot = (int*)(scratch + (size_t)n_slots_total * 28) + s0;
+    int* state = (int*)(scratch + (size_t)n_slots_total * 32) + s0;
+    if (tid == 0) { s_n = 0; s_wmax = mf_ord(0.f); s_hmax = mf_ord(0.f); s_ymin = 0xffffffffu; }
+    __syncthreads();
+
+    // 1. records out (frame coordinates, not merged) + candidate keys
+    for (int i = tid; i < ns; i += MF_THREADS) {
+        wm_box_record r = rec[s0 + i];
+        const int tile = t0 + i / WM_NUM_QUERIES;
+        const float oy = (float)origins[2 * tile], ox = (float)origins[2 * tile + 1];
+        r.box[0] += ox; r.box[1] += oy; r.box[2] += ox; r.box[3] += oy;
+        const bool cand = (r.flags & WM_FLAG_NMS) != 0;
+        r.flags &= ~WM_FLAG_MERGED;
+        r.nms_rank = -1;
+        out[s0 + i] = r;
+        if (cand) {
+            const float sc = r.score == 0.f ? 0.f : r.score;          // -0 ties with +0, as the comparison does
+            const int c = atomicAdd(&s_n, 1);
+            g_key[c] = ((uint64_t)(~mf_ord(sc)) << 32) | (unsigned)i;
+        }
+    }
+    __syncthreads();
+    const int n = s_n;
+    const bool in_lds = n <= MF_LDS_SORT;
+    uint64_t* key = in_lds ? l_key : g_key;
+    int* val = in_lds ? l_val : g_val;
+
+    // 2. priority order
+    if (in_lds)
+        for (int c = tid; c < n; c += MF_THREADS) l_key[c] = g_key[c];
+    __syncthreads();
+    mf_bitonic(key, val, n);
+
+    // 3. candidate boxes in priority order, frame extents
+    for (int c = tid; c < n; c += MF_THREADS) {
+        const int slot = (int)(key[c] & 0xffffffffu);
+        cslot[c] = slot;
+        const float4 b = *(const float4*)&out[s0 + slot].box[0];
+        cbox[c] = b;
+        state[c] = MF_UNDECIDED;
+        atomicMax(&s_wmax, mf_ord(fmaxf(b.z - b.x, 0.f)));
+        atomicMax(&s_hmax, mf_ord(fmaxf(b.w - b.y, 0.f)));
+        atomicMin(&s_ymin, mf_ord(b.y));
+    }
+    __syncthreads();
+    const float wmax = __uint_as_float(s_wmax & 0x7fffffffu), hmax = __uint_as_float(s_hmax & 0x7fffffffu);
+    const unsigned ym = s_ymin;
+    const float y_min = n > 0 ? __uint_as_float((ym & 0x80000000u) ? (ym & 0x7fffffffu) : ~ym) : 0.f;
+    const float row_h = fmaxf(hmax, 1.f);
+
+    // 4. spatial order: (row of y0, x0)
+    for (int c = tid; c < n; c += MF_THREADS) {
+        const float4 b = cbox[c];
+        key[c] = ((uint64_t)mf_row(b.y, y_min, row_h) << 32) | mf_ord(b.x);
+        val[c] = c;
+    }
+    __syncthreads();
+    mf_bitonic(key, val, n);
+
+    // 5. rounds.  A box q meets p only if q.y0 in (p.y0 - h_q, p.y1) and q.x0 in (p.x0 - w_q, p.x1); the search window
+    // widens the lower ends by a margin that covers the rounding of the fp32 widths.
+    for (;;) {
+        int pending_any = 0;
+        for (int c = tid; c < n; c += MF_THREADS) {
+            if (mf_load_state(&state[c]) != MF_UNDECIDED) continue;
+            const float4 p = cbox[c];
+            const float parea = (p.z - p.x) * (p.w - p.y);
+            const float ylo = p.y - (hmax + (1.f + hmax * 0x1p-20f + fabsf(p.y) * 0x1p-20f));
+            const float xlo = p.x - (wmax + (1.f + wmax * 0x1p-20f + fabsf(p.x) * 0x1p-20f));
+            const int r0 = mf_row(ylo, y_min, row_h), r1 = mf_row(p.w, y_min, row_h);
+            bool dead = false, pending = false;
+            for (int r = r0; r <= r1 && !dead; ++r) {
+                const uint64_t row = (uint64_t)r << 32;
+                int m = mf_lower_bound(key, n, row | mf_ord(xlo));
+                const int m1 = mf_lower_bound(key, n, (row | mf_ord(p.z)) + 1);
+                for (; m < m1 && !dead; ++m) {
+                    const int q = val[m];
+                    if (q >= c) continue;
+                    const int st = mf_load_state(&state[q]);
+                    if (st == MF_SUPPRESSED) continue;
+                    const float4 a = cbox[q];
+                    const float xx0 = fmaxf(a.x, p.x), yy0 = fmaxf(a.y, p.y);
+                    const float xx1 = fminf(a.z, p.z), yy1 = fminf(a.w, p.w);
+                    const float iw = fmaxf(0.f, xx1 - xx0), ih = fmaxf(0.f, yy1 - yy0);
+                    const float inter = iw * ih;
+                    const float aarea = (a.z - a.x) * (a.w - a.y);
+                    const float iou = inter / (aarea + parea - inter);
+                    if (iou > iou_thr) {
+                        if (st == MF_KEPT) dead = true;
+                        else pending = true;
+                    }
+                }
+            }
+            if (dead || !pending)
+                __hip_atomic_store(&state[c], dead ? MF_SUPPRESSED : MF_KEPT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            else
+                pending_any = 1;
+        }
+        if (!__syncthreads_or(pending_any)) break;
+    }
+
+    // 6. ranks, records, detection list
+    int base = 0;
+    for (int c0 = 0; c0 < n; c0 += MF_THREADS) {
+        const int c = c0 + tid;
+        const bool kept = c < n && state[c] == MF_KEPT;
+        int total;
+        const int rank = base + mf_scan(kept ? 1 : 0, s_wave, total);
+        if (kept) {
+            const int slot = cslot[c];
+            wm_box_record r = out[s0 + slot];
+            r.flags |= WM_FLAG_MERGED;
+            r.nms_rank = rank;
+            out[s0 + slot] = r;
+            det[s0 + rank] = r;
+            det_tile[s0 + rank] = slot / WM_NUM_QUERIES;
+        }
+        base += total;
+    }
+    if (tid == 0) det_count[frame_base + f] = base;
+}
+
+}  // namespace wm

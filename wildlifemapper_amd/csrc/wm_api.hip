@@ -29,6 +29,7 @@
 #include "gemm32.h"
 #include "gemm8.h"
 #include "misc_kernels.h"
+#include "survey_kernels.h"
 #include "wm_common.h"
 
 // Dev instrumentation (in-kernel timelines of the GEMMs: tools/gemm_bench.py with WM_GEMM_DBG / WM_GEMM8_DBG /
@@ -2108,6 +2109,52 @@ extern "C" int wm_merge_tiles_nms(const wm_box_record* records_dev, const int32_
     hipLaunchKernelGGL(merge_tiles_nms_kernel, dim3(1), dim3(MERGE_THREADS), LDS, (hipStream_t)stream, records_dev, (const int*)origins_dev, n_slots,
                        iou_thr, merged_dev);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static_assert(sizeof(wm_frame_desc) == sizeof(frame_desc), "wm_frame_desc layout");
+
+extern "C" int wm_tile_frames_u8(const wm_frame_desc* frames_dev, int n_frames, const int32_t* tiles_dev, float* out_dev, int n_tiles,
+                                 void* stream) {
+    if (!frames_dev || !tiles_dev || !out_dev) return fail("wm_tile_frames_u8: null buffer");
+    if (n_frames <= 0 || n_tiles <= 0) return fail("wm_tile_frames_u8: n_frames %d, n_tiles %d", n_frames, n_tiles);
+    hipLaunchKernelGGL(tile_frames_u8_kernel, dim3(grid_for((int64_t)n_tiles * 1024 * 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const frame_desc*)frames_dev, n_frames, (const int*)tiles_dev, out_dev, n_tiles);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int64_t wm_merge_frames_scratch_bytes(int n_tiles) {
+    if (n_tiles <= 0 || (int64_t)n_tiles * WM_NUM_QUERIES > INT32_MAX) return fail("wm_merge_frames_scratch_bytes: n_tiles %d", n_tiles);
+    return (int64_t)n_tiles * WM_NUM_QUERIES * MF_SCRATCH_PER_SLOT;
+}
+
+extern "C" int wm_merge_frames_nms(const wm_box_record* records_dev, const int32_t* origins_dev, const int32_t* frame_tile_offsets,
+                                   int n_frames, float iou_thr, void* scratch_dev, int64_t scratch_bytes, wm_box_record* merged_dev,
+                                   wm_box_record* det_dev, int32_t* det_tile_dev, int32_t* det_count_dev, void* stream) {
+    if (!records_dev || !origins_dev || !frame_tile_offsets || !scratch_dev || !merged_dev || !det_dev || !det_tile_dev || !det_count_dev)
+        return fail("wm_merge_frames_nms: null buffer");
+    if (n_frames <= 0) return fail("wm_merge_frames_nms: n_frames %d", n_frames);
+    if (!(iou_thr >= 0.f && iou_thr < 1.f)) return fail("wm_merge_frames_nms: iou_thr %g outside [0, 1)", (double)iou_thr);
+    if (frame_tile_offsets[0] != 0) return fail("wm_merge_frames_nms: frame_tile_offsets[0] = %d, not 0", frame_tile_offsets[0]);
+    for (int f = 0; f < n_frames; ++f)
+        if (frame_tile_offsets[f + 1] <= frame_tile_offsets[f])
+            return fail("wm_merge_frames_nms: frame_tile_offsets not strictly increasing at frame %d (%d -> %d)", f, frame_tile_offsets[f],
+                        frame_tile_offsets[f + 1]);
+    const int n_tiles = frame_tile_offsets[n_frames];
+    const int64_t need = wm_merge_frames_scratch_bytes(n_tiles);
+    if (need < 0) return -1;
+    if (scratch_bytes < need) return fail("wm_merge_frames_nms: scratch of %lld bytes, %lld needed", (long long)scratch_bytes, (long long)need);
+    if ((uintptr_t)scratch_dev % 16) return fail("wm_merge_frames_nms: scratch not 16-byte aligned");
+    for (int f0 = 0; f0 < n_frames; f0 += MF_MAX_FRAMES) {
+        const int nf = std::min(MF_MAX_FRAMES, n_frames - f0);
+        mf_offsets offs;
+        for (int f = 0; f <= nf; ++f) offs.tile[f] = frame_tile_offsets[f0 + f];
+        hipLaunchKernelGGL(merge_frames_nms_kernel, dim3(nf), dim3(MF_THREADS), 0, (hipStream_t)stream, records_dev, (const int*)origins_dev,
+                           offs, iou_thr, (char*)scratch_dev, n_tiles * WM_NUM_QUERIES, merged_dev, det_dev, (int*)det_tile_dev,
+                           (int*)det_count_dev, f0);
+        HIP_TRY(hipGetLastError());
+    }
     return 0;
 }
 

@@ -7,11 +7,17 @@ match: the checker is oracle/tiling_oracle.py, a numpy restatement of exactly wh
     last flush with the frame edges (no padding unless the frame is smaller than a tile): 7 x 5 tiles for 6000 x 4000;
   * frame_to_tiles: wm_tile_frame_u8 (cut + ToTensor + Normalize on the GPU);
   * detect_frame: model.detect per batch of tiles, then wm_merge_tiles_nms -- detections that survived their own tile's
-    score cut + NMS move to frame coordinates and compete in one more class-agnostic NMS (IoU 0.4).
+    score cut + NMS move to frame coordinates and compete in one more class-agnostic NMS (IoU 0.4);
+  * detect_frames: a survey -- many frames of any size, device or host -- with the tiles of consecutive frames packed
+    into full batches (wm_tile_frames_u8) and one segmented merge (wm_merge_frames_nms) per batch for the frames it
+    completes.  Frames with more than 80 tiles (the single-workgroup merge's limit) go through the segmented merge.
+Frame coordinates are fp32: a box coordinate keeps a fractional resolution below 0.01 px up to 65536 px (ulp 2**-8).
 """
 from __future__ import annotations
 
-from typing import Dict, List, Tuple
+from typing import Dict, Iterable, Iterator, List, NamedTuple, Tuple
+
+import numpy as np
 
 import torch
 
@@ -47,10 +53,44 @@ def frame_to_tiles(frame: torch.Tensor, origins: torch.Tensor) -> torch.Tensor:
     return out
 
 
+MERGE_ONE_WORKGROUP_MAX_TILES = 80        # wm_merge_tiles_nms: n_tiles * 51 <= 4096
+
+
+def merge_frames(records: torch.Tensor, origins: torch.Tensor, frame_tile_offsets, iou_thr: float = 0.4) -> Dict[str, torch.Tensor]:
+    """Segmented cross-tile merge (wm_merge_frames_nms).  records (n,51,8) raw per-tile records of several frames,
+    origins (n,2) each tile's (y0, x0) in its own frame, frame_tile_offsets (n_frames + 1) host ints: frame f is tiles
+    [offsets[f], offsets[f+1]).  Returns 'merged' (n,51,8) as merge_tile_records gives per frame, and the compacted
+    detection list: frame f's survivors in merged order are 'det' / 'det_tile' [offsets[f] * 51 + k], k < 'det_count'[f]."""
+    N.require_cuda(records, "records")
+    offs = np.ascontiguousarray(np.asarray(frame_tile_offsets, dtype=np.int32))
+    n = records.shape[0]
+    if offs.ndim != 1 or offs.shape[0] < 2 or int(offs[-1]) != n or tuple(records.shape[1:]) != (N.NUM_QUERIES, 8):
+        raise RuntimeError(f"merge_frames: records {tuple(records.shape)} do not match frame_tile_offsets ending at {offs[-1] if offs.size else None}")
+    origins = origins.to(device=records.device, dtype=torch.int32).contiguous()
+    nf = offs.shape[0] - 1
+    nbytes = N.lib().wm_merge_frames_scratch_bytes(n)
+    if nbytes < 0:
+        N.check(-1)
+    dev = records.device
+    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    merged = torch.empty_like(records)
+    det = torch.empty((n * N.NUM_QUERIES, 8), device=dev, dtype=torch.float32)
+    det_tile = torch.empty(n * N.NUM_QUERIES, device=dev, dtype=torch.int32)
+    det_count = torch.empty(nf, device=dev, dtype=torch.int32)
+    import ctypes as C
+    with torch.cuda.device(dev):
+        N.check(N.lib().wm_merge_frames_nms(N.ptr(records), N.ptr(origins), offs.ctypes.data_as(C.POINTER(C.c_int32)), nf, float(iou_thr),
+                                            N.ptr(scratch), nbytes, N.ptr(merged), N.ptr(det), N.ptr(det_tile), N.ptr(det_count),
+                                            N.stream_ptr(dev)))
+    return {"merged": merged, "det": det, "det_tile": det_tile, "det_count": det_count}
+
+
 def merge_tile_records(records: torch.Tensor, origins: torch.Tensor, iou_thr: float = 0.4) -> torch.Tensor:
     """records (n,51,8) raw per-tile records (boxes in tile pixels) -> (n,51,8) merged records in frame coordinates with
-    FLAG_MERGED / nms_rank of the cross-tile NMS (wm_merge_tiles_nms)."""
+    FLAG_MERGED / nms_rank of the cross-tile NMS (wm_merge_tiles_nms up to 80 tiles, wm_merge_frames_nms above)."""
     N.require_cuda(records, "records")
+    if records.shape[0] > MERGE_ONE_WORKGROUP_MAX_TILES:
+        return merge_frames(records, origins, [0, records.shape[0]], iou_thr)["merged"]
     origins = origins.to(device=records.device, dtype=torch.int32).contiguous()
     out = torch.empty_like(records)
     with torch.cuda.device(records.device):
@@ -76,3 +116,186 @@ def detect_frame(model, frame: torch.Tensor, overlap: int = 128, batch: int = 16
     kept = kept[torch.argsort(flat["nms_rank"][kept])]
     return {"boxes": flat["boxes"][kept], "scores": flat["scores"][kept], "labels": flat["labels"][kept],
             "tile": kept // N.NUM_QUERIES, "origins": org, "records": merged}
+
+
+# ---- survey: many frames of any size ---------------------------------------------------------------------------------
+
+class SurveyBatch(NamedTuple):
+    segments: List[Tuple[int, int, int]]     # (frame index, first tile, end tile) in batch order
+    completes: List[int]                     # frames whose last tile is in this batch
+
+
+def plan_batches(tile_counts: Iterable[int], batch: int) -> Iterator[SurveyBatch]:
+    """Pack the tiles of consecutive frames into batches of `batch`: every tile of every frame once, in frame order, every
+    batch full except the last.  Lazy: a frame's tile count is read only when a batch needs its tiles."""
+    if batch <= 0:
+        raise ValueError(f"plan_batches: batch {batch}")
+    segs: List[Tuple[int, int, int]] = []
+    done: List[int] = []
+    fill = 0
+    for f, n in enumerate(tile_counts):
+        if n <= 0:
+            raise ValueError(f"plan_batches: frame {f} has {n} tiles")
+        t = 0
+        while t < n:
+            take = min(batch - fill, n - t)
+            segs.append((f, t, t + take))
+            t += take
+            fill += take
+            if t == n:
+                done.append(f)
+            if fill == batch:
+                yield SurveyBatch(segs, done)
+                segs, done, fill = [], [], 0
+    if segs:
+        yield SurveyBatch(segs, done)
+
+
+class _Frame:
+    __slots__ = ("data", "height", "width", "origins", "origins_dev", "ready", "records")
+
+    def __init__(self, data, height, width, origins, ready):
+        self.data, self.height, self.width, self.origins, self.ready = data, height, width, origins, ready
+        self.records: List[torch.Tensor] = []
+        self.origins_dev = None
+
+
+def _as_frame_array(frame, i: int, device: torch.device):
+    """Validate one survey frame as frame_to_tiles does: (H,W,3) uint8.  Returns (device tensor or None, host tensor or None)."""
+    if isinstance(frame, np.ndarray):
+        frame = torch.from_numpy(frame)
+    if not isinstance(frame, torch.Tensor) or frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[-1] != 3 \
+            or frame.shape[0] <= 0 or frame.shape[1] <= 0:
+        what = f"{tuple(frame.shape)} {frame.dtype} on {frame.device}" if isinstance(frame, torch.Tensor) else type(frame).__name__
+        raise RuntimeError(f"detect_frames: frame {i}: expected an (H,W,3) uint8 tensor or array, got {what}")
+    if frame.is_cuda:
+        if frame.device != device:
+            raise RuntimeError(f"detect_frames: frame {i} is on {frame.device}, the survey runs on {device}")
+        return frame.contiguous(), None
+    if frame.device.type != "cpu":
+        raise RuntimeError(f"detect_frames: frame {i} is on {frame.device}")
+    return None, frame.contiguous()
+
+
+@torch.no_grad()
+def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, iou_thr: float = 0.4) -> Iterator[Dict[str, torch.Tensor]]:
+    """Survey of frames of any sizes ((H,W,3) uint8 ROCm tensors, CPU tensors or numpy arrays) -> one dict per frame, in
+    input order, with detect_frame's keys and values.  Tiles of consecutive frames fill batches of `batch` (plan_batches);
+    after each batch one wm_merge_frames_nms covers the frames it completed.  Host frames go through one pinned staging
+    buffer (grown to the largest frame) and a copy stream: the next frame's upload overlaps the current batches, ordered
+    by events.  A frame's result is yielded once the batch after its merge is queued, so the host never waits on the
+    batch it just launched."""
+    from .engine import split_records
+    import ctypes as C
+    if batch <= 0:
+        raise ValueError(f"detect_frames: batch {batch}")
+    device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+    staged: Dict[int, _Frame] = {}
+    pinned = [None, None]                     # staging buffer, event of the last copy out of it
+    copy = [None]                             # copy stream, made for the first host frame
+    it = iter(frames)
+
+    def stage(i: int) -> bool:
+        try:
+            fr = next(it)
+        except StopIteration:
+            return False
+        d, h = _as_frame_array(fr, i, device)
+        if device is None:
+            raise RuntimeError("detect_frames: no ROCm device (there is no CPU fallback in wildlifemapper_amd)")
+        src = d if d is not None else h
+        H, W = int(src.shape[0]), int(src.shape[1])
+        org = tile_origins(H, W, 1024, overlap)
+        ready = None
+        if d is None:
+            nbytes = H * W * 3
+            if pinned[1] is not None:
+                pinned[1].synchronize()       # the previous upload has left the staging buffer
+            if pinned[0] is None or pinned[0].numel() < nbytes:
+                pinned[0] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+            buf = pinned[0][:nbytes]
+            buf.copy_(h.view(-1))
+            if copy[0] is None:
+                copy[0] = torch.cuda.Stream(device)
+            with torch.cuda.stream(copy[0]):
+                d = torch.empty((H, W, 3), dtype=torch.uint8, device=device)
+                d.view(-1).copy_(buf, non_blocking=True)
+                ready = torch.cuda.Event()
+                ready.record(copy[0])
+            d.record_stream(torch.cuda.current_stream(device))
+            pinned[1] = ready
+        staged[i] = _Frame(d, H, W, org, ready)
+        return True
+
+    def tile_counts():
+        i = 0
+        have = stage(0)
+        while have:
+            have_next = stage(i + 1)          # upload of frame i+1 overlaps the batches of frame i
+            yield len(staged[i].origins)
+            i += 1
+            have = have_next
+
+    def finish(pending):
+        out, frames_done, offs = pending
+        out["ready"].synchronize()
+        counts = out["count_host"].tolist()
+        for j, f in enumerate(frames_done):
+            fr = staged.pop(f)
+            s0, n = offs[j] * N.NUM_QUERIES, offs[j + 1] - offs[j]
+            k = counts[j]
+            det = split_records(out["det"][s0:s0 + k].view(k, 1, 8))
+            yield {"boxes": det["boxes"].reshape(k, 4), "scores": det["scores"].reshape(k), "labels": det["labels"].reshape(k),
+                   "tile": out["det_tile"][s0:s0 + k].to(torch.int64), "origins": fr.origins_dev,
+                   "records": out["merged"][offs[j]:offs[j] + n]}
+
+    pending = None
+    main = None
+    for b in plan_batches(tile_counts(), batch):
+        if main is None:
+            main = torch.cuda.current_stream(device)
+        used = list(dict.fromkeys(f for f, _, _ in b.segments))
+        local = {f: j for j, f in enumerate(used)}
+        for f in used:
+            if staged[f].ready is not None:
+                main.wait_event(staged[f].ready)
+                staged[f].ready = None
+        desc = np.zeros((len(used), 2), dtype=np.int64)
+        for j, f in enumerate(used):
+            fr = staged[f]
+            desc[j, 0] = fr.data.data_ptr()
+            desc[j, 1] = np.array([fr.height, fr.width], dtype=np.int32).view(np.int64)[0]
+        tiles = np.array([(local[f], *staged[f].origins[t]) for f, t0, t1 in b.segments for t in range(t0, t1)], dtype=np.int32)
+        desc_d = torch.from_numpy(desc).pin_memory().to(device, non_blocking=True)
+        tiles_d = torch.from_numpy(tiles).pin_memory().to(device, non_blocking=True)
+        n = tiles.shape[0]
+        x = torch.empty((n, 3, 1024, 1024), device=device, dtype=torch.float32)
+        N.check(N.lib().wm_tile_frames_u8(N.ptr(desc_d), len(used), N.ptr(tiles_d), N.ptr(x), n, N.stream_ptr(device)))
+        rec = model.detect(x)["records"]
+        pos = 0
+        for f, t0, t1 in b.segments:
+            staged[f].records.append(rec[pos:pos + t1 - t0])
+            pos += t1 - t0
+        for f in b.completes:
+            staged[f].data = None             # last tile cut: the frame is no longer needed
+        if pending is not None:
+            yield from finish(pending)
+            pending = None
+        if b.completes:
+            offs = [0]
+            for f in b.completes:
+                offs.append(offs[-1] + len(staged[f].origins))
+            recs = torch.cat([r for f in b.completes for r in staged[f].records])
+            org_all = torch.from_numpy(np.array([o for f in b.completes for o in staged[f].origins], dtype=np.int32)).pin_memory()
+            org_d = org_all.to(device, non_blocking=True)
+            for j, f in enumerate(b.completes):
+                staged[f].records = []
+                staged[f].origins_dev = org_d[offs[j]:offs[j + 1]]
+            out = merge_frames(recs, org_d, offs, iou_thr)
+            out["count_host"] = torch.empty(len(b.completes), dtype=torch.int32, pin_memory=True)
+            out["count_host"].copy_(out["det_count"], non_blocking=True)
+            out["ready"] = torch.cuda.Event()
+            out["ready"].record(main)
+            pending = (out, list(b.completes), offs)
+    if pending is not None:
+        yield from finish(pending)
