@@ -29,14 +29,16 @@
 extern "C" {
 #endif
 
-/* 5: wm_frame_desc, wm_tile_frames_u8, wm_merge_frames_scratch_bytes, wm_merge_frames_nms (many frames of any size);
+/* 6: wm_resample_u8, wm_scaled_size (survey frames resampled to the model's training scale before tiling); nothing
+ *    else changed.
+ * 5: wm_frame_desc, wm_tile_frames_u8, wm_merge_frames_scratch_bytes, wm_merge_frames_nms (many frames of any size);
  *    nothing else changed.
  * 3 (round 3, second half): wm_op_encoder_attention_qkv added; nothing else changed.
  * 2 (round 3): wm_config.fp8_gemms; wm_debug_saturation_*; wm_op_layernorm rejects WM_PREC_FP8 with an fp32 output;
  * wm_profile_read no longer reports the fused-LayerNorm time-out (wm_forward / wm_encoder_forward do); precision value 2
  * (fp8), WM_FLAG_MERGED and a NULL handle in wm_postprocess_nms date from round 2.  The Python binding refuses a library
  * whose wm_abi_version() differs from the value it was written for. */
-#define WM_ABI_VERSION 5
+#define WM_ABI_VERSION 6
 
 /* operand type of the transformer blocks' MFMA GEMMs / attention (accumulation, residual stream, LayerNorm
  * statistics, softmax and the whole decoder are fp32; the stem, the HFC adaptor and the neck -- 2.9 % of the
@@ -216,6 +218,20 @@ int64_t wm_merge_frames_scratch_bytes(int n_tiles);    /* <0 on error */
 int wm_merge_frames_nms(const wm_box_record* records_dev, const int32_t* origins_dev, const int32_t* frame_tile_offsets,
                         int n_frames, float iou_thr, void* scratch_dev, int64_t scratch_bytes, wm_box_record* merged_dev,
                         wm_box_record* det_dev, int32_t* det_tile_dev, int32_t* det_count_dev, void* stream);
+
+/* Survey resampling (tiling.detect_frames(scale=..., resize=...)): a frame brought to the scale the checkpoint was trained
+ * at (the val transform's long side of 768, dataloader_coco.py:288) before it is tiled.
+ * wm_resample_u8: in_dev [height][width][3] uint8 -> out_dev [out_height][out_width][3] uint8, any size to any size (down
+ * and up), with the 8-bit arithmetic of wm_preprocess_u8_resized = Pillow's ImagingResample bilinear filter: 22-bit
+ * fixed-point coefficients, horizontal pass into an 8-bit intermediate, then the vertical pass, clip8((acc + 2^21) >> 22);
+ * bit-exact with PIL.Image.resize(..., BILINEAR).  A pass whose size does not change is the identity (Pillow skips it).
+ * Sides 1..65536; buffers must not overlap.  Coefficient tables are cached per (device, stream) for the last 8 geometries
+ * and uploaded on the stream (a new geometry does not block the host); the intermediate image is scratch per (device,
+ * stream), so calls on different streams may overlap.
+ * wm_scaled_size: (out_h, out_w) = (max(1, floor(height * scale + 0.5)), the same for width), in double; scale positive
+ * and finite, result sides <= 65536.  Host only. */
+int wm_resample_u8(const uint8_t* in_dev, int height, int width, uint8_t* out_dev, int out_height, int out_width, void* stream);
+int wm_scaled_size(int height, int width, double scale, int* out_h, int* out_w);
 
 /* ---- intermediate taps (parity tests) -------------------------------------
  * Copies the fp32 token stream (B,64,64,embed_dim) as it stood after the patch embed + pos_embed

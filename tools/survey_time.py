@@ -3,6 +3,13 @@
   python tools/survey_time.py rate  [--model vit_h] [--batch 16]
       tiles/s of detect_frames over a mixed survey (8 x 6000x4000, 8 x 3648x5472, 1 x 20000x15000) with device-resident
       frames and with host frames, against model.detect on resident tiles at the same batch, in one process.
+  python tools/survey_time.py rate --resize 768 768 | --scale 0.25  [--repeat 8]
+      the same survey resampled first (detect_frames(resize=...) / (scale=...)), --repeat times over; the resident
+      baseline runs model.detect on the same batch sizes with the tiles' content extents as target sizes, and frames/s
+      are printed next to tiles/s.
+  python tools/survey_time.py resample [--reps 20]
+      wm_resample_u8 of a 6000 x 4000 frame to 768 x 512 and to 3000 x 2000; run under `rocprofv3 --kernel-trace --stats`
+      for the per-kernel times; the algorithmic bytes of each pass are printed.
   python tools/survey_time.py merge [--reps 20]
       synthetic per-tile records, old (wm_merge_tiles_nms) and new (wm_merge_frames_nms) merge at 35 tiles, new at 391;
       run under `rocprofv3 --kernel-trace --stats` for the per-kernel times (wall times printed here include the launch).
@@ -39,17 +46,31 @@ def rate(args):
     g = torch.Generator(device=dev).manual_seed(0)
     dframes = [torch.randint(0, 256, (h, w, 3), dtype=torch.uint8, device=dev, generator=g) for h, w in SURVEY]
     hframes = [f.cpu().numpy() for f in dframes]
-    n_tiles = sum(len(tiling.tile_origins(h, w)) for h, w in SURVEY)
+    shapes = SURVEY * args.repeat
+    dframes, hframes = dframes * args.repeat, hframes * args.repeat
+    resampling = args.scale is not None or args.resize is not None
+    kw = dict(scale=args.scale, resize=tuple(args.resize) if args.resize else None) if resampling else {}
+    sizes = [tiling.resampled_size(i, h, w, **kw) for i, (h, w) in enumerate(shapes)] if resampling else shapes
+    origins = [tiling.tile_origins(h, w) for h, w in sizes]
+    n_tiles = sum(len(o) for o in origins)
     x = tiling.frame_to_tiles(dframes[0], torch.tensor(tiling.tile_origins(4000, 6000)[:args.batch], dtype=torch.int32))
     n_batches = -(-n_tiles // args.batch)
+    if resampling:                            # the survey's own batch sizes and content-extent target sizes
+        ext = torch.tensor([(min(1024, w - x0), min(1024, h - y0)) for (h, w), org in zip(sizes, origins) for y0, x0 in org],
+                           dtype=torch.float32, device=dev)
+        batches = [(x[:min(args.batch, n_tiles - i)], ext[i:i + args.batch]) for i in range(0, n_tiles, args.batch)]
 
     def resident():
+        if resampling:
+            for xb, tb in batches:
+                m.detect(xb, tb)
+            return
         for _ in range(n_batches):
             m.detect(x)
 
     def survey(frames):
         def run():
-            for _ in tiling.detect_frames(m, frames, batch=args.batch):
+            for _ in tiling.detect_frames(m, frames, batch=args.batch, **kw):
                 pass
         return run
 
@@ -64,12 +85,36 @@ def rate(args):
             torch.cuda.synchronize()
             dt = time.perf_counter() - t
             best = dt if best is None else min(best, dt)
-        res[name] = n_batches * args.batch / best if name == "resident_tiles" else n_tiles / best
+        res[name] = (n_tiles if resampling or name != "resident_tiles" else n_batches * args.batch) / best
+        if resampling:
+            res[name.split("_")[0] + "_frames_per_s"] = len(shapes) / best
         print(f"{name}: {res[name]:.2f} tiles/s (best of {args.reps}, {best:.3f} s)", flush=True)
     res["device_over_resident"] = res["device_frames"] / res["resident_tiles"]
     res["host_over_resident"] = res["host_frames"] / res["resident_tiles"]
-    print(json.dumps({"survey_tiles": n_tiles, "frames": len(SURVEY), "model": args.model, "precision": args.prec, "batch": args.batch,
-                      **{k: round(v, 4) for k, v in res.items()}}))
+    extra = {"scale": args.scale, "resize": args.resize} if resampling else {}
+    print(json.dumps({"survey_tiles": n_tiles, "frames": len(shapes), "model": args.model, "precision": args.prec, "batch": args.batch,
+                      **extra, **{k: round(v, 4) for k, v in res.items()}}))
+
+
+def resample(args):
+    from wildlifemapper_amd import preprocess
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    f = torch.randint(0, 256, (4000, 6000, 3), dtype=torch.uint8, device=dev, generator=g)
+    out = {}
+    for oh, ow in [(512, 768), (2000, 3000)]:
+        preprocess.resample_u8(f, (oh, ow))
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for _ in range(args.reps):
+            preprocess.resample_u8(f, (oh, ow))
+        torch.cuda.synchronize()
+        key = f"{ow}x{oh}"
+        out[f"{key}_ms_wall"] = round((time.perf_counter() - t) / args.reps * 1e3, 4)
+        # horizontal pass: H*W*3 read, H*ow*3 written; vertical pass: H*ow*3 read, oh*ow*3 written
+        out[f"{key}_h_bytes"] = 4000 * 6000 * 3 + 4000 * ow * 3
+        out[f"{key}_v_bytes"] = 4000 * ow * 3 + oh * ow * 3
+    print(json.dumps(out))
 
 
 def synth_records(H, W, rng, p_cand=0.1):
@@ -119,13 +164,17 @@ def merge(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=("rate", "merge"))
+    ap.add_argument("mode", choices=("rate", "merge", "resample"))
     ap.add_argument("--model", default="vit_h")
     ap.add_argument("--prec", default="fp16")
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--scale", type=float, default=None, help="rate: resample every frame by this factor first")
+    ap.add_argument("--resize", type=int, nargs=2, default=None, metavar=("SIZE", "MAX_SIZE"),
+                    help="rate: resample every frame to the val transform's geometry first, e.g. 768 768")
+    ap.add_argument("--repeat", type=int, default=1, help="rate: the survey this many times over")
     args = ap.parse_args()
-    rate(args) if args.mode == "rate" else merge(args)
+    {"rate": rate, "merge": merge, "resample": resample}[args.mode](args)
 
 
 if __name__ == "__main__":

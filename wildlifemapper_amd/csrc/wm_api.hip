@@ -29,6 +29,7 @@
 #include "gemm32.h"
 #include "gemm8.h"
 #include "misc_kernels.h"
+#include "resample_kernels.h"
 #include "survey_kernels.h"
 #include "wm_common.h"
 
@@ -2307,6 +2308,162 @@ extern "C" int wm_preprocess_u8_resized(const uint8_t* img_dev, float* out_dev, 
         hipLaunchKernelGGL(resize_v_normalize_kernel, dim3(grid_for((int64_t)batch * 1024 * 1024)), dim3(256), 0, s, (const unsigned char*)tmp.p, out_dev,
                            (const int*)pl.by, (const int*)pl.ky, pl.ksy, batch, height, ow, oh);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- survey resampling: any size -> any size, uint8 HWC (PIL bilinear semantics) ----
+namespace {
+
+constexpr int RESAMPLE_MAX_SIDE = 65536;       // the merge's fp32 frame coordinates keep sub-0.01 px resolution up to here
+constexpr int RESAMPLE_PLAN_SLOTS = 8;         // coefficient tables cached per (device, stream), least recently used evicted
+
+// One geometry's tables, both axes in one device buffer (bx, kx, by, ky; an unchanged axis has none), uploaded on the
+// caller's stream from a pinned copy, so a new geometry neither allocates nor blocks the host: a slot is refilled only
+// after the event of its last upload, RESAMPLE_PLAN_SLOTS geometries ago, and the stream orders the device buffer's
+// overwrite after every kernel that read it.
+struct ResampleSlot {
+    std::array<int, 4> key{0, 0, 0, 0};        // (h, w, oh, ow); h == 0: empty
+    int ksx = 0, ksy = 0;
+    size_t off_kx = 0, off_by = 0, off_ky = 0; // in ints; bx at 0
+    int* dev = nullptr;
+    int* host = nullptr;
+    size_t cap = 0;                            // ints of dev and host
+    hipEvent_t copied = nullptr;               // recorded after the upload out of `host`
+    bool fast_h = false;                       // horizontal pass on resample_h_cols_kernel
+    int opt = 1, lds_h = 0;
+    uint64_t used = 0;
+};
+struct ResampleStreamState {
+    ResampleSlot slot[RESAMPLE_PLAN_SLOTS];
+    ResizeTmp tmp;                             // the horizontally resampled image
+    uint64_t clock = 0;
+};
+std::map<std::pair<int, hipStream_t>, ResampleStreamState> g_resample;
+
+// the column-blocked horizontal kernel: <= 20 taps, and the input span of the widest block of 256 * opt columns fits LDS
+void resample_h_geometry(const std::vector<int>& b, int ow, int ks, ResampleSlot& sl) {
+    sl.opt = std::min(4, (ow + 255) / 256);
+    sl.fast_h = false;
+    if (ks > 20) return;
+    for (int x = 1; x < ow; ++x)
+        if (b[2 * x] < b[2 * x - 2] || b[2 * x] + b[2 * x + 1] < b[2 * x - 2] + b[2 * x - 1]) return;
+    int span = 0;
+    for (int c0 = 0; c0 < ow; c0 += 256 * sl.opt) {
+        const int c1 = std::min(c0 + 256 * sl.opt, ow) - 1;
+        span = std::max(span, b[2 * c1] + b[2 * c1 + 1] - b[2 * c0]);
+    }
+    sl.lds_h = (span * 3 + 3 + 3) / 4 * 4 + 64;     // span + alignment shift, + slack for the zero-coefficient taps (KMAX * 3 bytes)
+    sl.fast_h = sl.lds_h <= 64 * 1024;
+}
+
+int resample_plan(ResampleStreamState& st, int h, int w, int oh, int ow, hipStream_t s, ResampleSlot** out) {
+    const std::array<int, 4> key{h, w, oh, ow};
+    ResampleSlot* sl = &st.slot[0];
+    for (ResampleSlot& c : st.slot) {
+        if (c.key == key) { c.used = ++st.clock; *out = &c; return 0; }
+        if (c.used < sl->used) sl = &c;
+    }
+    if (sl->copied) HIP_TRY(hipEventSynchronize(sl->copied));
+    else HIP_TRY(hipEventCreateWithFlags(&sl->copied, hipEventDisableTiming));
+    std::vector<int> bx, kx, by, ky;
+    sl->ksx = sl->ksy = 0;
+    if (ow != w) resize_coeffs(w, ow, bx, kx, sl->ksx);
+    if (oh != h) resize_coeffs(h, oh, by, ky, sl->ksy);
+    sl->off_kx = bx.size();
+    sl->off_by = sl->off_kx + kx.size();
+    sl->off_ky = sl->off_by + by.size();
+    const size_t total = sl->off_ky + ky.size();
+    sl->key = {0, 0, 0, 0};
+    if (total > sl->cap) {
+        if (sl->dev) HIP_TRY(hipFree(sl->dev));            // hipFree synchronises the device: no kernel still reads the old tables
+        if (sl->host) HIP_TRY(hipHostFree(sl->host));
+        sl->dev = nullptr; sl->host = nullptr; sl->cap = 0;
+        HIP_TRY(hipMalloc((void**)&sl->dev, total * 4));
+        HIP_TRY(hipHostMalloc((void**)&sl->host, total * 4, hipHostMallocDefault));
+        sl->cap = total;
+    }
+    if (!bx.empty()) memcpy(sl->host, bx.data(), bx.size() * 4);
+    if (!kx.empty()) memcpy(sl->host + sl->off_kx, kx.data(), kx.size() * 4);
+    if (!by.empty()) memcpy(sl->host + sl->off_by, by.data(), by.size() * 4);
+    if (!ky.empty()) memcpy(sl->host + sl->off_ky, ky.data(), ky.size() * 4);
+    if (total) HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, total * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(sl->copied, s));
+    if (ow != w) resample_h_geometry(bx, ow, sl->ksx, *sl);
+    sl->key = key;
+    sl->used = ++st.clock;
+    *out = sl;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int wm_scaled_size(int height, int width, double scale, int* out_h, int* out_w) {
+    if (!out_h || !out_w) return fail("wm_scaled_size: null output");
+    if (height < 1 || width < 1 || height > RESAMPLE_MAX_SIDE || width > RESAMPLE_MAX_SIDE)
+        return fail("wm_scaled_size: frame %dx%d outside 1..%d", height, width, RESAMPLE_MAX_SIDE);
+    if (!(scale > 0.0) || !std::isfinite(scale)) return fail("wm_scaled_size: scale %g is not a positive finite number", scale);
+    const double oh = std::max(1.0, std::floor(height * scale + 0.5)), ow = std::max(1.0, std::floor(width * scale + 0.5));
+    if (oh > RESAMPLE_MAX_SIDE || ow > RESAMPLE_MAX_SIDE)
+        return fail("wm_scaled_size: %dx%d at scale %g exceeds %d", height, width, scale, RESAMPLE_MAX_SIDE);
+    *out_h = (int)oh;
+    *out_w = (int)ow;
+    return 0;
+}
+
+extern "C" int wm_resample_u8(const uint8_t* in_dev, int height, int width, uint8_t* out_dev, int out_height, int out_width,
+                              void* stream) {
+    if (!in_dev || !out_dev) return fail("wm_resample_u8: null buffer");
+    for (int v : {height, width, out_height, out_width})
+        if (v < 1 || v > RESAMPLE_MAX_SIDE)
+            return fail("wm_resample_u8: %dx%d -> %dx%d, sides must be in 1..%d", height, width, out_height, out_width, RESAMPLE_MAX_SIDE);
+    hipStream_t s = (hipStream_t)stream;
+    if (height == out_height && width == out_width) {                  // both of Pillow's passes skipped
+        HIP_TRY(hipMemcpyAsync(out_dev, in_dev, (size_t)height * width * 3, hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_dev_mu);
+    ResampleStreamState& st = g_resample[{dev, s}];
+    ResampleSlot* pl = nullptr;
+    WM_TRY(resample_plan(st, height, width, out_height, out_width, s, &pl));
+    const unsigned char* src = in_dev;
+    if (out_width != width) {
+        unsigned char* dst = out_dev;                                  // no vertical pass: straight into the output
+        if (out_height != height) {
+            const size_t need = (size_t)height * out_width * 3;
+            if (need > st.tmp.bytes) {
+                if (st.tmp.p) HIP_TRY(hipFree(st.tmp.p));              // hipFree synchronises the device
+                st.tmp.p = nullptr; st.tmp.bytes = 0;
+                HIP_TRY(hipMalloc((void**)&st.tmp.p, need));
+                st.tmp.bytes = need;
+            }
+            dst = st.tmp.p;
+        }
+        const int* bx = pl->dev;
+        const int* kx = pl->dev + pl->off_kx;
+        if (pl->fast_h) {
+            const int rpb = std::max(4, std::min(16, height / (256 * 8)));
+            const dim3 grid((unsigned)((height + rpb - 1) / rpb), (unsigned)((out_width + 256 * pl->opt - 1) / (256 * pl->opt)));
+#define WM_RS(KM, OP) hipLaunchKernelGGL((resample_h_cols_kernel<KM, OP>), grid, dim3(256), pl->lds_h, s, in_dev, dst, bx, kx, pl->ksx, height, \
+                                         width, out_width, rpb)
+            const int opt = pl->opt;
+            if (pl->ksx <= 4) { if (opt <= 1) WM_RS(4, 1); else if (opt <= 2) WM_RS(4, 2); else if (opt <= 3) WM_RS(4, 3); else WM_RS(4, 4); }
+            else if (pl->ksx <= 12) { if (opt <= 1) WM_RS(12, 1); else if (opt <= 2) WM_RS(12, 2); else if (opt <= 3) WM_RS(12, 3); else WM_RS(12, 4); }
+            else { if (opt <= 1) WM_RS(20, 1); else if (opt <= 2) WM_RS(20, 2); else if (opt <= 3) WM_RS(20, 3); else WM_RS(20, 4); }
+#undef WM_RS
+        } else {                                                       // > 20 taps (scale below ~0.1): one thread per output pixel
+            hipLaunchKernelGGL(resize_h_u8_kernel, dim3(grid_for((int64_t)height * out_width)), dim3(256), 0, s, in_dev, dst, bx, kx, pl->ksx,
+                               1, height, width, out_width);
+        }
+        HIP_TRY(hipGetLastError());
+        src = dst;
+    }
+    if (out_height != height) {
+        hipLaunchKernelGGL(resample_v_u8_kernel, dim3((unsigned)out_height), dim3(256), 0, s, src, out_dev, (const int*)(pl->dev + pl->off_by),
+                           (const int*)(pl->dev + pl->off_ky), pl->ksy, (int64_t)out_width * 3);
+        HIP_TRY(hipGetLastError());
+    }
     return 0;
 }
 

@@ -31,3 +31,24 @@ def tiles_from_u8(images: torch.Tensor, resize=None) -> torch.Tensor:
             size, max_size = resize
             N.check(N.lib().wm_preprocess_u8_resized(N.ptr(images), N.ptr(out), B, h, w, int(size), int(max_size or 0), N.stream_ptr(images.device)))
     return out
+
+
+def scaled_size(height: int, width: int, scale: float):
+    """(oh, ow) = (max(1, floor(height * scale + 0.5)), the same for width), in double (wm_scaled_size; host-only call)."""
+    import ctypes as C
+    oh, ow = C.c_int(), C.c_int()
+    N.check(N.lib().wm_scaled_size(int(height), int(width), float(scale), C.byref(oh), C.byref(ow)))
+    return oh.value, ow.value
+
+
+def resample_u8(frame: torch.Tensor, size) -> torch.Tensor:
+    """frame (H,W,3) uint8 on a ROCm device -> (oh,ow,3) uint8 on the same device, size = (oh, ow), any size to any size
+    with PIL's bilinear arithmetic (wm_resample_u8: bit-exact with PIL.Image.resize).  Runs on the current stream."""
+    if not frame.is_cuda or frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[-1] != 3:
+        raise RuntimeError(f"resample_u8: expected an (H,W,3) uint8 ROCm tensor, got {tuple(frame.shape)} {frame.dtype} on {frame.device}")
+    oh, ow = int(size[0]), int(size[1])
+    frame = frame.contiguous()
+    out = torch.empty((oh, ow, 3), device=frame.device, dtype=torch.uint8)
+    with torch.cuda.device(frame.device):
+        N.check(N.lib().wm_resample_u8(N.ptr(frame), frame.shape[0], frame.shape[1], N.ptr(out), oh, ow, N.stream_ptr(frame.device)))
+    return out

@@ -11,10 +11,16 @@ match: the checker is oracle/tiling_oracle.py, a numpy restatement of exactly wh
   * detect_frames: a survey -- many frames of any size, device or host -- with the tiles of consecutive frames packed
     into full batches (wm_tile_frames_u8) and one segmented merge (wm_merge_frames_nms) per batch for the frames it
     completes.  Frames with more than 80 tiles (the single-workgroup merge's limit) go through the segmented merge.
+  * scale= / resize= (detect_frame, detect_frames): opt-in resampling to the scale the checkpoint was trained at -- the
+    reference shrinks whole frames to a long side of 768 (dataloader_coco.py:288) -- with PIL's bilinear arithmetic on the
+    GPU (wm_resample_u8), then the same tile cut and merge in the resampled frame.  Each tile's target size is its content
+    extent (min(1024, ow - x0), min(1024, oh - y0)), the reference's content-normalised boxes (augmentation.py:246-258);
+    returned boxes are mapped back to source pixels.
 Frame coordinates are fp32: a box coordinate keeps a fractional resolution below 0.01 px up to 65536 px (ulp 2**-8).
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, Iterable, Iterator, List, NamedTuple, Tuple
 
 import numpy as np
@@ -22,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import preprocess
 
 
 def _axis_origins(size: int, tile: int, overlap: int) -> List[int]:
@@ -98,9 +105,49 @@ def merge_tile_records(records: torch.Tensor, origins: torch.Tensor, iou_thr: fl
     return out
 
 
+def _check_scale(scale, what: str) -> float:
+    try:
+        s = float(scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: scale {scale!r} is not a number") from None
+    if not (math.isfinite(s) and s > 0.0):
+        raise ValueError(f"{what}: scale {scale!r} must be positive and finite")
+    return s
+
+
+def _check_resample_args(scale, resize, what: str) -> bool:
+    """Validate detect_frame(s)' scale= / resize= before any device work.  True if frames are resampled."""
+    if scale is not None and resize is not None:
+        raise ValueError(f"{what}: scale= and resize= are mutually exclusive")
+    if resize is not None:
+        try:
+            size, max_size = resize
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: resize must be (size, max_size), got {resize!r}") from None
+        if int(size) <= 0 or (max_size is not None and int(max_size) < 0):
+            raise ValueError(f"{what}: resize {resize!r}")
+    if scale is not None and not callable(scale):
+        _check_scale(scale, what)
+    return scale is not None or resize is not None
+
+
+def resampled_size(index: int, height: int, width: int, scale=None, resize=None) -> Tuple[int, int]:
+    """(oh, ow) frame `index` of size height x width is resampled to: resize=(size, max_size) -> preprocess.resized_size
+    (the val transform's geometry; (768, 768) is the reference's); scale -> preprocess.scaled_size, scale a float or a
+    callable (index, height, width) -> float (per-frame ground sampling distance)."""
+    if resize is not None:
+        return preprocess.resized_size(height, width, int(resize[0]), int(resize[1] or 0))
+    s = scale(index, height, width) if callable(scale) else scale
+    return preprocess.scaled_size(height, width, _check_scale(s, f"frame {index}"))
+
+
 @torch.no_grad()
-def detect_frame(model, frame: torch.Tensor, overlap: int = 128, batch: int = 16, iou_thr: float = 0.4) -> Dict[str, torch.Tensor]:
-    """One frame -> merged detections {'boxes' (k,4) frame xyxy, 'scores', 'labels', 'tile'} in merged-NMS order."""
+def detect_frame(model, frame: torch.Tensor, overlap: int = 128, batch: int = 16, iou_thr: float = 0.4, scale=None,
+                 resize=None) -> Dict[str, torch.Tensor]:
+    """One frame -> merged detections {'boxes' (k,4) frame xyxy, 'scores', 'labels', 'tile'} in merged-NMS order.
+    scale= / resize=: the frame is resampled first, as in detect_frames (a callable scale is called with index 0)."""
+    if _check_resample_args(scale, resize, "detect_frame"):
+        return next(detect_frames(model, [frame], overlap, batch, iou_thr, scale=scale, resize=resize))
     from .engine import split_records
     H, W = int(frame.shape[0]), int(frame.shape[1])
     org = torch.tensor(tile_origins(H, W, 1024, overlap), dtype=torch.int32, device=frame.device)
@@ -152,12 +199,13 @@ def plan_batches(tile_counts: Iterable[int], batch: int) -> Iterator[SurveyBatch
 
 
 class _Frame:
-    __slots__ = ("data", "height", "width", "origins", "origins_dev", "ready", "records")
+    __slots__ = ("data", "height", "width", "origins", "origins_dev", "ready", "records", "scale_xy")
 
-    def __init__(self, data, height, width, origins, ready):
+    def __init__(self, data, height, width, origins, ready, scale_xy=None):
         self.data, self.height, self.width, self.origins, self.ready = data, height, width, origins, ready
         self.records: List[torch.Tensor] = []
         self.origins_dev = None
+        self.scale_xy = scale_xy              # resampled mode: (sx, sy) = float32(W / ow), float32(H / oh); else None
 
 
 def _as_frame_array(frame, i: int, device: torch.device):
@@ -178,22 +226,55 @@ def _as_frame_array(frame, i: int, device: torch.device):
 
 
 @torch.no_grad()
-def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, iou_thr: float = 0.4) -> Iterator[Dict[str, torch.Tensor]]:
+def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, iou_thr: float = 0.4, scale=None,
+                  resize=None) -> Iterator[Dict[str, torch.Tensor]]:
     """Survey of frames of any sizes ((H,W,3) uint8 ROCm tensors, CPU tensors or numpy arrays) -> one dict per frame, in
     input order, with detect_frame's keys and values.  Tiles of consecutive frames fill batches of `batch` (plan_batches);
     after each batch one wm_merge_frames_nms covers the frames it completed.  Host frames go through one pinned staging
     buffer (grown to the largest frame) and a copy stream: the next frame's upload overlaps the current batches, ordered
     by events.  A frame's result is yielded once the batch after its merge is queued, so the host never waits on the
-    batch it just launched."""
+    batch it just launched.
+
+    scale= (a float, or a callable (frame index, H, W) -> float) or resize=(size, max_size), mutually exclusive: each frame
+    is first resampled to resampled_size(...) on the GPU (wm_resample_u8; device frames on the current stream, host frames
+    on the copy stream after their upload) and tiled in the resampled frame, each tile's target size its content extent.
+    'boxes' are then in source-frame pixels (merged boxes * (sx, sy) in fp32, sx = float32(W / ow), sy = float32(H / oh));
+    'records' and 'origins' stay in resampled-frame pixels, and the dict gains 'resampled_size' = (oh, ow)."""
     from .engine import split_records
     import ctypes as C
     if batch <= 0:
         raise ValueError(f"detect_frames: batch {batch}")
+    resampling = _check_resample_args(scale, resize, "detect_frames")
     device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
     staged: Dict[int, _Frame] = {}
     pinned = [None, None]                     # staging buffer, event of the last copy out of it
     copy = [None]                             # copy stream, made for the first host frame
     it = iter(frames)
+
+    def upload(h, H: int, W: int, resample_to=None):
+        """Host frame -> device frame through the pinned staging buffer on the copy stream; resample_to=(oh, ow): the
+        upload is resampled there too, after the copy.  Returns the device frame and the event its use waits for."""
+        nbytes = H * W * 3
+        if pinned[1] is not None:
+            pinned[1].synchronize()           # the previous upload has left the staging buffer
+        if pinned[0] is None or pinned[0].numel() < nbytes:
+            pinned[0] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        buf = pinned[0][:nbytes]
+        buf.copy_(h.view(-1))
+        if copy[0] is None:
+            copy[0] = torch.cuda.Stream(device)
+        with torch.cuda.stream(copy[0]):
+            d = torch.empty((H, W, 3), dtype=torch.uint8, device=device)
+            d.view(-1).copy_(buf, non_blocking=True)
+            ready = uploaded = torch.cuda.Event()
+            uploaded.record(copy[0])
+            if resample_to is not None:       # the uploaded source goes once its resample is queued
+                d = preprocess.resample_u8(d, resample_to)
+                ready = torch.cuda.Event()
+                ready.record(copy[0])
+        d.record_stream(torch.cuda.current_stream(device))
+        pinned[1] = uploaded
+        return d, ready
 
     def stage(i: int) -> bool:
         try:
@@ -201,29 +282,25 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
         except StopIteration:
             return False
         d, h = _as_frame_array(fr, i, device)
-        if device is None:
-            raise RuntimeError("detect_frames: no ROCm device (there is no CPU fallback in wildlifemapper_amd)")
         src = d if d is not None else h
         H, W = int(src.shape[0]), int(src.shape[1])
+        if resampling:
+            oh, ow = resampled_size(i, H, W, scale, resize)          # a bad per-frame scale raises before any device work
+        if device is None:
+            raise RuntimeError("detect_frames: no ROCm device (there is no CPU fallback in wildlifemapper_amd)")
+        if resampling:                        # the resampled frame is what gets tiled; a caller's device frame is only read
+            size = None if (oh, ow) == (H, W) else (oh, ow)
+            if d is None:
+                d, ready = upload(h, H, W, size)
+            else:
+                d, ready = (d if size is None else preprocess.resample_u8(d, size)), None
+            sxy = (float(np.float32(W / ow)), float(np.float32(H / oh)))
+            staged[i] = _Frame(d, oh, ow, tile_origins(oh, ow, 1024, overlap), ready, sxy)
+            return True
         org = tile_origins(H, W, 1024, overlap)
         ready = None
         if d is None:
-            nbytes = H * W * 3
-            if pinned[1] is not None:
-                pinned[1].synchronize()       # the previous upload has left the staging buffer
-            if pinned[0] is None or pinned[0].numel() < nbytes:
-                pinned[0] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-            buf = pinned[0][:nbytes]
-            buf.copy_(h.view(-1))
-            if copy[0] is None:
-                copy[0] = torch.cuda.Stream(device)
-            with torch.cuda.stream(copy[0]):
-                d = torch.empty((H, W, 3), dtype=torch.uint8, device=device)
-                d.view(-1).copy_(buf, non_blocking=True)
-                ready = torch.cuda.Event()
-                ready.record(copy[0])
-            d.record_stream(torch.cuda.current_stream(device))
-            pinned[1] = ready
+            d, ready = upload(h, H, W)
         staged[i] = _Frame(d, H, W, org, ready)
         return True
 
@@ -245,9 +322,17 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
             s0, n = offs[j] * N.NUM_QUERIES, offs[j + 1] - offs[j]
             k = counts[j]
             det = split_records(out["det"][s0:s0 + k].view(k, 1, 8))
-            yield {"boxes": det["boxes"].reshape(k, 4), "scores": det["scores"].reshape(k), "labels": det["labels"].reshape(k),
+            res = {"boxes": det["boxes"].reshape(k, 4), "scores": det["scores"].reshape(k), "labels": det["labels"].reshape(k),
                    "tile": out["det_tile"][s0:s0 + k].to(torch.int64), "origins": fr.origins_dev,
                    "records": out["merged"][offs[j]:offs[j] + n]}
+            if fr.scale_xy is not None:       # resampled-frame pixels -> source-frame pixels, one fp32 multiply per coordinate
+                b = res["boxes"]
+                src = torch.empty_like(b)
+                src[:, 0::2] = b[:, 0::2] * fr.scale_xy[0]
+                src[:, 1::2] = b[:, 1::2] * fr.scale_xy[1]
+                res["boxes"] = src
+                res["resampled_size"] = (fr.height, fr.width)
+            yield res
 
     pending = None
     main = None
@@ -271,7 +356,12 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
         n = tiles.shape[0]
         x = torch.empty((n, 3, 1024, 1024), device=device, dtype=torch.float32)
         N.check(N.lib().wm_tile_frames_u8(N.ptr(desc_d), len(used), N.ptr(tiles_d), N.ptr(x), n, N.stream_ptr(device)))
-        rec = model.detect(x)["records"]
+        if resampling:                        # each tile's content extent (w, h): boxes normalised to the content
+            ext = np.array([(min(1024, staged[f].width - o[1]), min(1024, staged[f].height - o[0]))
+                            for f, t0, t1 in b.segments for o in staged[f].origins[t0:t1]], dtype=np.float32)
+            rec = model.detect(x, torch.from_numpy(ext).pin_memory().to(device, non_blocking=True))["records"]
+        else:
+            rec = model.detect(x)["records"]
         pos = 0
         for f, t0, t1 in b.segments:
             staged[f].records.append(rec[pos:pos + t1 - t0])
