@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-/* 6: wm_resample_u8, wm_scaled_size (survey frames resampled to the model's training scale before tiling); nothing
+/* 7: WM_GEMM32_PRESPLIT for wm_op_gemm32; the split fp32 GEMM carries its lo parts scaled by 2^11 (no change in its
+ *    contract beyond accuracy); nothing else changed.
+ * 6: wm_resample_u8, wm_scaled_size (survey frames resampled to the model's training scale before tiling); nothing
  *    else changed.
  * 5: wm_frame_desc, wm_tile_frames_u8, wm_merge_frames_scratch_bytes, wm_merge_frames_nms (many frames of any size);
  *    nothing else changed.
@@ -38,7 +40,7 @@ extern "C" {
  * wm_profile_read no longer reports the fused-LayerNorm time-out (wm_forward / wm_encoder_forward do); precision value 2
  * (fp8), WM_FLAG_MERGED and a NULL handle in wm_postprocess_nms date from round 2.  The Python binding refuses a library
  * whose wm_abi_version() differs from the value it was written for. */
-#define WM_ABI_VERSION 6
+#define WM_ABI_VERSION 7
 
 /* operand type of the transformer blocks' MFMA GEMMs / attention (accumulation, residual stream, LayerNorm
  * statistics, softmax and the whole decoder are fp32; the stem, the HFC adaptor and the neck -- 2.9 % of the
@@ -414,9 +416,14 @@ int wm_op_patch_embed16(const void* img16_dev, const void* w_dev, const float* b
                         int batch, int n_out, int c_in, int precision, void* stream);
 
 /* fp32 GEMM, fp32 in and out, same contract (act 3 = sigmoid): on the fp32-input MFMA, or with act | WM_GEMM32_SPLIT in the form the
- * decoder runs since round 4: every operand value split into two fp16 numbers (hi + lo = x to 2^-22), three 16-bit MFMAs per product
- * (the lo x lo term dropped), fp32 accumulate: rel-L2 3e-7 against float64 (the fp32 MFMA: 1e-7).  K % 32 == 0 for that form. */
+ * decoder runs since round 4: every operand value split into two fp16 numbers (hi + 2^-11 lo = x to 2^-22 |x| + 2^-36), three 16-bit
+ * MFMAs per product (the lo x lo term dropped), fp32 accumulate: rel-L2 3e-7 against float64 (the fp32 MFMA: 1e-7); the error of
+ * each row of A and column of W stays below 2e-7 of that row / column of |A| |W|^T down to rows of size 1e-4, and below 2e-6 down
+ * to 1e-5 (tests/test_gpu_ranges.py).  K % 32 == 0 for that form. */
 #define WM_GEMM32_SPLIT 0x100
+/* act | WM_GEMM32_PRESPLIT: the same split form as the decoder inside wm_forward runs it, W split once into fp16 planes
+ * (split_w32_kernel, into a scratch buffer of the stream) and read pre-split by the GEMM.  Exclusive with WM_GEMM32_SPLIT. */
+#define WM_GEMM32_PRESPLIT 0x200
 int wm_op_gemm32(const float* a_dev, const float* w_dev, const float* bias_dev,
                  const float* residual_dev, float* out_dev, int M, int N, int K, int act, void* stream);
 

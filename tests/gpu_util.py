@@ -5,6 +5,7 @@ import ctypes as C
 
 import torch
 
+from oracle import wm_oracle as O          # checker only
 from wildlifemapper_amd import _native as N
 
 PRECS = {"bf16": (N.PREC_BF16, torch.bfloat16), "fp16": (N.PREC_FP16, torch.float16)}
@@ -26,6 +27,11 @@ def rel_l2(a: torch.Tensor, b: torch.Tensor) -> float:
 def max_rel(a: torch.Tensor, b: torch.Tensor) -> float:
     a, b = a.double().cpu(), b.double().cpu()
     return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
+
+
+def rnd16(t: torch.Tensor, prec: str, dtype=torch.float32) -> torch.Tensor:
+    """Round to the 16-bit type of `prec`, then widen to `dtype`."""
+    return t.to(PRECS[prec][1]).to(dtype)
 
 
 def to16(x: torch.Tensor, prec: str) -> torch.Tensor:
@@ -245,6 +251,35 @@ def encoder_attention(qkv16, qkv_bias, rel_h, rel_w, batch, heads, hd, window, p
     N.check(N.lib().wm_op_encoder_attention(N.ptr(qkv16), N.ptr(qkv_bias), N.ptr(rel_h), N.ptr(rel_w), N.ptr(out),
                                             batch, heads, hd, window, code, sp()))
     return out
+
+
+def ref_encoder_attention(qkv, bias16, rel_h, rel_w, B, heads, hd, window, prec, dtype=torch.float32):
+    """Evaluation of image_encoder.py:246-262 (+ window partition :190-199) in `dtype` from a 16-bit-rounded
+    packed qkv; padded tokens carry the (16-bit rounded) qkv bias, P is rounded before P.V like the kernel."""
+    D = heads * hd
+    x = qkv.to(dtype).reshape(B, 64, 64, 3 * D)
+    bias16 = bias16.to(dtype)
+    if window:
+        xw, n = O.to_windows(x - bias16, window)
+        xw = xw + bias16
+        S = window
+    else:
+        xw, n, S = x, 0, 64
+    Bp = xw.shape[0]
+    t = xw.reshape(Bp, S * S, 3, heads, hd).permute(2, 0, 3, 1, 4)
+    q, k, v = t[0], t[1], t[2]
+    Rh = O.rel_pos_table(S, rnd16(rel_h, prec, dtype))
+    Rw = O.rel_pos_table(S, rnd16(rel_w, prec, dtype))
+    a = (q @ k.transpose(-1, -2)) * (hd ** -0.5)
+    rq = q.reshape(Bp, heads, S, S, hd)
+    rh = torch.einsum("bnhwc,hkc->bnhwk", rq, Rh)
+    rw = torch.einsum("bnhwc,wkc->bnhwk", rq, Rw)
+    a = (a.view(Bp, heads, S, S, S, S) + rh[..., :, None] + rw[..., None, :]).view(Bp, heads, S * S, S * S)
+    p = rnd16(a.softmax(-1), prec, dtype)
+    o = (p @ v).permute(0, 2, 1, 3).reshape(Bp, S, S, D)
+    if window:
+        o = O.from_windows(o, window, n, 64)
+    return o.reshape(B * 4096, D)
 
 
 def mha16(q, k, v, batch, heads, hd, nq, nk, prec="bf16"):

@@ -254,6 +254,41 @@ def test_vit_b_sensitive_profile_fp16(golden_dir):
     assert all(same)
 
 
+def test_vit_b_global_block_with_sunken_own_row_vs_oracle():
+    """A global block whose decomposed rel-pos term sinks every query's own grid row ~240 natural units (q . rel_pos_h[63] with a
+    common q component of ~8 from the qkv bias): for the queries of grid row 0 that row is the first key tile, which once turned
+    their attention rows into NaN (the logits then came out finite but 0.67 rel-L2 off).  Against the CPU oracle run live on the
+    same weights, bf16 mode, with test_vit_l_vs_oracle's checks (measured 4.7e-4)."""
+    m, post = _model("vit_b", "bf16")
+    blk = m.image_encoder.blocks[2]
+    hd = blk.attn.qkv.weight.shape[1] // blk.attn.num_heads
+    touched = [blk.attn.qkv.bias, blk.attn.rel_pos_h]
+    saved = [t.detach().clone() for t in touched]
+    try:
+        with torch.no_grad():
+            blk.attn.qkv.bias[torch.arange(blk.attn.num_heads) * hd] = 8.0
+            blk.attn.rel_pos_h[63, 0] = -30.0
+        m._hub.close()                                                          # a fresh handle: full upload of these weights
+        x = torch.from_numpy(synth.make_batch(3, 1))
+        sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
+        ref = O.model_forward(x, sd, O.OracleCfg.from_model_type("vit_b"))
+        with torch.no_grad():
+            out = m.detect(x.to(G.dev()))
+        assert torch.isfinite(out["pred_logits"]).all() and torch.isfinite(out["pred_boxes"]).all()
+        lerr = G.rel_l2(out["pred_logits"].cpu(), ref["pred_logits"])
+        berr = (out["pred_boxes"].cpu() - ref["pred_boxes"]).abs().max().item()
+        print(f"[vit_b/bf16/sunken own row] logits={lerr:.2e} boxes_maxabs={berr:.2e}")
+        assert lerr < LOGIT_ASSERT["bf16"]["vit_b"], lerr
+        assert berr < 5 * LOGIT_TOL["bf16"], berr
+        det = O.detect(O.postprocess(ref["pred_logits"], ref["pred_boxes"], torch.tensor([[1024, 1024]]))[0])
+        assert _nms_positions(split_records(out["records"].cpu()), 0) == det["nms_index"].tolist()
+    finally:
+        with torch.no_grad():
+            for t, s0 in zip(touched, saved):
+                t.copy_(s0)
+        m._hub.close()
+
+
 # ---------------------------------------------------------------------------
 # drop-in surface
 # ---------------------------------------------------------------------------

@@ -543,32 +543,7 @@ def test_layernorm(C, eps, prec):
 # ---------------------------------------------------------------------------
 # attention
 # ---------------------------------------------------------------------------
-def _ref_encoder_attention(qkv, bias16, rel_h, rel_w, B, heads, hd, window, prec):
-    """fp32 evaluation of image_encoder.py:246-262 (+ window partition :190-199) from a 16-bit-rounded
-    packed qkv; padded tokens carry the (16-bit rounded) qkv bias, P is rounded before P.V like the kernel."""
-    D = heads * hd
-    x = qkv.float().reshape(B, 64, 64, 3 * D)
-    if window:
-        xw, n = O.to_windows(x - bias16, window)
-        xw = xw + bias16
-        S = window
-    else:
-        xw, n, S = x, 0, 64
-    Bp = xw.shape[0]
-    t = xw.reshape(Bp, S * S, 3, heads, hd).permute(2, 0, 3, 1, 4)
-    q, k, v = t[0], t[1], t[2]
-    Rh = O.rel_pos_table(S, _rnd(rel_h, prec))
-    Rw = O.rel_pos_table(S, _rnd(rel_w, prec))
-    a = (q @ k.transpose(-1, -2)) * (hd ** -0.5)
-    rq = q.reshape(Bp, heads, S, S, hd)
-    rh = torch.einsum("bnhwc,hkc->bnhwk", rq, Rh)
-    rw = torch.einsum("bnhwc,wkc->bnhwk", rq, Rw)
-    a = (a.view(Bp, heads, S, S, S, S) + rh[..., :, None] + rw[..., None, :]).view(Bp, heads, S * S, S * S)
-    p = _rnd(a.softmax(-1), prec)
-    o = (p @ v).permute(0, 2, 1, 3).reshape(Bp, S, S, D)
-    if window:
-        o = O.from_windows(o, window, n, 64)
-    return o.reshape(B * 4096, D)
+_ref_encoder_attention = G.ref_encoder_attention
 
 
 @pytest.mark.parametrize("prec", ["bf16", "fp16"])

@@ -22,10 +22,11 @@ FLAG_CONF, FLAG_SCORE, FLAG_NMS, FLAG_MERGED = 1, 2, 4, 8
 CFG_FUSE_LN = 1
 CFG_FOLD_LN = 2
 CFG_FOLD_LN_BF16 = 4
-ABI_VERSION = 6            # include/wm_hip.h WM_ABI_VERSION this binding was written for
+ABI_VERSION = 7            # include/wm_hip.h WM_ABI_VERSION this binding was written for
 FP8_QKV, FP8_PROJ, FP8_MLP, FP8_ALL = 1, 2, 4, 7
 GEMM_W_PACKED, GEMM_A_PACKED, GEMM_OUT_PACKED, LAYOUT_PACKED = 0x1000, 0x2000, 0x4000, 0x100
-GEMM32_SPLIT = 0x100          # wm_op_gemm32: act | GEMM32_SPLIT = the fp16-split form the decoder runs
+GEMM32_SPLIT = 0x100          # wm_op_gemm32: act | GEMM32_SPLIT = the fp16-split form the decoder runs (W split per K-step)
+GEMM32_PRESPLIT = 0x200       # wm_op_gemm32: act | GEMM32_PRESPLIT = the same form with W pre-split once, as inside wm_forward
 SAT_NAMES = ("layernorm_out", "qkv", "attention_out", "mlp_hidden", "last_block_16")
 
 

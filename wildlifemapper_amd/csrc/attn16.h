@@ -186,12 +186,14 @@ __device__ __forceinline__ void softmax_pv(SoftmaxState<AttnGeom<HD>::NDT>& st, 
     }
     if (first || !__all(mx <= RESCALE_THR)) {
         const float d = first ? mx : fmaxf(mx, 0.f);
-        const float alpha = __builtin_amdgcn_exp2f(-d);
-        st.l *= alpha;
+        if (!first) {                                       // at the first tile l and o are still 0, and alpha is inf when the tile's
+            const float alpha = __builtin_amdgcn_exp2f(-d); // maximum is below -128: 0 * inf = nan (the window kernel's form)
+            st.l *= alpha;
 #pragma unroll
-        for (int dt = 0; dt < G::NDT; ++dt)
+            for (int dt = 0; dt < G::NDT; ++dt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) st.o[dt][r] *= alpha;
+                for (int r = 0; r < 16; ++r) st.o[dt][r] *= alpha;
+        }
         st.m += d;
     }
     const float off = tile_bias - st.m;

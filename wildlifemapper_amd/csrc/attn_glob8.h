@@ -417,12 +417,14 @@ __global__ __launch_bounds__(512, 2) void attn_global8_kernel(AttnArgs p) {
         // the reference point st.m moves at the first tile and when a maximum grew past the threshold (attn16.h "Scores")
         if (j == 0 || !__all(mx <= RESCALE_THR)) {
             const float d = j == 0 ? mx : fmaxf(mx, 0.f);
-            const float alpha = __builtin_amdgcn_exp2f(-d);
-            st.l *= alpha;
+            if (j > 0) {                                    // first tile: l and o are still 0, and alpha may be inf (softmax_pv)
+                const float alpha = __builtin_amdgcn_exp2f(-d);
+                st.l *= alpha;
 #pragma unroll
-            for (int dt = 0; dt < G::NDT; ++dt)
+                for (int dt = 0; dt < G::NDT; ++dt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) st.o[dt][r] *= alpha;
+                    for (int r = 0; r < 16; ++r) st.o[dt][r] *= alpha;
+            }
             st.m += d;
             if constexpr (!REL) {
 #pragma unroll

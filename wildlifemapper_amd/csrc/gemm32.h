@@ -85,11 +85,14 @@ __global__ __launch_bounds__(256) void gemm32_kernel(Gemm32Args p) {
 
 // ---------------------------------------------------------------------------
 // The same GEMM on the 16-bit matrix pipe, fp32 in and out (round 4): every fp32 operand value x is split into two fp16 numbers,
-// hi = fp16(x), lo = fp16(x - hi)  (x = hi + lo to 2^-22 |x|), and  A W^T ~= Ah Wh^T + Al Wh^T + Ah Wl^T  (the dropped Al Wl^T is
-// 2^-22 of a product; fp16 x fp16 products are exact in the fp32 accumulator).  Three 32x32x16 MFMAs (96 cycles per 16 of K) stand for
+// hi = fp16(x), lo = fp16((x - hi) 2^11)  (x = hi + 2^-11 lo to 2^-22 |x| + 2^-36), and  A W^T ~= Ah Wh^T + 2^-11 (Al Wh^T + Ah Wl^T)
+// (the dropped Al Wl^T is 2^-22 of a product; fp16 x fp16 products are exact in the fp32 accumulators; the two cross terms have an
+// accumulator of their own, scaled back in the epilogue).  Without the 2^11 the lo part of any |x| < 0.25 lay in fp16's subnormals,
+// whose absolute step 2^-24 bounded x = hi + lo only to 2^-22 |x| + 2^-25: rows of activations of size 1e-3 came out with relative
+// errors up to 3.6e-5, rows of 1e-5 up to 3.5e-3 (tests/test_gpu_ranges.py).  Three 32x32x16 MFMAs (96 cycles per 16 of K) stand for
 // the eight 32x32x2 fp32 MFMAs (512 cycles) of gemm32_kernel; measured error against float64: rel-L2 3e-7 (gemm32_kernel: 1e-7; the
 // test bound for both is 2e-6).  W is scaled by 2^6 before its split (exact; taken back in the epilogue) so that decoder-sized weights
-// (|w| ~ 0.02) keep their lo part out of fp16's subnormals.  W comes pre-split (two fp16 planes made once per weight upload:
+// (|w| ~ 0.02) keep their hi part out of fp16's subnormals.  W comes pre-split (two fp16 planes made once per weight upload:
 // `split_w32_kernel`) or as fp32 (split per K-step like A: the op-level entry).  |A| >= 65504 or |W| >= 1023 leaves fp16's range: the
 // conversions do not clamp, so such a row comes out inf / nan, and the kernels raise the handle's overflow word (wm_stream_overflow)
 // as the fp16 stream's producers do.
@@ -97,6 +100,7 @@ __global__ __launch_bounds__(256) void gemm32_kernel(Gemm32Args p) {
 // (the decoder's token-side calls are 13 x 4 workgroups: the load latency is all there is).
 // ---------------------------------------------------------------------------
 constexpr float G32X3_WSCALE = 64.0f;
+constexpr float G32X3_LOSCALE = 2048.0f;                      // lo = fp16((x - hi) 2^11): |lo| <= |x|, so no new fp16 overflow
 struct Gemm32x3Args {
     const float* A; const float* W; const u16* Whi; const u16* Wlo;      // W (fp32) or (Whi, Wlo)
     const float* bias; const float* residual; float* out;
@@ -112,7 +116,7 @@ __global__ __launch_bounds__(256) void split_w32_kernel(const float* __restrict_
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             h[j] = FP16::from_f32_bounded(v[j]);                 // no clamp: out of range = inf, i.e. a loud result
-            l[j] = FP16::from_f32_bounded(v[j] - FP16::to_f32(h[j]));
+            l[j] = FP16::from_f32_bounded((v[j] - FP16::to_f32(h[j])) * G32X3_LOSCALE);   // x - hi is exact; the scale too
             amax = fmaxf(amax, fabsf(v[j]));
         }
         *(typename FP16::vec4*)(hi + i * 4) = h;
@@ -132,9 +136,9 @@ __global__ __launch_bounds__(256) void gemm32x3_kernel(Gemm32x3Args p) {
     const int m0 = (lid / ntn) * BM, n0 = (lid % ntn) * BN;
     const int lrow = tid >> 2, lcol = (tid & 3) * 8;          // 8 consecutive k per thread and operand
 
-    f32x16 acc;
+    f32x16 acc, accx;                                         // Ah Wh^T; the cross terms Al Wh^T + Ah Wl^T (lo parts carry 2^11)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[r] = accx[r] = 0.f;
     const bool arow = m0 + lrow < p.M, wrow = n0 + lrow < p.N;
     const float* ap = p.A + (size_t)(arow ? m0 + lrow : 0) * p.lda + lcol;
     const size_t woff = (size_t)(wrow ? n0 + lrow : 0) * p.K + lcol;
@@ -158,7 +162,7 @@ __global__ __launch_bounds__(256) void gemm32x3_kernel(Gemm32x3Args p) {
             const float x = (j < 4 ? x0[j] : x1[j - 4]) * scale;
             amax = fmaxf(amax, fabsf(x));
             uh.h[j >> 2][j & 3] = FP16::from_f32_bounded(x);     // no clamp: |x| >= 65520 becomes inf and the row comes out nan / inf
-            ul.h[j >> 2][j & 3] = FP16::from_f32_bounded(x - FP16::to_f32(uh.h[j >> 2][j & 3]));
+            ul.h[j >> 2][j & 3] = FP16::from_f32_bounded((x - FP16::to_f32(uh.h[j >> 2][j & 3])) * G32X3_LOSCALE);
         }
         hi = uh.raw; lo = ul.raw;
     };
@@ -180,8 +184,8 @@ __global__ __launch_bounds__(256) void gemm32x3_kernel(Gemm32x3Args p) {
         for (int ks = 0; ks < 2; ++ks) {
             const typename FP16::vec8 a_hi = *(const typename FP16::vec8*)(sAh + fa + 16 * ks), a_lo = *(const typename FP16::vec8*)(sAl + fa + 16 * ks);
             const typename FP16::vec8 w_hi = *(const typename FP16::vec8*)(sWh + fw + 16 * ks), w_lo = *(const typename FP16::vec8*)(sWl + fw + 16 * ks);
-            acc = FP16::mfma32(a_lo, w_hi, acc);              // the two small terms first
-            acc = FP16::mfma32(a_hi, w_lo, acc);
+            accx = FP16::mfma32(a_lo, w_hi, accx);
+            accx = FP16::mfma32(a_hi, w_lo, accx);
             acc = FP16::mfma32(a_hi, w_hi, acc);
         }
     };
@@ -198,7 +202,7 @@ __global__ __launch_bounds__(256) void gemm32x3_kernel(Gemm32x3Args p) {
     for (int r = 0; r < 16; ++r) {
         const int m = m0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         if (m < p.M) {
-            float v = acc[r] * (1.0f / G32X3_WSCALE) + bv;
+            float v = (acc[r] + accx[r] * (1.0f / G32X3_LOSCALE)) * (1.0f / G32X3_WSCALE) + bv;
             if (p.act == ACT_RELU) v = fmaxf(v, 0.f);
             else if (p.act == ACT_GELU) v = gelu_erf(v);
             else if (p.act == ACT_SIGMOID) v = 1.0f / (1.0f + expf(-v));

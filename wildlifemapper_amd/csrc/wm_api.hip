@@ -707,14 +707,24 @@ unsigned grid_for(int64_t n, int per = 256, unsigned cap = 256 * 16);
 
 // fp32 GEMM (the decoder).  mode: 0 = the engine's choice (the fp16-split form on the 16-bit matrix pipe, gemm32.h gemm32x3_kernel,
 // where K % 32 == 0, with W pre-split once per weight upload; WM_GEMM32_F32=1 keeps the fp32-MFMA kernel: A/B runs), 1 = the fp32-MFMA
-// kernel, 2 = the split form with W split per K-step (op-level entry: no handle to cache planes in)
+// kernel, 2 = the split form with W split per K-step (op-level entry: no handle to cache planes in), 3 = the engine's form without a
+// handle: W split by split_w32_kernel into the stream's scratch planes, then gemm32x3_kernel<true> (op-level entry, WM_GEMM32_PRESPLIT)
 int launch_gemm32(wm_handle* h, hipStream_t s, const float* A, const float* W, const float* bias, const float* res,
                   float* out, int M, int N, int K, int act, int lda = 0, int mode = 0) {
     if (K % 16) return fail("gemm32: K=%d must be a multiple of 16", K);
     static const bool f32_only = getenv("WM_GEMM32_F32") && atoi(getenv("WM_GEMM32_F32")) != 0;
-    if (mode == 2 && K % 32) return fail("gemm32 (split form): K=%d must be a multiple of 32", K);
-    if (mode == 2 || (mode == 0 && h && !f32_only && K % 32 == 0)) {
+    if ((mode == 2 || mode == 3) && K % 32) return fail("gemm32 (split form): K=%d must be a multiple of 32", K);
+    if (mode == 2 || mode == 3 || (mode == 0 && h && !f32_only && K % 32 == 0)) {
         Gemm32x3Args a{A, W, nullptr, nullptr, bias, res, out, M, N, K, act, lda > 0 ? lda : K, h ? h->overflow + 1 : nullptr};
+        if (mode == 3) {                                    // no handle to cache the planes in: the stream's scratch, split on every call
+            const size_t n = (size_t)N * K;                 // K % 32 == 0: n % 4 == 0
+            void* pb = nullptr;
+            WM_TRY(op_scratch(s, 3, n * 4, &pb));
+            u16* hi = (u16*)pb;
+            hipLaunchKernelGGL(split_w32_kernel, dim3(grid_for((int64_t)n / 4)), dim3(256), 0, s, W, hi, hi + n, (int64_t)n / 4, (int*)nullptr);
+            HIP_TRY(hipGetLastError());
+            a.Whi = hi; a.Wlo = hi + n;
+        }
         if (mode == 0) {                                    // the weight's fp16 planes: made at first use, dropped with the weights
             auto it = h->w32x3.find(W);
             if (it == h->w32x3.end()) {
@@ -730,7 +740,7 @@ int launch_gemm32(wm_handle* h, hipStream_t s, const float* A, const float* W, c
         }
         Bracket br(h, s, WM_KCLASS_OTHER, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)M * N) + (mode == 0 ? 4.0 : 4.0) * (double)N * K);
         const dim3 grid(((N + 63) / 64) * ((M + 63) / 64));
-        if (mode == 0) hipLaunchKernelGGL(gemm32x3_kernel<true>, grid, dim3(256), 0, s, a);
+        if (mode == 0 || mode == 3) hipLaunchKernelGGL(gemm32x3_kernel<true>, grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(gemm32x3_kernel<false>, grid, dim3(256), 0, s, a);
         HIP_TRY(hipGetLastError());
         return 0;
@@ -2598,9 +2608,12 @@ extern "C" int wm_op_patch_embed16(const void* img16_dev, const void* w_dev, con
 
 extern "C" int wm_op_gemm32(const float* a_dev, const float* w_dev, const float* bias_dev, const float* residual_dev, float* out_dev,
                             int M, int N, int K, int act, void* stream) {
-    // act & WM_GEMM32_SPLIT: the fp16-split form (gemm32x3_kernel, W split per K-step); otherwise the fp32-MFMA kernel
-    const int split = (act & WM_GEMM32_SPLIT) != 0;
-    return launch_gemm32(nullptr, (hipStream_t)stream, a_dev, w_dev, bias_dev, residual_dev, out_dev, M, N, K, act & 0xff, 0, split ? 2 : 1);
+    // act & WM_GEMM32_SPLIT: the fp16-split form (gemm32x3_kernel, W split per K-step); act & WM_GEMM32_PRESPLIT: the same form with W
+    // split once by split_w32_kernel (the engine's); otherwise the fp32-MFMA kernel
+    const int split = (act & WM_GEMM32_SPLIT) != 0, presplit = (act & WM_GEMM32_PRESPLIT) != 0;
+    if (split && presplit) return fail("wm_op_gemm32: WM_GEMM32_SPLIT and WM_GEMM32_PRESPLIT are exclusive");
+    return launch_gemm32(nullptr, (hipStream_t)stream, a_dev, w_dev, bias_dev, residual_dev, out_dev, M, N, K, act & 0xff, 0,
+                         presplit ? 3 : split ? 2 : 1);
 }
 
 extern "C" int wm_op_layernorm(const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, float* out_f32_dev,
