@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-/* 7: WM_GEMM32_PRESPLIT for wm_op_gemm32; the split fp32 GEMM carries its lo parts scaled by 2^11 (no change in its
+/* 8: the single-frame tile cut and merge entries removed: a single frame is a survey of one frame (wm_tile_frames_u8,
+ *    wm_merge_frames_nms, same results); nothing else changed.
+ * 7: WM_GEMM32_PRESPLIT for wm_op_gemm32; the split fp32 GEMM carries its lo parts scaled by 2^11 (no change in its
  *    contract beyond accuracy); nothing else changed.
  * 6: wm_resample_u8, wm_scaled_size (survey frames resampled to the model's training scale before tiling); nothing
  *    else changed.
@@ -40,7 +42,7 @@ extern "C" {
  * wm_profile_read no longer reports the fused-LayerNorm time-out (wm_forward / wm_encoder_forward do); precision value 2
  * (fp8), WM_FLAG_MERGED and a NULL handle in wm_postprocess_nms date from round 2.  The Python binding refuses a library
  * whose wm_abi_version() differs from the value it was written for. */
-#define WM_ABI_VERSION 7
+#define WM_ABI_VERSION 8
 
 /* operand type of the transformer blocks' MFMA GEMMs / attention (accumulation, residual stream, LayerNorm
  * statistics, softmax and the whole decoder are fp32; the stem, the HFC adaptor and the neck -- 2.9 % of the
@@ -115,7 +117,7 @@ typedef struct wm_box_record {
 #define WM_FLAG_CONF 1
 #define WM_FLAG_SCORE 2
 #define WM_FLAG_NMS 4
-#define WM_FLAG_MERGED 8   /* wm_merge_tiles_nms: survives the cross-tile NMS of one frame */
+#define WM_FLAG_MERGED 8   /* wm_merge_frames_nms: survives the cross-tile NMS of its frame */
 
 const char* wm_last_error(void);
 int wm_abi_version(void);
@@ -186,30 +188,23 @@ int wm_forward(wm_handle* h, const float* x_dev, const float* target_sizes_dev,
                int batch, void* stream);
 
 /* ---- large-frame front end (no reference behaviour: the reference down-scales whole frames) -------
- * wm_tile_frame_u8: cut n tiles of 1024 x 1024 at origins[n][2] = (y0, x0) (int32, device) out of ONE uint8 HWC frame
- * [H,W,3] into the model input [n,3,1024,1024] fp32 (ToTensor + Normalize; zeros where a tile reaches past the frame).
- * wm_merge_tiles_nms: records [n_tiles * WM_NUM_QUERIES] of those tiles (wm_forward / wm_postprocess_nms output, boxes
- * in tile pixels) -> merged records in frame coordinates: slots that survived their tile's NMS compete in one more
- * greedy class-agnostic NMS (IoU > iou_thr suppresses, descending score, stable), survivors carry WM_FLAG_MERGED and
- * nms_rank = their position in the merged list.  n_tiles * WM_NUM_QUERIES <= 4096. */
-int wm_tile_frame_u8(const uint8_t* frame_dev, const int32_t* origins_dev, float* out_dev, int n_tiles, int height, int width,
-                     void* stream);
-int wm_merge_tiles_nms(const wm_box_record* records_dev, const int32_t* origins_dev, int n_tiles, float iou_thr,
-                       wm_box_record* merged_dev, void* stream);
-
-/* ---- survey front end: many frames of any size per launch ----------------------------------------------------------
- * wm_tile_frames_u8: one model batch cut from several frames.  frames_dev[n_frames] (device) gives each frame's uint8 HWC
- * base pointer and size; tiles_dev[n_tiles][3] = (frame index, y0, x0) (int32, device).  Output [n_tiles,3,1024,1024]
- * fp32 with wm_tile_frame_u8's arithmetic, each tile bit-identical to cutting it from its own frame alone.
- * wm_merge_frames_nms: wm_merge_tiles_nms applied to each frame independently, with no limit on tiles per frame.  Frame
- * f is the tiles [frame_tile_offsets[f], frame_tile_offsets[f+1]) of records_dev / origins_dev; frame_tile_offsets is
- * HOST memory, n_frames + 1 entries, starting at 0 and strictly increasing.  merged_dev[n_slots] (n_slots = total tiles
- * * WM_NUM_QUERIES): every slot with its box in frame coordinates, WM_FLAG_MERGED and nms_rank exactly as
- * wm_merge_tiles_nms would give for that frame alone.  The compacted detection list: frame f's survivors in merged order
- * are det_dev / det_tile_dev [frame_tile_offsets[f] * WM_NUM_QUERIES + k], k < det_count_dev[f] (det_tile = tile within
- * the frame).  scratch_dev (16-byte aligned, device) holds at least wm_merge_frames_scratch_bytes(total tiles) bytes;
- * nothing is allocated.  Boxes must be finite; iou_thr in [0, 1).  Frame coordinates are fp32: below 0.01 px of
- * fractional resolution up to 65536 px. */
+ * One frame or a survey of many frames of any size per launch.
+ * wm_tile_frames_u8: one model batch of 1024 x 1024 tiles cut from several frames.  frames_dev[n_frames] (device) gives
+ * each frame's uint8 HWC base pointer and size; tiles_dev[n_tiles][3] = (frame index, y0, x0) (int32, device).  Output
+ * [n_tiles,3,1024,1024] fp32: ToTensor + Normalize as in wm_preprocess_u8, zeros where a tile reaches past its frame;
+ * each tile depends only on its own frame and origin.
+ * wm_merge_frames_nms: records of the tiles of several frames (wm_forward / wm_postprocess_nms output, boxes in tile
+ * pixels) and each tile's origin (y0, x0) in its frame (int32, device) -> merged records in frame coordinates.  In each
+ * frame, with no limit on its tiles, the slots that survived their tile's NMS compete in one more greedy class-agnostic
+ * NMS (IoU > iou_thr suppresses, descending score, stable).  Frame f is the tiles [frame_tile_offsets[f],
+ * frame_tile_offsets[f+1]) of records_dev / origins_dev; frame_tile_offsets is HOST memory, n_frames + 1 entries,
+ * starting at 0 and strictly increasing.  merged_dev[n_slots] (n_slots = total tiles * WM_NUM_QUERIES): every slot with
+ * its box in frame coordinates and its other fields as given, except that survivors carry WM_FLAG_MERGED and nms_rank =
+ * their position in the frame's merged list (the flag clear and -1 otherwise).  The compacted detection list: frame f's
+ * survivors in merged order are det_dev / det_tile_dev [frame_tile_offsets[f] * WM_NUM_QUERIES + k], k <
+ * det_count_dev[f] (det_tile = tile within the frame).  scratch_dev (16-byte aligned, device) holds at least
+ * wm_merge_frames_scratch_bytes(total tiles) bytes; nothing is allocated.  Boxes must be finite; iou_thr in [0, 1).
+ * Frame coordinates are fp32: below 0.01 px of fractional resolution up to 65536 px. */
 typedef struct wm_frame_desc {
     const uint8_t* data;      /* [height, width, 3] uint8, device */
     int32_t height, width;

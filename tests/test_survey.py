@@ -167,7 +167,7 @@ def test_merge_frames_single_frame_300_plus_tiles():
     out, _ = _merge([(org, boxes, scores, cand, rec)])
     keep = _check_against_oracle(out["merged"], out["det"], out["det_tile"], int(out["det_count"][0]), boxes, scores, cand, org)
     assert 0 < len(keep) < int(cand.sum())
-    # merge_tile_records above 80 tiles goes through the same merge instead of raising
+    # merge_tile_records is this merge on a one-frame survey, at any tile count
     m = tiling.merge_tile_records(rec.to("cuda:0"), torch.tensor(org, dtype=torch.int32), 0.4).cpu()
     assert torch.equal(m.view(torch.int32), out["merged"].view(torch.int32))
 
@@ -187,19 +187,24 @@ def test_merge_frames_many_frames_one_launch():
 
 
 @pytest.mark.gpu
-def test_merge_frames_bit_identical_to_one_workgroup_merge():
-    """Up to 80 tiles: records (boxes, flags, nms_rank, everything) identical to wm_merge_tiles_nms."""
-    dev = torch.device("cuda:0")
+def test_merge_frames_up_to_80_tiles_every_field():
+    """One frame per merge at common frame sizes (1 to 72 tiles): every field of every record pinned -- boxes, survivors,
+    nms_rank, the count and the compacted list against the oracle; score, label and the flag bits other than
+    FLAG_MERGED as given."""
     rng = np.random.default_rng(13)
     for H, W, pc in [(4000, 6000, 0.4), (1024, 1024, 1.0), (7000, 8000, 0.3), (3000, 2000, 0.0)]:
         org, boxes, scores, cand = _synth_frame(H, W, rng, p_cand=pc, dup=4 if pc > 0 else 0, wide=True)
         assert len(org) <= 80
-        rec = _records(boxes, scores, cand, rng).to(dev)
-        orgt = torch.tensor(org, dtype=torch.int32)
-        old = torch.empty_like(rec)
-        N.check(N.lib().wm_merge_tiles_nms(N.ptr(rec), N.ptr(orgt.to(dev)), len(org), 0.4, N.ptr(old), N.stream_ptr(dev)))
-        new = tiling.merge_frames(rec, orgt, [0, len(org)], 0.4)["merged"]
-        assert torch.equal(new.view(torch.int32).cpu(), old.view(torch.int32).cpu()), (H, W, pc)
+        rec = _records(boxes, scores, cand, rng)
+        out, _ = _merge([(org, boxes, scores, cand, rec)])
+        keep = _check_against_oracle(out["merged"], out["det"], out["det_tile"], int(out["det_count"][0]), boxes, scores, cand,
+                                     org)
+        got, given = out["merged"].view(torch.int32), rec.view(torch.int32)
+        assert torch.equal(got[..., 4:6], given[..., 4:6]), (H, W, pc)                       # score bits, label
+        assert torch.equal(got[..., 6] & ~N.FLAG_MERGED, given[..., 6] & ~N.FLAG_MERGED), (H, W, pc)
+        rank = np.full(len(org) * NQ, -1, np.int32)
+        rank[keep] = np.arange(len(keep))
+        assert np.array_equal(got[..., 7].reshape(-1).numpy(), rank), (H, W, pc)
 
 
 @pytest.mark.gpu

@@ -38,7 +38,7 @@ def test_frame_to_tiles_bit_exact():
 
 
 @pytest.mark.gpu
-def test_merge_tiles_nms_matches_oracle():
+def test_merge_tile_records_matches_oracle():
     """Synthetic per-tile records: random boxes, some duplicated in the neighbouring tile (same frame box, shifted tile
     coordinates, slightly different score), ties, non-candidates: merged keep list identical to the numpy NMS."""
     from oracle import tiling_oracle as TO

@@ -11,8 +11,8 @@
       wm_resample_u8 of a 6000 x 4000 frame to 768 x 512 and to 3000 x 2000; run under `rocprofv3 --kernel-trace --stats`
       for the per-kernel times; the algorithmic bytes of each pass are printed.
   python tools/survey_time.py merge [--reps 20]
-      synthetic per-tile records, old (wm_merge_tiles_nms) and new (wm_merge_frames_nms) merge at 35 tiles, new at 391;
-      run under `rocprofv3 --kernel-trace --stats` for the per-kernel times (wall times printed here include the launch).
+      synthetic per-tile records, wm_merge_frames_nms at 35 tiles and at 391; run under `rocprofv3 --kernel-trace --stats`
+      for the per-kernel times (wall times printed here include the launch).
 """
 import argparse
 import json
@@ -147,17 +147,13 @@ def merge(args):
         rec, org, ncand = synth_records(H, W, rng)
         rec, org = rec.to(dev), org.to(dev)
         n = rec.shape[0]
-        runs = [("new", lambda: tiling.merge_frames(rec, org, [0, n], 0.4))]
-        if n <= tiling.MERGE_ONE_WORKGROUP_MAX_TILES:
-            runs.insert(0, ("old", lambda: tiling.merge_tile_records(rec, org, 0.4)))
-        for name, fn in runs:
-            fn()
-            torch.cuda.synchronize()
-            t = time.perf_counter()
-            for _ in range(args.reps):
-                fn()
-            torch.cuda.synchronize()
-            out[f"{name}_{label}_ms_wall"] = round((time.perf_counter() - t) / args.reps * 1e3, 4)
+        tiling.merge_frames(rec, org, [0, n], 0.4)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for _ in range(args.reps):
+            tiling.merge_frames(rec, org, [0, n], 0.4)
+        torch.cuda.synchronize()
+        out[f"merge_{label}_ms_wall"] = round((time.perf_counter() - t) / args.reps * 1e3, 4)
         out[f"candidates_{label}"] = ncand
     print(json.dumps(out))
 

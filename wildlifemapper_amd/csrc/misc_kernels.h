@@ -501,8 +501,6 @@ __global__ __launch_bounds__(256) void cvt_16_to_f32_kernel(const u16* __restric
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void preprocess_u8_kernel(const unsigned char* __restrict__ in, float* __restrict__ out,
                                                             int B, int h, int w) {
-#pragma clang fp contract(off)
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
     const int64_t total = (int64_t)B * 1024 * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int x4 = (int)(i & 255) * 4;
@@ -516,7 +514,7 @@ __global__ __launch_bounds__(256) void preprocess_u8_kernel(const unsigned char*
                 const int x = x4 + j;
                 if (x < w) {
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) v[c][j] = ((float)row[x * 3 + c] / 255.0f - mean[c]) / stdv[c];
+                    for (int c = 0; c < 3; ++c) v[c][j] = normalize_u8(row[x * 3 + c], c);
                 }
             }
         }
@@ -562,8 +560,6 @@ __global__ __launch_bounds__(256) void resize_h_u8_kernel(const unsigned char* _
 __global__ __launch_bounds__(256) void resize_v_normalize_kernel(const unsigned char* __restrict__ tmp, float* __restrict__ out,
                                                                  const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
                                                                  int B, int h, int ow, int oh) {
-#pragma clang fp contract(off)
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
     const int64_t total = (int64_t)B * 1024 * 1024;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int xx = (int)(i & 1023), yy = (int)((i >> 10) & 1023);
@@ -580,10 +576,7 @@ __global__ __launch_bounds__(256) void resize_v_normalize_kernel(const unsigned 
                 a[0] += p[0] * c; a[1] += p[1] * c; a[2] += p[2] * c;
             }
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int u = min(max(a[c] >> RESIZE_PREC_BITS, 0), 255);
-                v[c] = ((float)u / 255.0f - mean[c]) / stdv[c];
-            }
+            for (int c = 0; c < 3; ++c) v[c] = normalize_u8(min(max(a[c] >> RESIZE_PREC_BITS, 0), 255), c);
         }
 #pragma unroll
         for (int c = 0; c < 3; ++c) out[((b * 3 + c) * 1024 + yy) * (int64_t)1024 + xx] = v[c];
@@ -657,8 +650,6 @@ __global__ __launch_bounds__(256) void resize_h_rows_kernel(const unsigned char*
 __global__ __launch_bounds__(256) void resize_v_normalize4_kernel(const unsigned char* __restrict__ tmp, float* __restrict__ out,
                                                                   const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
                                                                   int h, int ow, int oh) {
-#pragma clang fp contract(off)
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
     const int yy = blockIdx.x & 1023;
     const int64_t b = blockIdx.x >> 10;
     const int xx4 = threadIdx.x * 4;
@@ -685,10 +676,7 @@ __global__ __launch_bounds__(256) void resize_v_normalize4_kernel(const unsigned
 #pragma unroll
         for (int px = 0; px < 4; ++px)
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int u = min(max(a[px * 3 + c] >> RESIZE_PREC_BITS, 0), 255);
-                v[c][px] = ((float)u / 255.0f - mean[c]) / stdv[c];
-            }
+            for (int c = 0; c < 3; ++c) v[c][px] = normalize_u8(min(max(a[px * 3 + c] >> RESIZE_PREC_BITS, 0), 255), c);
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) *(f32x4*)(out + ((b * 3 + c) * 1024 + yy) * (int64_t)1024 + xx4) = v[c];

@@ -1,9 +1,13 @@
-// Survey front end: the large-frame tile cut and cross-tile merge (dec_kernels.h) generalised to many frames of any
-// size per launch.
-//   * tile_frames_u8_kernel: one model batch cut from several frames (per-tile frame index), arithmetic of
-//     tile_frame_u8_kernel.
-//   * merge_frames_nms_kernel: the greedy NMS of merge_tiles_nms_kernel applied to each frame (a segment of tiles)
-//     independently, without a slot limit.
+// Large-frame and survey front end: overlapping 1024 x 1024 tiles cut out of frames of any size, and
+// the cross-tile merge of their detections, for one or many frames per launch.  No reference behaviour exists for this
+// step (the reference down-scales whole frames, dataloader_coco.py:288); the checker is the numpy restatement in
+// oracle/tiling_oracle.py.
+//   * tile_frames_u8_kernel: one model batch cut from several frames (per-tile frame index): ToTensor + Normalize
+//     (normalize_u8), zeros where a tile reaches past its frame.
+//   * merge_frames_nms_kernel: per frame (a segment of tiles), the slots that survived their own tile's NMS move to frame
+//     coordinates and compete in one more greedy class-agnostic NMS (descending score, ties by ascending slot): an animal
+//     seen by two overlapping tiles is reported once.  Survivors carry WM_FLAG_MERGED and nms_rank = their position in
+//     the frame's merged list (-1 otherwise).  No limit on tiles per frame.
 #pragma once
 
 #include "wm_common.h"
@@ -19,13 +23,12 @@ struct frame_desc {
 // tiles[n][3] = (frame index, y0, x0).  A tile whose frame index is out of range is written as zeros.
 __global__ __launch_bounds__(256) void tile_frames_u8_kernel(const frame_desc* __restrict__ frames, int n_frames,
                                                              const int* __restrict__ tiles, float* __restrict__ out, int n) {
-#pragma clang fp contract(off)
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
     const int64_t total = (int64_t)n * 1024 * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int x4 = (int)(i & 255) * 4;
         const int y = (int)((i >> 8) & 1023);
-        const int64_t t = i >> 18;
+        // one tile row per 256 threads, so t is wave-uniform: the tile's row and its frame descriptor are scalar loads
+        const int64_t t = __builtin_amdgcn_readfirstlane((int)(i >> 18));
         const int f = tiles[3 * t];
         f32x4 v[3] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
         if (f >= 0 && f < n_frames) {
@@ -33,13 +36,14 @@ __global__ __launch_bounds__(256) void tile_frames_u8_kernel(const frame_desc* _
             const int H = fd.height, W = fd.width;
             const int fy = tiles[3 * t + 1] + y, fx0 = tiles[3 * t + 2] + x4;
             if (fy >= 0 && fy < H) {
-                const unsigned char* row = fd.data + (int64_t)fy * W * 3;
+                // a global, not generic, pointer: global_load instead of flat_load for the pixels
+                const auto* row = (const __attribute__((address_space(1))) unsigned char*)fd.data + (int64_t)fy * W * 3;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int fx = fx0 + j;
                     if (fx >= 0 && fx < W) {
 #pragma unroll
-                        for (int c = 0; c < 3; ++c) v[c][j] = ((float)row[(int64_t)fx * 3 + c] / 255.0f - mean[c]) / stdv[c];
+                        for (int c = 0; c < 3; ++c) v[c][j] = normalize_u8(row[(int64_t)fx * 3 + c], c);
                     }
                 }
             }
@@ -62,8 +66,9 @@ __global__ __launch_bounds__(256) void tile_frames_u8_kernel(const frame_desc* _
 //      decided and none is kept, suppressed as soon as one of them is kept.  The fixed point is sequential greedy NMS;
 //      the rounds number the longest dependency chain;
 //   6. survivors' nms_rank = prefix count of kept in priority order; records and the compacted detection list.
-// The IoU test is merge_tiles_nms_kernel's: un-contracted, the higher-priority box as `a`.  Pairs with inter == 0 can
-// never suppress (iou_thr >= 0), so only boxes whose interiors meet are compared.  Boxes must be finite.
+// The IoU test is postprocess_nms_kernel's: inter / (area_a + area_p - inter) > iou_thr, un-contracted, the
+// higher-priority box as `a`.  Pairs with inter == 0 can never suppress (iou_thr >= 0), so only boxes whose interiors
+// meet are compared.  Boxes must be finite.
 // ---------------------------------------------------------------------------
 constexpr int MF_THREADS = 1024, MF_MAX_FRAMES = 64, MF_LDS_SORT = 4096;
 constexpr int MF_UNDECIDED = 0, MF_KEPT = 1, MF_SUPPRESSED = 2;

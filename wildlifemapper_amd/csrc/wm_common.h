@@ -66,6 +66,14 @@ __device__ __forceinline__ unsigned pack4_e4m3(f32x4 v) {
     return __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], r, true);
 }
 
+// ToTensor + Normalize(ImageNet mean / std) of channel c of one uint8 pixel (dataloader_coco.py:286-292), un-contracted:
+// the one definition behind every kernel that writes the model's input from 8-bit pixels.
+__device__ __forceinline__ float normalize_u8(int u, int c) {
+#pragma clang fp contract(off)
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+    return ((float)u / 255.0f - mean[c]) / stdv[c];
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

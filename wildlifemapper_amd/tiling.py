@@ -5,12 +5,12 @@ The reference has no such step (it down-scales whole frames to 768 px, dataloade
 match: the checker is oracle/tiling_oracle.py, a numpy restatement of exactly what is done here.
   * tile_origins: the fewest tiles per axis whose neighbours overlap by at least `overlap`, evenly spread, the first and
     last flush with the frame edges (no padding unless the frame is smaller than a tile): 7 x 5 tiles for 6000 x 4000;
-  * frame_to_tiles: wm_tile_frame_u8 (cut + ToTensor + Normalize on the GPU);
-  * detect_frame: model.detect per batch of tiles, then wm_merge_tiles_nms -- detections that survived their own tile's
-    score cut + NMS move to frame coordinates and compete in one more class-agnostic NMS (IoU 0.4);
+  * frame_to_tiles: wm_tile_frames_u8 (cut + ToTensor + Normalize on the GPU) on one frame;
+  * merge_tile_records / merge_frames: wm_merge_frames_nms -- detections that survived their own tile's score cut + NMS
+    move to frame coordinates and compete in one more class-agnostic NMS (IoU 0.4), per frame;
   * detect_frames: a survey -- many frames of any size, device or host -- with the tiles of consecutive frames packed
-    into full batches (wm_tile_frames_u8) and one segmented merge (wm_merge_frames_nms) per batch for the frames it
-    completes.  Frames with more than 80 tiles (the single-workgroup merge's limit) go through the segmented merge.
+    into full batches (wm_tile_frames_u8) and one merge per batch for the frames it completes; detect_frame is a survey
+    of one frame.
   * scale= / resize= (detect_frame, detect_frames): opt-in resampling to the scale the checkpoint was trained at -- the
     reference shrinks whole frames to a long side of 768 (dataloader_coco.py:288) -- with PIL's bilinear arithmetic on the
     GPU (wm_resample_u8), then the same tile cut and merge in the resampled frame.  Each tile's target size is its content
@@ -47,27 +47,37 @@ def tile_origins(height: int, width: int, tile: int = 1024, overlap: int = 128) 
     return [(y, x) for y in _axis_origins(height, tile, overlap) for x in _axis_origins(width, tile, overlap)]
 
 
+def _frame_descs(frames: List[torch.Tensor], device: torch.device) -> torch.Tensor:
+    """wm_frame_desc of each contiguous (H,W,3) uint8 device frame -- data pointer, then (height, width) as two int32 in
+    one int64 -- uploaded to `device` through pinned memory without blocking the host."""
+    desc = np.zeros((len(frames), 2), dtype=np.int64)
+    for j, fr in enumerate(frames):
+        desc[j, 0] = fr.data_ptr()
+        desc[j, 1] = np.array(fr.shape[:2], dtype=np.int32).view(np.int64)[0]
+    return torch.from_numpy(desc).pin_memory().to(device, non_blocking=True)
+
+
 def frame_to_tiles(frame: torch.Tensor, origins: torch.Tensor) -> torch.Tensor:
-    """frame (H,W,3) uint8 on a ROCm device, origins (n,2) int32 (y0, x0) on the same device -> (n,3,1024,1024) fp32."""
+    """frame (H,W,3) uint8 on a ROCm device, origins (n,2) int32 (y0, x0) on the host or the frame's device ->
+    (n,3,1024,1024) fp32."""
     if not frame.is_cuda or frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[-1] != 3:
         raise RuntimeError(f"frame_to_tiles: expected an (H,W,3) uint8 ROCm tensor, got {tuple(frame.shape)} {frame.dtype} on {frame.device}")
     frame = frame.contiguous()
-    origins = origins.to(device=frame.device, dtype=torch.int32).contiguous()
-    n = origins.shape[0]
-    out = torch.empty((n, 3, 1024, 1024), device=frame.device, dtype=torch.float32)
-    with torch.cuda.device(frame.device):
-        N.check(N.lib().wm_tile_frame_u8(N.ptr(frame), N.ptr(origins), N.ptr(out), n, frame.shape[0], frame.shape[1], N.stream_ptr(frame.device)))
+    dev = frame.device
+    tiles = torch.nn.functional.pad(origins.to(device=dev, dtype=torch.int32), (1, 0))      # (frame 0, y0, x0)
+    n = tiles.shape[0]
+    out = torch.empty((n, 3, 1024, 1024), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        N.check(N.lib().wm_tile_frames_u8(N.ptr(_frame_descs([frame], dev)), 1, N.ptr(tiles), N.ptr(out), n, N.stream_ptr(dev)))
     return out
-
-
-MERGE_ONE_WORKGROUP_MAX_TILES = 80        # wm_merge_tiles_nms: n_tiles * 51 <= 4096
 
 
 def merge_frames(records: torch.Tensor, origins: torch.Tensor, frame_tile_offsets, iou_thr: float = 0.4) -> Dict[str, torch.Tensor]:
     """Segmented cross-tile merge (wm_merge_frames_nms).  records (n,51,8) raw per-tile records of several frames,
     origins (n,2) each tile's (y0, x0) in its own frame, frame_tile_offsets (n_frames + 1) host ints: frame f is tiles
-    [offsets[f], offsets[f+1]).  Returns 'merged' (n,51,8) as merge_tile_records gives per frame, and the compacted
-    detection list: frame f's survivors in merged order are 'det' / 'det_tile' [offsets[f] * 51 + k], k < 'det_count'[f]."""
+    [offsets[f], offsets[f+1]).  Returns 'merged' (n,51,8), the records in frame coordinates with FLAG_MERGED / nms_rank
+    of each frame's cross-tile NMS, and the compacted detection list: frame f's survivors in merged order are 'det' /
+    'det_tile' [offsets[f] * 51 + k], k < 'det_count'[f]."""
     N.require_cuda(records, "records")
     offs = np.ascontiguousarray(np.asarray(frame_tile_offsets, dtype=np.int32))
     n = records.shape[0]
@@ -93,16 +103,9 @@ def merge_frames(records: torch.Tensor, origins: torch.Tensor, frame_tile_offset
 
 
 def merge_tile_records(records: torch.Tensor, origins: torch.Tensor, iou_thr: float = 0.4) -> torch.Tensor:
-    """records (n,51,8) raw per-tile records (boxes in tile pixels) -> (n,51,8) merged records in frame coordinates with
-    FLAG_MERGED / nms_rank of the cross-tile NMS (wm_merge_tiles_nms up to 80 tiles, wm_merge_frames_nms above)."""
-    N.require_cuda(records, "records")
-    if records.shape[0] > MERGE_ONE_WORKGROUP_MAX_TILES:
-        return merge_frames(records, origins, [0, records.shape[0]], iou_thr)["merged"]
-    origins = origins.to(device=records.device, dtype=torch.int32).contiguous()
-    out = torch.empty_like(records)
-    with torch.cuda.device(records.device):
-        N.check(N.lib().wm_merge_tiles_nms(N.ptr(records), N.ptr(origins), records.shape[0], float(iou_thr), N.ptr(out), N.stream_ptr(records.device)))
-    return out
+    """records (n,51,8) raw per-tile records of one frame (boxes in tile pixels) -> (n,51,8) merged records in frame
+    coordinates with FLAG_MERGED / nms_rank of the cross-tile NMS: merge_frames of a one-frame survey."""
+    return merge_frames(records, origins, [0, records.shape[0]], iou_thr)["merged"]
 
 
 def _check_scale(scale, what: str) -> float:
@@ -141,28 +144,11 @@ def resampled_size(index: int, height: int, width: int, scale=None, resize=None)
     return preprocess.scaled_size(height, width, _check_scale(s, f"frame {index}"))
 
 
-@torch.no_grad()
 def detect_frame(model, frame: torch.Tensor, overlap: int = 128, batch: int = 16, iou_thr: float = 0.4, scale=None,
                  resize=None) -> Dict[str, torch.Tensor]:
-    """One frame -> merged detections {'boxes' (k,4) frame xyxy, 'scores', 'labels', 'tile'} in merged-NMS order.
-    scale= / resize=: the frame is resampled first, as in detect_frames (a callable scale is called with index 0)."""
-    if _check_resample_args(scale, resize, "detect_frame"):
-        return next(detect_frames(model, [frame], overlap, batch, iou_thr, scale=scale, resize=resize))
-    from .engine import split_records
-    H, W = int(frame.shape[0]), int(frame.shape[1])
-    org = torch.tensor(tile_origins(H, W, 1024, overlap), dtype=torch.int32, device=frame.device)
-    recs = []
-    for i in range(0, org.shape[0], batch):
-        x = frame_to_tiles(frame, org[i:i + batch])
-        recs.append(model.detect(x)["records"])                      # target size 1024 x 1024: boxes in tile pixels
-    rec = torch.cat(recs, dim=0)
-    merged = merge_tile_records(rec, org, iou_thr)
-    r = split_records(merged)
-    flat = {k: v.reshape(-1, *v.shape[2:]) for k, v in r.items()}
-    kept = torch.nonzero((flat["flags"] & N.FLAG_MERGED) != 0).flatten()
-    kept = kept[torch.argsort(flat["nms_rank"][kept])]
-    return {"boxes": flat["boxes"][kept], "scores": flat["scores"][kept], "labels": flat["labels"][kept],
-            "tile": kept // N.NUM_QUERIES, "origins": org, "records": merged}
+    """One frame -> merged detections {'boxes' (k,4) frame xyxy, 'scores', 'labels', 'tile', 'origins', 'records'} in
+    merged-NMS order: detect_frames on a survey of this one frame (a callable scale is called with index 0)."""
+    return next(detect_frames(model, [frame], overlap, batch, iou_thr, scale=scale, resize=resize))
 
 
 # ---- survey: many frames of any size ---------------------------------------------------------------------------------
@@ -345,13 +331,8 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
             if staged[f].ready is not None:
                 main.wait_event(staged[f].ready)
                 staged[f].ready = None
-        desc = np.zeros((len(used), 2), dtype=np.int64)
-        for j, f in enumerate(used):
-            fr = staged[f]
-            desc[j, 0] = fr.data.data_ptr()
-            desc[j, 1] = np.array([fr.height, fr.width], dtype=np.int32).view(np.int64)[0]
+        desc_d = _frame_descs([staged[f].data for f in used], device)
         tiles = np.array([(local[f], *staged[f].origins[t]) for f, t0, t1 in b.segments for t in range(t0, t1)], dtype=np.int32)
-        desc_d = torch.from_numpy(desc).pin_memory().to(device, non_blocking=True)
         tiles_d = torch.from_numpy(tiles).pin_memory().to(device, non_blocking=True)
         n = tiles.shape[0]
         x = torch.empty((n, 3, 1024, 1024), device=device, dtype=torch.float32)
