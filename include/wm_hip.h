@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-/* 8: the single-frame tile cut and merge entries removed: a single frame is a survey of one frame (wm_tile_frames_u8,
+/* 9: wm_merge_frames_fuse (the survey merge's opt-in fuse policy: detections split by tile seams become one, with the
+ *    union box); nothing else changed.
+ * 8: the single-frame tile cut and merge entries removed: a single frame is a survey of one frame (wm_tile_frames_u8,
  *    wm_merge_frames_nms, same results); nothing else changed.
  * 7: WM_GEMM32_PRESPLIT for wm_op_gemm32; the split fp32 GEMM carries its lo parts scaled by 2^11 (no change in its
  *    contract beyond accuracy); nothing else changed.
@@ -42,7 +44,7 @@ extern "C" {
  * wm_profile_read no longer reports the fused-LayerNorm time-out (wm_forward / wm_encoder_forward do); precision value 2
  * (fp8), WM_FLAG_MERGED and a NULL handle in wm_postprocess_nms date from round 2.  The Python binding refuses a library
  * whose wm_abi_version() differs from the value it was written for. */
-#define WM_ABI_VERSION 8
+#define WM_ABI_VERSION 9
 
 /* operand type of the transformer blocks' MFMA GEMMs / attention (accumulation, residual stream, LayerNorm
  * statistics, softmax and the whole decoder are fp32; the stem, the HFC adaptor and the neck -- 2.9 % of the
@@ -117,7 +119,7 @@ typedef struct wm_box_record {
 #define WM_FLAG_CONF 1
 #define WM_FLAG_SCORE 2
 #define WM_FLAG_NMS 4
-#define WM_FLAG_MERGED 8   /* wm_merge_frames_nms: survives the cross-tile NMS of its frame */
+#define WM_FLAG_MERGED 8   /* wm_merge_frames_nms: survives the cross-tile NMS of its frame (_fuse: a keeper) */
 
 const char* wm_last_error(void);
 int wm_abi_version(void);
@@ -204,7 +206,16 @@ int wm_forward(wm_handle* h, const float* x_dev, const float* target_sizes_dev,
  * survivors in merged order are det_dev / det_tile_dev [frame_tile_offsets[f] * WM_NUM_QUERIES + k], k <
  * det_count_dev[f] (det_tile = tile within the frame).  scratch_dev (16-byte aligned, device) holds at least
  * wm_merge_frames_scratch_bytes(total tiles) bytes; nothing is allocated.  Boxes must be finite; iou_thr in [0, 1).
- * Frame coordinates are fp32: below 0.01 px of fractional resolution up to 65536 px. */
+ * Frame coordinates are fp32: below 0.01 px of fractional resolution up to 65536 px.
+ * wm_merge_frames_fuse: the same inputs, candidates and priority order, greedy absorption instead of suppression.  Walking
+ * the candidates in priority order, one not yet absorbed becomes a keeper and absorbs every later unabsorbed candidate
+ * of ANOTHER tile whose box matches its own: inter / min(area_keeper, area_other) > fuse_thr (intersection over the
+ * smaller box, fp32 as in the NMS; 0 / 0 never matches).  merged_dev as for the NMS, every slot with its own box:
+ * keepers carry WM_FLAG_MERGED and nms_rank = their position in the frame's list, absorbed slots neither.  det_dev[k] is
+ * keeper k's record with the union box of its members (elementwise min / max, exact), det_tile_dev[k] its tile,
+ * det_members_dev[k] = 1 + the number of boxes it absorbed (same indexing as det_dev); slot_det_dev[n_slots] = the list
+ * index of the detection a candidate slot belongs to (kept or absorbed), -1 for every other slot.  Same scratch;
+ * fuse_thr in [0, 1). */
 typedef struct wm_frame_desc {
     const uint8_t* data;      /* [height, width, 3] uint8, device */
     int32_t height, width;
@@ -215,6 +226,10 @@ int64_t wm_merge_frames_scratch_bytes(int n_tiles);    /* <0 on error */
 int wm_merge_frames_nms(const wm_box_record* records_dev, const int32_t* origins_dev, const int32_t* frame_tile_offsets,
                         int n_frames, float iou_thr, void* scratch_dev, int64_t scratch_bytes, wm_box_record* merged_dev,
                         wm_box_record* det_dev, int32_t* det_tile_dev, int32_t* det_count_dev, void* stream);
+int wm_merge_frames_fuse(const wm_box_record* records_dev, const int32_t* origins_dev, const int32_t* frame_tile_offsets,
+                         int n_frames, float fuse_thr, void* scratch_dev, int64_t scratch_bytes, wm_box_record* merged_dev,
+                         wm_box_record* det_dev, int32_t* det_tile_dev, int32_t* det_count_dev,
+                         int32_t* det_members_dev, int32_t* slot_det_dev, void* stream);
 
 /* Survey resampling (tiling.detect_frames(scale=..., resize=...)): a frame brought to the scale the checkpoint was trained
  * at (the val transform's long side of 768, dataloader_coco.py:288) before it is tiled.

@@ -10,9 +10,10 @@
   python tools/survey_time.py resample [--reps 20]
       wm_resample_u8 of a 6000 x 4000 frame to 768 x 512 and to 3000 x 2000; run under `rocprofv3 --kernel-trace --stats`
       for the per-kernel times; the algorithmic bytes of each pass are printed.
-  python tools/survey_time.py merge [--reps 20]
+  python tools/survey_time.py merge [--reps 20] [--fuse [--fuse-thr 0.5]]
       synthetic per-tile records, wm_merge_frames_nms at 35 tiles and at 391; run under `rocprofv3 --kernel-trace --stats`
-      for the per-kernel times (wall times printed here include the launch).
+      for the per-kernel times (wall times printed here include the launch).  --fuse: wm_merge_frames_fuse on the same
+      records too (merge_frames_nms_kernel<1>; the NMS is <0>), each mode's calls back to back, and the detection counts.
 """
 import argparse
 import json
@@ -147,13 +148,17 @@ def merge(args):
         rec, org, ncand = synth_records(H, W, rng)
         rec, org = rec.to(dev), org.to(dev)
         n = rec.shape[0]
-        tiling.merge_frames(rec, org, [0, n], 0.4)
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        for _ in range(args.reps):
-            tiling.merge_frames(rec, org, [0, n], 0.4)
-        torch.cuda.synchronize()
-        out[f"merge_{label}_ms_wall"] = round((time.perf_counter() - t) / args.reps * 1e3, 4)
+        modes = [("merge", None)] + ([("fuse", args.fuse_thr)] if args.fuse else [])
+        for name, fuse_thr in modes:
+            res = tiling.merge_frames(rec, org, [0, n], 0.4, fuse_thr=fuse_thr)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(args.reps):
+                tiling.merge_frames(rec, org, [0, n], 0.4, fuse_thr=fuse_thr)
+            torch.cuda.synchronize()
+            out[f"{name}_{label}_ms_wall"] = round((time.perf_counter() - t) / args.reps * 1e3, 4)
+            if args.fuse:
+                out[f"{name}_{label}_detections"] = int(res["det_count"][0])
         out[f"candidates_{label}"] = ncand
     print(json.dumps(out))
 
@@ -169,6 +174,8 @@ def main():
     ap.add_argument("--resize", type=int, nargs=2, default=None, metavar=("SIZE", "MAX_SIZE"),
                     help="rate: resample every frame to the val transform's geometry first, e.g. 768 768")
     ap.add_argument("--repeat", type=int, default=1, help="rate: the survey this many times over")
+    ap.add_argument("--fuse", action="store_true", help="merge: time wm_merge_frames_fuse on the same records too")
+    ap.add_argument("--fuse-thr", type=float, default=0.5, help="merge --fuse: the fuse threshold")
     args = ap.parse_args()
     {"rate": rate, "merge": merge, "resample": resample}[args.mode](args)
 

@@ -22,7 +22,7 @@ FLAG_CONF, FLAG_SCORE, FLAG_NMS, FLAG_MERGED = 1, 2, 4, 8
 CFG_FUSE_LN = 1
 CFG_FOLD_LN = 2
 CFG_FOLD_LN_BF16 = 4
-ABI_VERSION = 8            # include/wm_hip.h WM_ABI_VERSION this binding was written for
+ABI_VERSION = 9            # include/wm_hip.h WM_ABI_VERSION this binding was written for
 FP8_QKV, FP8_PROJ, FP8_MLP, FP8_ALL = 1, 2, 4, 7
 GEMM_W_PACKED, GEMM_A_PACKED, GEMM_OUT_PACKED, LAYOUT_PACKED = 0x1000, 0x2000, 0x4000, 0x100
 GEMM32_SPLIT = 0x100          # wm_op_gemm32: act | GEMM32_SPLIT = the fp16-split form the decoder runs (W split per K-step)
@@ -61,6 +61,7 @@ SYMBOLS = {
     "wm_tile_frames_u8": (_I, [_P, _I, _P, _P, _I, _P]),
     "wm_merge_frames_scratch_bytes": (_L, [_I]),
     "wm_merge_frames_nms": (_I, [_P, _P, C.POINTER(C.c_int32), _I, _F, _P, _L, _P, _P, _P, _P, _P]),
+    "wm_merge_frames_fuse": (_I, [_P, _P, C.POINTER(C.c_int32), _I, _F, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
     "wm_resample_u8": (_I, [_P, _I, _I, _P, _I, _I, _P]),
     "wm_scaled_size": (_I, [_I, _I, C.c_double, C.POINTER(_I), C.POINTER(_I)]),
     "wm_hfc_fft": (_I, [_P, _P, _P, _I, _P]),

@@ -4,10 +4,14 @@
 // oracle/tiling_oracle.py.
 //   * tile_frames_u8_kernel: one model batch cut from several frames (per-tile frame index): ToTensor + Normalize
 //     (normalize_u8), zeros where a tile reaches past its frame.
-//   * merge_frames_nms_kernel: per frame (a segment of tiles), the slots that survived their own tile's NMS move to frame
-//     coordinates and compete in one more greedy class-agnostic NMS (descending score, ties by ascending slot): an animal
-//     seen by two overlapping tiles is reported once.  Survivors carry WM_FLAG_MERGED and nms_rank = their position in
-//     the frame's merged list (-1 otherwise).  No limit on tiles per frame.
+//   * merge_frames_nms_kernel<MF_NMS>: per frame (a segment of tiles), the slots that survived their own tile's NMS move to
+//     frame coordinates and compete in one more greedy class-agnostic NMS (descending score, ties by ascending slot): an
+//     animal seen by two overlapping tiles is reported once.  Survivors carry WM_FLAG_MERGED and nms_rank = their
+//     position in the frame's merged list (-1 otherwise).  No limit on tiles per frame.
+//   * merge_frames_nms_kernel<MF_FUSE>: the same candidates and order, greedy absorption instead of suppression: a keeper
+//     absorbs every later unabsorbed candidate of another tile whose intersection over the smaller box exceeds fuse_thr,
+//     and its detection's box is the union of its members' boxes -- an animal cut by a tile seam is reported once, with
+//     its whole box.
 #pragma once
 
 #include "wm_common.h"
@@ -69,9 +73,22 @@ __global__ __launch_bounds__(256) void tile_frames_u8_kernel(const frame_desc* _
 // The IoU test is postprocess_nms_kernel's: inter / (area_a + area_p - inter) > iou_thr, un-contracted, the
 // higher-priority box as `a`.  Pairs with inter == 0 can never suppress (iou_thr >= 0), so only boxes whose interiors
 // meet are compared.  Boxes must be finite.
+//
+// MF_FUSE (greedy absorption; thr = fuse_thr) changes three steps.  A pair matches when its boxes come from different
+// tiles and inter / min(area_a, area_p) > fuse_thr (the same un-contracted inter and areas; 0 / 0 never matches, so the
+// search window of step 5 is unchanged).
+//   5. p is decided once the matching, not absorbed q < p of the smallest priority index is known: kept -> p is absorbed
+//      by q (state MF_SUPPRESSED + q); none -> p is kept; undecided -> p waits.  That q is the first keeper that matches
+//      p, so the fixed point is the sequential rule (each keeper absorbs every later unabsorbed candidate that matches
+//      its own box);
+//   union pass: every absorbed box applies min / max to its keeper's box, held as order-preserving u32 encodings in
+//      place of the keeper's cbox, and adds 1 to its member count (the sval scratch): order-independent, deterministic;
+//   6. det carries the union box, det_members the member count, slot_det[slot] the list index of the slot's detection
+//      (kept or absorbed; -1 for a non-candidate): keepers' ranks go through the skey scratch to their members.
 // ---------------------------------------------------------------------------
 constexpr int MF_THREADS = 1024, MF_MAX_FRAMES = 64, MF_LDS_SORT = 4096;
-constexpr int MF_UNDECIDED = 0, MF_KEPT = 1, MF_SUPPRESSED = 2;
+constexpr int MF_NMS = 0, MF_FUSE = 1;
+constexpr int MF_UNDECIDED = 0, MF_KEPT = 1, MF_SUPPRESSED = 2;   // MF_FUSE: MF_SUPPRESSED + q = absorbed by candidate q
 constexpr int MF_SCRATCH_PER_SLOT = 16 + 8 + 4 + 4 + 4;      // cbox, skey, sval, cslot, state
 
 struct mf_offsets {
@@ -81,6 +98,10 @@ struct mf_offsets {
 __device__ __forceinline__ unsigned mf_ord(float f) {       // order-preserving float -> u32
     const unsigned u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float mf_unord(unsigned u) {     // inverse of mf_ord
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
 // Ascending bitonic sort of (key, val) pairs, any n: the comparator of the first step of every merge stage pairs
@@ -150,11 +171,15 @@ __device__ __forceinline__ int mf_scan(int v, int* s_wave, int& total) {
     return before + incl - v;
 }
 
+// det_members / slot_det: MF_FUSE only (unused by MF_NMS).
+template <int MODE>
 __global__ __launch_bounds__(MF_THREADS) void merge_frames_nms_kernel(
-        const wm_box_record* __restrict__ rec, const int* __restrict__ origins, mf_offsets offs, float iou_thr,
+        const wm_box_record* __restrict__ rec, const int* __restrict__ origins, mf_offsets offs, float thr,
         char* __restrict__ scratch, int n_slots_total, wm_box_record* __restrict__ out, wm_box_record* __restrict__ det,
-        int* __restrict__ det_tile, int* __restrict__ det_count, int frame_base) {
+        int* __restrict__ det_tile, int* __restrict__ det_count, int* __restrict__ det_members, int* __restrict__ slot_det,
+        int frame_base) {
 #pragma clang fp contract(off)
+    constexpr bool FUSE = MODE == MF_FUSE;
     __shared__ uint64_t l_key[MF_LDS_SORT];
     __shared__ int l_val[MF_LDS_SORT];
     __shared__ int s_n, s_wave[MF_THREADS / 64];
@@ -184,6 +209,8 @@ __global__ __launch_bounds__(MF_THREADS) void merge_frames_nms_kernel(
             const float sc = r.score == 0.f ? 0.f : r.score;          // -0 ties with +0, as the comparison does
             const int c = atomicAdd(&s_n, 1);
             g_key[c] = ((uint64_t)(~mf_ord(sc)) << 32) | (unsigned)i;
+        } else if constexpr (FUSE) {
+            slot_det[s0 + i] = -1;
         }
     }
     __syncthreads();
@@ -211,8 +238,7 @@ __global__ __launch_bounds__(MF_THREADS) void merge_frames_nms_kernel(
     }
     __syncthreads();
     const float wmax = __uint_as_float(s_wmax & 0x7fffffffu), hmax = __uint_as_float(s_hmax & 0x7fffffffu);
-    const unsigned ym = s_ymin;
-    const float y_min = n > 0 ? __uint_as_float((ym & 0x80000000u) ? (ym & 0x7fffffffu) : ~ym) : 0.f;
+    const float y_min = n > 0 ? mf_unord(s_ymin) : 0.f;
     const float row_h = fmaxf(hmax, 1.f);
 
     // 4. spatial order: (row of y0, x0)
@@ -235,35 +261,78 @@ __global__ __launch_bounds__(MF_THREADS) void merge_frames_nms_kernel(
             const float ylo = p.y - (hmax + (1.f + hmax * 0x1p-20f + fabsf(p.y) * 0x1p-20f));
             const float xlo = p.x - (wmax + (1.f + wmax * 0x1p-20f + fabsf(p.x) * 0x1p-20f));
             const int r0 = mf_row(ylo, y_min, row_h), r1 = mf_row(p.w, y_min, row_h);
-            bool dead = false, pending = false;
+            bool dead = false, pending = false;                  // MF_NMS
+            int best = c, best_st = MF_UNDECIDED;                // MF_FUSE: smallest matching unabsorbed q seen, its state
+            const int ptile = FUSE ? cslot[c] / WM_NUM_QUERIES : 0;
             for (int r = r0; r <= r1 && !dead; ++r) {
                 const uint64_t row = (uint64_t)r << 32;
                 int m = mf_lower_bound(key, n, row | mf_ord(xlo));
                 const int m1 = mf_lower_bound(key, n, (row | mf_ord(p.z)) + 1);
                 for (; m < m1 && !dead; ++m) {
                     const int q = val[m];
-                    if (q >= c) continue;
+                    if (q >= best) continue;                     // MF_NMS: best == c throughout
                     const int st = mf_load_state(&state[q]);
-                    if (st == MF_SUPPRESSED) continue;
+                    if (FUSE ? st >= MF_SUPPRESSED : st == MF_SUPPRESSED) continue;
                     const float4 a = cbox[q];
                     const float xx0 = fmaxf(a.x, p.x), yy0 = fmaxf(a.y, p.y);
                     const float xx1 = fminf(a.z, p.z), yy1 = fminf(a.w, p.w);
                     const float iw = fmaxf(0.f, xx1 - xx0), ih = fmaxf(0.f, yy1 - yy0);
                     const float inter = iw * ih;
                     const float aarea = (a.z - a.x) * (a.w - a.y);
-                    const float iou = inter / (aarea + parea - inter);
-                    if (iou > iou_thr) {
-                        if (st == MF_KEPT) dead = true;
-                        else pending = true;
+                    if constexpr (FUSE) {
+                        const float ios = inter / fminf(aarea, parea);
+                        if (ios > thr && cslot[q] / WM_NUM_QUERIES != ptile) { best = q; best_st = st; }
+                    } else {
+                        const float iou = inter / (aarea + parea - inter);
+                        if (iou > thr) {
+                            if (st == MF_KEPT) dead = true;
+                            else pending = true;
+                        }
                     }
                 }
             }
-            if (dead || !pending)
-                __hip_atomic_store(&state[c], dead ? MF_SUPPRESSED : MF_KEPT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            else
-                pending_any = 1;
+            if constexpr (FUSE) {
+                // every matching q < best was seen absorbed (final), so best is the first keeper or still open
+                if (best == c || best_st == MF_KEPT)
+                    __hip_atomic_store(&state[c], best == c ? MF_KEPT : MF_SUPPRESSED + best, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+                else
+                    pending_any = 1;
+            } else {
+                if (dead || !pending)
+                    __hip_atomic_store(&state[c], dead ? MF_SUPPRESSED : MF_KEPT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                else
+                    pending_any = 1;
+            }
         }
         if (!__syncthreads_or(pending_any)) break;
+    }
+
+    // union pass: keepers' cbox -> order-preserving encodings, then every absorbed box widens its keeper's
+    uint4* ubox = (uint4*)cbox;
+    int* members = g_val;
+    int* krank = (int*)g_key;
+    if constexpr (FUSE) {
+        for (int c = tid; c < n; c += MF_THREADS) {
+            if (state[c] != MF_KEPT) continue;
+            const float4 b = cbox[c];
+            ubox[c] = uint4{mf_ord(b.x), mf_ord(b.y), mf_ord(b.z), mf_ord(b.w)};
+            members[c] = 1;
+        }
+        __syncthreads();
+        for (int c = tid; c < n; c += MF_THREADS) {
+            const int st = state[c];
+            if (st < MF_SUPPRESSED) continue;
+            const int q = st - MF_SUPPRESSED;
+            const float4 b = cbox[c];
+            unsigned* u = (unsigned*)&ubox[q];
+            __hip_atomic_fetch_min(&u[0], mf_ord(b.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_min(&u[1], mf_ord(b.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_max(&u[2], mf_ord(b.z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_max(&u[3], mf_ord(b.w), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(&members[q], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        __syncthreads();
     }
 
     // 6. ranks, records, detection list
@@ -279,12 +348,26 @@ __global__ __launch_bounds__(MF_THREADS) void merge_frames_nms_kernel(
             r.flags |= WM_FLAG_MERGED;
             r.nms_rank = rank;
             out[s0 + slot] = r;
+            if constexpr (FUSE) {
+                const uint4 u = ubox[c];
+                r.box[0] = mf_unord(u.x); r.box[1] = mf_unord(u.y); r.box[2] = mf_unord(u.z); r.box[3] = mf_unord(u.w);
+                det_members[s0 + rank] = members[c];
+                slot_det[s0 + slot] = rank;
+                krank[c] = rank;
+            }
             det[s0 + rank] = r;
             det_tile[s0 + rank] = slot / WM_NUM_QUERIES;
         }
         base += total;
     }
     if (tid == 0) det_count[frame_base + f] = base;
+    if constexpr (FUSE) {
+        __syncthreads();
+        for (int c = tid; c < n; c += MF_THREADS) {
+            const int st = state[c];
+            if (st >= MF_SUPPRESSED) slot_det[s0 + cslot[c]] = krank[st - MF_SUPPRESSED];
+        }
+    }
 }
 
 }  // namespace wm

@@ -2117,33 +2117,54 @@ extern "C" int64_t wm_merge_frames_scratch_bytes(int n_tiles) {
     return (int64_t)n_tiles * WM_NUM_QUERIES * MF_SCRATCH_PER_SLOT;
 }
 
-extern "C" int wm_merge_frames_nms(const wm_box_record* records_dev, const int32_t* origins_dev, const int32_t* frame_tile_offsets,
-                                   int n_frames, float iou_thr, void* scratch_dev, int64_t scratch_bytes, wm_box_record* merged_dev,
-                                   wm_box_record* det_dev, int32_t* det_tile_dev, int32_t* det_count_dev, void* stream) {
+// Argument checks and launches of both merge modes; `thr_name` is the threshold's name in error messages.
+template <int MODE>
+static int launch_merge_frames(const char* name, const char* thr_name, const wm_box_record* records_dev, const int32_t* origins_dev,
+                               const int32_t* frame_tile_offsets, int n_frames, float thr, void* scratch_dev, int64_t scratch_bytes,
+                               wm_box_record* merged_dev, wm_box_record* det_dev, int32_t* det_tile_dev, int32_t* det_count_dev,
+                               int32_t* det_members_dev, int32_t* slot_det_dev, void* stream) {
     if (!records_dev || !origins_dev || !frame_tile_offsets || !scratch_dev || !merged_dev || !det_dev || !det_tile_dev || !det_count_dev)
-        return fail("wm_merge_frames_nms: null buffer");
-    if (n_frames <= 0) return fail("wm_merge_frames_nms: n_frames %d", n_frames);
-    if (!(iou_thr >= 0.f && iou_thr < 1.f)) return fail("wm_merge_frames_nms: iou_thr %g outside [0, 1)", (double)iou_thr);
-    if (frame_tile_offsets[0] != 0) return fail("wm_merge_frames_nms: frame_tile_offsets[0] = %d, not 0", frame_tile_offsets[0]);
+        return fail("%s: null buffer", name);
+    if (MODE == MF_FUSE && (!det_members_dev || !slot_det_dev)) return fail("%s: null buffer", name);
+    if (n_frames <= 0) return fail("%s: n_frames %d", name, n_frames);
+    if (!(thr >= 0.f && thr < 1.f)) return fail("%s: %s %g outside [0, 1)", name, thr_name, (double)thr);
+    if (frame_tile_offsets[0] != 0) return fail("%s: frame_tile_offsets[0] = %d, not 0", name, frame_tile_offsets[0]);
     for (int f = 0; f < n_frames; ++f)
         if (frame_tile_offsets[f + 1] <= frame_tile_offsets[f])
-            return fail("wm_merge_frames_nms: frame_tile_offsets not strictly increasing at frame %d (%d -> %d)", f, frame_tile_offsets[f],
+            return fail("%s: frame_tile_offsets not strictly increasing at frame %d (%d -> %d)", name, f, frame_tile_offsets[f],
                         frame_tile_offsets[f + 1]);
     const int n_tiles = frame_tile_offsets[n_frames];
     const int64_t need = wm_merge_frames_scratch_bytes(n_tiles);
     if (need < 0) return -1;
-    if (scratch_bytes < need) return fail("wm_merge_frames_nms: scratch of %lld bytes, %lld needed", (long long)scratch_bytes, (long long)need);
-    if ((uintptr_t)scratch_dev % 16) return fail("wm_merge_frames_nms: scratch not 16-byte aligned");
+    if (scratch_bytes < need) return fail("%s: scratch of %lld bytes, %lld needed", name, (long long)scratch_bytes, (long long)need);
+    if ((uintptr_t)scratch_dev % 16) return fail("%s: scratch not 16-byte aligned", name);
     for (int f0 = 0; f0 < n_frames; f0 += MF_MAX_FRAMES) {
         const int nf = std::min(MF_MAX_FRAMES, n_frames - f0);
         mf_offsets offs;
         for (int f = 0; f <= nf; ++f) offs.tile[f] = frame_tile_offsets[f0 + f];
-        hipLaunchKernelGGL(merge_frames_nms_kernel, dim3(nf), dim3(MF_THREADS), 0, (hipStream_t)stream, records_dev, (const int*)origins_dev,
-                           offs, iou_thr, (char*)scratch_dev, n_tiles * WM_NUM_QUERIES, merged_dev, det_dev, (int*)det_tile_dev,
-                           (int*)det_count_dev, f0);
+        hipLaunchKernelGGL(merge_frames_nms_kernel<MODE>, dim3(nf), dim3(MF_THREADS), 0, (hipStream_t)stream, records_dev,
+                           (const int*)origins_dev, offs, thr, (char*)scratch_dev, n_tiles * WM_NUM_QUERIES, merged_dev, det_dev,
+                           (int*)det_tile_dev, (int*)det_count_dev, (int*)det_members_dev, (int*)slot_det_dev, f0);
         HIP_TRY(hipGetLastError());
     }
     return 0;
+}
+
+extern "C" int wm_merge_frames_nms(const wm_box_record* records_dev, const int32_t* origins_dev, const int32_t* frame_tile_offsets,
+                                   int n_frames, float iou_thr, void* scratch_dev, int64_t scratch_bytes, wm_box_record* merged_dev,
+                                   wm_box_record* det_dev, int32_t* det_tile_dev, int32_t* det_count_dev, void* stream) {
+    return launch_merge_frames<MF_NMS>("wm_merge_frames_nms", "iou_thr", records_dev, origins_dev, frame_tile_offsets, n_frames,
+                                       iou_thr, scratch_dev, scratch_bytes, merged_dev, det_dev, det_tile_dev, det_count_dev, nullptr,
+                                       nullptr, stream);
+}
+
+extern "C" int wm_merge_frames_fuse(const wm_box_record* records_dev, const int32_t* origins_dev, const int32_t* frame_tile_offsets,
+                                    int n_frames, float fuse_thr, void* scratch_dev, int64_t scratch_bytes, wm_box_record* merged_dev,
+                                    wm_box_record* det_dev, int32_t* det_tile_dev, int32_t* det_count_dev, int32_t* det_members_dev,
+                                    int32_t* slot_det_dev, void* stream) {
+    return launch_merge_frames<MF_FUSE>("wm_merge_frames_fuse", "fuse_thr", records_dev, origins_dev, frame_tile_offsets, n_frames,
+                                        fuse_thr, scratch_dev, scratch_bytes, merged_dev, det_dev, det_tile_dev, det_count_dev,
+                                        det_members_dev, slot_det_dev, stream);
 }
 
 // ---- N1: val transform resize (PIL bilinear semantics) + normalise + pad ----

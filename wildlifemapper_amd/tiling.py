@@ -8,6 +8,9 @@ match: the checker is oracle/tiling_oracle.py, a numpy restatement of exactly wh
   * frame_to_tiles: wm_tile_frames_u8 (cut + ToTensor + Normalize on the GPU) on one frame;
   * merge_tile_records / merge_frames: wm_merge_frames_nms -- detections that survived their own tile's score cut + NMS
     move to frame coordinates and compete in one more class-agnostic NMS (IoU 0.4), per frame;
+  * fuse_thr= (merge_frames, detect_frame, detect_frames): opt-in wm_merge_frames_fuse instead -- a keeper absorbs the
+    other tiles' views whose intersection over the smaller box exceeds fuse_thr, and reports the union box, so an
+    animal cut by a tile seam is counted once with its whole box;
   * detect_frames: a survey -- many frames of any size, device or host -- with the tiles of consecutive frames packed
     into full batches (wm_tile_frames_u8) and one merge per batch for the frames it completes; detect_frame is a survey
     of one frame.
@@ -72,12 +75,32 @@ def frame_to_tiles(frame: torch.Tensor, origins: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def merge_frames(records: torch.Tensor, origins: torch.Tensor, frame_tile_offsets, iou_thr: float = 0.4) -> Dict[str, torch.Tensor]:
+def _check_fuse_thr(fuse_thr, what: str):
+    """Validate fuse_thr= before any device work: None (the NMS merge) or a number in [0, 1)."""
+    if fuse_thr is None:
+        return None
+    try:
+        t = float(fuse_thr)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: fuse_thr {fuse_thr!r} is not a number") from None
+    t = float(np.float32(t)) if math.isfinite(t) else t      # the kernel compares in fp32
+    if not (math.isfinite(t) and 0.0 <= t < 1.0):
+        raise ValueError(f"{what}: fuse_thr {fuse_thr!r} must be in [0, 1) in fp32")
+    return t
+
+
+def merge_frames(records: torch.Tensor, origins: torch.Tensor, frame_tile_offsets, iou_thr: float = 0.4,
+                 fuse_thr=None) -> Dict[str, torch.Tensor]:
     """Segmented cross-tile merge (wm_merge_frames_nms).  records (n,51,8) raw per-tile records of several frames,
     origins (n,2) each tile's (y0, x0) in its own frame, frame_tile_offsets (n_frames + 1) host ints: frame f is tiles
     [offsets[f], offsets[f+1]).  Returns 'merged' (n,51,8), the records in frame coordinates with FLAG_MERGED / nms_rank
     of each frame's cross-tile NMS, and the compacted detection list: frame f's survivors in merged order are 'det' /
-    'det_tile' [offsets[f] * 51 + k], k < 'det_count'[f]."""
+    'det_tile' [offsets[f] * 51 + k], k < 'det_count'[f].
+    fuse_thr (a float in [0, 1)): wm_merge_frames_fuse instead of the NMS (iou_thr unused) -- FLAG_MERGED / nms_rank
+    mark the keepers, 'det' carries each keeper's union box, and the result gains 'det_members' (indexed as 'det': 1 + the
+    boxes the keeper absorbed) and 'slot_det' (n*51: the frame's list index of the detection a candidate slot belongs
+    to, -1 for other slots)."""
+    fuse_thr = _check_fuse_thr(fuse_thr, "merge_frames")
     N.require_cuda(records, "records")
     offs = np.ascontiguousarray(np.asarray(frame_tile_offsets, dtype=np.int32))
     n = records.shape[0]
@@ -95,6 +118,15 @@ def merge_frames(records: torch.Tensor, origins: torch.Tensor, frame_tile_offset
     det_tile = torch.empty(n * N.NUM_QUERIES, device=dev, dtype=torch.int32)
     det_count = torch.empty(nf, device=dev, dtype=torch.int32)
     import ctypes as C
+    if fuse_thr is not None:
+        det_members = torch.empty(n * N.NUM_QUERIES, device=dev, dtype=torch.int32)
+        slot_det = torch.empty(n * N.NUM_QUERIES, device=dev, dtype=torch.int32)
+        with torch.cuda.device(dev):
+            N.check(N.lib().wm_merge_frames_fuse(N.ptr(records), N.ptr(origins), offs.ctypes.data_as(C.POINTER(C.c_int32)), nf,
+                                                 fuse_thr, N.ptr(scratch), nbytes, N.ptr(merged), N.ptr(det), N.ptr(det_tile),
+                                                 N.ptr(det_count), N.ptr(det_members), N.ptr(slot_det), N.stream_ptr(dev)))
+        return {"merged": merged, "det": det, "det_tile": det_tile, "det_count": det_count, "det_members": det_members,
+                "slot_det": slot_det}
     with torch.cuda.device(dev):
         N.check(N.lib().wm_merge_frames_nms(N.ptr(records), N.ptr(origins), offs.ctypes.data_as(C.POINTER(C.c_int32)), nf, float(iou_thr),
                                             N.ptr(scratch), nbytes, N.ptr(merged), N.ptr(det), N.ptr(det_tile), N.ptr(det_count),
@@ -145,10 +177,10 @@ def resampled_size(index: int, height: int, width: int, scale=None, resize=None)
 
 
 def detect_frame(model, frame: torch.Tensor, overlap: int = 128, batch: int = 16, iou_thr: float = 0.4, scale=None,
-                 resize=None) -> Dict[str, torch.Tensor]:
+                 resize=None, fuse_thr=None) -> Dict[str, torch.Tensor]:
     """One frame -> merged detections {'boxes' (k,4) frame xyxy, 'scores', 'labels', 'tile', 'origins', 'records'} in
     merged-NMS order: detect_frames on a survey of this one frame (a callable scale is called with index 0)."""
-    return next(detect_frames(model, [frame], overlap, batch, iou_thr, scale=scale, resize=resize))
+    return next(detect_frames(model, [frame], overlap, batch, iou_thr, scale=scale, resize=resize, fuse_thr=fuse_thr))
 
 
 # ---- survey: many frames of any size ---------------------------------------------------------------------------------
@@ -213,7 +245,7 @@ def _as_frame_array(frame, i: int, device: torch.device):
 
 @torch.no_grad()
 def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, iou_thr: float = 0.4, scale=None,
-                  resize=None) -> Iterator[Dict[str, torch.Tensor]]:
+                  resize=None, fuse_thr=None) -> Iterator[Dict[str, torch.Tensor]]:
     """Survey of frames of any sizes ((H,W,3) uint8 ROCm tensors, CPU tensors or numpy arrays) -> one dict per frame, in
     input order, with detect_frame's keys and values.  Tiles of consecutive frames fill batches of `batch` (plan_batches);
     after each batch one wm_merge_frames_nms covers the frames it completed.  Host frames go through one pinned staging
@@ -225,12 +257,18 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
     is first resampled to resampled_size(...) on the GPU (wm_resample_u8; device frames on the current stream, host frames
     on the copy stream after their upload) and tiled in the resampled frame, each tile's target size its content extent.
     'boxes' are then in source-frame pixels (merged boxes * (sx, sy) in fp32, sx = float32(W / ow), sy = float32(H / oh));
-    'records' and 'origins' stay in resampled-frame pixels, and the dict gains 'resampled_size' = (oh, ow)."""
+    'records' and 'origins' stay in resampled-frame pixels, and the dict gains 'resampled_size' = (oh, ow).
+
+    fuse_thr= (a float in [0, 1)): the frames are merged by wm_merge_frames_fuse (merge_frames(fuse_thr=...)) instead of
+    the NMS: 'boxes' are the keepers' union boxes (mapped back to source pixels as above when resampling), and the dict
+    gains 'members' (k,) int64 -- 1 + the views each detection absorbed -- and 'slot_det' (n,51) int64, aligned with
+    'records': the index of the detection each candidate slot belongs to, -1 for other slots."""
     from .engine import split_records
     import ctypes as C
     if batch <= 0:
         raise ValueError(f"detect_frames: batch {batch}")
     resampling = _check_resample_args(scale, resize, "detect_frames")
+    fuse_thr = _check_fuse_thr(fuse_thr, "detect_frames")
     device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
     staged: Dict[int, _Frame] = {}
     pinned = [None, None]                     # staging buffer, event of the last copy out of it
@@ -311,6 +349,9 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
             res = {"boxes": det["boxes"].reshape(k, 4), "scores": det["scores"].reshape(k), "labels": det["labels"].reshape(k),
                    "tile": out["det_tile"][s0:s0 + k].to(torch.int64), "origins": fr.origins_dev,
                    "records": out["merged"][offs[j]:offs[j] + n]}
+            if fuse_thr is not None:
+                res["members"] = out["det_members"][s0:s0 + k].to(torch.int64)
+                res["slot_det"] = out["slot_det"][s0:s0 + n * N.NUM_QUERIES].view(n, N.NUM_QUERIES).to(torch.int64)
             if fr.scale_xy is not None:       # resampled-frame pixels -> source-frame pixels, one fp32 multiply per coordinate
                 b = res["boxes"]
                 src = torch.empty_like(b)
@@ -362,7 +403,7 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
             for j, f in enumerate(b.completes):
                 staged[f].records = []
                 staged[f].origins_dev = org_d[offs[j]:offs[j + 1]]
-            out = merge_frames(recs, org_d, offs, iou_thr)
+            out = merge_frames(recs, org_d, offs, iou_thr, fuse_thr)
             out["count_host"] = torch.empty(len(b.completes), dtype=torch.int32, pin_memory=True)
             out["count_host"].copy_(out["det_count"], non_blocking=True)
             out["ready"] = torch.cuda.Event()
