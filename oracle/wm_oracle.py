@@ -103,7 +103,7 @@ def linear(x: Tensor, w: Tensor, b: Optional[Tensor], cfg: OracleCfg) -> Tensor:
 
 
 def linear8(x: Tensor, w: Tensor, b: Optional[Tensor]) -> Tensor:
-    """y = (e4m3(x) e4m3(W / s)^T) * s + b with s[n] = max_k |W[n, k]| / 448 (gemm8.h; packer in wm_api.hip)."""
+    """y = (e4m3(x) e4m3(W / s)^T) * s + b with s[n] = max_k |W[n, k]| / 448 (gemm8.h; packer in host_weights.h)."""
     sw = w.abs().amax(dim=1, keepdim=True) / 448.0
     sw = torch.where(sw > 0, sw, torch.ones_like(sw))
     y = (e4m3_round(x) @ e4m3_round(w / sw).t()) * sw.t()

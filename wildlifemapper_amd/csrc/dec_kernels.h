@@ -369,4 +369,16 @@ __global__ __launch_bounds__(64) void postprocess_nms_kernel(const float* __rest
     }
 }
 
+// elementwise fp32 add with a row-broadcast second operand: out[r,c] = a[r,c] + b[r % mod, c]
+__global__ __launch_bounds__(256) void add_bcast_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out,
+                                                        int64_t rows, int C, int mod) {
+    const int64_t n4 = rows * C / 4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = (i * 4) / C;
+        const int c = (int)((i * 4) % C);
+        const f32x4 y = *(const f32x4*)(b + (r % mod) * C + c);
+        *(f32x4*)(out + i * 4) = a ? *(const f32x4*)(a + i * 4) + y : y;        // a == null: the rows of b repeated
+    }
+}
+
 }  // namespace wm

@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void layernorm_tiled_kernel(const float* __res
 
 // The fp8 blocks' LayerNorm on the stream's hi plane (gemm8.h PLANES): position-wise.  Input: the hi plane of rows (16-bit type TIN,
 // column c at plane_pos(c)); output: e4m3 rows IN THE SAME ORDER (position p holds LN(x)[plane_col(p)]), consumed by a gemm8 launch whose
-// weight has its K columns permuted alike (wm_api.hip upload8: a dot product does not care).  So the kernel reads and writes whole
+// weight has its K columns permuted alike (host_weights.h upload8: a dot product does not care).  So the kernel reads and writes whole
 // contiguous runs: a lane owns the 16-byte chunks lane + 64 j of the row (1 KiB per load instruction, 512 B per store instruction;
 // the column-tiled kernel above wrote 64-byte pieces 320 columns apart).  Statistics: mean, then the centred second moment, both over
 // the wave.  One wave per row, NJ = ceil(C / 512) chunks per lane, grid (rows / 4) x 256 threads.
@@ -527,7 +527,7 @@ __global__ __launch_bounds__(256) void preprocess_u8_kernel(const unsigned char*
 // Input pipeline with the val transform's resize (dataloader_coco.py:286-292 -> augmentation.py:77-133
 // -> torchvision F.resize on a PIL image = PIL bilinear resample).  The arithmetic is Pillow's 8-bit ImagingResample:
 // separable antialiased triangle filter, 22-bit fixed-point coefficients (computed on the host in double exactly as
-// Resample.c does, wm_api.hip: resize_coeffs), horizontal pass into an 8-bit image, then the vertical pass, each output
+// Resample.c does, host_frontend.h: resize_coeffs), horizontal pass into an 8-bit image, then the vertical pass, each output
 // clip8((sum + 2^21) >> 22) -- integer work, bit-exact with PIL.  The second kernel fuses the vertical pass with ToTensor,
 // Normalize and the zero padding to 1024 x 1024 (utils/misc.py:46-67).
 // ---------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 // Survey resampling (wm_resample_u8): uint8 HWC frame of any size -> uint8 HWC frame of any size, with the 8-bit
 // arithmetic of Pillow's ImagingResample (bilinear filter) that the N1 kernels of misc_kernels.h use: 22-bit fixed-point
-// coefficient tables computed on the host (wm_api.hip: resize_coeffs), a horizontal pass into an 8-bit intermediate, then
+// coefficient tables computed on the host (host_frontend.h: resize_coeffs), a horizontal pass into an 8-bit intermediate, then
 // the vertical pass, every output clip8((acc + 2^21) >> 22).  Integer work: bit-exact with PIL.Image.resize.
 //   * resample_h_cols_kernel: horizontal pass for any output width.  Grid (row block, column block): a workgroup owns up
 //     to 256 * OPT output columns and stages in LDS, row by row, only the input span those columns read.
