@@ -195,6 +195,35 @@ def test_gemm16_dispatch_and_values_at_model_shapes(M, N, K, act, variant):
     assert G.rel_l2(o16.float(), y) < OUT16_TOL[prec]
 
 
+@pytest.mark.parametrize("prec", ["bf16", "fp16"])
+@pytest.mark.parametrize("case", ["gelu16", "res_both"])
+def test_gemm16_v1_128_kernel(prec, case):
+    """The 128 x 128 kernel (gemm16.h), which M % 256 != 0 selects.  M = 384: three row tiles in a partly filled group of the
+    grouped order; K = 192: three K-tiles, so both LDS buffers and the last-tile path run.  Values against fp32 torch on the
+    rounded operands, and the batch-invariance claim: the same rows inside an M = 512 launch, which takes the 256 x 128
+    kernel (gemm16_v2.h), come out with the same bits."""
+    M, N, K = 384, 256, 192
+    a = G.to16(torch.randn(M + 128, K, device=G.dev()), prec)
+    w = G.to16(torch.randn(N, K, device=G.dev()) / math.sqrt(K), prec)
+    bias = torch.randn(N, device=G.dev())
+    if case == "gelu16":        # bias + GELU, 16-bit output only
+        res, res_mod, act, want32 = None, 0, 1, False
+    else:                       # bias + broadcast fp32 residual (rows modulo 128), both outputs
+        res, res_mod, act, want32 = torch.randn(128, N, device=G.dev()), 128, 0, True
+    (o32, o16), var = _variants_run(lambda: G.gemm16(a[:M].contiguous(), w, bias, res, res_mod, act, prec, want32=want32, want16=True))
+    assert var == {"v1_128": 1}
+    y = a[:M].float() @ w.float().t() + bias
+    y = O.gelu_erf(y) if act == 1 else y + res.repeat(M // 128, 1)
+    if want32:
+        assert G.rel_l2(o32, y) < 2e-5
+    assert G.rel_l2(o16.float(), y) < OUT16_TOL[prec]
+    (b32, b16), var = _variants_run(lambda: G.gemm16(a, w, bias, res, res_mod, act, prec, want32=want32, want16=True))
+    assert var == {"v2_128": 1}
+    if want32:
+        assert torch.equal(b32[:M], o32)
+    assert torch.equal(b16[:M].view(torch.int16), o16.view(torch.int16))
+
+
 def test_pack16_is_the_documented_permutation():
     """wm_op_pack16 (the kernel that packs the weights at wm_finalize_weights) against the layout's definition restated with
     torch indexing, and the inverse."""
@@ -404,7 +433,7 @@ def test_gemm16_split_stream_producer_equals_fp32_path(M, N, K, prec):
 @pytest.mark.parametrize("B,Cin,N", [(2, 3, 1280), (1, 1, 1024), (3, 3, 768)])
 def test_patch_embed_implicit_gemm(B, Cin, N, prec):
     """PatchEmbed / HfcEmbed (image_encoder.py:386-450: Conv2d k16 s16 + NCHW -> NHWC) as an implicit GEMM that gathers the
-    patches from the 16-bit NCHW image (gemm16_v3.h AMODE 2, no im2col buffer) against F.conv2d on the same rounded operands."""
+    patches from the 16-bit NCHW image (gemm16_v3.h ALoad::PatchEmbed, no im2col buffer) against F.conv2d on the same rounded operands."""
     dev = G.dev()
     torch.manual_seed(B * 7 + Cin)
     x = torch.randn(B, Cin, 1024, 1024, device=dev)

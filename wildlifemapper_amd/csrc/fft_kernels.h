@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void fft_cols_kernel(float2* __restrict__ R, c
 
 // K3: inverse row transform of the 362 kept columns, out = |gray - Re(.)/N^2|.  grid (1024, B).
 // x16 / hfc16 (optional): 16-bit NCHW copies of the three input channels and of the result, for the im2col-free patch embeds
-// (gemm16_v3.h AMODE 2) -- this pass has both values in registers anyway.
+// (gemm16_v3.h ALoad::PatchEmbed) -- this pass has both values in registers anyway.
 template <class T>
 __global__ __launch_bounds__(256) void fft_rows_inv_kernel(const float* __restrict__ x, const float2* __restrict__ R,
                                                            const float2* __restrict__ tw, float* __restrict__ out,

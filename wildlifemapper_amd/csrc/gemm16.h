@@ -1,4 +1,5 @@
-// 16-bit (bf16 / fp16) MFMA GEMM with fused epilogue, gfx950.
+// 16-bit (bf16 / fp16) MFMA GEMM with fused epilogue, gfx950: the 128 x 128 kernel, which serves M % 256 != 0.
+// (Argument block, tile order and epilogue arithmetic of the whole family: gemm_common.h.)
 //
 //   C[M,N] = act(A[M,K] * W[N,K]^T + bias[N]) (+ residual[(m % res_mod), N])
 //
@@ -19,57 +20,12 @@
 // as B-operand) so each lane ends up with 4 consecutive N for one M row and the
 // epilogue stores 16 B (fp32) / 8 B (16-bit) per lane.
 #pragma once
-#include "wm_common.h"
+#include "gemm_common.h"
 
 namespace wm {
 
 constexpr int G16_BM = 128, G16_BN = 128, G16_BK = 64;
 constexpr int G16_LDS_BYTES = 2 * (G16_BM + G16_BN) * G16_BK * 2;   // 64 KiB
-constexpr int G16_GROUP_M = 8;
-
-enum { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2, ACT_SIGMOID = 3 };
-
-struct Gemm16Args {
-    const u16* A;
-    const u16* W;
-    const float* bias;       // [N] or null
-    const float* residual;   // [res_mod, N] fp32 or null
-    float* out32;            // [M,N] or null
-    u16* out16;              // [M,N] or null
-    int M, N, K;
-    int res_mod;             // rows of residual (M, or 4096 for a per-tile broadcast)
-    int act;
-    // implicit-GEMM A operand (gemm16_v3.h, AMODE 1): A is an NHWC activation [M = B*64*64, conv_c] and the
-    // GEMM's K runs over (tap, channel) of a 3x3 / pad 1 convolution, K = 9 * conv_c; out-of-image taps read
-    // `zero_page` (>= 64 B of zeros).  Unused (0 / null) for a plain A matrix.
-    int conv_c;
-    const u16* zero_page;
-    // row tiles per group of the grouped tile order (gemm16_v5.h; 0 = G16_GROUP_M): a group's row tiles x all column tiles
-    // are consecutive tile ids, so group_m * tilesN ~ the 32 workgroups co-resident on an XCD keeps each A panel to one XCD
-    int group_m;
-    // gemm16_v5.h only: W / A stored in LDS-image order ([rows / 16][K / 32][64 x 16 B], pack16_lds_image_kernel); out_packed:
-    // the 16-bit output is written in that order (it is the next GEMM's A operand; N % 32 == 0)
-    int w_packed, a_packed, out_packed;
-    // Folded LayerNorm (gemm16_v5.h "Folded LayerNorm").  Producer (FOLDP instance, fp32 + residual epilogue): st_stats
-    // [M][N / BN][2] receives each row's (mean, M2) over this tile's columns, out16 the finished rows as 16-bit in LDS-image
-    // order.  Consumer (16-bit epilogue): A is such a 16-bit copy x16 and W = gamma (.) W; with fold_stats = the producer's
-    // partials over fold_ntile tiles of fold_bn columns (fold_ntile * fold_bn = K), fold_c1[n] = sum_k W[n][k] and
-    // bias[n] = sum_k beta[k] W0[n][k] + b[n] the epilogue computes rstd (acc - mean c1) + bias = LayerNorm(x) W0^T + b.
-    float* st_stats;
-    const float* fold_stats;
-    const float* fold_c1;
-    int fold_ntile;
-    float fold_bn, fold_eps;
-    // Split residual stream (gemm16_v5.h "Split stream", round 4): the stream x as two 16-bit planes in LDS-image order,
-    // hi = T(x) (the folded LayerNorm's operand) and lo = fp16(x - hi).  SPLIT instance: the residual comes in as
-    // (res_hi, res_lo) and leaves as (out16 = hi, out_lo); the FOLDP instance (fp32 residual in) writes out_lo too when it is
-    // given and then skips out32 when that is null.  overflow: a host-visible word the producers set to 1 when a value of the
-    // stream reaches the fp16 clamp (|x| >= 65504), or null.
-    const u16* res_hi;
-    const u16* res_lo;
-    u16* out_lo;
-    int* overflow;
-};
 
 template <class T>
 __global__ __launch_bounds__(256, 2) void gemm16_kernel(Gemm16Args p) {
@@ -78,16 +34,8 @@ __global__ __launch_bounds__(256, 2) void gemm16_kernel(Gemm16Args p) {
     const int wr = wave >> 1, wc = wave & 1;
 
     const int tilesM = p.M / G16_BM, tilesN = p.N / G16_BN;
-    const int lid = xcd_remap(blockIdx.x, gridDim.x);
-    // grouped order: G16_GROUP_M row tiles share each W panel back to back
-    const int per_group = G16_GROUP_M * tilesN;
-    const int group = lid / per_group;
-    const int first_m = group * G16_GROUP_M;
-    const int gsz = min(G16_GROUP_M, tilesM - first_m);
-    const int in_group = lid - group * per_group;
-    const int tm = first_m + in_group % gsz;
-    const int tn = in_group / gsz;
-    const int m0 = tm * G16_BM, n0 = tn * G16_BN;
+    const TileOrigin o = grouped_tile_origin<G16_BM, G16_BN>(tilesM, tilesN, blockIdx.x, gridDim.x, G16_GROUP_M);
+    const int m0 = o.m0, n0 = o.n0;
     const int K = p.K;
     const int nk = K / G16_BK;
 
@@ -170,28 +118,7 @@ __global__ __launch_bounds__(256, 2) void gemm16_kernel(Gemm16Args p) {
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
             const int n = n0 + wc * 64 + ni * 16 + fq * 4;
-            f32x4 v = acc[mi][ni];
-            if (p.bias) {
-                const f32x4 b = *(const f32x4*)(p.bias + n);
-                v += b;
-            }
-            if (p.act == ACT_GELU) {
-                v = gelu_erf_fast4(v);      // the same arithmetic in every GEMM kernel: a tile's bits must not depend on which one its batch size selects
-            } else if (p.act == ACT_RELU) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-            }
-            if (p.residual) {
-                const f32x4 r = *(const f32x4*)(p.residual + (size_t)(m % res_mod) * p.N + n);
-                v += r;
-            }
-            if (p.out32) *(f32x4*)(p.out32 + (size_t)m * p.N + n) = v;
-            if (p.out16) {
-                typename T::vec4 o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = T::from_f32(v[j]);
-                *(typename T::vec4*)(p.out16 + (size_t)m * p.N + n) = o;
-            }
+            gemm16_direct_epilogue<T>(p, acc[mi][ni], m, n, p.act, res_mod);
         }
     }
 }

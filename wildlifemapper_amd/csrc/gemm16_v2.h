@@ -1,6 +1,6 @@
 // 16-bit MFMA GEMM, 256 x BN x 64 tile, 3-deep LDS-DMA ring (gfx950).
 //
-// Same contract and epilogue as gemm16.h, for M % 256 == 0 and N % BN == 0 with
+// Same contract as gemm16.h and the same epilogue (gemm_common.h), for M % 256 == 0 and N % BN == 0 with
 // BN = 128 or 160.  BN = 160 exists for the block GEMMs at 4 tiles per GPU
 // (M = 16384): N = 1280 / 3840 / 5120 give 512 / 1536 / 2048 workgroups, whole
 // multiples of the 256 CUs at one workgroup per CU, where 128- or 256-wide tiles
@@ -28,7 +28,7 @@
 #pragma once
 #include <type_traits>
 
-#include "gemm16.h"
+#include "gemm_common.h"
 
 namespace wm {
 
@@ -170,41 +170,11 @@ template <class T, int BN> struct G2Core {
 #pragma unroll
             for (int ni = 0; ni < C::NT; ++ni) {
                 const int n = n0 + wc * (BN / 2) + ni * 16 + fq * 4;
-                const f32x4 v = finish(p, acc[mi][ni], m, n, res_mod);
-                if (p.out32) *(f32x4*)(p.out32 + (size_t)m * p.N + n) = v;
-                if (p.out16) {
-                    typename T::vec4 o;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) o[j] = T::from_f32(v[j]);
-                    *(typename T::vec4*)(p.out16 + (size_t)m * p.N + n) = o;
-                }
+                gemm16_direct_epilogue<T>(p, acc[mi][ni], m, n, p.act, res_mod);
             }
         }
     }
-    static __device__ __forceinline__ f32x4 finish(const Gemm16Args& p, f32x4 v, int m, int n, int res_mod) {
-        if (p.bias) v += *(const f32x4*)(p.bias + n);
-        if (p.act == ACT_GELU) {
-            v = gelu_erf_fast4(v);      // the same arithmetic in every GEMM kernel: a tile's bits must not depend on which one its batch size selects
-        } else if (p.act == ACT_RELU) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-        }
-        if (p.residual) v += *(const f32x4*)(p.residual + (size_t)(m % res_mod) * p.N + n);
-        return v;
-    }
 };
-
-// grouped tile order: G16_GROUP_M row tiles share each W panel back to back
-template <int BN>
-__device__ __forceinline__ void g2_coords(int t, int tilesM, int tilesN, int& m0, int& n0) {
-    const int per_group = G16_GROUP_M * tilesN;
-    const int group = t / per_group;
-    const int first_m = group * G16_GROUP_M;
-    const int gsz = min(G16_GROUP_M, tilesM - first_m);
-    const int in_group = t - group * per_group;
-    m0 = (first_m + in_group % gsz) * 256;
-    n0 = (in_group / gsz) * BN;
-}
 
 template <class T, int BN>
 __global__ __launch_bounds__(512, 2) void gemm16v2_kernel(Gemm16Args p) {
@@ -212,8 +182,8 @@ __global__ __launch_bounds__(512, 2) void gemm16v2_kernel(Gemm16Args p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     G2Core<T, BN> g;
     g.init(smem, p);
-    int m0, n0;
-    g2_coords<BN>(xcd_remap(blockIdx.x, gridDim.x), p.M / C::BM, p.N / BN, m0, n0);
+    const TileOrigin o = grouped_tile_origin<C::BM, BN>(p.M / C::BM, p.N / BN, blockIdx.x, gridDim.x, G16_GROUP_M);
+    const int m0 = o.m0, n0 = o.n0;
     const int nk = p.K / C::BK;
 
     g.stage(0, m0, n0, 0);

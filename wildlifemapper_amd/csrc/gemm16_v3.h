@@ -1,45 +1,32 @@
-// 16-bit MFMA GEMM, 256 x BN tile with 128 x (BN/WN) per wave, K-steps of 32 (gfx950).
+// 16-bit MFMA GEMM with an implicit-GEMM A operand: the 3x3 convolution and the 16x16 patch embeds without an im2col buffer (gfx950).
 //
-// Measurements on gemm16_v2.h (256x160x64, 64x80 per wave) showed the block GEMMs are bound by the rate at
-// which a CU can pull operand tiles from L2 into LDS (~48 GB/s per CU against a ~70 GB/s ceiling for
-// L2-served LDS fills, MI355X_MICROARCH.md "Indexed rows") and, per tile, by the C write: neither persistent
-// workgroups, nor row-contiguous stores, nor two workgroups per CU moved it.  What does is fewer operand
-// bytes per FLOP.  This kernel doubles the per-wave tile to 128 x 80 (160 accumulator registers) and, with
-// 8 waves as 2(M) x 4(N), the workgroup tile to 256 x 320:
-//      operand bytes per FLOP   256x160: 1/98     256x320: 1/142   (-31 %)
-//      fragment reads per MFMA  0.45 -> 0.325
-// and N = 1280 / 3840 / 5120 at M = 16384 (4 tiles per GPU) still give 256 / 768 / 1024 workgroups: whole
-// rounds of the 256 CUs.  An XCD's 32 co-resident tiles form an 8(M) x 4(N) block of the grouped order, i.e.
-// 2048 x 1280 of C sharing 8 A panels and 4 W panels in one L2.
+//   C[M,N] = A'[M,K] * W[N,K]^T + bias[N] (+ residual[(m % res_mod), N]),   A' gathered from an image / activation by the loader
 //
-//   template <BN, WN>: waves = 2 x WN, per-wave columns BN / WN (80 or 64):
-//      <320,4> block GEMMs          <256,4> N = 256 / 1024 / 2048 (neck, HFC adaptor)
-//      <160,2> / <128,2>            4-wave variants (two workgroups per CU), kept for A/B runs
-//   K-step 32: LDS rows are 64 B; 3-slot ring of (256 + BN) x 64 B (108 KiB at BN = 320).
-//   DMA piece = 16 rows x 64 B; swizzle phys_chunk = chunk ^ ((-(row >> 2)) & 3) on the SOURCE address and
-//   on the ds_read_b128 address (conflict-free lane groups).
-//   AMODE 2 (round 4; im2col-free 16x16 / stride-16 patch embeds, image_encoder.py:386-450): the A tile is gathered from the
-//   16-bit NCHW image, see dma_a.
-//   AMODE 1 (im2col-free 3x3 conv, the neck's second conv image_encoder.py:113-119): the A tile of K-step s
-//   is the 32-channel slice ci0 = (32 s) % C of tap (32 s) / C of the NHWC activation, shifted by the tap's
-//   (dy, dx); the DMA source address is computed per lane and points at a zero page outside the image.
-//   W pieces do not divide evenly over the waves: waves < W_REM issue one more, and wait with their own
-//   counted vmcnt.  Synchronisation as gemm16_v2.h (counted vmcnt + raw s_barrier, DMA of step s+2 after the
-//   barrier, spread between the MFMAs).
+// 256 x BN tile (BN = 320 | 256), 8 waves as 2(M) x 4(N), 128 x BN/4 per wave (8 x NT MFMA 16x16x32 tiles), K-steps of 32:
+//   LDS rows are 64 B; 3-slot ring of (256 + BN) x 64 B (108 KiB at BN = 320).
+//   DMA piece = 16 rows x 64 B; swizzle phys_chunk = chunk ^ ((-(row >> 2)) & 3) on the SOURCE address and on the
+//   ds_read_b128 address (conflict-free lane groups).
+//   W pieces do not divide evenly over the waves: waves < W_REM issue one more, and wait with their own counted vmcnt.
+//   Synchronisation as gemm16_v2.h (counted vmcnt + raw s_barrier, DMA of step s+2 after the barrier, spread between the MFMAs):
+//   all 8 waves run in lockstep.  The tile geometry G3<BN> is shared with gemm16_v5.h, which runs the two wave groups half a
+//   K-step apart and serves every plain A matrix; this kernel keeps the loaders that compute a source address per lane.
+// The A loaders (ALoad):
+//   Conv3x3 (the neck's second conv, image_encoder.py:113-119): the A tile of K-step s is the 32-channel slice ci0 = (32 s) % C
+//     of tap (32 s) / C of the NHWC activation, shifted by the tap's (dy, dx); outside the image the source is a zero page.
+//   PatchEmbed (16x16 / stride-16 patch embeds, image_encoder.py:386-450): the A tile is gathered from the 16-bit NCHW image,
+//     see dma_a.
+// Epilogue: gemm_common.h's direct one.
 #pragma once
 #include <type_traits>
 
-#include "gemm16.h"
-
-#ifndef WM_GEMM_TIMING_BITS
-#define WM_GEMM_TIMING_BITS 0
-#endif
+#include "gemm_common.h"
 
 namespace wm {
 
-template <int BN, int WN> struct G3 {
-    static constexpr int BM = 256, BK = 32, WAVES = 2 * WN, THREADS = 64 * WAVES;
-    static constexpr int WCOLS = BN / WN, NT = WCOLS / 16, MT = 8;
+// tile geometry of the 256 x BN x 32 kernels (this one and gemm16_v5.h): 8 waves as 2(M) x 4(N)
+template <int BN> struct G3 {
+    static constexpr int BM = 256, BK = 32, WAVES = 8, THREADS = 64 * WAVES;
+    static constexpr int WCOLS = BN / 4, NT = WCOLS / 16, MT = 8;
     static constexpr int A_BYTES = BM * 64, W_BYTES = BN * 64;
     static constexpr int STAGE = A_BYTES + W_BYTES;
     static constexpr int LDS = 3 * STAGE;
@@ -49,63 +36,32 @@ template <int BN, int WN> struct G3 {
     static_assert((BM / 16) % WAVES == 0 && WCOLS % 16 == 0, "tile shape");
 };
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N <= 12, "extend the table");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-    else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else if constexpr (N == 11) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-}
+enum class ALoad { Conv3x3, PatchEmbed };
 
-template <class T, int BN, int WN, int AMODE = 0>
-__global__ __launch_bounds__((G3<BN, WN>::THREADS), 2) void gemm16v3_kernel(Gemm16Args p) {
-    using C = G3<BN, WN>;
+template <class T, int BN, ALoad ALOAD>
+__global__ __launch_bounds__((G3<BN>::THREADS), 2) void gemm16v3_kernel(Gemm16Args p) {
+    using C = G3<BN>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave / WN, wc = wave % WN;
+    const int wr = wave >> 2, wc = wave & 3;
     const int fr = lane & 15, fq = lane >> 4;
     const int K = p.K, ns = K / C::BK;
     const char* Ab = (const char*)p.A;
     const char* Wb = (const char*)p.W;
     const bool extra = wave < C::W_REM;                              // this wave issues W_LO + 1 W pieces
-    constexpr bool TB = WM_GEMM_TIMING_BITS != 0;                        // timing experiments (tools/gemm_bench.py), off in the product
-    const bool dbg_nostore = TB && (p.act & 0x100) != 0, dbg_nodma = TB && (p.act & 0x200) != 0;
-    const int act = p.act & 0xff;
+    const int act = p.act & 0xff;                                    // the low byte, as gemm16_v5.h reads it
 
-    // grouped tile order + XCD remap (as gemm16_v2.h)
-    int m0, n0;
-    {
-        const int tilesM = p.M / C::BM, tilesN = p.N / BN;
-        const int t = xcd_remap(blockIdx.x, gridDim.x);
-        const int per_group = G16_GROUP_M * tilesN;
-        const int group = t / per_group;
-        const int first_m = group * G16_GROUP_M;
-        const int gsz = min(G16_GROUP_M, tilesM - first_m);
-        const int in_group = t - group * per_group;
-        m0 = (first_m + in_group % gsz) * C::BM;
-        n0 = (in_group / gsz) * BN;
-    }
+    const int tilesM = p.M / C::BM, tilesN = p.N / BN;
+    const TileOrigin o = grouped_tile_origin<C::BM, BN>(tilesM, tilesN, blockIdx.x, gridDim.x, G16_GROUP_M);
+    const int m0 = o.m0, n0 = o.n0;
 
     // DMA: per-lane part of the source address (row in piece, swizzled chunk); piece bases are wave-uniform
     const unsigned lane_off = (unsigned)(lane >> 2) * (unsigned)(K * 2) + (unsigned)((((lane & 3) ^ ((0 - (lane >> 4)) & 3))) << 4);
     const size_t row_bytes = (size_t)K * 2;
     auto dma_a = [&](int slot, int s, int i) {
         const int seg = wave * C::A_PIECES + i;
-        if constexpr (AMODE == 0) {
-            const char* base = Ab + (size_t)(m0 + seg * 16) * row_bytes + (size_t)s * 64;
-            if (dbg_nodma) base = Ab;
-            __builtin_amdgcn_global_load_lds(base + (dbg_nodma ? (lane_off & 1023u) : lane_off), WM_LDS_PTR(smem + slot * C::STAGE + seg * 1024), 16, 0, 0);
-        } else if constexpr (AMODE == 2) {
+        if constexpr (ALOAD == ALoad::PatchEmbed) {
             // 16 x 16 / stride 16 patch embed without an im2col buffer (image_encoder.py:386-450): A[m][k] with m = (b, py, px) and
             // k = c * 256 + ky * 16 + kx is read straight from the 16-bit NCHW image [B][conv_c][1024][1024].  K-step s covers
             // channel s >> 3, image rows 2 (s & 7) and + 1 of the patch, all 16 kx: the lane's 16-byte chunk `ch` of the 64-byte
@@ -133,8 +89,7 @@ __global__ __launch_bounds__((G3<BN, WN>::THREADS), 2) void gemm16v3_kernel(Gemm
     };
     auto dma_w = [&](int slot, int s, int seg) {
         const char* base = Wb + (size_t)(n0 + seg * 16) * row_bytes + (size_t)s * 64;
-        if (dbg_nodma) base = Wb;
-        __builtin_amdgcn_global_load_lds(base + (dbg_nodma ? (lane_off & 1023u) : lane_off), WM_LDS_PTR(smem + slot * C::STAGE + C::A_BYTES + seg * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(base + lane_off, WM_LDS_PTR(smem + slot * C::STAGE + C::A_BYTES + seg * 1024), 16, 0, 0);
     };
     // pieces every wave issues (P_LO of them), then the remainder piece of the first W_REM waves
     auto stage_uniform = [&](int slot, int s) {
@@ -224,23 +179,7 @@ __global__ __launch_bounds__((G3<BN, WN>::THREADS), 2) void gemm16v3_kernel(Gemm
 #pragma unroll
         for (int ni = 0; ni < C::NT; ++ni) {
             const int n = n0 + wc * C::WCOLS + ni * 16 + fq * 4;
-            f32x4 v = acc[mi][ni];
-            if (p.bias) v += *(const f32x4*)(p.bias + n);
-            if (act == ACT_GELU) {
-                v = gelu_erf_fast4(v);      // the same arithmetic in every GEMM kernel: a tile's bits must not depend on which one its batch size selects
-            } else if (act == ACT_RELU) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-            }
-            if (p.residual) v += *(const f32x4*)(p.residual + (size_t)(m % res_mod) * p.N + n);
-            if (dbg_nostore) { if (v[0] == 12345.678f) p.out16[0] = 1; continue; }
-            if (p.out32) *(f32x4*)(p.out32 + (size_t)m * p.N + n) = v;
-            if (p.out16) {
-                typename T::vec4 o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = T::from_f32(v[j]);
-                *(typename T::vec4*)(p.out16 + (size_t)m * p.N + n) = o;
-            }
+            gemm16_direct_epilogue<T>(p, acc[mi][ni], m, n, act, res_mod);
         }
     }
 }

@@ -1,8 +1,9 @@
 // 16-bit MFMA GEMM, 256 x BN x 32 (BN = 320 | 256), 8 waves x (128 x BN/4): the two wave groups of a
 // workgroup run half a K-step apart (gfx950).
 //
-// gemm16_v3.h runs all 8 waves in lockstep: after each barrier both waves of a SIMD read their fragments and
-// issue their LDS-DMA pieces (~100 issue cycles each) at the same time, and the matrix pipe idles meanwhile;
+// With all 8 waves in lockstep (as gemm16_v3.h runs this tile for its implicit-GEMM loaders), both waves of a SIMD
+// read their fragments and issue their LDS-DMA pieces (~100 issue cycles each) at the same time after each barrier,
+// and the matrix pipe idles meanwhile;
 // with all memory traffic removed it still reaches only ~64 % MFMA utilisation.  Here the workgroup's barrier is
 // used twice per K-step and the upper wave group (waves 4-7, which share SIMDs with waves 0-3) is shifted by one
 // barrier interval:
@@ -15,7 +16,7 @@
 //
 // so each SIMD always has one wave in its MFMA phase while the other reads / issues DMA
 // (cdna_hip_programming.md: the 8-phase template's `if (wr == 1) s_barrier`; MI355X_MICROARCH.md "Two waves
-// per SIMD", item 9).  Ring, swizzle, counted vmcnt and tile order are gemm16_v3.h's; the epilogue (below, at its
+// per SIMD", item 9).  Ring, swizzle and counted vmcnt are gemm16_v3.h's, the tile order and the epilogue arithmetic gemm_common.h's; the epilogue (below, at its
 // code) goes through LDS so that global accesses are row-contiguous, and brings an fp32 residual in by LDS-DMA:
 //   RAW  a wave waits for its own pieces of step s (vmcnt) before X_s; every read of slot s follows X_s.
 //   WAR  slot (s+2)%3 = (s-1)%3 is overwritten after X_s: waves 0-3 read it before Y_s-1, waves 4-7 after
@@ -76,7 +77,7 @@ template <class T, int BN, int NSLOT = 3, bool DBG = false, bool FOLDP = false, 
 __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
     static_assert(!(FOLDC && (FOLDP || DBG)), "the folded-LayerNorm consumer is the plain 16-bit-output kernel");
     static_assert(!SPLIT || FOLDP, "the split-stream epilogue is a form of the statistics-producing one");
-    using C = G3<BN, 4>;
+    using C = G3<BN>;
     constexpr int AHEAD = NSLOT - 1;                       // K-steps of DMA in flight
     // timing experiments of tools/gemm_bench.py (--act 256 / 512 / 1024): compiled in only with -DWM_GEMM_TIMING_BITS=1
     constexpr bool TB = WM_GEMM_TIMING_BITS != 0;
@@ -94,19 +95,8 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
     const char* Wb = (const char*)p.W;
 
     const int tilesM = p.M / C::BM, tilesN = p.N / BN, total_tiles = tilesM * tilesN;
-    auto tile_origin = [&](int tile, int& tm0, int& tn0) {
-        const int t = xcd_remap(tile, total_tiles);
-        const int gm = p.group_m > 0 ? p.group_m : G16_GROUP_M;
-        const int per_group = gm * tilesN;
-        const int group = t / per_group;
-        const int first_m = group * gm;
-        const int gsz = min(gm, tilesM - first_m);
-        const int in_group = t - group * per_group;
-        tm0 = (first_m + in_group % gsz) * C::BM;
-        tn0 = (in_group / gsz) * BN;
-    };
-    int m0, n0;
-    tile_origin(blockIdx.x, m0, n0);
+    const TileOrigin o = grouped_tile_origin<C::BM, BN>(tilesM, tilesN, blockIdx.x, total_tiles, p.group_m);
+    const int m0 = o.m0, n0 = o.n0;
 
     const unsigned lane_off = (unsigned)(lane >> 2) * (unsigned)(K * 2) + (unsigned)((((lane & 3) ^ ((0 - (lane >> 4)) & 3))) << 4);
     const size_t row_bytes = (size_t)K * 2;
@@ -119,7 +109,7 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
         asm volatile("" : "+s"(b));
         return (const char*)b;
     };
-    auto stage_at = [&](int slot, int s, auto extra_tag, int m0, int n0) {     // (m0, n0): the tile the pieces belong to
+    auto stage = [&](int slot, int s, auto extra_tag) {
         constexpr bool EXTRA = decltype(extra_tag)::value;
         if (dbg_noissue && s >= AHEAD) return;
         if (dbg_nodma) s = 0;
@@ -139,18 +129,16 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
             __builtin_amdgcn_global_load_lds(base + (p.w_packed ? (unsigned)lane * 16u : lane_off), WM_LDS_PTR(smem + slot * C::STAGE + C::A_BYTES + seg * 1024), 16, 0, 0);
         }
     };
-    auto stage = [&](int slot, int s, auto extra_tag) { stage_at(slot, s, extra_tag, m0, n0); };
 
     const int frag_off = fr * 64 + ((fq ^ ((0 - (fr >> 2)) & 3)) << 4);
-    const int rd_a_k = (wr * 128) * 64 + frag_off;
-    const int rd_w_k = C::A_BYTES + (wc * C::WCOLS) * 64 + frag_off;
+    const int rd_a = (wr * 128) * 64 + frag_off;
+    const int rd_w = C::A_BYTES + (wc * C::WCOLS) * 64 + frag_off;
 
     f32x4 acc[C::MT][C::NT];
     typename T::vec8 wf[C::NT], af[C::MT];
 
     auto read_frags = [&](int slot) {
         const char* sS = smem + slot * C::STAGE;
-        const int rd_a = rd_a_k, rd_w = rd_w_k;
         af[0] = *(const typename T::vec8*)(sS + rd_a);
 #pragma unroll
         for (int i = 0; i < C::NT; ++i) wf[i] = *(const typename T::vec8*)(sS + rd_w + i * 1024);
@@ -190,12 +178,10 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
     // fp32 residual (proj / lin2: out = residual + A W^T + b): the residual tile comes in by LDS-DMA, 32 rows (16 per
     // wave group) per epilogue pass, one pass ahead; pass 0 is requested at the start of the tile and lands beside the ring.
     constexpr int RES_BYTES = 32 * BN * 4;
-    constexpr int EPI_BASE = 0;                                                   // staging of the 16-bit / fp32 epilogues
-    constexpr int RES_STG = 0;                                                    // staging of the residual epilogue
     constexpr int RES_L1 = 45056;
     constexpr int RES_L0 = NSLOT * C::STAGE;
     constexpr int LDS_TOTAL = NSLOT * C::STAGE + RES_BYTES;
-    static_assert(RES_STG + 32 * (BN * 4 + 16) <= RES_L1 && RES_L0 >= NSLOT * C::STAGE && RES_L0 + RES_BYTES <= LDS_TOTAL &&
+    static_assert(32 * (BN * 4 + 16) <= RES_L1 && RES_L0 >= NSLOT * C::STAGE && RES_L0 + RES_BYTES <= LDS_TOTAL &&
                   RES_L1 + RES_BYTES <= NSLOT * C::STAGE && RES_L1 % 16 == 0 && RES_L0 % 16 == 0,
                   "epilogue LDS map");
     const int res_mod = p.res_mod > 0 ? p.res_mod : p.M;
@@ -216,13 +202,13 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
             }
         } else {
 #pragma unroll
-        for (int i = 0; i < RP_PW; ++i) {
-            const int piece = wave * RP_PW + i;
-            const int c = piece * 64 + lane, r = c / RP_CPR, ch = c - r * RP_CPR;
-            int m = m0 + (r >> 4) * 128 + q * 16 + (r & 15);
-            if (res_wrap) m %= res_mod;
-            __builtin_amdgcn_global_load_lds((const char*)(p.residual + (size_t)m * p.N + n0 + ch * 4), WM_LDS_PTR(dst + piece * 1024), 16, 0, 0);
-        }
+            for (int i = 0; i < RP_PW; ++i) {
+                const int piece = wave * RP_PW + i;
+                const int c = piece * 64 + lane, r = c / RP_CPR, ch = c - r * RP_CPR;
+                int m = m0 + (r >> 4) * 128 + q * 16 + (r & 15);
+                if (res_wrap) m %= res_mod;
+                __builtin_amdgcn_global_load_lds((const char*)(p.residual + (size_t)m * p.N + n0 + ch * 4), WM_LDS_PTR(dst + piece * 1024), 16, 0, 0);
+            }
         }
     };
 
@@ -310,27 +296,24 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
     // 128 rows (16-bit output) or 64 rows (fp32 output), each thread then moves 16-byte chunks that are consecutive
     // along the row, and the residual is read the same way.
     const int act = p.act & 0xff;
-    const int tid_e = tid, fr_e = fr, fq_e = fq;
     f32x4 bias_v[FOLDC ? 1 : C::NT];
     if constexpr (!FOLDC) {
 #pragma unroll
         for (int ni = 0; ni < C::NT; ++ni)
-            bias_v[ni] = p.bias ? *(const f32x4*)(p.bias + n0 + wc * C::WCOLS + ni * 16 + fq_e * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+            bias_v[ni] = p.bias ? *(const f32x4*)(p.bias + n0 + wc * C::WCOLS + ni * 16 + fq * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
     if constexpr (FOLDC) {
-        {
-            if (tid < C::BM) {                              // one row per thread: Chan combination of its column-tile partials
-                const float2* raw = (const float2*)(smem + FOLD_RAW) + tid * p.fold_ntile;
-                float mk[8], qk[8];
+        if (tid < C::BM) {                                  // one row per thread: Chan combination of its column-tile partials
+            const float2* raw = (const float2*)(smem + FOLD_RAW) + tid * p.fold_ntile;
+            float mk[8], qk[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    mk[i] = qk[i] = 0.f;
-                    if (i < p.fold_ntile) { const float2 t = raw[i]; mk[i] = t.x; qk[i] = t.y; }
-                }
-                float rstd;
-                const float mean = ln_combine(mk, qk, p.fold_ntile, p.fold_bn, (float)p.K, p.fold_eps, rstd);
-                *(float2*)(smem + FOLD_MR + tid * 8) = make_float2(mean, rstd);
+            for (int i = 0; i < 8; ++i) {
+                mk[i] = qk[i] = 0.f;
+                if (i < p.fold_ntile) { const float2 t = raw[i]; mk[i] = t.x; qk[i] = t.y; }
             }
+            float rstd;
+            const float mean = ln_combine(mk, qk, p.fold_ntile, p.fold_bn, (float)p.K, p.fold_eps, rstd);
+            *(float2*)(smem + FOLD_MR + tid * 8) = make_float2(mean, rstd);
         }
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);                     // lgkmcnt(0): this wave's fragment reads are back
@@ -339,216 +322,207 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
     // (the epilogue's staging never touches FOLD_RAW / FOLD_MR / FOLD_C)
     // one straight-line instance per activation (a per-fragment runtime branch costs more than the stores)
     auto epilogue = [&](auto act_tag, auto fold_tag) {
-    constexpr int ACT = decltype(act_tag)::value;
-    constexpr bool FOLD = decltype(fold_tag)::value && FOLDC;
-    const int tid = tid_e, fr = fr_e, fq = fq_e;           // shadow the kernel-scope values (see tid_e)
-    auto finish = [&](f32x4 v, int ni) {
-        if constexpr (!FOLD) v += bias_v[ni];              // FOLD: the caller has applied rstd (acc - mean c1) + c2
-        if constexpr (ACT == ACT_GELU) {
-            v = gelu_erf_fast4(v);
-        } else if constexpr (ACT == ACT_RELU) {
+        constexpr int ACT = decltype(act_tag)::value;
+        constexpr bool FOLD = decltype(fold_tag)::value && FOLDC;
+        auto finish = [&](f32x4 v, int ni) {
+            if constexpr (!FOLD) v += bias_v[ni];              // FOLD: the caller has applied rstd (acc - mean c1) + c2
+            return gemm_act<ACT>(v);
+        };
+        if constexpr (FOLDP) {
+            // ---- fp32 + residual, per-row partial LayerNorm statistics, 16-bit copy in LDS-image order (see "Folded LayerNorm") ----
+            constexpr int ROWB = BN * 4 + 16, CPT = RP_CPR / 16;
+            const int r = tid >> 4, l16 = tid & 15;              // row of the pass, position in the row's 16-lane group
+            const int ntile = p.N / BN, nt = n0 / BN;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-        }
-        return v;
-    };
-    if constexpr (FOLDP) {
-        // ---- fp32 + residual, per-row partial LayerNorm statistics, 16-bit copy in LDS-image order (see "Folded LayerNorm") ----
-        constexpr int ROWB = BN * 4 + 16, CPT = RP_CPR / 16;
-        const int r = tid >> 4, l16 = tid & 15;              // row of the pass, position in the row's 16-lane group
-        const int ntile = p.N / BN, nt = n0 / BN;
+            for (int q = 0; q < C::MT; ++q) {
+                if (q + 1 < C::MT) res_dma(q + 1);
 #pragma unroll
-        for (int q = 0; q < C::MT; ++q) {
-            if (q + 1 < C::MT) res_dma(q + 1);
-#pragma unroll
-            for (int ni = 0; ni < C::NT; ++ni)
-                *(f32x4*)(smem + RES_STG + (wr * 16 + fr) * ROWB + (wc * C::WCOLS + ni * 16 + fq * 4) * 4) = finish(acc[q][ni], ni);
-            if (q + 1 < C::MT) wait_vmcnt<RP_PW>(); else wait_vmcnt<0>();
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            barrier();
-            const char* land = smem + ((q & 1) ? RES_L1 : RES_L0);
-            const int m = m0 + (r >> 4) * 128 + q * 16 + (r & 15);
-            f32x4 v[CPT];
-            float amax = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < CPT; ++kk) {
-                const int ch = l16 + 16 * kk;
-                f32x4 res;
-                if constexpr (SPLIT) {
-                    // the landed planes are in LDS-image order: piece (strip, kt), position = row * 4 + swizzled chunk
-                    const int rr = r & 15, kt = ch >> 3, pos = rr * 4 + ((((ch & 7) >> 1)) ^ ((0 - (rr >> 2)) & 3));
-                    const int off = (((r >> 4) * SP_KT + kt) << 10) + pos * 16 + (ch & 1) * 8;
-                    const typename T::vec4 h4 = *(const typename T::vec4*)(land + off);
-                    const f16x4 l4 = *(const f16x4*)(land + 2 * SP_KT * 1024 + off);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) res[j] = T::to_f32(h4[j]) + (float)l4[j];
-                } else {
-                    res = *(const f32x4*)(land + (r * RP_CPR + ch) * 16);
-                }
-                v[kk] = *(const f32x4*)(smem + RES_STG + r * ROWB + ch * 16) + res;
-                if (p.out32) *(f32x4*)(p.out32 + (size_t)m * p.N + n0 + ch * 4) = v[kk];
-                if constexpr (std::is_same<T, FP16>::value) amax = fmaxf(fmaxf(fmaxf(fabsf(v[kk][0]), fabsf(v[kk][1])), fmaxf(fabsf(v[kk][2]), fabsf(v[kk][3]))), amax);
-            }
-            float mean, m2;
-            ln_partial16<CPT>(v, 1.0f / BN, mean, m2);
-            if (l16 == 0) *(float2*)(p.st_stats + ((size_t)m * ntile + nt) * 2) = make_float2(mean, m2);
-            if constexpr (std::is_same<T, FP16>::value) {
-                if (amax >= 65504.f && p.overflow) *(volatile int*)p.overflow = 1;     // the fp16 plane clamps: loud on the host side (wm_overflow_count)
-            }
-            // a wave holds 4 consecutive rows: per K-step of the copy its 16 lanes x 4 rows write 256 contiguous bytes
-#pragma unroll
-            for (int kk = 0; kk < CPT; ++kk) {
-                typename T::vec4 o;
-                f16x4 lo;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    o[j] = T::from_f32(v[kk][j]);
-                    lo[j] = FP16::from_f32(v[kk][j] - T::to_f32(o[j]));
-                }
-                const int64_t e = lds_image_index(m, n0 + (l16 + 16 * kk) * 4, p.N);
-                *(typename T::vec4*)(p.out16 + e) = o;
-                if (SPLIT || p.out_lo) *(f16x4*)(p.out_lo + e) = lo;
-            }
-            if (q + 1 < C::MT) {
+                for (int ni = 0; ni < C::NT; ++ni)
+                    *(f32x4*)(smem + (wr * 16 + fr) * ROWB + (wc * C::WCOLS + ni * 16 + fq * 4) * 4) = finish(acc[q][ni], ni);
+                if (q + 1 < C::MT) wait_vmcnt<RP_PW>(); else wait_vmcnt<0>();
                 __builtin_amdgcn_s_waitcnt(0xc07f);
                 barrier();
+                const char* land = smem + ((q & 1) ? RES_L1 : RES_L0);
+                const int m = m0 + (r >> 4) * 128 + q * 16 + (r & 15);
+                f32x4 v[CPT];
+                float amax = 0.f;
+#pragma unroll
+                for (int kk = 0; kk < CPT; ++kk) {
+                    const int ch = l16 + 16 * kk;
+                    f32x4 res;
+                    if constexpr (SPLIT) {
+                        // the landed planes are in LDS-image order: piece (strip, kt), position = row * 4 + swizzled chunk
+                        const int rr = r & 15, kt = ch >> 3, pos = rr * 4 + ((((ch & 7) >> 1)) ^ ((0 - (rr >> 2)) & 3));
+                        const int off = (((r >> 4) * SP_KT + kt) << 10) + pos * 16 + (ch & 1) * 8;
+                        const typename T::vec4 h4 = *(const typename T::vec4*)(land + off);
+                        const f16x4 l4 = *(const f16x4*)(land + 2 * SP_KT * 1024 + off);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) res[j] = T::to_f32(h4[j]) + (float)l4[j];
+                    } else {
+                        res = *(const f32x4*)(land + (r * RP_CPR + ch) * 16);
+                    }
+                    v[kk] = *(const f32x4*)(smem + r * ROWB + ch * 16) + res;
+                    if (p.out32) *(f32x4*)(p.out32 + (size_t)m * p.N + n0 + ch * 4) = v[kk];
+                    if constexpr (std::is_same<T, FP16>::value) amax = fmaxf(fmaxf(fmaxf(fabsf(v[kk][0]), fabsf(v[kk][1])), fmaxf(fabsf(v[kk][2]), fabsf(v[kk][3]))), amax);
+                }
+                float mean, m2;
+                ln_partial16<CPT>(v, 1.0f / BN, mean, m2);
+                if (l16 == 0) *(float2*)(p.st_stats + ((size_t)m * ntile + nt) * 2) = make_float2(mean, m2);
+                if constexpr (std::is_same<T, FP16>::value) {
+                    if (amax >= 65504.f && p.overflow) *(volatile int*)p.overflow = 1;     // the fp16 plane clamps: loud on the host side (wm_overflow_count)
+                }
+                // a wave holds 4 consecutive rows: per K-step of the copy its 16 lanes x 4 rows write 256 contiguous bytes
+#pragma unroll
+                for (int kk = 0; kk < CPT; ++kk) {
+                    typename T::vec4 o;
+                    f16x4 lo;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        o[j] = T::from_f32(v[kk][j]);
+                        lo[j] = FP16::from_f32(v[kk][j] - T::to_f32(o[j]));
+                    }
+                    const int64_t e = lds_image_index(m, n0 + (l16 + 16 * kk) * 4, p.N);
+                    *(typename T::vec4*)(p.out16 + e) = o;
+                    if (SPLIT || p.out_lo) *(f16x4*)(p.out_lo + e) = lo;
+                }
+                if (q + 1 < C::MT) {
+                    __builtin_amdgcn_s_waitcnt(0xc07f);
+                    barrier();
+                }
             }
-        }
-    } else if (p.out32 == nullptr && p.residual == nullptr) {
-        // 16-bit staging: 2 passes of 4 row-fragments; LDS row = BN * 2 + 16 bytes
-        constexpr int ROWB = BN * 2 + 16, CPR = BN * 2 / 16, MTP = 4, ROWS = 2 * MTP * 16;
-        static_assert(EPI_BASE + ROWS * ROWB <= LDS_TOTAL && (ROWS * CPR) % 512 == 0, "epilogue staging");
-        auto epi_sync = [&]() { __syncthreads(); };
+        } else if (p.out32 == nullptr && p.residual == nullptr) {
+            // 16-bit staging: 2 passes of 4 row-fragments; LDS row = BN * 2 + 16 bytes
+            constexpr int ROWB = BN * 2 + 16, CPR = BN * 2 / 16, MTP = 4, ROWS = 2 * MTP * 16;
+            static_assert(ROWS * ROWB <= LDS_TOTAL && (ROWS * CPR) % 512 == 0, "epilogue staging");
 #pragma unroll
-        for (int q = 0; q < C::MT / MTP; ++q) {
-            if constexpr (FOLD) {
-                // LayerNorm folded into this GEMM: rstd (acc - mean c1) + c2.  (mean, rstd) of the pass's MTP rows and, per column
-                // fragment, c1 / c2 are read from LDS once and reused (28 reads per lane and tile instead of 120)
-                float2 mr[MTP];
+            for (int q = 0; q < C::MT / MTP; ++q) {
+                if constexpr (FOLD) {
+                    // LayerNorm folded into this GEMM: rstd (acc - mean c1) + c2.  (mean, rstd) of the pass's MTP rows and, per column
+                    // fragment, c1 / c2 are read from LDS once and reused (28 reads per lane and tile instead of 120)
+                    float2 mr[MTP];
 #pragma unroll
-                for (int mm = 0; mm < MTP; ++mm) mr[mm] = *(const float2*)(smem + FOLD_MR + (wr * 128 + (q * MTP + mm) * 16 + fr) * 8);
+                    for (int mm = 0; mm < MTP; ++mm) mr[mm] = *(const float2*)(smem + FOLD_MR + (wr * 128 + (q * MTP + mm) * 16 + fr) * 8);
 #pragma unroll
-                for (int ni = 0; ni < C::NT; ++ni) {
-                    const f32x4 c1 = *(const f32x4*)(smem + FOLD_C + (wc * C::WCOLS + ni * 16 + fq * 4) * 4);
-                    const f32x4 c2 = *(const f32x4*)(smem + FOLD_C + BN * 4 + (wc * C::WCOLS + ni * 16 + fq * 4) * 4);
+                    for (int ni = 0; ni < C::NT; ++ni) {
+                        const f32x4 c1 = *(const f32x4*)(smem + FOLD_C + (wc * C::WCOLS + ni * 16 + fq * 4) * 4);
+                        const f32x4 c2 = *(const f32x4*)(smem + FOLD_C + BN * 4 + (wc * C::WCOLS + ni * 16 + fq * 4) * 4);
 #pragma unroll
-                    for (int mm = 0; mm < MTP; ++mm) {
-                        f32x4 v = acc[q * MTP + mm][ni];
+                        for (int mm = 0; mm < MTP; ++mm) {
+                            f32x4 v = acc[q * MTP + mm][ni];
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] = fmaf(fmaf(-mr[mm].x, c1[j], v[j]), mr[mm].y, c2[j]);
-                        v = finish(v, ni);
+                            for (int j = 0; j < 4; ++j) v[j] = fmaf(fmaf(-mr[mm].x, c1[j], v[j]), mr[mm].y, c2[j]);
+                            v = finish(v, ni);
+                            typename T::vec4 o;
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) o[j] = T::from_f32(v[j]);
+                            *(typename T::vec4*)(smem + (wr * MTP * 16 + mm * 16 + fr) * ROWB + (wc * C::WCOLS + ni * 16 + fq * 4) * 2) = o;
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int mm = 0; mm < MTP; ++mm)
+#pragma unroll
+                        for (int ni = 0; ni < C::NT; ++ni) {
+                            const f32x4 v = finish(acc[q * MTP + mm][ni], ni);
+                            typename T::vec4 o;
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) o[j] = T::from_f32(v[j]);
+                            *(typename T::vec4*)(smem + (wr * MTP * 16 + mm * 16 + fr) * ROWB + (wc * C::WCOLS + ni * 16 + fq * 4) * 2) = o;
+                        }
+                }
+                __syncthreads();
+                if constexpr (DBG) { if (q < 2) we[1 + 2 * q] = wall_clock64(); }
+                if (p.out_packed) {
+                    // the output is the next GEMM's A operand: written in LDS-image order.  A wave moves one 16 x 32 tile (1 KiB,
+                    // contiguous in memory) per iteration: lane l = position l of the piece = row l >> 2, logical chunk
+                    // (l & 3) ^ ((-(l >> 4)) & 3) of the staged rows.
+                    constexpr int KT = BN / 32;
+                    static_assert((ROWS / 16) * KT * 64 == ROWS * CPR, "packed epilogue");
+#pragma unroll
+                    for (int it = 0; it < ROWS * CPR / 512; ++it) {
+                        const int tile = it * 8 + wave, rt = tile / KT, kt = tile - rt * KT;
+                        const int l = tid & 63, lc = (l & 3) ^ ((0 - (l >> 4)) & 3);
+                        const f32x4 v = *(const f32x4*)(smem + (rt * 16 + (l >> 2)) * ROWB + (kt * 4 + lc) * 16);
+                        const int mt = (m0 + (rt / MTP) * 128 + q * MTP * 16 + (rt % MTP) * 16) >> 4;
+                        if (!dbg_nostore) *(f32x4*)((char*)p.out16 + ((size_t)mt * (p.N >> 5) + (n0 >> 5) + kt) * 1024 + l * 16) = v;
+                    }
+                } else {
+#pragma unroll
+                    for (int it = 0; it < ROWS * CPR / 512; ++it) {
+                        const int c = it * 512 + tid, r = c / CPR, ch = c - r * CPR;
+                        const int m = m0 + (r / (MTP * 16)) * 128 + q * MTP * 16 + (r % (MTP * 16));
+                        const f32x4 v = *(const f32x4*)(smem + r * ROWB + ch * 16);
+                        if (!dbg_nostore) *(f32x4*)((char*)p.out16 + ((size_t)m * p.N + n0) * 2 + ch * 16) = v;
+                    }
+                }
+                if constexpr (DBG) { if (q < 2) we[2 + 2 * q] = wall_clock64(); }
+                if (q + 1 < C::MT / MTP) __syncthreads();
+            }
+        } else if (p.residual != nullptr) {
+            // fp32 + residual: 8 passes of one row-fragment (32 rows).  Pass q: request the residual rows of pass q + 1,
+            // stage this pass's accumulators, wait for this wave's residual pieces of pass q (everything but the DMA
+            // just issued is complete: the C stores of pass q - 1 are older and have had a pass to be acknowledged),
+            // barrier, then add and store 16-byte chunks along the rows.
+            constexpr int ROWB = BN * 4 + 16, NIT = 32 * RP_CPR / 512;
+            static_assert((32 * RP_CPR) % 512 == 0, "epilogue staging");
+#pragma unroll
+            for (int q = 0; q < C::MT; ++q) {
+                if (q + 1 < C::MT) res_dma(q + 1);
+#pragma unroll
+                for (int ni = 0; ni < C::NT; ++ni)
+                    *(f32x4*)(smem + (wr * 16 + fr) * ROWB + (wc * C::WCOLS + ni * 16 + fq * 4) * 4) = finish(acc[q][ni], ni);
+                if (q + 1 < C::MT) wait_vmcnt<RP_PW>(); else wait_vmcnt<0>();
+                __builtin_amdgcn_s_waitcnt(0xc07f);             // lgkmcnt(0): staging writes done
+                barrier();
+                const char* land = smem + ((q & 1) ? RES_L1 : RES_L0);
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    const int c = it * 512 + tid, r = c / RP_CPR, ch = c - r * RP_CPR;
+                    const int m = m0 + (r >> 4) * 128 + q * 16 + (r & 15);
+                    const f32x4 v = *(const f32x4*)(smem + r * ROWB + ch * 16) + *(const f32x4*)(land + c * 16);
+                    if (dbg_nostore) { if (v[0] == 12345.678f) p.out16[0] = 1; continue; }
+                    if (p.out32) *(f32x4*)(p.out32 + (size_t)m * p.N + n0 + ch * 4) = v;
+                    if (p.out16) {
                         typename T::vec4 o;
 #pragma unroll
                         for (int j = 0; j < 4; ++j) o[j] = T::from_f32(v[j]);
-                        *(typename T::vec4*)(smem + EPI_BASE + (wr * MTP * 16 + mm * 16 + fr) * ROWB + (wc * C::WCOLS + ni * 16 + fq * 4) * 2) = o;
+                        *(typename T::vec4*)(p.out16 + (size_t)m * p.N + n0 + ch * 4) = o;
                     }
                 }
-            } else {
-#pragma unroll
-            for (int mm = 0; mm < MTP; ++mm)
-#pragma unroll
-                for (int ni = 0; ni < C::NT; ++ni) {
-                    const f32x4 v = finish(acc[q * MTP + mm][ni], ni);
-                    typename T::vec4 o;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) o[j] = T::from_f32(v[j]);
-                    *(typename T::vec4*)(smem + EPI_BASE + (wr * MTP * 16 + mm * 16 + fr) * ROWB + (wc * C::WCOLS + ni * 16 + fq * 4) * 2) = o;
+                if (q + 1 < C::MT) {
+                    __builtin_amdgcn_s_waitcnt(0xc07f);         // the LDS reads of this pass are back before anyone overwrites
+                    barrier();
                 }
             }
-            epi_sync();
-            if constexpr (DBG) { if (q < 2) we[1 + 2 * q] = wall_clock64(); }
-            if (p.out_packed) {
-                // the output is the next GEMM's A operand: written in LDS-image order.  A wave moves one 16 x 32 tile (1 KiB,
-                // contiguous in memory) per iteration: lane l = position l of the piece = row l >> 2, logical chunk
-                // (l & 3) ^ ((-(l >> 4)) & 3) of the staged rows.
-                constexpr int KT = BN / 32;
-                static_assert((ROWS / 16) * KT * 64 == ROWS * CPR, "packed epilogue");
+        } else {
+            // fp32 staging: 4 passes of 2 row-fragments; LDS row = BN * 4 + 16 bytes
+            constexpr int ROWB = BN * 4 + 16, CPR = BN * 4 / 16, MTP = 2, ROWS = 2 * MTP * 16;
+            static_assert(ROWS * ROWB <= LDS_TOTAL && (ROWS * CPR) % 512 == 0, "epilogue staging");
+#pragma unroll
+            for (int q = 0; q < C::MT / MTP; ++q) {
+#pragma unroll
+                for (int mm = 0; mm < MTP; ++mm)
+#pragma unroll
+                    for (int ni = 0; ni < C::NT; ++ni)
+                        *(f32x4*)(smem + (wr * MTP * 16 + mm * 16 + fr) * ROWB + (wc * C::WCOLS + ni * 16 + fq * 4) * 4) = finish(acc[q * MTP + mm][ni], ni);
+                __syncthreads();
 #pragma unroll
                 for (int it = 0; it < ROWS * CPR / 512; ++it) {
-                    const int tile = it * 8 + wave, rt = tile / KT, kt = tile - rt * KT;
-                    const int l = tid & 63, lc = (l & 3) ^ ((0 - (l >> 4)) & 3);
-                    const f32x4 v = *(const f32x4*)(smem + EPI_BASE + (rt * 16 + (l >> 2)) * ROWB + (kt * 4 + lc) * 16);
-                    const int mt = (m0 + (rt / MTP) * 128 + q * MTP * 16 + (rt % MTP) * 16) >> 4;
-                    if (!dbg_nostore) *(f32x4*)((char*)p.out16 + ((size_t)mt * (p.N >> 5) + (n0 >> 5) + kt) * 1024 + l * 16) = v;
+                    const int c = it * 512 + tid, r = c / CPR, ch = c - r * CPR;
+                    const int m = m0 + (r / (MTP * 16)) * 128 + q * MTP * 16 + (r % (MTP * 16));
+                    f32x4 v = *(const f32x4*)(smem + r * ROWB + ch * 16);
+                    if (dbg_nostore) { if (v[0] == 12345.678f) p.out16[0] = 1; continue; }
+                    if (p.out32) *(f32x4*)(p.out32 + (size_t)m * p.N + n0 + ch * 4) = v;
+                    if (p.out16) {
+                        typename T::vec4 o;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) o[j] = T::from_f32(v[j]);
+                        *(typename T::vec4*)(p.out16 + (size_t)m * p.N + n0 + ch * 4) = o;
+                    }
                 }
-            } else {
-#pragma unroll
-            for (int it = 0; it < ROWS * CPR / 512; ++it) {
-                const int c = it * 512 + tid, r = c / CPR, ch = c - r * CPR;
-                const int m = m0 + (r / (MTP * 16)) * 128 + q * MTP * 16 + (r % (MTP * 16));
-                const f32x4 v = *(const f32x4*)(smem + EPI_BASE + r * ROWB + ch * 16);
-                if (!dbg_nostore) *(f32x4*)((char*)p.out16 + ((size_t)m * p.N + n0) * 2 + ch * 16) = v;
-            }
-            }
-            if constexpr (DBG) { if (q < 2) we[2 + 2 * q] = wall_clock64(); }
-            if (q + 1 < C::MT / MTP) epi_sync();
-        }
-    } else if (p.residual != nullptr) {
-        // fp32 + residual: 8 passes of one row-fragment (32 rows).  Pass q: request the residual rows of pass q + 1,
-        // stage this pass's accumulators, wait for this wave's residual pieces of pass q (everything but the DMA
-        // just issued is complete: the C stores of pass q - 1 are older and have had a pass to be acknowledged),
-        // barrier, then add and store 16-byte chunks along the rows.
-        constexpr int ROWB = BN * 4 + 16, NIT = 32 * RP_CPR / 512;
-        static_assert((32 * RP_CPR) % 512 == 0, "epilogue staging");
-#pragma unroll
-        for (int q = 0; q < C::MT; ++q) {
-            if (q + 1 < C::MT) res_dma(q + 1);
-#pragma unroll
-            for (int ni = 0; ni < C::NT; ++ni)
-                *(f32x4*)(smem + RES_STG + (wr * 16 + fr) * ROWB + (wc * C::WCOLS + ni * 16 + fq * 4) * 4) = finish(acc[q][ni], ni);
-            if (q + 1 < C::MT) wait_vmcnt<RP_PW>(); else wait_vmcnt<0>();
-            __builtin_amdgcn_s_waitcnt(0xc07f);             // lgkmcnt(0): staging writes done
-            barrier();
-            const char* land = smem + ((q & 1) ? RES_L1 : RES_L0);
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int c = it * 512 + tid, r = c / RP_CPR, ch = c - r * RP_CPR;
-                const int m = m0 + (r >> 4) * 128 + q * 16 + (r & 15);
-                const f32x4 v = *(const f32x4*)(smem + RES_STG + r * ROWB + ch * 16) + *(const f32x4*)(land + c * 16);
-                if (dbg_nostore) { if (v[0] == 12345.678f) p.out16[0] = 1; continue; }
-                if (p.out32) *(f32x4*)(p.out32 + (size_t)m * p.N + n0 + ch * 4) = v;
-                if (p.out16) {
-                    typename T::vec4 o;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) o[j] = T::from_f32(v[j]);
-                    *(typename T::vec4*)(p.out16 + (size_t)m * p.N + n0 + ch * 4) = o;
-                }
-            }
-            if (q + 1 < C::MT) {
-                __builtin_amdgcn_s_waitcnt(0xc07f);         // the LDS reads of this pass are back before anyone overwrites
-                barrier();
+                if (q + 1 < C::MT / MTP) __syncthreads();
             }
         }
-    } else {
-        // fp32 staging: 4 passes of 2 row-fragments; LDS row = BN * 4 + 16 bytes
-        constexpr int ROWB = BN * 4 + 16, CPR = BN * 4 / 16, MTP = 2, ROWS = 2 * MTP * 16;
-        static_assert(EPI_BASE + ROWS * ROWB <= LDS_TOTAL && (ROWS * CPR) % 512 == 0, "epilogue staging");
-        auto epi_sync = [&]() { __syncthreads(); };
-#pragma unroll
-        for (int q = 0; q < C::MT / MTP; ++q) {
-#pragma unroll
-            for (int mm = 0; mm < MTP; ++mm)
-#pragma unroll
-                for (int ni = 0; ni < C::NT; ++ni)
-                    *(f32x4*)(smem + EPI_BASE + (wr * MTP * 16 + mm * 16 + fr) * ROWB + (wc * C::WCOLS + ni * 16 + fq * 4) * 4) = finish(acc[q * MTP + mm][ni], ni);
-            epi_sync();
-#pragma unroll
-            for (int it = 0; it < ROWS * CPR / 512; ++it) {
-                const int c = it * 512 + tid, r = c / CPR, ch = c - r * CPR;
-                const int m = m0 + (r / (MTP * 16)) * 128 + q * MTP * 16 + (r % (MTP * 16));
-                f32x4 v = *(const f32x4*)(smem + EPI_BASE + r * ROWB + ch * 16);
-                if (dbg_nostore) { if (v[0] == 12345.678f) p.out16[0] = 1; continue; }
-                if (p.out32) *(f32x4*)(p.out32 + (size_t)m * p.N + n0 + ch * 4) = v;
-                if (p.out16) {
-                    typename T::vec4 o;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) o[j] = T::from_f32(v[j]);
-                    *(typename T::vec4*)(p.out16 + (size_t)m * p.N + n0 + ch * 4) = o;
-                }
-            }
-            if (q + 1 < C::MT / MTP) epi_sync();
-        }
-    }
     };
     if constexpr (FOLDP) {                                    // (SPLIT is a form of it)
         epilogue(std::integral_constant<int, ACT_NONE>{}, std::false_type{});

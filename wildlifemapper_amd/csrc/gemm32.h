@@ -9,7 +9,7 @@
 // 64x64x32 tile per 256-thread workgroup, 4 waves as 2x2, one 32x32 MFMA tile each.
 #pragma once
 #include "wm_common.h"
-#include "gemm16.h"   // ACT_* enum
+#include "gemm_common.h"   // ACT_* enum
 
 namespace wm {
 

@@ -20,7 +20,7 @@
 // 64-deep MFMA step in its 32 operand bytes; C/D as every 32x32 MFMA: col = l & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).
 // Operand roles are swapped as in gemm16_v5.h (W fragment as the A operand), so a lane holds 4 consecutive n of one row m.
 #pragma once
-#include "gemm16_v5.h"
+#include "gemm_common.h"
 #include "misc_kernels.h"
 
 #ifndef WM_GEMM8_GELU
@@ -54,25 +54,24 @@ struct Gemm8Args {
     u16* out_lo;
 };
 
-// BKB = bytes (= fp8 elements) of K per LDS step: 128 (two MFMAs deep, 2 slots of 64 KiB, DMA issued after X_s) or
-// 64 (one MFMA deep, 4 slots of 32 KiB, three K-steps of DMA in flight, each wave's pieces issued between the MFMAs of its
-// own MFMA interval).  Measured (tools/gemm8_bench.py, B = 16): see DESIGN.md section 5.
-template <int BKB_> struct G8 {
-    static constexpr int BM = 256, BN = 256, BKB = BKB_, NSLOT = BKB_ == 128 ? 2 : 4;
+// K-step = BKB = 128 bytes (= fp8 elements): two MFMAs deep, 2 slots of 64 KiB, DMA issued after X_s.  (A 64-byte step -- one MFMA
+// deep, 4 slots of 32 KiB, three K-steps of DMA in flight -- measured equal or 1-3 % slower: tools/experiments/gemm8_bk64.h,
+// DESIGN.md section 5.)
+struct G8 {
+    static constexpr int BM = 256, BN = 256, BKB = 128, NSLOT = 2;
     static constexpr int A_BYTES = BM * BKB, W_BYTES = BN * BKB, STAGE = A_BYTES + W_BYTES;
     static constexpr int LDS = NSLOT * STAGE + 32 * 1024;          // ring + epilogue room (second residual landing buffer)
     static constexpr int MT = 4, NT = 2, KS = BKB / 64;
     static constexpr int PROWS = 1024 / BKB;                       // rows per 1-KiB DMA piece
     static constexpr int PW = (BM / PROWS) / 8;                    // A (and W) pieces per wave and K-step
-    static constexpr int AHEAD = NSLOT - 1;
 };
 constexpr int G8_BM = 256, G8_BN = 256;
 
 // DBG (dev, WM_GEMM8_DBG=1): every workgroup records wall-clock stamps (entry, first barrier passed, loop end, stores
 // acknowledged) into p.dbg; a separate instance, the product kernel carries none of it.
-template <class T, int BKB, bool DBG = false, bool PLANES = false>
+template <class T, bool DBG = false, bool PLANES = false>
 __global__ __launch_bounds__(512, 2) void gemm8_kernel(Gemm8Args p) {
-    using C = G8<BKB>;
+    using C = G8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned long long wt0 = 0, wt1 = 0, wt2 = 0, mt1 = 0, mt2 = 0;
     if constexpr (DBG) wt0 = wall_clock64();
@@ -84,29 +83,16 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(Gemm8Args p) {
     const char* Ab = (const char*)p.A;
     const char* Wb = (const char*)p.W;
 
-    int m0, n0;
-    {
-        const int tilesM = p.M / C::BM, tilesN = p.N / C::BN;
-        const int t = xcd_remap(blockIdx.x, gridDim.x);
-        const int per_group = G16_GROUP_M * tilesN;
-        const int group = t / per_group;
-        const int first_m = group * G16_GROUP_M;
-        const int gsz = min(G16_GROUP_M, tilesM - first_m);
-        const int in_group = t - group * per_group;
-        m0 = (first_m + in_group % gsz) * C::BM;
-        n0 = (in_group / gsz) * C::BN;
-    }
+    const TileOrigin o = grouped_tile_origin<C::BM, C::BN>(p.M / C::BM, p.N / C::BN, blockIdx.x, gridDim.x, G16_GROUP_M);
+    const int m0 = o.m0, n0 = o.n0;
 
     // DMA piece = 1 KiB = PROWS rows of BKB bytes; lane -> row, physical 16-byte chunk.  Swizzle key of a row:
-    //   BKB 128: (row >> 1) & 7 = (4 (piece & 1) + (lane >> 4)) & 7: even and odd pieces have their own per-lane source offset
-    //   BKB  64: (row >> 2) & 3 = (lane >> 4) & 3, the same for every piece
+    // (row >> 1) & 7 = (4 (piece & 1) + (lane >> 4)) & 7: even and odd pieces have their own per-lane source offset
     const size_t row_bytes = (size_t)K;
     unsigned lane_off[2];
 #pragma unroll
-    for (int par = 0; par < 2; ++par) {
-        if constexpr (BKB == 128) lane_off[par] = (unsigned)(lane >> 3) * (unsigned)K + (unsigned)((((lane & 7) ^ ((4 * par + (lane >> 4)) & 7))) << 4);
-        else lane_off[par] = (unsigned)(lane >> 2) * (unsigned)K + (unsigned)((((lane & 3) ^ ((lane >> 4) & 3))) << 4);
-    }
+    for (int par = 0; par < 2; ++par)
+        lane_off[par] = (unsigned)(lane >> 3) * (unsigned)K + (unsigned)((((lane & 7) ^ ((4 * par + (lane >> 4)) & 7))) << 4);
     const char* a_wave = Ab + (size_t)(m0 + wave * 32) * row_bytes;             // this wave's A pieces: rows 32 wave .. + 31
     const char* w_wave = Wb + (size_t)(n0 + wave * 32) * row_bytes;
     auto piece_dma = [&](int slot, int s, int i) {                              // i < PW: A pieces, else W pieces
@@ -122,7 +108,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(Gemm8Args p) {
 
     // fragment read: row r32 of a 32-row tile, 32 bytes = chunks c, c + 1 -> two ds_read_b128 whose addresses differ by XOR
     // constants only (the swizzle key has no bit in common with them)
-    const int key = BKB == 128 ? ((r32 >> 1) & 7) : ((r32 >> 2) & 3);
+    const int key = (r32 >> 1) & 7;
     const int frag_off = r32 * C::BKB + ((((2 * h) ^ key)) << 4);
     const int rd_a = (wr * 128) * C::BKB + frag_off;
     const int rd_w = C::A_BYTES + (wc * 64) * C::BKB + frag_off;
@@ -151,168 +137,54 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(Gemm8Args p) {
         }
     };
     const int one = 0x7f7f7f7f;                              // E8M0 127 = 2^0 for every 32-element block
-    // the MFMAs of one K-step; DMA: this wave's pieces of step `s` between the first of them (one piece per 64-cycle MFMA:
-    // its issue hides behind the matrix pipe instead of lengthening the load interval)
-    auto mfmas = [&](int slot, int s, auto dma_tag) {
-        constexpr bool DMA = decltype(dma_tag)::value;
-        int idx = 0;
+    auto mfmas = [&]() {                                     // the MFMAs of one K-step
 #pragma unroll
         for (int ks = 0; ks < C::KS; ++ks)
 #pragma unroll
             for (int mi = 0; mi < C::MT; ++mi)
 #pragma unroll
-                for (int ni = 0; ni < C::NT; ++ni) {
+                for (int ni = 0; ni < C::NT; ++ni)
                     acc[mi][ni] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf[ks][ni], af[ks][mi], acc[mi][ni], 0, 0, 0, one, 0, one);
-                    if constexpr (DMA) {
-                        if (idx < 2 * C::PW) piece_dma(slot, s, idx);
-                    }
-                    ++idx;
-                }
-        if constexpr (DMA) {
-#pragma unroll
-            for (int i = 0; i < 2 * C::PW; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, C::KS * C::MT * C::NT - 2 * C::PW, 0);
-        }
     };
     auto barrier = [&]() {
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     };
-    using NO = std::false_type;
-    using YES = std::true_type;
-    // DBG: waves 0 and 4 of workgroup 0 record s_memtime at 6 points of K-steps 4..7 (lane = (step - 4) * 6 + point)
-    unsigned tmark = 0;
-    auto mark = [&](int s, int k) {
-        if constexpr (DBG) {
-            const unsigned t = (unsigned)__builtin_readcyclecounter();
-            const int idx = (s - 4) * 6 + k;
-            tmark = (lane == idx) ? t : tmark;
-        }
-    };
 
-    if constexpr (BKB == 128) {
-        // ---- two slots, one K-step of DMA in flight.  Both wave groups issue the pieces of step s + 1 right after X_s: slot
-        // (s + 1) & 1 was last read for step s - 1, by waves 0-3 before Y_(s-1) and by waves 4-7 between Y_(s-1) and X_s
-        // (drained with lgkmcnt(0) before they arrive at X_s).  A wave waits for its own pieces of step s (vmcnt(0): nothing
-        // younger is outstanding at that point) before X_s, and every read of slot s & 1 follows X_s.  (Placing the pieces in
-        // each group's own load interval as gemm16_v5.h does measured 3-7 % slower; between the MFMAs needs more than the
-        // 256 registers: 128 accumulators + 96 operand registers leave no room for the address temporaries.)
-        stage(0, 0);
-        if (wr == 0) {
+    // ---- two slots, one K-step of DMA in flight.  Both wave groups issue the pieces of step s + 1 right after X_s: slot
+    // (s + 1) & 1 was last read for step s - 1, by waves 0-3 before Y_(s-1) and by waves 4-7 between Y_(s-1) and X_s
+    // (drained with lgkmcnt(0) before they arrive at X_s).  A wave waits for its own pieces of step s (vmcnt(0): nothing
+    // younger is outstanding at that point) before X_s, and every read of slot s & 1 follows X_s.  (Placing the pieces in
+    // each group's own load interval as gemm16_v5.h does measured 3-7 % slower; between the MFMAs needs more than the
+    // 256 registers: 128 accumulators + 96 operand registers leave no room for the address temporaries.)
+    stage(0, 0);
+    if (wr == 0) {
 #pragma unroll 1
-            for (int s = 0; s < ns; ++s) {
-                wait_vmcnt<0>();
-                barrier();                                  // X_s
-                if constexpr (DBG) { if (s == 0) { wt1 = wall_clock64(); mt1 = __builtin_readcyclecounter(); } }
-                if (s + 1 < ns) stage((s + 1) & 1, s + 1);
-                read_frags(s & 1);
-                barrier();                                  // Y_s
-                mfmas(0, 0, NO{});
-            }
-        } else {
-#pragma unroll 1
-            for (int s = 0; s < ns; ++s) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // my reads of the slot about to be overwritten are back
-                wait_vmcnt<0>();
-                barrier();                                  // X_s
-                if (s + 1 < ns) stage((s + 1) & 1, s + 1);
-                if (s > 0) mfmas(0, 0, NO{});               // step s - 1
-                barrier();                                  // Y_s
-                read_frags(s & 1);
-            }
-            mfmas(0, 0, NO{});                              // step ns - 1
+        for (int s = 0; s < ns; ++s) {
+            wait_vmcnt<0>();
+            barrier();                                  // X_s
+            if constexpr (DBG) { if (s == 0) { wt1 = wall_clock64(); mt1 = __builtin_readcyclecounter(); } }
+            if (s + 1 < ns) stage((s + 1) & 1, s + 1);
+            read_frags(s & 1);
+            barrier();                                  // Y_s
+            mfmas();
         }
     } else {
-        // ---- NSLOT slots, AHEAD = NSLOT - 1 K-steps of DMA in flight.  During step s a wave issues its pieces of step s + AHEAD
-        // into slot (s - 1) % NSLOT, between the MFMAs of its MFMA interval (waves 0-3: after Y_s; waves 4-7: after X_s).  That
-        // slot was last read for step s - 1: by waves 0-3 before Y_(s-1), by waves 4-7 between Y_(s-1) and X_s (drained with
-        // lgkmcnt(0) before X_s), so every issue follows the last read.  A wave waits for its own pieces of step s -- all but
-        // the (AHEAD - 1) younger steps' pieces -- before X_s; every read of slot s % NSLOT follows X_s.
-        constexpr int PWS = 2 * C::PW;                      // pieces per wave and step
-        static_assert(C::AHEAD == 3, "wait ladder below is written for three steps in flight");
-        auto wait_tail = [&](int s) {                       // last AHEAD steps: fewer younger pieces outstanding
-            if (s + 2 < ns) wait_vmcnt<2 * PWS>();
-            else if (s + 1 < ns) wait_vmcnt<PWS>();
-            else wait_vmcnt<0>();
-        };
-#pragma unroll
-        for (int i = 0; i < C::AHEAD; ++i) stage(i, i);     // ns > AHEAD (K >= 256)
-        int slot = 0;                                       // slot of step s
-        auto prev = [](int v) { return v == 0 ? C::NSLOT - 1 : v - 1; };
-        auto next = [](int v) { return v == C::NSLOT - 1 ? 0 : v + 1; };
-        const int n_main = ns - C::AHEAD;                   // steps that still have a step s + AHEAD to request
-        // (the loops are peeled so that each has ONE MFMA block: with / without the DMA pieces between the MFMAs)
-        if (wr == 0) {
 #pragma unroll 1
-            for (int s = 0; s < n_main; ++s) {
-                mark(s, 0);
-                wait_vmcnt<2 * PWS>();
-                mark(s, 1);
-                barrier();                                  // X_s
-                if constexpr (DBG) { if (s == 0) { wt1 = wall_clock64(); mt1 = __builtin_readcyclecounter(); } }
-                mark(s, 2);
-                read_frags(slot);
-                mark(s, 3);
-                barrier();                                  // Y_s
-                mark(s, 4);
-                mfmas(prev(slot), s + C::AHEAD, YES{});
-                mark(s, 5);
-                slot = next(slot);
-            }
-#pragma unroll 1
-            for (int s = n_main; s < ns; ++s) {
-                wait_tail(s);
-                barrier();                                  // X_s
-                read_frags(slot);
-                barrier();                                  // Y_s
-                mfmas(0, 0, NO{});
-                slot = next(slot);
-            }
-        } else {
-            {                                               // s = 0: nothing to multiply yet
-                wait_vmcnt<2 * PWS>();
-                barrier();                                  // X_0
-                stage(prev(slot), C::AHEAD);
-                barrier();                                  // Y_0
-                read_frags(slot);
-                slot = next(slot);
-            }
-#pragma unroll 1
-            for (int s = 1; s < n_main; ++s) {
-                mark(s, 0);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                wait_vmcnt<2 * PWS>();
-                mark(s, 1);
-                barrier();                                  // X_s
-                mark(s, 2);
-                mfmas(prev(slot), s + C::AHEAD, YES{});      // MFMAs of step s - 1
-                mark(s, 3);
-                barrier();                                  // Y_s
-                mark(s, 4);
-                read_frags(slot);
-                mark(s, 5);
-                slot = next(slot);
-            }
-#pragma unroll 1
-            for (int s = n_main > 1 ? n_main : 1; s < ns; ++s) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                wait_tail(s);
-                barrier();                                  // X_s
-                mfmas(0, 0, NO{});                          // MFMAs of step s - 1
-                barrier();                                  // Y_s
-                read_frags(slot);
-                slot = next(slot);
-            }
-            mfmas(0, 0, NO{});                              // step ns - 1
+        for (int s = 0; s < ns; ++s) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // my reads of the slot about to be overwritten are back
+            wait_vmcnt<0>();
+            barrier();                                  // X_s
+            if (s + 1 < ns) stage((s + 1) & 1, s + 1);
+            if (s > 0) mfmas();                         // step s - 1
+            barrier();                                  // Y_s
+            read_frags(s & 1);
         }
+        mfmas();                                        // step ns - 1
     }
 
     if constexpr (DBG) {
         wt2 = wall_clock64(); mt2 = __builtin_readcyclecounter();
-        if (blockIdx.x == 0 && (wave == 0 || wave == 4) && lane < 24) ((unsigned*)(p.dbg + (size_t)gridDim.x * 4 + 2))[wr * 24 + lane] = tmark;
     }
     // ---- epilogue (through LDS so that every global access is row-contiguous; see gemm16_v5.h) ----
     // lane holds, per 32 x 32 tile (mi, ni): row m = r32, columns n = 8 g + 4 h + (0..3) for g = 0..3 (registers 4 g .. 4 g + 3)
@@ -429,10 +301,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(Gemm8Args p) {
                 for (int mi = 0; mi < C::MT; ++mi) {
                     f32x4 v = scaled(mi, ni, g, scv[ni][g], biv[ni][g]);
                     if (act == ACT_GELU) v = WM_GEMM8_GELU(v);       // e4m3 output: the 3-bit-mantissa-grade form (wm_common.h)
-                    else if (act == ACT_RELU) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-                    }
+                    else v = gemm_act(v, act);
                     *(unsigned*)(smem + (wr * 128 + mi * 32 + r32) * ROWB + nl) = pack4_e4m3(v);
                 }
             }
@@ -455,11 +324,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(Gemm8Args p) {
 #pragma unroll
                 for (int mi = 0; mi < C::MT; ++mi) {
                     f32x4 v = scaled(mi, ni, g, scv[ni][g], biv[ni][g]);
-                    if (act == ACT_GELU) v = gelu_erf_fast4(v);
-                    else if (act == ACT_RELU) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-                    }
+                    v = gemm_act(v, act);
                     typename T::vec4 o;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) o[j] = T::from_f32(v[j]);

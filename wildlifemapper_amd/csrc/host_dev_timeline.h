@@ -80,20 +80,20 @@ int dev_gemm16v5_timeline(hipStream_t s, const Gemm16Args& a, int grid, int lds)
 }
 
 // WM_GEMM8_DBG: per-workgroup wall-clock stamps of an instance's 5th launch (not the plane form)
-template <class T16, int BKB, bool PLANES>
+template <class T16, bool PLANES>
 int dev_gemm8_timeline(hipStream_t s, Gemm8Args a, int grid) {
-    using G = G8<BKB>;
+    using G = G8;
     static const bool dbg = getenv("WM_GEMM8_DBG") != nullptr;
     static int dbg_count = 0;
     if (PLANES || !dbg || ++dbg_count != 5) return 0;
     unsigned long long* buf = nullptr;
-    HIP_TRY(hipMalloc((void**)&buf, (size_t)grid * 32 + 16 + 256));
-    HIP_TRY(hipMemset(buf, 0, (size_t)grid * 32 + 16 + 256));
+    HIP_TRY(hipMalloc((void**)&buf, (size_t)grid * 32 + 16));
+    HIP_TRY(hipMemset(buf, 0, (size_t)grid * 32 + 16));
     a.dbg = buf;
-    WM_TRY(set_max_lds((const void*)gemm8_kernel<T16, BKB, true>, G::LDS));
-    hipLaunchKernelGGL((gemm8_kernel<T16, BKB, true>), dim3(grid), dim3(512), G::LDS, s, a);
+    WM_TRY(set_max_lds((const void*)gemm8_kernel<T16, true>, G::LDS));
+    hipLaunchKernelGGL((gemm8_kernel<T16, true>), dim3(grid), dim3(512), G::LDS, s, a);
     HIP_TRY(hipStreamSynchronize(s));
-    std::vector<unsigned long long> r((size_t)grid * 4 + 2 + 32);
+    std::vector<unsigned long long> r((size_t)grid * 4 + 2);
     HIP_TRY(hipMemcpy(r.data(), buf, r.size() * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipFree(buf));
     unsigned long long t_min = ~0ull, t_max = 0;
@@ -102,17 +102,10 @@ int dev_gemm8_timeline(hipStream_t s, Gemm8Args a, int grid) {
         t_min = std::min(t_min, r[i * 4]); t_max = std::max(t_max, r[i * 4 + 3]);
         pro += (double)(r[i * 4 + 1] - r[i * 4]); loop += (double)(r[i * 4 + 2] - r[i * 4 + 1]); epi += (double)(r[i * 4 + 3] - r[i * 4 + 2]);
     }
-    const unsigned* mk = (const unsigned*)(r.data() + (size_t)grid * 4 + 2);
-    for (int g = 0; g < 2; ++g)
-        for (int st = 0; st < 4; ++st) {
-            fprintf(stderr, "  [gemm8 dbg] group %d step %d marks (cycles rel. to group-0 step-4 mark 0):", g, st + 4);
-            for (int k = 0; k < 6; ++k) fprintf(stderr, " %7d", (int)(mk[g * 24 + st * 6 + k] - mk[0]));
-            fprintf(stderr, "\n");
-        }
     fprintf(stderr, "[gemm8 dbg] workgroup 0 main loop: %llu shader cycles in %.2f us -> %.0f MHz\n", r[(size_t)grid * 4], r[(size_t)grid * 4 + 1] * 0.01,
             (double)r[(size_t)grid * 4] / (r[(size_t)grid * 4 + 1] * 0.01));
     fprintf(stderr, "[gemm8 dbg] BK=%d M=%d N=%d K=%d out=%s: span %.2f us; per workgroup avg: prologue %.2f us, loop %.2f us (%.0f ns per 128 of K), epilogue %.2f us; %d workgroups\n",
-            BKB, a.M, a.N, a.K, a.residual ? "f32+res" : (a.out8 ? "fp8" : "16"), (t_max - t_min) * 0.01, pro / grid * 0.01, loop / grid * 0.01,
+            G::BKB, a.M, a.N, a.K, a.residual ? "f32+res" : (a.out8 ? "fp8" : "16"), (t_max - t_min) * 0.01, pro / grid * 0.01, loop / grid * 0.01,
             loop / grid * 10.0 / (a.K / 128.0), epi / grid * 0.01, grid);
     return 1;
 }

@@ -38,7 +38,7 @@ int encoder_impl(wm_handle* h, const float* x, const float* hfc, float* out_nchw
     const std::string e = "image_encoder.", a = e + "hfc_attn.";
     // ---- stem: patch / HFC embeds (image_encoder.py:124-128) ----
     // the embeds read 16-bit NCHW copies of x and hfc (p16, h16) -- left there by the FFT's last pass (wm_forward) or made here --
-    // through the implicit-GEMM loader (gemm16_v3.h AMODE 2): no im2col buffer
+    // through the implicit-GEMM loader (gemm16_v3.h ALoad::PatchEmbed): no im2col buffer
     if (!have16) {
         WM_TRY(launch_simple(h, s, B * 18.9e6, cvt_f32_to_16_kernel<FP16>, dim3(grid_for((int64_t)B * 3 * 1024 * 256)), dim3(256), x, (u16*)h->p16, (int64_t)B * 3 * 1024 * 256));
         WM_TRY(launch_simple(h, s, B * 6.3e6, cvt_f32_to_16_kernel<FP16>, dim3(grid_for((int64_t)B * 1024 * 256)), dim3(256), hfc, (u16*)h->h16, (int64_t)B * 1024 * 256));

@@ -18,33 +18,34 @@ double gemm16_bytes(const Gemm16Args& a) {
            (a.residual ? 4.0 * (double)(a.res_mod > 0 ? a.res_mod : a.M) * a.N : 0.0);
 }
 
-template <class T16>
-int launch_gemm16_t(wm_handle* h, hipStream_t s, const Gemm16Args& a) {
-    WM_TRY(set_max_lds((const void*)gemm16_kernel<T16>, G16_LDS_BYTES));
-    count_variant(WM_GEMM_V1_128);
-    const int grid = (a.M / G16_BM) * (a.N / G16_BN);
-    Bracket br(h, s, WM_KCLASS_GEMM16, gemm16_flops(a), gemm16_bytes(a));
-    hipLaunchKernelGGL(gemm16_kernel<T16>, dim3(grid), dim3(256), G16_LDS_BYTES, s, a);
+// The launch sequence of the family's kernels: raise the kernel's dynamic-LDS limit (once per kernel and device), count the variant
+// (variant < 0: the caller has), open the profile bracket, launch, check.
+template <class Kern, class Args>
+int launch_gemm_kernel(wm_handle* h, hipStream_t s, Kern kern, int grid, int threads, int lds, const Args& a, int variant, double flops, double bytes) {
+    WM_TRY(set_max_lds((const void*)kern, lds));
+    if (variant >= 0) count_variant(variant);
+    Bracket br(h, s, WM_KCLASS_GEMM16, flops, bytes);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
+template <class T16>
+int launch_gemm16_t(wm_handle* h, hipStream_t s, const Gemm16Args& a) {
+    return launch_gemm_kernel(h, s, gemm16_kernel<T16>, (a.M / G16_BM) * (a.N / G16_BN), 256, G16_LDS_BYTES, a, WM_GEMM_V1_128, gemm16_flops(a), gemm16_bytes(a));
+}
+
 template <class T16, int BN>
 int launch_gemm16v2_t(wm_handle* h, hipStream_t s, const Gemm16Args& a) {
-    WM_TRY(set_max_lds((const void*)gemm16v2_kernel<T16, BN>, G2<BN>::LDS));
-    count_variant(BN == 160 ? WM_GEMM_V2_160 : WM_GEMM_V2_128);
-    const int grid = (a.M / 256) * (a.N / BN);
-    Bracket br(h, s, WM_KCLASS_GEMM16, gemm16_flops(a), gemm16_bytes(a));
-    hipLaunchKernelGGL((gemm16v2_kernel<T16, BN>), dim3(grid), dim3(512), G2<BN>::LDS, s, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_gemm_kernel(h, s, gemm16v2_kernel<T16, BN>, (a.M / 256) * (a.N / BN), 512, G2<BN>::LDS, a, BN == 160 ? WM_GEMM_V2_160 : WM_GEMM_V2_128,
+                              gemm16_flops(a), gemm16_bytes(a));
 }
 
 // The 256-row-tile kernel (gemm16_v5.h); FOLDP / FOLDC / SPLIT / NSLOT are the kernel's own flags: the folded LayerNorm's producer
 // (statistics out; SPLIT: the stream as two 16-bit planes) and consumer (normalisation in the epilogue), ring slots.
 template <class T16, int BN, bool FOLDP, bool FOLDC, bool SPLIT, int NSLOT = 3>
 int launch_gemm16v5_t(wm_handle* h, hipStream_t s, const Gemm16Args& a_in) {
-    using G = G3<BN, 4>;
+    using G = G3<BN>;
     constexpr int LDS = NSLOT * G::STAGE + 32 * BN * 4;        // ring + the first residual landing buffer
     static_assert(LDS <= 160 * 1024, "LDS");
     WM_TRY(set_max_lds((const void*)gemm16v5_kernel<T16, BN, NSLOT, false, FOLDP, FOLDC, SPLIT>, LDS));
@@ -61,7 +62,7 @@ int launch_gemm16v5_t(wm_handle* h, hipStream_t s, const Gemm16Args& a_in) {
     const double stream_bytes = SPLIT ? 8.0 : 4.0 + (a.out32 ? 4.0 : 0.0) + 2.0 + (a.out_lo ? 2.0 : 0.0);
     Bracket br(h, s, WM_KCLASS_GEMM16, gemm16_flops(a),
                FOLDP ? 2.0 * ((double)a.M * a.K + (double)a.N * a.K) + stream_bytes * a.M * a.N : gemm16_bytes(a));
-    WM_DEV_HOOK((dev_gemm16v5_timeline<T16, BN, NSLOT, FOLDP, FOLDC>(s, a, grid, LDS)));
+    WM_DEV_HOOK((dev_gemm16v5_timeline<T16, BN, NSLOT, FOLDP, FOLDC>(s, a, grid, LDS)));     // between bracket and launch: not the helper's sequence
     hipLaunchKernelGGL((gemm16v5_kernel<T16, BN, NSLOT, false, FOLDP, FOLDC, SPLIT>), dim3(grid), dim3(512), LDS, s, a);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -164,15 +165,10 @@ int launch_gemm16(wm_handle* h, hipStream_t s, int prec, const void* A, const vo
 
 // fp8 GEMM (gemm8.h).  prec16 = type of a 16-bit output.  K-step 128 (the 64-byte / 4-slot variant measured equal or
 // 1-3 % slower: tools/experiments/gemm8_bk64.h, profiles/r2_dev/gemm8_bench_b16_bk64.txt).
-template <class T16, int BKB, bool PLANES = false>
+template <class T16, bool PLANES = false>
 int launch_gemm8_t(wm_handle* h, hipStream_t s, Gemm8Args a, int grid, double flops, double bytes) {
-    using G = G8<BKB>;
-    WM_DEV_HOOK((dev_gemm8_timeline<T16, BKB, PLANES>(s, a, grid)));
-    WM_TRY(set_max_lds((const void*)gemm8_kernel<T16, BKB, false, PLANES>, G::LDS));
-    Bracket br(h, s, WM_KCLASS_GEMM16, flops, bytes);
-    hipLaunchKernelGGL((gemm8_kernel<T16, BKB, false, PLANES>), dim3(grid), dim3(512), G::LDS, s, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    WM_DEV_HOOK((dev_gemm8_timeline<T16, PLANES>(s, a, grid)));
+    return launch_gemm_kernel(h, s, gemm8_kernel<T16, false, PLANES>, grid, 512, G8::LDS, a, -1, flops, bytes);
 }
 
 int launch_gemm8(wm_handle* h, hipStream_t s, int prec16, const void* A, const void* W, const float* wscale, const float* bias,
@@ -186,7 +182,7 @@ int launch_gemm8(wm_handle* h, hipStream_t s, int prec16, const void* A, const v
                     (const u16*)hi, (const u16*)lo, (u16*)hi, (u16*)lo};
         count_variant(WM_GEMM_FP8_256_PLANES);
         const double flops = 2.0 * M * (double)N * K, bytes = (double)M * K + (double)N * K + 8.0 * M * N;
-        return by_type16(prec16, [&](auto t) { return launch_gemm8_t<decltype(t), 128, true>(h, s, a, (M / G8_BM) * (N / G8_BN), flops, bytes); });
+        return by_type16(prec16, [&](auto t) { return launch_gemm8_t<decltype(t), true>(h, s, a, (M / G8_BM) * (N / G8_BN), flops, bytes); });
     }
     const int modes = (res != nullptr) + (out8 != nullptr) + (res == nullptr && out8 == nullptr && out16 != nullptr);
     if (modes != 1 || (res && !out32 && !out16) || (!res && out32)) return fail("gemm8: outputs must be (residual + out32 [+ out16]) | out8 | out16");
@@ -196,7 +192,7 @@ int launch_gemm8(wm_handle* h, hipStream_t s, int prec16, const void* A, const v
     count_variant(WM_GEMM_FP8_256);
     const double flops = 2.0 * M * (double)N * K;
     const double bytes = (double)M * K + (double)N * K + (res ? 8.0 : 0.0) * M * N + (out16 ? 2.0 : 0.0) * M * N + (out8 ? 1.0 : 0.0) * M * N;
-    return by_type16(prec16, [&](auto t) { return launch_gemm8_t<decltype(t), 128>(h, s, a, grid, flops, bytes); });
+    return by_type16(prec16, [&](auto t) { return launch_gemm8_t<decltype(t)>(h, s, a, grid, flops, bytes); });
 }
 
 // 3x3 / pad 1 convolution over an NHWC [B,64,64,C] 16-bit activation as an implicit GEMM (no im2col buffer):
@@ -207,18 +203,15 @@ int launch_conv3x3_16(wm_handle* h, hipStream_t s, int prec, const void* A, cons
     WM_TRY(zero_page_for_device(&zero_page));
     Gemm16Args a{};
     a.A = (const u16*)A; a.W = (const u16*)W; a.out32 = out32; a.M = M; a.N = N; a.K = 9 * Cin; a.act = ACT_NONE; a.conv_c = Cin; a.zero_page = (const u16*)zero_page;
-    using G = G3<256, 4>;
+    using G = G3<256>;
     count_variant(WM_GEMM_V3_CONV3X3);
     return by_type16(prec, [&](auto t) {
-        WM_TRY(set_max_lds((const void*)gemm16v3_kernel<decltype(t), 256, 4, 1>, G::LDS));
-        Bracket br(h, s, WM_KCLASS_GEMM16, 2.0 * M * (double)N * 9 * Cin, 2.0 * ((double)M * Cin + 9.0 * N * Cin) + 4.0 * M * N);
-        hipLaunchKernelGGL((gemm16v3_kernel<decltype(t), 256, 4, 1>), dim3((M / 256) * (N / 256)), dim3(G::THREADS), G::LDS, s, a);
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return launch_gemm_kernel(h, s, gemm16v3_kernel<decltype(t), 256, ALoad::Conv3x3>, (M / 256) * (N / 256), G::THREADS, G::LDS, a, -1,
+                                  2.0 * M * (double)N * 9 * Cin, 2.0 * ((double)M * Cin + 9.0 * N * Cin) + 4.0 * M * N);
     });
 }
 
-// 16 x 16 / stride-16 patch embed as an implicit GEMM (gemm16_v3.h AMODE 2): img16 [B][Cin][1024][1024] 16-bit, W [N][Cin * 256]
+// 16 x 16 / stride-16 patch embed as an implicit GEMM (gemm16_v3.h ALoad::PatchEmbed): img16 [B][Cin][1024][1024] 16-bit, W [N][Cin * 256]
 // row-major, out[M = B * 4096][N] = patches W^T + bias (+ residual[m % res_mod])  (image_encoder.py:386-450)
 int launch_patch_embed16(wm_handle* h, hipStream_t s, int prec, const void* img16, const void* W, const float* bias, const float* res, int res_mod,
                          float* out32, void* out16, int B, int N, int Cin) {
@@ -229,15 +222,13 @@ int launch_patch_embed16(wm_handle* h, hipStream_t s, int prec, const void* img1
     a.A = (const u16*)img16; a.W = (const u16*)W; a.bias = bias; a.residual = res; a.out32 = out32; a.out16 = (u16*)out16;
     a.M = M; a.N = N; a.K = K; a.res_mod = res_mod; a.act = ACT_NONE; a.conv_c = Cin;
     count_variant(WM_GEMM_V3_PATCH);
-    Bracket br(h, s, WM_KCLASS_GEMM16, 2.0 * M * (double)N * K, 2.0 * ((double)M * K + (double)N * K) + (out32 ? 4.0 : 0.0) * M * N + (out16 ? 2.0 : 0.0) * M * N);
+    const double bytes = 2.0 * ((double)M * K + (double)N * K) + (out32 ? 4.0 : 0.0) * M * N + (out16 ? 2.0 : 0.0) * M * N;
     return by_type16(prec, [&](auto t) {
         return by_tile_width(N, [&](auto bn) {
             constexpr int BN = decltype(bn)::value;
-            using G = G3<BN, 4>;
-            WM_TRY(set_max_lds((const void*)gemm16v3_kernel<decltype(t), BN, 4, 2>, G::LDS));
-            hipLaunchKernelGGL((gemm16v3_kernel<decltype(t), BN, 4, 2>), dim3((M / 256) * (N / BN)), dim3(G::THREADS), G::LDS, s, a);
-            HIP_TRY(hipGetLastError());
-            return 0;
+            using G = G3<BN>;
+            return launch_gemm_kernel(h, s, gemm16v3_kernel<decltype(t), BN, ALoad::PatchEmbed>, (M / 256) * (N / BN), G::THREADS, G::LDS, a, -1,
+                                      2.0 * M * (double)N * K, bytes);
         });
     });
 }
