@@ -590,6 +590,32 @@ def test_window_attention(prec, heads, hd):
     assert (out.float() - ref).abs().max().item() < (0.06 if prec == "bf16" else 0.01)
 
 
+@pytest.mark.parametrize("heads,hd,prec", [(4, 80, "fp16"), (6, 64, "bf16")])
+def test_window_attention_multi_item_walk(heads, hd, prec):
+    """The window kernel is persistent (grid = min(items, CUs)); with 25 * heads * B items just above the CU count some workgroups
+    walk two items and the others one, so the loop's back edge (the next item's K / V prefetch and commit, the Q hand-over) runs
+    at op level.  An item's arithmetic does not depend on which workgroup walks it or what it walked before: each image's rows
+    must be bit-identical to that image run alone (B = 1: fewer items than CUs, one item per workgroup)."""
+    dev = G.dev()
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    B = cus // (25 * heads) + 1                     # the smallest B with 25 * heads * B > cus
+    D = heads * hd
+    torch.manual_seed(heads * hd)
+    qkv = G.to16(torch.randn(B * 4096, 3 * D, device=dev), prec)
+    bias = torch.randn(3 * D, device=dev) * 0.5
+    rel_h = torch.randn(27, hd, device=dev) * 0.3
+    rel_w = torch.randn(27, hd, device=dev) * 0.3
+    out = G.encoder_attention(qkv, bias, rel_h, rel_w, B, heads, hd, 14, prec)
+    ref = _ref_encoder_attention(qkv, _rnd(bias, prec), rel_h, rel_w, B, heads, hd, 14, prec)
+    rel, mx = G.rel_l2(out.float(), ref), (out.float() - ref).abs().max().item()
+    print(f"multi-item walk {heads}x{hd} {prec}: B={B} items={25 * heads * B} CUs={cus} rel-L2 {rel:.3e} max abs {mx:.3e}")
+    assert rel < 2 * OUT16_TOL[prec]
+    assert mx < (0.06 if prec == "bf16" else 0.01)
+    for b in range(B):
+        alone = G.encoder_attention(qkv[b * 4096:(b + 1) * 4096].contiguous(), bias, rel_h, rel_w, 1, heads, hd, 14, prec)
+        assert torch.equal(out[b * 4096:(b + 1) * 4096], alone), b
+
+
 @pytest.mark.parametrize("prec", ["bf16", "fp16"])
 @pytest.mark.parametrize("heads,hd", [(2, 80), (2, 64)])
 def test_global_attention_relpos(prec, heads, hd):
@@ -714,10 +740,12 @@ def test_mha16_hfc_shape(prec):
     assert G.rel_l2(out.float(), ref) < 2 * OUT16_TOL[prec]
 
 
-@pytest.mark.parametrize("nq,nk,hd", [(256, 128, 80), (512, 192, 80), (256, 256, 64), (128, 192, 80), (384, 64, 80)])
+@pytest.mark.parametrize("nq,nk,hd", [(256, 128, 80), (512, 192, 80), (256, 256, 64), (128, 192, 80), (384, 64, 80), (128, 128, 128),
+                                      (128, 64, 64)])
 def test_mha16_short_key_counts(nq, nk, hd):
     """Key counts of 2, 3 and 4 tiles of 64: the 8-wave kernel's 3-slot K / V ring below, at and just past its depth (nq a
-    multiple of 256, nk >= 128); (128, 192) and (384, 64) fall outside its geometry and take the 4-wave kernel."""
+    multiple of 256, nk >= 128); (128, 192) and (384, 64) fall outside its geometry and take the 4-wave kernel, and so do
+    (128, 128) at head_dim 128 and (128, 64) at head_dim 64: the 4-wave kernel's other two instances without rel-pos."""
     B, heads, prec, dev = 2, 2, "fp16", G.dev()
     torch.manual_seed(nq + nk)
     q = G.to16(torch.randn(B * nq, heads * hd, device=dev), prec)

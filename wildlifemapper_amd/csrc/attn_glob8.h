@@ -1,6 +1,6 @@
 // Global attention with the two waves of a SIMD held in ANTI-PHASE (round 3), gfx950.
 //
-// attn_global_kernel (attn16.h) runs 4-wave workgroups, two per CU: the two waves that share a SIMD belong to different
+// attn_global_kernel (attn_glob4.h) runs 4-wave workgroups, two per CU: the two waves that share a SIMD belong to different
 // workgroups and drift freely, so most of the time both are in the same kind of phase.  Counters (B = 16, hd 80): matrix pipe
 // busy 43 % of the SIMD cycles, vector ALU 42 %, both at once 12 %, neither 27 %.  A wave's key tile is a chain -- QK^T (10 MFMAs),
 // softmax (~150 vector issue slots), P V (12 MFMAs) -- whose matrix and vector halves take about the same time, so the SIMD's
@@ -22,7 +22,7 @@
 // Same arithmetic per query as attn_global_kernel (same tile order, same deferred-max rule): bit-identical outputs.
 #pragma once
 #include <type_traits>
-#include "attn16.h"
+#include "attn_common.h"
 
 namespace wm {
 
@@ -52,16 +52,6 @@ template <class T>
 __device__ __forceinline__ typename T::vec8 lds_read_v8_at(unsigned base, int off) {
     typedef __attribute__((address_space(3))) const typename T::vec8* lptr;
     return *(lptr)(size_t)(base + off);
-}
-template <class T>
-__device__ __forceinline__ typename T::vec8 lds_read_vT_at(unsigned base, int off, int second_off) {
-    typedef __attribute__((address_space(3))) s16x4* lptr;
-    s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(size_t)(base + off));
-    s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(size_t)(base + off + second_off));
-    s16x8 r;
-    r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; r[3] = a[3];
-    r[4] = b[0]; r[5] = b[1]; r[6] = b[2]; r[7] = b[3];
-    return __builtin_bit_cast(typename T::vec8, r);
 }
 
 template <int HD, bool REL> struct Global8Lds {
@@ -148,11 +138,7 @@ __global__ __launch_bounds__(512, 2) void attn_global8_kernel(AttnArgs p) {
 #if WM_DEV_TIMELINE
     // dev: coarse stamps in slots 60..63 of the wave's timeline: kernel entry, rel-pos prologue done, K / V prologue done, key loop done
     auto stamp_at = [&](int slot) {
-        if (p.tl && blockIdx.x == 0) {
-            unsigned long long t;
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-            if (lane == 0) ((unsigned long long*)(smem + L::TOTAL) + wave * 64)[slot] = t;
-        }
+        if (p.tl && blockIdx.x == 0) dev_stamp((unsigned long long*)(smem + L::TOTAL) + wave * 64, slot, lane);
     };
     stamp_at(60);
 #define WM_G8_COARSE(slot) stamp_at(slot)
@@ -160,7 +146,10 @@ __global__ __launch_bounds__(512, 2) void attn_global8_kernel(AttnArgs p) {
 #define WM_G8_COARSE(slot)
 #endif
     if constexpr (REL) {
-        // ---- prologue: rel_w (registers) and rel_h (LDS) for this wave's 32 queries; as attn_global_kernel ----
+        // ---- prologue: rel_w (registers) and rel_h (LDS) for this wave's 32 queries ----
+        // relpos_stage_tables and relpos_terms (attn_common.h, which the 4-wave kernel calls), written out: through the helpers hipcc
+        // folds the index arithmetic of the select reads in another order (profiles/attn_family/README.md).  Keep them in step: the
+        // two kernels' bits are pinned to each other by test_global_attention_8wave_bit_identical_to_4wave.
         const int qh = q0 >> 6, qw0 = q0 & 63;
         const float inv_scale = 1.0f / p.scale;
         char* sTab = sKV;
@@ -194,15 +183,12 @@ __global__ __launch_bounds__(512, 2) void attn_global8_kernel(AttnArgs p) {
         WM_G8_COARSE(48);
         {   // rel_w: T[c][i] = q_c . table_w[i] for the 127 rows in two passes of 64; lane (c, h) keeps the entries its keys need
             const int qw = qw0 + c;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) relw[t][r] = 0.f;
+            zero_acc(relw);
 #pragma unroll 1
             for (int pass = 0; pass < 2; ++pass) {
                 f32x16 acc[2];
 #pragma unroll
-                for (int t = 0; t < 2; ++t)
+                for (int t = 0; t < 2; ++t)                // (zero_acc, written out: inside this rolled loop the helper changes the loop's scalar code)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
                 qk_tile<T, HD, 2>(acc, qf, sTab + pass * 64 * G::KS, lane);
@@ -210,7 +196,7 @@ __global__ __launch_bounds__(512, 2) void attn_global8_kernel(AttnArgs p) {
                 for (int t = 0; t < 2; ++t)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int il = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const int il = acc_key(t, r, h);
                         sT[c * 65 + il] = acc[t][r];
                     }
                 __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -221,14 +207,14 @@ __global__ __launch_bounds__(512, 2) void attn_global8_kernel(AttnArgs p) {
                 for (int t = 0; t < 2; ++t)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int kw = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const int kw = acc_key(t, r, h);
                         tv[t][r] = sT[c * 65 + ((qw + 63 - kw) & 63)];
                     }
 #pragma unroll
                 for (int t = 0; t < 2; ++t)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int kw = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h;
+                        const int kw = acc_key(t, r, h);
                         const int idx = qw + 63 - kw;
                         asm volatile("" : "+v"(tv[t][r]));     // the read stays unconditional (hipcc sinks it under the condition otherwise)
                         relw[t][r] = (idx >> 6) == pass ? tv[t][r] * inv_scale : relw[t][r];
@@ -240,10 +226,7 @@ __global__ __launch_bounds__(512, 2) void attn_global8_kernel(AttnArgs p) {
         {   // rel_h: the 64 table rows qh + 63 - kh of this wave's query row, straight from the table image
             const char* sTabH = sTab + 128 * G::KS;
             f32x16 acc[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+            zero_acc(acc);
             const int r31 = lane & 31;
 #pragma unroll
             for (int ks = 0; ks < G::NKS; ++ks)
@@ -257,7 +240,7 @@ __global__ __launch_bounds__(512, 2) void attn_global8_kernel(AttnArgs p) {
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int kh = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int kh = acc_key(t, r, h);
                     sRelH[kh * 32 + c] = acc[t][r] * inv_scale;
                 }
         }
@@ -278,8 +261,7 @@ __global__ __launch_bounds__(512, 2) void attn_global8_kernel(AttnArgs p) {
     st.init();
     f32x16 s[NT];
     typename T::vec8 pb[2 * NT];                            // P^T fragments of the tile last softmax-ed
-    // the bias k-step's B fragment (attn16.h "Scores"): -m and, with REL, the kh rel-pos terms of 8 tiles; rebuilt every 8 tiles
-    // (matrix phase, in front of the tile's QK^T) and when m moves (vector phase, for the next tile's QK^T)
+    // the bias k-step's B fragment (attn_common.h "Scores"): -m; rebuilt when m moves (vector phase, for the next tile's QK^T)
     // (REL instances add their per-tile scalar -- the kh rel-pos term minus m -- per score on the vector pipe instead: with 24 MFMAs
     // per tile the matrix phase became the longer one, 1676 vs 1640 us per launch at B = 16; head_dim 128 without rel-pos gained
     // 14 %, 1257 -> 1086 us, and moved from the 4-wave kernel to this one)
@@ -295,11 +277,7 @@ __global__ __launch_bounds__(512, 2) void attn_global8_kernel(AttnArgs p) {
     unsigned long long* tls = (unsigned long long*)(smem + L::TOTAL) + wave * 64;
     const bool tl_on = p.tl && blockIdx.x == 0;
     auto stamp = [&](int k, int j) {
-        if (tl_on && j >= 4 && j < 8) {                    // slots 48..59 belong to the coarse prologue stamps
-            unsigned long long t;
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-            if (lane == 0) tls[(j - 4) * 12 + k] = t;
-        }
+        if (tl_on && j >= 4 && j < 8) dev_stamp(tls, (j - 4) * 12 + k, lane);      // slots 48..59 belong to the coarse prologue stamps
     };
 #define WM_G8_STAMP(k, j) stamp(k, j)
 #else
@@ -318,14 +296,13 @@ __global__ __launch_bounds__(512, 2) void attn_global8_kernel(AttnArgs p) {
         WM_G8_STAMP(3, j - 1);
         const char* sV = sKV + ((j + 1) % 3) * L::TILE + L::K_BYTES;          // slot of tile j - 1
         const char* sK = sKV + ((j + 2) % 3) * L::TILE;
-        const int g = lane >> 4, lq = (lane & 15) >> 2, lp = lane & 3;
-        const int v_lane_off = (4 * (g >> 1) + lq) * G::VS + (16 * (g & 1) + 4 * lp) * 2;
+        const int vlo = v_lane_off<HD>(lane);
         const int r31 = lane & 31;
         constexpr int AHEAD = 2;                             // fragments requested ahead of the MFMA that consumes them (2..8 and
                                                              // s_setprio 3 around the phase: all within 1 %)
         constexpr int NF_PV = 2 * NT * G::NDT, NF_QK = G::NKS * NT;                  // fragments read from LDS (the bias k-step's NT MFMAs read none)
         auto pv_body = [&]() {
-            const unsigned vbase = lds_base_opaque(sV + v_lane_off);
+            const unsigned vbase = lds_base_opaque(sV + vlo);
 #pragma unroll
             for (int ks = 0; ks < 2 * NT; ++ks)
 #pragma unroll
@@ -339,10 +316,7 @@ __global__ __launch_bounds__(512, 2) void attn_global8_kernel(AttnArgs p) {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) s[t] = relw[t];
             } else {
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) s[t][r] = 0.f;
+                zero_acc(s);
             }
             const unsigned kbase = lds_base_opaque(sK + r31 * G::KS + 16 * h);
 #pragma unroll
@@ -352,7 +326,7 @@ __global__ __launch_bounds__(512, 2) void attn_global8_kernel(AttnArgs p) {
                     typename T::vec8 kf = lds_read_v8_at<T>(kbase, 32 * t * G::KS + 32 * ks);
                     s[t] = T::mfma32(kf, qf[ks], s[t]);
                 }
-            if constexpr (!REL) {                            // the bias k-step: -m from the matrix pipe (attn16.h "Scores")
+            if constexpr (!REL) {                            // the bias k-step: -m from the matrix pipe (attn_common.h "Scores")
                 const typename T::vec8 ax = bias_a_frag<T>(0, h == 0);
 #pragma unroll
                 for (int t = 0; t < NT; ++t) s[t] = T::mfma32(ax, bx, s[t]);
@@ -406,27 +380,15 @@ __global__ __launch_bounds__(512, 2) void attn_global8_kernel(AttnArgs p) {
         for (int r = 0; r < 16; ++r) { mx0 = fmaxf(mx0, s[0][r]); mx1 = fmaxf(mx1, s[NT - 1][r]); }
         float mx = fmaxf(mx0, mx1);
         if constexpr (REL) mx = mx + (rh - st.m);           // REL: the scores lack the kh term and the reference point; !REL: they are relative already
-        {   // the other half of the keys sits in lane ^ 32: v_permlane32_swap (vector pipe) instead of ds_bpermute (an LDS round trip)
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-        }
+        mx = max_across_halves(mx);
 #if WM_DEV_TIMELINE
         asm volatile("" : "+v"(mx));
         WM_G8_STAMP(1, j);
 #endif
-        // the reference point st.m moves at the first tile and when a maximum grew past the threshold (attn16.h "Scores")
-        if (j == 0 || !__all(mx <= RESCALE_THR)) {
-            const float d = j == 0 ? mx : fmaxf(mx, 0.f);
-            if (j > 0) {                                    // first tile: l and o are still 0, and alpha may be inf (softmax_pv)
-                const float alpha = __builtin_amdgcn_exp2f(-d);
-                st.l *= alpha;
-#pragma unroll
-                for (int dt = 0; dt < G::NDT; ++dt)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) st.o[dt][r] *= alpha;
-            }
-            st.m += d;
-            if constexpr (!REL) {
+        // the reference point st.m moves at the first tile and when a maximum grew past the threshold (attn_common.h "Scores")
+        float d;
+        if (move_reference(st, mx, j, d)) {
+            if constexpr (!REL) {                           // the scores are relative to the old reference point, and so is bx
 #pragma unroll
                 for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -494,6 +456,7 @@ __global__ __launch_bounds__(512, 2) void attn_global8_kernel(AttnArgs p) {
         for (int i = 0; i < 64; ++i) p.tl[wave * 64 + i] = tls[i];
 #endif
 
+    // out_row (attn_common.h), written out: through the helper hipcc orders this epilogue's address arithmetic differently
     u16* orow = p.out + ((size_t)b * p.nq + q0 + c) * p.out_stride + head * HD;
     unsigned char* orow8 = p.out8 ? p.out8 + ((size_t)b * p.nq + q0 + c) * p.out_stride + head * HD : nullptr;
     store_out<T, HD>(st, orow, lane, true, orow8);

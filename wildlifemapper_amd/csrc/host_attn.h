@@ -1,48 +1,48 @@
 // Attention launchers: the encoder's global / window kernels and their instance pickers, the decoder's fp32 attention.
 #pragma once
-#include "attn16.h"
+#include "attn_glob4.h"
 #include "attn_glob8.h"
+#include "attn_window.h"
 #include "dec_kernels.h"
 #include "misc_kernels.h"
 #include "host_core.h"
 
 namespace {
 
-template <class T16, int HD, bool REL>
-int launch_attn_global_t(wm_handle* h, hipStream_t s, const AttnArgs& a, int batch, int kclass) {
-    // the 8-wave anti-phase kernel (attn_glob8.h); WM_ATTN_4WAVE=1 (read once per process; A/B runs) keeps every shape on the 4-wave one
-    static const bool four_wave = getenv("WM_ATTN_4WAVE") && atoi(getenv("WM_ATTN_4WAVE")) != 0;
-    // (head_dim 128, the HFC cross-attention: on the 8-wave kernel since round 4 -- with -m through the bias k-step its phases balance,
-    // 1086 vs 1257 us on the 4-wave kernel, profiles/r4_dev/attn_kernels_log2_domain.txt)
-    if (a.nq % 256 == 0 && a.nk >= 128 && !four_wave) {
-        using L8 = Global8Lds<HD, REL>;
-        constexpr int LDS = L8::TOTAL + (WM_DEV_TIMELINE ? 4096 : 0);          // dev build: room for the phase stamps
-        const dim3 grid((a.nq / 256) * a.heads * batch);
-        WM_TRY(set_max_lds((const void*)attn_global8_kernel<T16, HD, REL>, LDS));
-        Bracket br(h, s, kclass, 4.0 * batch * a.heads * (double)a.nq * a.nk * HD, 0.0);
-        WM_DEV_HOOK((dev_attn_timeline<attn_global8_kernel<T16, HD, REL>>("g8", 8, 64, grid, dim3(512), LDS, s, a)));
-        hipLaunchKernelGGL((attn_global8_kernel<T16, HD, REL>), grid, dim3(512), LDS, s, a);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    using L = GlobalLds<HD, REL>;
-    WM_TRY(set_max_lds((const void*)attn_global_kernel<T16, HD, REL>, L::TOTAL));
-    Bracket br(h, s, kclass, 4.0 * batch * a.heads * (double)a.nq * a.nk * HD, 0.0);
-    hipLaunchKernelGGL((attn_global_kernel<T16, HD, REL>), dim3((a.nq / 128) * a.heads * batch), dim3(256), L::TOTAL, s, a);
+// One attention launch, the same sequence for the three kernels: LDS limit, bracket, dev hook, launch, check.  tl: the dev build's
+// timeline of the instance (dev_attn_timeline: tag, waves, stamps per wave), tag null = the kernel has none.
+struct AttnTimeline { const char* tag = nullptr; int waves = 0, marks = 0; };
+template <auto KERN, class... Extra>
+int launch_attn(wm_handle* h, hipStream_t s, int kclass, double flops, AttnTimeline tl, int grid, int block, int lds, const AttnArgs& a, Extra... extra) {
+    lds += (tl.tag && WM_DEV_TIMELINE) ? 4096 : 0;         // dev build: room for the phase stamps
+    WM_TRY(set_max_lds((const void*)KERN, lds));
+    Bracket br(h, s, kclass, flops, 0.0);
+    if (tl.tag) WM_DEV_HOOK((dev_attn_timeline<KERN>(tl.tag, tl.waves, tl.marks, dim3(grid), dim3(block), lds, s, a, extra...)));
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(block), lds, s, a, extra...);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
+template <class T16, int HD, bool REL>
+int launch_attn_global_t(wm_handle* h, hipStream_t s, const AttnArgs& a, int batch, int kclass) {
+    // the 8-wave anti-phase kernel (attn_glob8.h); WM_ATTN_4WAVE=1 (read once per process; A/B runs) keeps every shape on the 4-wave one
+    static const bool four_wave = getenv("WM_ATTN_4WAVE") && atoi(getenv("WM_ATTN_4WAVE")) != 0;
+    const double flops = 4.0 * batch * a.heads * (double)a.nq * a.nk * HD;
+    // (head_dim 128, the HFC cross-attention: on the 8-wave kernel since round 4 -- with -m through the bias k-step its phases balance,
+    // 1086 vs 1257 us on the 4-wave kernel, profiles/r4_dev/attn_kernels_log2_domain.txt)
+    if (a.nq % 256 == 0 && a.nk >= 128 && !four_wave)
+        return launch_attn<attn_global8_kernel<T16, HD, REL>>(h, s, kclass, flops, {"g8", 8, 64}, (a.nq / 256) * a.heads * batch, 512, Global8Lds<HD, REL>::TOTAL, a);
+    return launch_attn<attn_global_kernel<T16, HD, REL>>(h, s, kclass, flops, {}, (a.nq / 128) * a.heads * batch, 256, GlobalLds<HD, REL>::TOTAL, a);
+}
+
+// the built instances: rel-pos for the encoder's head dims, 128 (the HFC cross-attention) without
 template <class T16>
 int launch_attn_global_p(wm_handle* h, hipStream_t s, const AttnArgs& a, int batch, int hd, bool rel, int kclass) {
     if (a.nq % 128 || a.nk % 64) return fail("attention: nq=%d nk=%d must be multiples of 128/64", a.nq, a.nk);
     if (rel && (a.nq != T || a.nk != T)) return fail("attention: rel-pos path needs 4096 queries and keys");
-    if (hd == 80 && rel) return launch_attn_global_t<T16, 80, true>(h, s, a, batch, kclass);
-    if (hd == 64 && rel) return launch_attn_global_t<T16, 64, true>(h, s, a, batch, kclass);
-    if (hd == 128 && !rel) return launch_attn_global_t<T16, 128, false>(h, s, a, batch, kclass);
-    if (hd == 64 && !rel) return launch_attn_global_t<T16, 64, false>(h, s, a, batch, kclass);
-    if (hd == 80 && !rel) return launch_attn_global_t<T16, 80, false>(h, s, a, batch, kclass);
-    return fail("attention: head_dim=%d rel=%d not built (64, 80, 128)", hd, (int)rel);
+    auto none = [&] { return fail("attention: head_dim=%d rel=%d not built (64, 80, 128)", hd, (int)rel); };
+    if (rel) return by_head_dim<64, 80>(hd, [&](auto d) { return launch_attn_global_t<T16, decltype(d)::value, true>(h, s, a, batch, kclass); }, none);
+    return by_head_dim<64, 80, 128>(hd, [&](auto d) { return launch_attn_global_t<T16, decltype(d)::value, false>(h, s, a, batch, kclass); }, none);
 }
 int launch_attn_global(wm_handle* h, hipStream_t s, int prec, const AttnArgs& a, int batch, int hd, bool rel) {
     return by_type16(prec, [&](auto t) { return launch_attn_global_p<decltype(t)>(h, s, a, batch, hd, rel, WM_KCLASS_ATTN_GLOBAL); });
@@ -56,13 +56,8 @@ int launch_attn_window_t(wm_handle* h, hipStream_t s, const AttnArgs& a, int bat
     // (round 4: an 8-wave anti-phase form of this kernel -- key tiles of 64 slots in a 4-slot ring filled by LDS-DMA, SIMD partners one
     // phase apart, ten barriers per item -- was built, is correct and measured 388 vs 274 us per launch: tools/experiments/
     // attn_win8_antiphase_window.h)
-    constexpr int LDS = WindowLds<HD>::TOTAL + (WM_DEV_TIMELINE ? 4096 : 0);       // dev build: room for the phase stamps
-    WM_TRY(set_max_lds((const void*)attn_window_kernel<T16, HD>, LDS));
-    Bracket br(h, s, WM_KCLASS_ATTN_WIN, 4.0 * batch * a.heads * 4096.0 * 196.0 * HD, 0.0);   // useful work only
-    WM_DEV_HOOK((dev_attn_timeline<attn_window_kernel<T16, HD>>("win", 7, 48, dim3(grid), dim3(448), LDS, s, a, nitems)));
-    hipLaunchKernelGGL((attn_window_kernel<T16, HD>), dim3(grid), dim3(448), LDS, s, a, nitems);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    const double flops = 4.0 * batch * a.heads * 4096.0 * 196.0 * HD;      // useful work only
+    return launch_attn<attn_window_kernel<T16, HD>>(h, s, WM_KCLASS_ATTN_WIN, flops, {"win", 7, 48}, grid, 448, WindowLds<HD>::TOTAL, a, nitems);
 }
 
 // n4 groups of four fp32 values -> the 16-bit type of `prec`, unbracketed (the window attention's bias row, wm_op_cvt_f32_to_16)
@@ -70,7 +65,7 @@ int launch_cvt_f32_to_16(hipStream_t s, int prec, const float* in, void* out, in
     return by_type16(prec, [&](auto t) { return launch_simple(nullptr, s, 0.0, cvt_f32_to_16_kernel<decltype(t)>, dim3(grid_for(n4)), dim3(256), in, (u16*)out, n4); });
 }
 
-// The attention kernels take q in the log2 domain, c1 q with c1 = head_dim^-0.5 * log2 e (attn16.h "Scores").  A caller that holds the
+// The attention kernels take q in the log2 domain, c1 q with c1 = head_dim^-0.5 * log2 e (attn_common.h "Scores").  A caller that holds the
 // reference's plain q (the single-op entry points) gets a scaled copy in a scratch buffer: a.q / a.q_stride are redirected to it.
 int scale_q_copy(hipStream_t s, int prec, AttnArgs& a, int batch, int cols) {
     const int64_t rows = (int64_t)batch * a.nq;
@@ -85,23 +80,34 @@ int scale_q_copy(hipStream_t s, int prec, AttnArgs& a, int batch, int cols) {
     return 0;
 }
 
-// q_prescaled: q already carries softmax scale * log2 e (the engine folds it into the q rows of the qkv weight at wm_finalize_weights,
-// attn16.h "Scores"); 0 for the single-op entry points, whose callers pass the reference's plain q
+// What launch_encoder_attention takes beyond the packed-qkv form.
+//   out8: write the output as e4m3 bytes there instead of 16-bit to `out` (the A operand of an fp8 proj GEMM);
+//   k_sep / v_sep / tok_stride: q / k / v as three tensors of one token stride (`qkv` is then q);
+//   q_prescaled: q already carries softmax scale * log2 e (the engine folds it into the q rows of the qkv weight at
+//             wm_finalize_weights, attn_common.h "Scores"); 0 for the single-op entry points, whose callers pass the reference's plain q.
+struct AttnExtra {
+    void* out8 = nullptr;
+    const void* k_sep = nullptr;
+    const void* v_sep = nullptr;
+    int tok_stride = 0;
+    int q_prescaled = 0;
+};
+
 int launch_encoder_attention(wm_handle* h, hipStream_t s, int prec, const void* qkv, const float* qkv_bias,
-                             const float* rel_h, const float* rel_w, void* out, int batch, int heads, int hd, int window, void* out8 = nullptr,
-                             const void* k_sep = nullptr, const void* v_sep = nullptr, int tok_stride = 0, int q_prescaled = 0) {
+                             const float* rel_h, const float* rel_w, void* out, int batch, int heads, int hd, int window,
+                             const AttnExtra& x = AttnExtra{}) {
     const int D = heads * hd;
     AttnArgs a{};
-    a.out8 = (unsigned char*)out8;
+    a.out8 = (unsigned char*)x.out8;
     a.q = (const u16*)qkv; a.k = (const u16*)qkv + D; a.v = (const u16*)qkv + 2 * D;
     a.out = (u16*)out;
     a.q_stride = a.k_stride = a.v_stride = 3 * D;
-    if (k_sep) { a.k = (const u16*)k_sep; a.v = (const u16*)v_sep; a.q_stride = a.k_stride = a.v_stride = tok_stride; }   // q / k / v as three tensors
+    if (x.k_sep) { a.k = (const u16*)x.k_sep; a.v = (const u16*)x.v_sep; a.q_stride = a.k_stride = a.v_stride = x.tok_stride; }   // q / k / v as three tensors
     a.out_stride = D;
     a.nq = a.nk = T;
     a.scale = 1.0f / sqrtf((float)hd);
     a.rel_h = rel_h; a.rel_w = rel_w; a.qkv_bias = qkv_bias; a.heads = heads;
-    if (!q_prescaled) WM_TRY(scale_q_copy(s, prec, a, batch, D));
+    if (!x.q_prescaled) WM_TRY(scale_q_copy(s, prec, a, batch, D));
     if (window == 0) return launch_attn_global(h, s, prec, a, batch, hd, true);
     if (window != 14) return fail("attention: window=%d unsupported (14 or 0)", window);
     {   // the bias as a 16-bit row (AttnArgs::qkv_bias16): cached per handle, converted per call without one
@@ -119,8 +125,9 @@ int launch_encoder_attention(wm_handle* h, hipStream_t s, int prec, const void* 
         if (convert) WM_TRY(launch_cvt_f32_to_16(s, prec, qkv_bias, b16, 3 * D / 4));
         a.qkv_bias16 = (const u16*)b16;
     }
-    if (hd != 80 && hd != 64) return fail("attention: head_dim=%d not built for windows (64, 80)", hd);
-    return by_type16(prec, [&](auto t) { return hd == 80 ? launch_attn_window_t<decltype(t), 80>(h, s, a, batch) : launch_attn_window_t<decltype(t), 64>(h, s, a, batch); });
+    return by_head_dim<64, 80>(hd, [&](auto d) {
+        return by_type16(prec, [&](auto t) { return launch_attn_window_t<decltype(t), decltype(d)::value>(h, s, a, batch); });
+    }, [&] { return fail("attention: head_dim=%d not built for windows (64, 80)", hd); });
 }
 
 int launch_mha16(wm_handle* h, hipStream_t s, int prec, const void* q, int qs, const void* k, int ks, const void* v, int vs,

@@ -151,6 +151,14 @@ static int fold_bn_for(int C) { return C % 320 == 0 ? 320 : 256; }
 template <class F>
 static auto by_tile_width(int n, F&& f) { return fold_bn_for(n) == 320 ? f(int_c<320>{}) : f(int_c<256>{}); }
 
+// head_dim of an attention kernel instance: f(int_c<HD>{}) for the one of HDS that equals hd, none() where
+// no instance is built for it
+template <int... HDS, class F, class N>
+static int by_head_dim(int hd, F&& f, N&& none) {
+    int r = 0;
+    return ((hd == HDS && ((r = f(int_c<HDS>{})), true)) || ...) ? r : none();
+}
+
 // ---------------------------------------------------------------------------
 // engine
 // ---------------------------------------------------------------------------

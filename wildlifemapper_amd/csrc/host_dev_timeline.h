@@ -4,7 +4,7 @@
 // environment switches.  Each timeline function is called through WM_DEV_HOOK: 0 = not taken (the launcher goes on), 1 = the instrumented
 // launch replaced the launcher's own, < 0 = error.
 #pragma once
-#include "attn16.h"
+#include "attn_common.h"
 #include "gemm16_v5.h"
 #include "gemm8.h"
 #include "host_core.h"

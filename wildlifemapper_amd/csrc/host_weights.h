@@ -337,7 +337,7 @@ int finalize_impl(wm_handle* h) {
         else h->dec_ready = nmiss == 0;
     }
     if (!h->enc_ready && !h->dec_ready) return fail("wm_finalize_weights: no weights loaded");
-    // Attention scores are computed in the log2 domain with the scale inside q (attn16.h "Scores"): the q rows of every qkv
+    // Attention scores are computed in the log2 domain with the scale inside q (attn_common.h "Scores"): the q rows of every qkv
     // weight and bias (and of the HFC cross-attention's in_proj) are multiplied by head_dim^-0.5 * log2 e here, in fp32, BEFORE the one
     // rounding to the operand type (16-bit, folded gamma (.) W, or e4m3 with its per-channel scale), so q = (c1 q_ref) costs no rounding.
     // Each staged tensor passes here exactly once (the staging area is cleared at the end of this call).

@@ -427,8 +427,10 @@ extern "C" int wm_op_encoder_attention(const void* qkv_dev, const float* qkv_bia
 extern "C" int wm_op_encoder_attention_qkv(const void* q_dev, const void* k_dev, const void* v_dev, int token_stride, const float* qkv_bias_dev,
                                            const float* rel_pos_h_dev, const float* rel_pos_w_dev, void* out_dev, int batch, int heads,
                                            int head_dim, int window, int precision, void* stream) {
+    AttnExtra x;
+    x.k_sep = k_dev; x.v_sep = v_dev; x.tok_stride = token_stride;
     return launch_encoder_attention(nullptr, (hipStream_t)stream, precision, q_dev, qkv_bias_dev, rel_pos_h_dev, rel_pos_w_dev, out_dev,
-                                    batch, heads, head_dim, window, nullptr, k_dev, v_dev, token_stride);
+                                    batch, heads, head_dim, window, x);
 }
 
 extern "C" int wm_op_mha16(const void* q_dev, int q_stride, const void* k_dev, int k_stride, const void* v_dev, int v_stride,
