@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-/* 9: wm_merge_frames_fuse (the survey merge's opt-in fuse policy: detections split by tile seams become one, with the
+/* 10: wm_criterion_scratch_bytes, wm_criterion (the validation losses of `evaluate`: Hungarian match + DETR losses);
+ *    nothing else changed.
+ * 9: wm_merge_frames_fuse (the survey merge's opt-in fuse policy: detections split by tile seams become one, with the
  *    union box); nothing else changed.
  * 8: the single-frame tile cut and merge entries removed: a single frame is a survey of one frame (wm_tile_frames_u8,
  *    wm_merge_frames_nms, same results); nothing else changed.
@@ -44,7 +46,7 @@ extern "C" {
  * wm_profile_read no longer reports the fused-LayerNorm time-out (wm_forward / wm_encoder_forward do); precision value 2
  * (fp8), WM_FLAG_MERGED and a NULL handle in wm_postprocess_nms date from round 2.  The Python binding refuses a library
  * whose wm_abi_version() differs from the value it was written for. */
-#define WM_ABI_VERSION 9
+#define WM_ABI_VERSION 10
 
 /* operand type of the transformer blocks' MFMA GEMMs / attention (accumulation, residual stream, LayerNorm
  * statistics, softmax and the whole decoder are fp32; the stem, the HFC adaptor and the neck -- 2.9 % of the
@@ -188,6 +190,43 @@ int wm_postprocess_nms(wm_handle* h, const float* logits_dev, const float* boxes
 int wm_forward(wm_handle* h, const float* x_dev, const float* target_sizes_dev,
                float* logits_dev, float* boxes_dev, wm_box_record* records_dev,
                int batch, void* stream);
+
+/* ---- validation losses (inference.py:52, contract row A23) -----------------------------------------------------------
+ * wm_criterion replaces criterion(outputs, targets) of the reference's evaluate: HungarianMatcher.forward
+ * (segment_anything/modeling/matcher.py:33-81, which copies the cost matrix to the host and calls scipy's
+ * linear_sum_assignment per image) followed by the forward losses of SetCriterion (segment_anything/build_sam.py:93-147;
+ * utils/box_ops.py:9-61, utils/misc.py accuracy).  Forward only: no gradients.  Weightless like wm_postprocess_nms: h may
+ * be NULL, nothing is allocated, the launches are asynchronous on the caller's stream.
+ * Inputs: logits (B,51,8) and boxes (B,51,4) fp32, cxcywh in [0,1]; the images' targets packed, tgt_boxes_dev
+ * (total,4) fp32 cxcywh normalised and tgt_labels_dev (total) int32 in 0..6 (both may be NULL when total = 0); image b owns
+ * the targets [tgt_offsets[b], tgt_offsets[b+1]).  tgt_offsets is HOST memory (as wm_merge_frames_nms's), batch + 1
+ * entries, starting at 0, not decreasing; at most WM_CRITERION_MAX_TARGETS targets per image, more is an error.
+ * Cost (fp32, the reference's operation order): C[q][t] = w_bbox L1(box_q, box_t) - w_class softmax(logits_q)[label_t]
+ * - w_giou GIoU(xyxy(box_q), xyxy(box_t)).  Assignment: shortest augmenting paths with row and column duals (the
+ * algorithm of scipy's linear_sum_assignment) in double on the fp32 costs, one workgroup per image, ties to the lowest
+ * index, every loop bounded by the matrix size.
+ * Outputs: match_dev (B,51) int32 = the target (index within its image) matched to each query, or -1;
+ * status_dev (B) int32, 0 or WM_CRITERION_* bits: an image whose cost matrix holds a non-finite value (scipy raises
+ * there) or a label outside 0..6 is not solved -- all its matches are -1; sums_dev [WM_CRITERION_SUMS] double, the raw
+ * sums over the call, added in a fixed order (bit-identical from run to run), all NaN if any status is set:
+ *   [0] sum of w nll and [1] sum of w over the B * 51 slots (target class = the matched label or 7, w[7] = eos_coef:
+ *       F.cross_entropy(..., empty_weight) = [0] / [1], build_sam.py:100-106),
+ *   [2] sum of L1 and [3] sum of (1 - GIoU) over the matched pairs (:138-146; the caller divides by num_boxes, which
+ *       needs an all-reduce), [4] the matched pairs, [5] those whose argmax over logits[:7] is the label (:111),
+ *   [6] sum over images of |#{q: argmax over 8 != 7} - T_b| (:119-124), [7] reserved (0).
+ * Debug outputs, each may be NULL: cost_dev [51 * total] fp32, image b's matrix [51][T_b] at 51 * tgt_offsets[b];
+ * dual_u_dev (B,51) and dual_v_dev (total) double, the final duals of the queries and the targets (u_q + v_t <= C[q][t],
+ * equal on matched pairs).  scratch_dev (16-byte aligned, device) holds at least wm_criterion_scratch_bytes(batch,
+ * total) bytes. */
+#define WM_CRITERION_MAX_TARGETS 2048   /* per image: the solver's column state lives in LDS */
+#define WM_CRITERION_SUMS 8
+#define WM_CRITERION_NONFINITE 1        /* status bit 0 */
+#define WM_CRITERION_UNSOLVED 2         /* status bit 1: the solver's structural step bound was reached (finite costs cannot) */
+int64_t wm_criterion_scratch_bytes(int batch, int total_targets);    /* <0 on error */
+int wm_criterion(wm_handle* h, const float* logits_dev, const float* boxes_dev, const float* tgt_boxes_dev,
+                 const int32_t* tgt_labels_dev, const int32_t* tgt_offsets, int batch, float w_class, float w_bbox, float w_giou,
+                 float eos_coef, void* scratch_dev, int64_t scratch_bytes, int32_t* match_dev, double* sums_dev,
+                 int32_t* status_dev, float* cost_dev, double* dual_u_dev, double* dual_v_dev, void* stream);
 
 /* ---- large-frame front end (no reference behaviour: the reference down-scales whole frames) -------
  * One frame or a survey of many frames of any size per launch.

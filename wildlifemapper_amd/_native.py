@@ -19,10 +19,11 @@ KCLASS_NAMES = ("gemm16", "attn_window", "attn_global", "layernorm", "other")
 GEMM_VARIANTS = ("v1_128", "v2_160", "v2_128", "v3_lockstep", "v3_conv3x3", "v5_320", "v5_320_res", "v5_256", "v5_256_res",
                  "v5_320_lnf", "v5_256_lnf", "fp8_320", "fp8_256", "v5_320_foldp", "v5_256_foldp", "v5_320_split", "v5_256_split", "v3_patch_embed", "fp8_256_planes")
 FLAG_CONF, FLAG_SCORE, FLAG_NMS, FLAG_MERGED = 1, 2, 4, 8
+CRITERION_MAX_TARGETS, CRITERION_SUMS, CRITERION_NONFINITE, CRITERION_UNSOLVED = 2048, 8, 1, 2
 CFG_FUSE_LN = 1
 CFG_FOLD_LN = 2
 CFG_FOLD_LN_BF16 = 4
-ABI_VERSION = 9            # include/wm_hip.h WM_ABI_VERSION this binding was written for
+ABI_VERSION = 10           # include/wm_hip.h WM_ABI_VERSION this binding was written for
 FP8_QKV, FP8_PROJ, FP8_MLP, FP8_ALL = 1, 2, 4, 7
 GEMM_W_PACKED, GEMM_A_PACKED, GEMM_OUT_PACKED, LAYOUT_PACKED = 0x1000, 0x2000, 0x4000, 0x100
 GEMM32_SPLIT = 0x100          # wm_op_gemm32: act | GEMM32_SPLIT = the fp16-split form the decoder runs (W split per K-step)
@@ -68,6 +69,8 @@ SYMBOLS = {
     "wm_encoder_forward": (_I, [_P, _P, _P, _P, _I, _P]),
     "wm_decoder_forward": (_I, [_P, _P, _P, _P, _I, _P]),
     "wm_postprocess_nms": (_I, [_P, _P, _P, _P, _F, _F, _F, _P, _I, _P]),
+    "wm_criterion_scratch_bytes": (_L, [_I, _I]),
+    "wm_criterion": (_I, [_P, _P, _P, _P, _P, C.POINTER(C.c_int32), _I, _F, _F, _F, _F, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
     "wm_forward": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
     "wm_set_tap": (_I, [_P, _I]),
     "wm_read_tap": (_I, [_P, _P, _I, _P]),

@@ -12,6 +12,7 @@
 #include "host_encoder.h"
 #include "host_decoder.h"
 #include "host_frontend.h"
+#include "host_criterion.h"
 
 extern "C" const char* wm_last_error(void) { return g_err; }
 extern "C" int wm_abi_version(void) { return WM_ABI_VERSION; }
@@ -142,6 +143,18 @@ extern "C" int wm_forward(wm_handle* h, const float* x_dev, const float* target_
     WM_TRY(check_ready(h, batch, "wm_forward", true, true));
     if (!x_dev) return fail("wm_forward: null input");
     return forward_impl(h, x_dev, target_sizes_dev, logits_dev, boxes_dev, records_dev, batch, (hipStream_t)stream);
+}
+
+// ---- validation losses ----
+extern "C" int64_t wm_criterion_scratch_bytes(int batch, int total_targets) { return criterion_scratch_bytes(batch, total_targets); }
+
+extern "C" int wm_criterion(wm_handle* h, const float* logits_dev, const float* boxes_dev, const float* tgt_boxes_dev,
+                            const int32_t* tgt_labels_dev, const int32_t* tgt_offsets, int batch, float w_class, float w_bbox, float w_giou,
+                            float eos_coef, void* scratch_dev, int64_t scratch_bytes, int32_t* match_dev, double* sums_dev,
+                            int32_t* status_dev, float* cost_dev, double* dual_u_dev, double* dual_v_dev, void* stream) {
+    if (h) HIP_TRY(hipSetDevice(h->device));     // weightless kernels: a NULL handle launches on the current device
+    return launch_criterion(logits_dev, boxes_dev, tgt_boxes_dev, tgt_labels_dev, tgt_offsets, batch, w_class, w_bbox, w_giou, eos_coef,
+                            scratch_dev, scratch_bytes, match_dev, sums_dev, status_dev, cost_dev, dual_u_dev, dual_v_dev, (hipStream_t)stream);
 }
 
 // ---- large-frame and survey front end ----

@@ -286,6 +286,49 @@ def postprocess_nms(logits: torch.Tensor, boxes: torch.Tensor, target_sizes: tor
     return rec
 
 
+def criterion_native(logits: torch.Tensor, boxes: torch.Tensor, tgt_boxes: torch.Tensor, tgt_labels: torch.Tensor, sizes,
+                     cost_class: float, cost_bbox: float, cost_giou: float, eos_coef: float, debug: bool = False) -> Dict[str, torch.Tensor]:
+    """Hungarian match + raw loss sums of one batch (wm_criterion).  Weightless, asynchronous: nothing is read back.
+    tgt_boxes (total,4) fp32 / tgt_labels (total) int32 are the images' targets packed, `sizes` their counts per image
+    (host ints).  Returns device tensors: match (B,51) int32, sums (8) float64, status (B) int32; with debug also cost
+    (51 * total) fp32 and the duals u (B,51), v (total) float64."""
+    N.require_cuda(logits, "pred_logits")
+    N.require_cuda(boxes, "pred_boxes")
+    B = logits.shape[0]
+    if tuple(logits.shape[1:]) != (N.NUM_QUERIES, N.NUM_LOGITS) or tuple(boxes.shape) != (B, N.NUM_QUERIES, 4):
+        raise RuntimeError(f"criterion: expected (B,51,8) logits and (B,51,4) boxes, got {tuple(logits.shape)}, {tuple(boxes.shape)}")
+    if len(sizes) != B:
+        raise RuntimeError(f"criterion: {len(sizes)} targets for a batch of {B}")
+    total = int(sum(sizes))
+    dev = logits.device
+    if total:
+        N.require_cuda(tgt_boxes, "target boxes")
+        if tuple(tgt_boxes.shape) != (total, 4) or tuple(tgt_labels.shape) != (total,) or tgt_labels.dtype != torch.int32 \
+                or tgt_labels.device != dev or not tgt_labels.is_contiguous():
+            raise RuntimeError(f"criterion: expected ({total},4) float32 target boxes and ({total},) int32 labels on {dev}")
+    offs = (C.c_int32 * (B + 1))()
+    for i, n in enumerate(sizes):
+        offs[i + 1] = offs[i] + int(n)
+    lib = N.lib()
+    need = int(lib.wm_criterion_scratch_bytes(B, total))
+    if need < 0:
+        N.check(-1)
+    scratch = torch.empty((need + 7) // 8, device=dev, dtype=torch.float64)
+    out = {"match": torch.empty((B, N.NUM_QUERIES), device=dev, dtype=torch.int32),
+           "sums": torch.empty(N.CRITERION_SUMS, device=dev, dtype=torch.float64),
+           "status": torch.empty(B, device=dev, dtype=torch.int32)}
+    if debug:
+        out["cost"] = torch.empty(N.NUM_QUERIES * total, device=dev, dtype=torch.float32)
+        out["dual_u"] = torch.empty((B, N.NUM_QUERIES), device=dev, dtype=torch.float64)
+        out["dual_v"] = torch.empty(total, device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        N.check(lib.wm_criterion(None, N.ptr(logits), N.ptr(boxes), N.ptr(tgt_boxes) if total else None,
+                                 N.ptr(tgt_labels) if total else None, offs, B, cost_class, cost_bbox, cost_giou, eos_coef,
+                                 N.ptr(scratch), scratch.numel() * 8, N.ptr(out["match"]), N.ptr(out["sums"]), N.ptr(out["status"]),
+                                 N.ptr(out.get("cost")), N.ptr(out.get("dual_u")), N.ptr(out.get("dual_v")), N.stream_ptr(dev)))
+    return out
+
+
 def _check_image(x: torch.Tensor, chans: int) -> None:
     if x.dim() != 4 or x.shape[1] != chans or x.shape[2] != 1024 or x.shape[3] != 1024:
         raise RuntimeError(f"expected (B,{chans},1024,1024), got {tuple(x.shape)}")

@@ -6,8 +6,12 @@ synchronize -> accumulate -> summarize and return `(stats, coco_evaluator)` with
 `stats['coco_eval_bbox'] = coco_evaluator.coco_eval['bbox'].stats.tolist()` (inference.py:72-89).
 
 Differences, all outside the accelerated path:
-  * the loss (`criterion`) may be None or return an empty dict (training-loss code is out of scope); its entries, if any,
-    are averaged into `stats` as the reference's MetricLogger does;
+  * the loss (`criterion`) may be None or return an empty dict (a model built without the criterion's `args`).  With the
+    SetCriterion that `_build_sam(args=...)` returns, `stats` carries the reference's keys (inference.py:52-64, :84):
+    `loss`, each `weight_dict` key scaled, every key `_unscaled`, `class_error`, each the mean over batches and ranks as
+    MetricLogger.global_avg gives it; the sums stay on the device and are read back once after the loop, where a batch
+    whose targets could not be matched (non-finite cost matrix) raises RuntimeError.  The entries of any other
+    criterion are averaged into `stats` under their own names;
   * COCO mAP is computed by the build's own evaluator (coco_eval.py): pycocotools, which the reference imports
     (inference.py:15-18), is absent from this image, so that parity is unpinned;
   * `base_ds` may be a pycocotools-like object with `.dataset`, a COCO-format dict (coco_annotations/*.json) or a path;
@@ -38,6 +42,7 @@ def evaluate(model, criterion, postprocessors, data_loader, base_ds, device, arg
     coco_evaluator = CocoEvaluator(base_ds, iou_types) if base_ds is not None else None
     loss_sums: Dict[str, float] = defaultdict(float)
     n_batches = 0
+    ref_keys, ref_sums, ref_bad = None, None, None   # the reference's loss stats: key order, device sums, batches with a status set
     seen: Dict[int, int] = {}                     # image id -> detections (this rank), used when no evaluator merges
     for data in data_loader:
         image, targets = data[0], data[1]
@@ -49,8 +54,25 @@ def evaluate(model, criterion, postprocessors, data_loader, base_ds, device, arg
         outputs = model(image, boxes_np)
         if criterion is not None:
             loss_dict = criterion(outputs, targets) or {}
-            for k, v in loss_dict.items():
-                loss_sums[k] += float(v)
+            weight_dict = getattr(criterion, "weight_dict", None)
+            if loss_dict and weight_dict and all(torch.is_tensor(v) for v in loss_dict.values()):
+                # inference.py:52-64, accumulated on the device
+                red = {k: v.double() for k, v in utils.reduce_dict(loss_dict).items()}       # scaled and summed in double
+                scaled = {k: v * weight_dict[k] for k, v in red.items() if k in weight_dict}
+                entries = {"loss": sum(scaled.values()), **scaled, **{f"{k}_unscaled": v for k, v in red.items()}}
+                if "class_error" in red:
+                    entries["class_error"] = red["class_error"]
+                vec = torch.stack([entries[k].double().reshape(()) for k in entries])
+                if ref_keys is None:
+                    ref_keys, ref_sums = list(entries), torch.zeros_like(vec)
+                    ref_bad = torch.zeros((), dtype=torch.int64, device=vec.device)
+                ref_sums += vec
+                status = getattr(criterion, "last_status", None)
+                if status is not None:
+                    ref_bad += (status != 0).any().to(torch.int64)
+            else:
+                for k, v in loss_dict.items():
+                    loss_sums[k] += float(v)
         n_batches += 1
         orig_target_sizes = torch.stack([t["orig_size"] for t in targets], dim=0)
         results = postprocessors["bbox"](outputs, orig_target_sizes)
@@ -66,6 +88,13 @@ def evaluate(model, criterion, postprocessors, data_loader, base_ds, device, arg
         coco_evaluator.accumulate()
         coco_evaluator.summarize()
     stats = {k: v / max(n_batches, 1) for k, v in loss_sums.items()}
+    if ref_keys is not None:
+        # MetricLogger.synchronize_between_processes + global_avg (utils/misc.py): total / count over all ranks; one read-back
+        tot = utils.all_reduce_sum(torch.cat([ref_sums, ref_bad.double().reshape(1), ref_sums.new_tensor([float(n_batches)])])).cpu()
+        if tot[-2] > 0:
+            raise RuntimeError(f"evaluate: the targets of {int(tot[-2])} batch(es) could not be matched to the predictions "
+                               "(non-finite cost matrix or a label outside 0..6); criterion.check_status() names the images of the last one")
+        stats.update({k: float(tot[i] / tot[-1]) for i, k in enumerate(ref_keys)})
     # images / detections of the whole job, each image once: DistributedSampler pads the last shard with repeats, so a sum
     # over ranks would count those twice; the evaluator's merged set (or, without an evaluator, the same merge) does not
     if coco_evaluator is not None:

@@ -3,8 +3,11 @@
 `build_sam(checkpoint=None, args=None)` and `sam_model_registry[...]` return the same
 TUPLE `(sam, criterion, postprocessors)` as the reference (:334).  `sam` holds the HIP-backed
 encoder / decoder / prompt encoder; `postprocessors['bbox']` is the HIP PostProcess.
-The DETR criterion + Hungarian matcher (:62-210, matcher.py) are training-loss code and out of
-scope for this inference path: `criterion` is a stub whose loss dict is empty.
+`criterion` is the reference's pair when `args` carries its fields (set_cost_class, set_cost_bbox, set_cost_giou,
+bbox_loss_coef, giou_loss_coef, eos_coef; :325-331): SetCriterion over a HungarianMatcher, both on the GPU (wm_criterion),
+FORWARD only -- the validation losses `evaluate` logs (inference.py:52-64).  Gradients and the training loop stay out of
+scope.  With `args=None`, or without those fields, `criterion` is a stub whose loss dict is empty (the reference would
+crash there).
 """
 from __future__ import annotations
 
@@ -17,6 +20,8 @@ from torch import nn
 from ..engine import postprocess_nms, split_records
 from .. import _native as N
 from .modeling import ImageEncoderViT, MaskDecoder, PromptEncoder, Sam, TwoWayTransformer
+from .modeling.matcher import HungarianMatcher, build_matcher, raise_on_status
+from .utils.misc import all_reduce_sum, get_world_size
 
 
 def build_sam_vit_h(checkpoint=None, args=None):
@@ -54,6 +59,64 @@ class InferenceCriterion(nn.Module):
 
     def forward(self, outputs, targets):
         return {}
+
+
+CRITERION_ARGS = ("set_cost_class", "set_cost_bbox", "set_cost_giou", "bbox_loss_coef", "giou_loss_coef", "eos_coef")
+
+
+class SetCriterion(nn.Module):
+    """The DETR losses of the reference (build_sam.py:62-210), forward only, on the GPU: the Hungarian match and every
+    sum are HIP kernels (wm_criterion); nothing is read back, so the returned 0-d tensors are still in flight.
+
+    `forward` returns loss_ce, class_error, loss_bbox, loss_giou and cardinality_error as the reference does for
+    losses = ['labels', 'boxes', 'cardinality'] (:93-147).  With no matched pair at all class_error is 100 (the
+    reference's `accuracy` returns 0 for an empty target).  An image whose cost matrix is not finite cannot be matched
+    (scipy raises there): every loss of that call is NaN, `last_status` holds the per-image status words and
+    `check_status()` raises; `evaluate` checks once after its loop."""
+
+    def __init__(self, num_classes, matcher, weight_dict, eos_coef, losses):
+        super().__init__()
+        if num_classes != N.NUM_LOGITS - 1:
+            raise NotImplementedError(f"SetCriterion: num_classes {num_classes}; the kernels are built for {N.NUM_LOGITS - 1} (+ no-object)")
+        unknown = set(losses) - {"labels", "boxes", "cardinality"}
+        assert not unknown, f"do you really want to compute {sorted(unknown)} loss?"
+        self.num_classes = num_classes
+        self.matcher = matcher
+        self.weight_dict = weight_dict
+        self.eos_coef = eos_coef
+        self.losses = losses
+        empty_weight = torch.ones(self.num_classes + 1)
+        empty_weight[-1] = self.eos_coef
+        self.register_buffer("empty_weight", empty_weight)
+        self.last_status: Optional[torch.Tensor] = None
+
+    def check_status(self) -> None:
+        """Synchronises on the last call's status words and raises RuntimeError if one is set."""
+        if self.last_status is not None:
+            raise_on_status(self.last_status)
+
+    @torch.no_grad()
+    def forward(self, outputs, targets):
+        if "aux_outputs" in outputs:
+            raise NotImplementedError("SetCriterion: auxiliary decoder outputs (training) are not built")
+        r = self.matcher.match(outputs, targets, eos_coef=self.eos_coef)
+        self.last_status = r["status"]
+        sums = r["sums"]
+        device = sums.device
+        # the average number of target boxes across all nodes (:183-187), without leaving the device
+        num_boxes = torch.as_tensor([float(sum(r["sizes"]))], dtype=torch.float64, device=device)
+        num_boxes = torch.clamp(all_reduce_sum(num_boxes) / get_world_size(), min=1)[0]
+        losses = {}
+        if "labels" in self.losses:
+            losses["loss_ce"] = (sums[0] / sums[1]).float()
+            # no matched pair: 100; a NaN count (a status is set) is not == 0 and stays NaN like the other losses
+            losses["class_error"] = torch.where(sums[4] == 0, torch.full_like(sums[4], 100.0), 100.0 - 100.0 * sums[5] / sums[4]).float()
+        if "boxes" in self.losses:
+            losses["loss_bbox"] = (sums[2] / num_boxes).float()
+            losses["loss_giou"] = (sums[3] / num_boxes).float()
+        if "cardinality" in self.losses:
+            losses["cardinality_error"] = (sums[6] / len(r["sizes"])).float()
+        return losses
 
 
 class PostProcess(nn.Module):
@@ -132,6 +195,12 @@ def _build_sam(encoder_embed_dim, encoder_depth, encoder_num_heads, encoder_glob
         for k in [k for k in state_dict if "mask_decoder" in k and "transformer" not in k]:
             del state_dict[k]
         sam.load_state_dict(state_dict, strict=False)
-    criterion = InferenceCriterion()
+    if args is not None and all(hasattr(args, k) for k in CRITERION_ARGS):
+        # build_sam.py:324-332.  `empty_weight` is kept for the reference's surface only: the kernels take eos_coef as a scalar
+        weight_dict = {"loss_ce": 3, "loss_bbox": args.bbox_loss_coef, "loss_giou": args.giou_loss_coef}
+        criterion = SetCriterion(6 + 1, matcher=build_matcher(args), weight_dict=weight_dict, eos_coef=args.eos_coef,
+                                 losses=["labels", "boxes", "cardinality"])
+    else:
+        criterion = InferenceCriterion()
     postprocessors = {"bbox": PostProcess(confidence_threshold=0.05)}
     return sam, criterion, postprocessors

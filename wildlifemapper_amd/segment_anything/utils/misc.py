@@ -87,3 +87,29 @@ def all_gather(data: Tensor) -> List[Tensor]:
     out = [torch.empty_like(data) for _ in range(world)]
     dist.all_gather(out, data.contiguous())
     return out
+
+
+def all_reduce_sum(values: Tensor) -> Tensor:
+    """Sum of a tensor over ranks, returned on its own device.  The collective runs where dist.py runs its own: RCCL
+    ("nccl") reduces device buffers directly, gloo (CPU tests, single-GPU rehearsals) needs host memory."""
+    if get_world_size() < 2:
+        return values
+    home = values.device
+    work = torch.device("cpu") if (dist.get_backend() == "gloo" and values.is_cuda) else home
+    values = values.to(work, copy=True)
+    dist.all_reduce(values)
+    return values.to(home)
+
+
+def reduce_dict(input_dict, average: bool = True):
+    """Mean (or sum) over ranks of every value of a dict of same-shaped tensors (reference: utils/misc.py:154-178): one
+    all-reduce of the stacked values, keys sorted so that ranks agree."""
+    world = get_world_size()
+    if world < 2:
+        return input_dict
+    with torch.no_grad():
+        names = sorted(input_dict.keys())
+        values = all_reduce_sum(torch.stack([input_dict[k] for k in names], dim=0))
+        if average:
+            values = values / world
+        return {k: v for k, v in zip(names, values)}
