@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-/* 10: wm_criterion_scratch_bytes, wm_criterion (the validation losses of `evaluate`: Hungarian match + DETR losses);
+/* 11: wm_chip_window, wm_crop_chips_u8, WM_CHIP_MAX_SIDE (survey review chips: one PIL-exact crop per detection, cut on
+ *    the GPU); nothing else changed.
+ * 10: wm_criterion_scratch_bytes, wm_criterion (the validation losses of `evaluate`: Hungarian match + DETR losses);
  *    nothing else changed.
  * 9: wm_merge_frames_fuse (the survey merge's opt-in fuse policy: detections split by tile seams become one, with the
  *    union box); nothing else changed.
@@ -46,7 +48,7 @@ extern "C" {
  * wm_profile_read no longer reports the fused-LayerNorm time-out (wm_forward / wm_encoder_forward do); precision value 2
  * (fp8), WM_FLAG_MERGED and a NULL handle in wm_postprocess_nms date from round 2.  The Python binding refuses a library
  * whose wm_abi_version() differs from the value it was written for. */
-#define WM_ABI_VERSION 10
+#define WM_ABI_VERSION 11
 
 /* operand type of the transformer blocks' MFMA GEMMs / attention (accumulation, residual stream, LayerNorm
  * statistics, softmax and the whole decoder are fp32; the stem, the HFC adaptor and the neck -- 2.9 % of the
@@ -283,6 +285,31 @@ int wm_merge_frames_fuse(const wm_box_record* records_dev, const int32_t* origin
  * and finite, result sides <= 65536.  Host only. */
 int wm_resample_u8(const uint8_t* in_dev, int height, int width, uint8_t* out_dev, int out_height, int out_width, void* stream);
 int wm_scaled_size(int height, int width, double scale, int* out_h, int* out_w);
+
+/* Survey review chips (tiling.detect_frames(chips=...), tiling.crop_chips): one chip x chip uint8 crop per detection, each
+ * with a window and a scale of its own, in one launch.
+ * The chip rule, fp32 with every operation rounded on its own, for a box (x0, y0, x1, y1) in frame pixels:
+ *   m = max(x1 - x0, y1 - y0);  s = ceilf(m * context) clamped to [min_side, max_side];  side = (int)s
+ *   cx = (x0 + x1) * 0.5f;  cy = (y0 + y1) * 0.5f
+ *   x0w = floorf(cx - 0.5f * side);  y0w = floorf(cy - 0.5f * side), each clamped to [-2^30, 2^30];  window = (y0w, x0w, side)
+ * A box with a non-finite coordinate, or a frame index outside [0, n_frames), has the window (0, 0, 0) and an all-zero chip.
+ * The chip is PIL.Image.fromarray(Wimg).resize((chip, chip), BILINEAR) bit for bit, Wimg the side x side x 3 image of the
+ * window's pixels with zeros where the window reaches past the frame: wm_resample_u8's arithmetic, filter taps clipped at
+ * the WINDOW's edge, zeros from outside the frame taking part as ordinary pixels, both passes the identity where side ==
+ * chip.  A window that does not meet its frame gives an all-zero chip.
+ * wm_chip_window: the rule on the host (no device call).
+ * wm_crop_chips_u8: frames_dev [n_frames] as for wm_tile_frames_u8, boxes_dev [n][4] xyxy fp32 and box_frame_dev [n] (NULL:
+ * every box in frame 0) on the device, n a host count -> chips_dev [n][chip][chip][3] uint8 and, unless NULL, windows_dev
+ * [n][3] = (y0, x0, side).  Windows and coefficient tables are derived on the device: no handle, no scratch, no
+ * allocation, no upload; asynchronous on `stream`.  chip a multiple of 4 in 16..256, chips_dev 4-byte aligned, context in
+ * [1, 8], 1 <= min_side <= max_side <= WM_CHIP_MAX_SIDE, n >= 0 (n == 0 returns 0 before looking at any pointer); bad
+ * arguments fail before any HIP call. */
+#define WM_CHIP_MAX_SIDE 1024
+int wm_chip_window(const float box[4], float context, int min_side, int max_side, int32_t out[3]);   /* host only */
+int wm_crop_chips_u8(const wm_frame_desc* frames_dev, int n_frames, const float* boxes_dev /* [n][4] xyxy */,
+                     const int32_t* box_frame_dev /* [n], NULL = all frame 0 */, int n, int chip, float context,
+                     int min_side, int max_side, uint8_t* chips_dev /* [n][chip][chip][3] */,
+                     int32_t* windows_dev /* [n][3] (y0, x0, side), may be NULL */, void* stream);
 
 /* ---- intermediate taps (parity tests) -------------------------------------
  * Copies the fp32 token stream (B,64,64,embed_dim) as it stood after the patch embed + pos_embed

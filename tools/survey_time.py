@@ -7,6 +7,9 @@
       the same survey resampled first (detect_frames(resize=...) / (scale=...)), --repeat times over; the resident
       baseline runs model.detect on the same batch sizes with the tiles' content extents as target sizes, and frames/s
       are printed next to tiles/s.
+  python tools/survey_time.py rate --chips 128
+      the same survey (any of the forms above) with a review chip per detection (detect_frames(chips=...)); the JSON
+      line gains the detections of one pass, so the added time per frame and per chip follows from a run without --chips.
   python tools/survey_time.py resample [--reps 20]
       wm_resample_u8 of a 6000 x 4000 frame to 768 x 512 and to 3000 x 2000; run under `rocprofv3 --kernel-trace --stats`
       for the per-kernel times; the algorithmic bytes of each pass are printed.
@@ -69,10 +72,14 @@ def rate(args):
         for _ in range(n_batches):
             m.detect(x)
 
+    ckw = dict(chips=args.chips) if args.chips else {}
+    detections = [0]
+
     def survey(frames):
         def run():
-            for _ in tiling.detect_frames(m, frames, batch=args.batch, **kw):
-                pass
+            detections[0] = 0
+            for r in tiling.detect_frames(m, frames, batch=args.batch, **kw, **ckw):
+                detections[0] += r["boxes"].shape[0]
         return run
 
     res = {}
@@ -93,6 +100,8 @@ def rate(args):
     res["device_over_resident"] = res["device_frames"] / res["resident_tiles"]
     res["host_over_resident"] = res["host_frames"] / res["resident_tiles"]
     extra = {"scale": args.scale, "resize": args.resize} if resampling else {}
+    if args.chips:
+        extra.update(chips=args.chips, detections=detections[0])
     print(json.dumps({"survey_tiles": n_tiles, "frames": len(shapes), "model": args.model, "precision": args.prec, "batch": args.batch,
                       **extra, **{k: round(v, 4) for k, v in res.items()}}))
 
@@ -173,6 +182,7 @@ def main():
     ap.add_argument("--scale", type=float, default=None, help="rate: resample every frame by this factor first")
     ap.add_argument("--resize", type=int, nargs=2, default=None, metavar=("SIZE", "MAX_SIZE"),
                     help="rate: resample every frame to the val transform's geometry first, e.g. 768 768")
+    ap.add_argument("--chips", type=int, default=None, help="rate: cut a review chip of this size for every detection")
     ap.add_argument("--repeat", type=int, default=1, help="rate: the survey this many times over")
     ap.add_argument("--fuse", action="store_true", help="merge: time wm_merge_frames_fuse on the same records too")
     ap.add_argument("--fuse-thr", type=float, default=0.5, help="merge --fuse: the fuse threshold")

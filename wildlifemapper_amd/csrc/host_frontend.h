@@ -1,9 +1,10 @@
-// Image front end: the val-transform resize (plan cache per device), the survey resampler (plan slots per stream) and the
-// survey merge launcher.
+// Image front end: the val-transform resize (plan cache per device), the survey resampler (plan slots per stream), the
+// survey merge launcher and the review-chip launcher.
 #pragma once
 #include "misc_kernels.h"
 #include "resample_kernels.h"
 #include "survey_kernels.h"
+#include "chip_kernels.h"
 #include "host_core.h"
 
 namespace {
@@ -56,38 +57,14 @@ void resized_size(int w, int h, int size, int max_size, int* oh, int* ow) {
 }
 
 // Pillow Resample.c precompute_coeffs + normalize_coeffs_8bpc, bilinear filter (support 1), whole axis; double arithmetic
-// in the same operation order
+// in the same operation order (resample_kernels.h: resize_coeff_row, which crop_chips_kernel runs on the device too)
 void resize_coeffs(int in_size, int out_size, std::vector<int>& bounds, std::vector<int>& kk, int& ksize) {
-    const double scale = (double)in_size / out_size;
-    const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 1.0 * filterscale;
-    ksize = (int)ceil(support) * 2 + 1;
+    const resize_axis ax = resize_axis_of(in_size, out_size);
+    ksize = ax.ksize;
     bounds.assign((size_t)out_size * 2, 0);
     kk.assign((size_t)out_size * ksize, 0);
-    const double ss = 1.0 / filterscale;
-    std::vector<double> w((size_t)ksize + 2);
-    for (int xx = 0; xx < out_size; ++xx) {
-        const double center = (xx + 0.5) * scale;
-        int xmin = (int)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5);
-        if (xmax > in_size) xmax = in_size;
-        xmax -= xmin;
-        double ww = 0.0;
-        for (int x = 0; x < xmax; ++x) {
-            double v = (x + xmin - center + 0.5) * ss;
-            if (v < 0.0) v = -v;
-            const double wt = v < 1.0 ? 1.0 - v : 0.0;
-            w[x] = wt;
-            ww += wt;
-        }
-        for (int x = 0; x < xmax; ++x) {
-            if (ww != 0.0) w[x] /= ww;
-            kk[(size_t)xx * ksize + x] = w[x] < 0 ? (int)(-0.5 + w[x] * (1 << RESIZE_PREC_BITS)) : (int)(0.5 + w[x] * (1 << RESIZE_PREC_BITS));
-        }
-        bounds[(size_t)xx * 2] = xmin;
-        bounds[(size_t)xx * 2 + 1] = xmax;
-    }
+    for (int xx = 0; xx < out_size; ++xx)
+        resize_coeff_row(ax, in_size, xx, &bounds[(size_t)xx * 2], &bounds[(size_t)xx * 2 + 1], &kk[(size_t)xx * ksize]);
 }
 
 // the row / column-blocked horizontal kernels' instance: KMAX taps (4 | 12 | 20, the caller has checked ks <= 20), 256 * (1..4) columns per workgroup
@@ -296,6 +273,37 @@ int resample_impl(const uint8_t* in_dev, int height, int width, uint8_t* out_dev
                            (const int*)(pl->dev + pl->off_ky), pl->ksy, (int64_t)out_width * 3);
         HIP_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+// ---- survey review chips: one PIL-exact crop per detection, windows and coefficients derived on the device ----
+static_assert(CHIP_MAX_SIDE == WM_CHIP_MAX_SIDE, "WM_CHIP_MAX_SIDE");
+
+// the arguments wm_chip_window and wm_crop_chips_u8 share
+int check_chip_rule(const char* name, float context, int min_side, int max_side) {
+    if (!(context >= 1.f && context <= 8.f)) return fail("%s: context %g outside [1, 8]", name, (double)context);
+    if (min_side < 1 || min_side > max_side || max_side > WM_CHIP_MAX_SIDE)
+        return fail("%s: min_side %d, max_side %d: need 1 <= min_side <= max_side <= %d", name, min_side, max_side, WM_CHIP_MAX_SIDE);
+    return 0;
+}
+
+// Weightless and asynchronous: no handle, no scratch, no allocation, no table upload.
+int launch_crop_chips(const wm_frame_desc* frames_dev, int n_frames, const float* boxes_dev, const int32_t* box_frame_dev, int n, int chip,
+                      float context, int min_side, int max_side, uint8_t* chips_dev, int32_t* windows_dev, hipStream_t s) {
+    const char* name = "wm_crop_chips_u8";
+    if (n < 0) return fail("%s: n %d", name, n);
+    if (n == 0) return 0;
+    if (!frames_dev || !boxes_dev || !chips_dev) return fail("%s: null buffer", name);
+    if (n_frames <= 0) return fail("%s: n_frames %d", name, n_frames);
+    if (chip < 16 || chip > 256 || chip % 4) return fail("%s: chip %d: need a multiple of 4 in 16..256", name, chip);
+    if ((uintptr_t)chips_dev % 4) return fail("%s: chips_dev not 4-byte aligned", name);
+    WM_TRY(check_chip_rule(name, context, min_side, max_side));
+    const int64_t grid = (int64_t)n * ((chip + CHIP_BAND_ROWS - 1) / CHIP_BAND_ROWS);
+    if (grid > INT32_MAX) return fail("%s: n %d chips of %d rows exceed one launch", name, n, chip);
+    const int lds = chip_lds_bytes(chip, max_side);           // <= 54 KiB at chip 256, max_side 1024
+    hipLaunchKernelGGL(crop_chips_kernel, dim3((unsigned)grid), dim3(256), lds, s, (const frame_desc*)frames_dev, n_frames, boxes_dev,
+                       (const int*)box_frame_dev, chip, context, min_side, max_side, chips_dev, (int*)windows_dev);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

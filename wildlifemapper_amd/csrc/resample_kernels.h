@@ -13,6 +13,53 @@
 
 namespace wm {
 
+// Pillow Resample.c precompute_coeffs + normalize_coeffs_8bpc for one axis, bilinear filter (support 1): the one definition
+// behind the host tables (host_frontend.h: resize_coeffs) and the tables crop_chips_kernel builds in LDS.  Double
+// arithmetic in Pillow's operation order, every operation rounded on its own (no contraction).
+struct resize_axis {
+    double scale, support, ss;
+    int ksize;                 // taps per output: the row length of kk
+};
+
+__host__ __device__ inline resize_axis resize_axis_of(int in_size, int out_size) {
+#pragma clang fp contract(off)
+    resize_axis a;
+    a.scale = (double)in_size / out_size;
+    const double filterscale = a.scale < 1.0 ? 1.0 : a.scale;
+    a.support = 1.0 * filterscale;
+    a.ksize = (int)ceil(a.support) * 2 + 1;
+    a.ss = 1.0 / filterscale;
+    return a;
+}
+
+// Output xx of an axis of in_size inputs: first input *xmin_out, taps *n_out (<= ksize), coefficients kk_row[0 .. taps).
+// Pillow keeps the weights in an array between its two loops; here the second loop computes each weight again, the same
+// operations on the same values.
+__host__ __device__ inline void resize_coeff_row(const resize_axis& a, int in_size, int xx, int* xmin_out, int* n_out, int* kk_row) {
+#pragma clang fp contract(off)
+    const double center = (xx + 0.5) * a.scale;
+    int xmin = (int)(center - a.support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + a.support + 0.5);
+    if (xmax > in_size) xmax = in_size;
+    xmax -= xmin;
+    double ww = 0.0;
+    for (int x = 0; x < xmax; ++x) {
+        double v = (x + xmin - center + 0.5) * a.ss;
+        if (v < 0.0) v = -v;
+        ww += v < 1.0 ? 1.0 - v : 0.0;
+    }
+    for (int x = 0; x < xmax; ++x) {
+        double v = (x + xmin - center + 0.5) * a.ss;
+        if (v < 0.0) v = -v;
+        double wt = v < 1.0 ? 1.0 - v : 0.0;
+        if (ww != 0.0) wt /= ww;
+        kk_row[x] = wt < 0 ? (int)(-0.5 + wt * (1 << RESIZE_PREC_BITS)) : (int)(0.5 + wt * (1 << RESIZE_PREC_BITS));
+    }
+    *xmin_out = xmin;
+    *n_out = xmax;
+}
+
 // in [h, w, 3] u8 -> out [h, ow, 3] u8.  bounds [ow][2] = (first input column, taps), kk [ow][ksize]; bounds are
 // non-decreasing in both entries (Pillow's triangle filter), so the columns [c0, c1) of a block read the input columns
 // [bounds[c0].first, bounds[c1-1].first + bounds[c1-1].taps).  LDS: that span of one row + its alignment shift + KMAX * 3

@@ -210,6 +210,21 @@ extern "C" int wm_scaled_size(int height, int width, double scale, int* out_h, i
     return 0;
 }
 
+extern "C" int wm_chip_window(const float box[4], float context, int min_side, int max_side, int32_t out[3]) {
+    if (!box || !out) return fail("wm_chip_window: null argument");
+    WM_TRY(check_chip_rule("wm_chip_window", context, min_side, max_side));
+    const chip_window w = chip_window_of(box, context, min_side, max_side);
+    out[0] = w.y0; out[1] = w.x0; out[2] = w.side;
+    return 0;
+}
+
+extern "C" int wm_crop_chips_u8(const wm_frame_desc* frames_dev, int n_frames, const float* boxes_dev, const int32_t* box_frame_dev, int n,
+                                int chip, float context, int min_side, int max_side, uint8_t* chips_dev, int32_t* windows_dev,
+                                void* stream) {
+    return launch_crop_chips(frames_dev, n_frames, boxes_dev, box_frame_dev, n, chip, context, min_side, max_side, chips_dev, windows_dev,
+                             (hipStream_t)stream);
+}
+
 // ---- taps / profiling / debug counters ----
 extern "C" int wm_set_tap(wm_handle* h, int which) {
     if (!h) return fail("wm_set_tap: null handle");

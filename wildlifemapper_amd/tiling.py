@@ -19,6 +19,9 @@ match: the checker is oracle/tiling_oracle.py, a numpy restatement of exactly wh
     GPU (wm_resample_u8), then the same tile cut and merge in the resampled frame.  Each tile's target size is its content
     extent (min(1024, ow - x0), min(1024, oh - y0)), the reference's content-normalised boxes (augmentation.py:246-258);
     returned boxes are mapped back to source pixels.
+  * chips= (detect_frame, detect_frames), crop_chips, chip_windows: opt-in review chips -- one fixed-size crop per
+    detection, cut from the source-resolution frame around its box (chip rule: include/wm_hip.h) and resampled with PIL's
+    bilinear arithmetic, every chip of the frames a merge completed in one launch (wm_crop_chips_u8).
 Frame coordinates are fp32: a box coordinate keeps a fractional resolution below 0.01 px up to 65536 px (ulp 2**-8).
 """
 from __future__ import annotations
@@ -176,11 +179,91 @@ def resampled_size(index: int, height: int, width: int, scale=None, resize=None)
     return preprocess.scaled_size(height, width, _check_scale(s, f"frame {index}"))
 
 
+# ---- review chips ----------------------------------------------------------------------------------------------------
+
+CHIP_MAX_SIDE = 1024          # include/wm_hip.h WM_CHIP_MAX_SIDE
+
+
+def _check_chip(chip, what: str) -> int:
+    """Validate a chip size before any device work: an integer multiple of 4 in 16..256."""
+    if isinstance(chip, bool) or not isinstance(chip, (int, np.integer)):
+        raise ValueError(f"{what}: chip size {chip!r} is not an integer")
+    if chip < 16 or chip > 256 or chip % 4:
+        raise ValueError(f"{what}: chip size {chip!r} must be a multiple of 4 in 16..256")
+    return int(chip)
+
+
+def _check_chip_rule(context, min_side, max_side, what: str):
+    try:
+        context, min_side, max_side = float(context), int(min_side), int(max_side)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: context {context!r}, min_side {min_side!r}, max_side {max_side!r}") from None
+    if not (1.0 <= context <= 8.0):
+        raise ValueError(f"{what}: context {context!r} must be in [1, 8]")
+    if not (1 <= min_side <= max_side <= CHIP_MAX_SIDE):
+        raise ValueError(f"{what}: need 1 <= min_side <= max_side <= {CHIP_MAX_SIDE}, got {min_side}, {max_side}")
+    return context, min_side, max_side
+
+
+def chip_windows(boxes, context: float = 1.5, min_side: int = 32, max_side: int = CHIP_MAX_SIDE) -> np.ndarray:
+    """The chip rule on the host (wm_chip_window; no device call): boxes (n,4) xyxy in frame pixels -> (n,3) int32
+    windows (y0, x0, side).  A box with a non-finite coordinate gives (0, 0, 0)."""
+    import ctypes as C
+    context, min_side, max_side = _check_chip_rule(context, min_side, max_side, "chip_windows")
+    if isinstance(boxes, torch.Tensor):
+        boxes = boxes.detach().cpu().numpy()
+    b = np.ascontiguousarray(np.asarray(boxes, dtype=np.float32).reshape(-1, 4))
+    out = np.zeros((b.shape[0], 3), dtype=np.int32)
+    fn = N.lib().wm_chip_window
+    FP, IP = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    for i in range(b.shape[0]):
+        N.check(fn(b[i].ctypes.data_as(FP), context, min_side, max_side, out[i].ctypes.data_as(IP)))
+    return out
+
+
+def crop_chips(frames, boxes: torch.Tensor, box_frame=None, chip: int = 128, context: float = 1.5, min_side: int = 32,
+               max_side: int = CHIP_MAX_SIDE) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One chip x chip review crop per box, all in one launch (wm_crop_chips_u8).  frames: one (H,W,3) uint8 ROCm frame
+    or a list of them; boxes (n,4) fp32 xyxy in the pixels of their frame, on the frames' device; box_frame (n,) the
+    frame index of each box (None: all in frame 0; an index outside the list gives a zero chip).  Returns (chips
+    (n,chip,chip,3) uint8, windows (n,3) int32 = (y0, x0, side)) on the device.  Each chip is the window of the chip
+    rule -- a square of side clamp(ceil(max(w, h) * context), min_side, max_side) centred on the box, zeros where it
+    reaches past the frame -- resized as PIL.Image.resize((chip, chip), BILINEAR) does, bit for bit.  Runs on the current
+    stream; windows and filter coefficients are derived on the device."""
+    chip = _check_chip(chip, "crop_chips")
+    context, min_side, max_side = _check_chip_rule(context, min_side, max_side, "crop_chips")
+    frames = [frames] if isinstance(frames, torch.Tensor) else list(frames)
+    if not frames:
+        raise RuntimeError("crop_chips: no frames")
+    for i, fr in enumerate(frames):
+        if not isinstance(fr, torch.Tensor) or not fr.is_cuda or fr.dtype != torch.uint8 or fr.dim() != 3 or fr.shape[-1] != 3:
+            raise RuntimeError(f"crop_chips: frame {i}: expected an (H,W,3) uint8 ROCm tensor")
+    dev = frames[0].device
+    frames = [fr.contiguous() for fr in frames]
+    N.require_cuda(boxes, "crop_chips: boxes")
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or boxes.device != dev or any(fr.device != dev for fr in frames):
+        raise RuntimeError(f"crop_chips: boxes {tuple(boxes.shape)} on {boxes.device}, frames on {dev}: expected (n,4) on one device")
+    n = boxes.shape[0]
+    if box_frame is not None:
+        box_frame = torch.as_tensor(box_frame).to(device=dev, dtype=torch.int32).contiguous()
+        if tuple(box_frame.shape) != (n,):
+            raise RuntimeError(f"crop_chips: box_frame {tuple(box_frame.shape)} for {n} boxes")
+    chips = torch.empty((n, chip, chip, 3), device=dev, dtype=torch.uint8)
+    windows = torch.empty((n, 3), device=dev, dtype=torch.int32)
+    if n:
+        with torch.cuda.device(dev):
+            desc = _frame_descs(frames, dev)
+            N.check(N.lib().wm_crop_chips_u8(N.ptr(desc), len(frames), N.ptr(boxes), N.ptr(box_frame), n, chip, context, min_side,
+                                             max_side, N.ptr(chips), N.ptr(windows), N.stream_ptr(dev)))
+    return chips, windows
+
+
 def detect_frame(model, frame: torch.Tensor, overlap: int = 128, batch: int = 16, iou_thr: float = 0.4, scale=None,
-                 resize=None, fuse_thr=None) -> Dict[str, torch.Tensor]:
+                 resize=None, fuse_thr=None, chips=None, chip_context: float = 1.5, chip_min_side: int = 32) -> Dict[str, torch.Tensor]:
     """One frame -> merged detections {'boxes' (k,4) frame xyxy, 'scores', 'labels', 'tile', 'origins', 'records'} in
     merged-NMS order: detect_frames on a survey of this one frame (a callable scale is called with index 0)."""
-    return next(detect_frames(model, [frame], overlap, batch, iou_thr, scale=scale, resize=resize, fuse_thr=fuse_thr))
+    return next(detect_frames(model, [frame], overlap, batch, iou_thr, scale=scale, resize=resize, fuse_thr=fuse_thr, chips=chips,
+                              chip_context=chip_context, chip_min_side=chip_min_side))
 
 
 # ---- survey: many frames of any size ---------------------------------------------------------------------------------
@@ -217,10 +300,11 @@ def plan_batches(tile_counts: Iterable[int], batch: int) -> Iterator[SurveyBatch
 
 
 class _Frame:
-    __slots__ = ("data", "height", "width", "origins", "origins_dev", "ready", "records", "scale_xy")
+    __slots__ = ("data", "height", "width", "origins", "origins_dev", "ready", "records", "scale_xy", "source")
 
-    def __init__(self, data, height, width, origins, ready, scale_xy=None):
+    def __init__(self, data, height, width, origins, ready, scale_xy=None, source=None):
         self.data, self.height, self.width, self.origins, self.ready = data, height, width, origins, ready
+        self.source = source                  # chips= only: the source-resolution device frame, kept until finish()
         self.records: List[torch.Tensor] = []
         self.origins_dev = None
         self.scale_xy = scale_xy              # resampled mode: (sx, sy) = float32(W / ow), float32(H / oh); else None
@@ -245,7 +329,8 @@ def _as_frame_array(frame, i: int, device: torch.device):
 
 @torch.no_grad()
 def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, iou_thr: float = 0.4, scale=None,
-                  resize=None, fuse_thr=None) -> Iterator[Dict[str, torch.Tensor]]:
+                  resize=None, fuse_thr=None, chips=None, chip_context: float = 1.5,
+                  chip_min_side: int = 32) -> Iterator[Dict[str, torch.Tensor]]:
     """Survey of frames of any sizes ((H,W,3) uint8 ROCm tensors, CPU tensors or numpy arrays) -> one dict per frame, in
     input order, with detect_frame's keys and values.  Tiles of consecutive frames fill batches of `batch` (plan_batches);
     after each batch one wm_merge_frames_nms covers the frames it completed.  Host frames go through one pinned staging
@@ -262,13 +347,26 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
     fuse_thr= (a float in [0, 1)): the frames are merged by wm_merge_frames_fuse (merge_frames(fuse_thr=...)) instead of
     the NMS: 'boxes' are the keepers' union boxes (mapped back to source pixels as above when resampling), and the dict
     gains 'members' (k,) int64 -- 1 + the views each detection absorbed -- and 'slot_det' (n,51) int64, aligned with
-    'records': the index of the detection each candidate slot belongs to, -1 for other slots."""
+    'records': the index of the detection each candidate slot belongs to, -1 for other slots.
+
+    chips= (a multiple of 4 in 16..256; chip_context, chip_min_side: crop_chips' context and min_side): every detection
+    also comes with a review chip, and the dict gains 'chips' (k,S,S,3) uint8, 'chip_windows' (k,3) int32 (y0, x0, side)
+    and 'chip_boxes' (k,4) fp32, the detection's box in chip pixels = (boxes - (x0, y0, x0, y0)) * float32(S / side) in
+    fp32; all three aligned with 'boxes' (the union boxes when fusing).  Chips are cut from the SOURCE frame at 'boxes',
+    when resampling too, by one wm_crop_chips_u8 launch for the frames a merge completed, queued on the main stream once
+    their detection counts have reached the host (no detections: an empty tensor and no launch).  A frame is therefore
+    kept until its result is yielded instead of being released at its last tile cut, and in resampled mode its source is
+    kept beside its resample instead of being released once the resample is queued: one extra source-resolution frame
+    (H * W * 3 bytes, 72 MB at 6000 x 4000) of device memory per frame in flight.  chips=None: none of this."""
     from .engine import split_records
     import ctypes as C
     if batch <= 0:
         raise ValueError(f"detect_frames: batch {batch}")
     resampling = _check_resample_args(scale, resize, "detect_frames")
     fuse_thr = _check_fuse_thr(fuse_thr, "detect_frames")
+    if chips is not None:
+        chips = _check_chip(chips, "detect_frames")
+        chip_context, chip_min_side, _ = _check_chip_rule(chip_context, chip_min_side, CHIP_MAX_SIDE, "detect_frames")
     device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
     staged: Dict[int, _Frame] = {}
     pinned = [None, None]                     # staging buffer, event of the last copy out of it
@@ -277,7 +375,8 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
 
     def upload(h, H: int, W: int, resample_to=None):
         """Host frame -> device frame through the pinned staging buffer on the copy stream; resample_to=(oh, ow): the
-        upload is resampled there too, after the copy.  Returns the device frame and the event its use waits for."""
+        upload is resampled there too, after the copy.  Returns the device frame, the event its use waits for and the
+        uploaded source frame."""
         nbytes = H * W * 3
         if pinned[1] is not None:
             pinned[1].synchronize()           # the previous upload has left the staging buffer
@@ -290,15 +389,18 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
         with torch.cuda.stream(copy[0]):
             d = torch.empty((H, W, 3), dtype=torch.uint8, device=device)
             d.view(-1).copy_(buf, non_blocking=True)
+            src = d
             ready = uploaded = torch.cuda.Event()
             uploaded.record(copy[0])
-            if resample_to is not None:       # the uploaded source goes once its resample is queued
+            if resample_to is not None:       # the uploaded source goes once its resample is queued (chips= keeps it)
                 d = preprocess.resample_u8(d, resample_to)
                 ready = torch.cuda.Event()
                 ready.record(copy[0])
         d.record_stream(torch.cuda.current_stream(device))
+        if chips is not None:
+            src.record_stream(torch.cuda.current_stream(device))
         pinned[1] = uploaded
-        return d, ready
+        return d, ready, src
 
     def stage(i: int) -> bool:
         try:
@@ -315,17 +417,18 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
         if resampling:                        # the resampled frame is what gets tiled; a caller's device frame is only read
             size = None if (oh, ow) == (H, W) else (oh, ow)
             if d is None:
-                d, ready = upload(h, H, W, size)
+                d, ready, src = upload(h, H, W, size)
             else:
+                src = d
                 d, ready = (d if size is None else preprocess.resample_u8(d, size)), None
             sxy = (float(np.float32(W / ow)), float(np.float32(H / oh)))
-            staged[i] = _Frame(d, oh, ow, tile_origins(oh, ow, 1024, overlap), ready, sxy)
+            staged[i] = _Frame(d, oh, ow, tile_origins(oh, ow, 1024, overlap), ready, sxy, src if chips is not None else None)
             return True
         org = tile_origins(H, W, 1024, overlap)
         ready = None
         if d is None:
-            d, ready = upload(h, H, W)
-        staged[i] = _Frame(d, H, W, org, ready)
+            d, ready, _ = upload(h, H, W)
+        staged[i] = _Frame(d, H, W, org, ready, None, d if chips is not None else None)
         return True
 
     def tile_counts():
@@ -341,6 +444,7 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
         out, frames_done, offs = pending
         out["ready"].synchronize()
         counts = out["count_host"].tolist()
+        done = []
         for j, f in enumerate(frames_done):
             fr = staged.pop(f)
             s0, n = offs[j] * N.NUM_QUERIES, offs[j + 1] - offs[j]
@@ -359,6 +463,34 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
                 src[:, 1::2] = b[:, 1::2] * fr.scale_xy[1]
                 res["boxes"] = src
                 res["resampled_size"] = (fr.height, fr.width)
+            if chips is None:
+                yield res
+            else:
+                done.append((fr, res))
+        if chips is not None:
+            yield from with_chips(done)
+
+    def with_chips(done):
+        """One crop launch for every detection of the frames of one merge, cut from the source frames at 'boxes'."""
+        S = chips
+        ks = [res["boxes"].shape[0] for _, res in done]
+        if sum(ks):
+            boxes = torch.cat([res["boxes"] for _, res in done]).contiguous()
+            idx = torch.from_numpy(np.repeat(np.arange(len(done), dtype=np.int32), ks)).pin_memory().to(device, non_blocking=True)
+            all_chips, all_win = crop_chips([fr.source for fr, _ in done], boxes, idx, S, chip_context, chip_min_side)
+        else:
+            all_chips = torch.empty((0, S, S, 3), device=device, dtype=torch.uint8)
+            all_win = torch.empty((0, 3), device=device, dtype=torch.int32)
+        pos = 0
+        for (fr, res), k in zip(done, ks):
+            win = all_win[pos:pos + k]
+            res["chips"], res["chip_windows"] = all_chips[pos:pos + k], win
+            side = win[:, 2].to(torch.float64)
+            zoom = torch.where(side > 0, S / side.clamp(min=1), torch.zeros_like(side)).to(torch.float32)    # float32(S / side)
+            org = win[:, [1, 0, 1, 0]].to(torch.float32)
+            res["chip_boxes"] = (res["boxes"] - org) * zoom[:, None]
+            pos += k
+            fr.source = None
             yield res
 
     pending = None
