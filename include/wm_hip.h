@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-/* 11: wm_chip_window, wm_crop_chips_u8, WM_CHIP_MAX_SIDE (survey review chips: one PIL-exact crop per detection, cut on
+/* 12: wm_box_outline_rect, wm_draw_boxes_u8, wm_plot_image_u8, WM_DRAW_MAX_WIDTH, WM_DRAW_MAX_PALETTE, WM_PLOT_SCRATCH_BYTES
+ *    (survey overlays: detections outlined on frames and tiles, on the GPU); nothing else changed.
+ * 11: wm_chip_window, wm_crop_chips_u8, WM_CHIP_MAX_SIDE (survey review chips: one PIL-exact crop per detection, cut on
  *    the GPU); nothing else changed.
  * 10: wm_criterion_scratch_bytes, wm_criterion (the validation losses of `evaluate`: Hungarian match + DETR losses);
  *    nothing else changed.
@@ -48,7 +50,7 @@ extern "C" {
  * wm_profile_read no longer reports the fused-LayerNorm time-out (wm_forward / wm_encoder_forward do); precision value 2
  * (fp8), WM_FLAG_MERGED and a NULL handle in wm_postprocess_nms date from round 2.  The Python binding refuses a library
  * whose wm_abi_version() differs from the value it was written for. */
-#define WM_ABI_VERSION 11
+#define WM_ABI_VERSION 12
 
 /* operand type of the transformer blocks' MFMA GEMMs / attention (accumulation, residual stream, LayerNorm
  * statistics, softmax and the whole decoder are fp32; the stem, the HFC adaptor and the neck -- 2.9 % of the
@@ -310,6 +312,48 @@ int wm_crop_chips_u8(const wm_frame_desc* frames_dev, int n_frames, const float*
                      const int32_t* box_frame_dev /* [n], NULL = all frame 0 */, int n, int chip, float context,
                      int min_side, int max_side, uint8_t* chips_dev /* [n][chip][chip][3] */,
                      int32_t* windows_dev /* [n][3] (y0, x0, side), may be NULL */, void* stream);
+
+/* Survey overlays (tiling.detect_frames(overlay=...), tiling.draw_boxes, visualize.plot_points): box outlines drawn onto
+ * uint8 frames in place, and the reference's tile preparation (visualize_prediction.py:118-133).
+ * The outline rule, for a box (x0, y0, x1, y1) in the pixels of its frame:
+ *   each coordinate is clamped to [-2^30, 2^30] and truncated toward zero, as the reference's int(box[k]) does: (l, t, r, b),
+ *   with r and b INCLUSIVE.
+ *   A box is skipped -- it draws nothing and is not an error -- if a coordinate is not finite, if r < l or b < t, if its
+ *   frame index is outside [0, n_frames), or if its label is outside [0, palette_size).
+ *   The outline is every pixel (x, y) with l <= x <= r and t <= y <= b that lies inside the frame and satisfies
+ *     x - l < width  or  r - x < width  or  y - t < width  or  b - y < width.
+ *   The border grows inward, clipped to the frame; nothing is drawn outside the box.  This is the pixel set of
+ *   PIL.ImageDraw.rectangle([l, t, r, b], outline=c, width=width) whenever r - l + 1 and b - t + 1 both exceed width
+ *   (Pillow 12.2.0; its line code paints outside the box when a side is smaller, which is not copied).  cv2.rectangle's
+ *   thickness-2 raster, which the reference calls, is not matched: OpenCV straddles the edge, this rule stays inside it.
+ *   An outline pixel gets the three bytes palette[label], no blending.
+ *   Painter's order: the frames end as if the boxes had been drawn one after another in index order, later over earlier,
+ *   bit for bit, with exactly one store per written pixel (deterministic, race-free).
+ * wm_box_outline_rect: the first step on the host (no device call): out = (l, t, r, b) and 0, or out = zeros and 1 for a
+ * box that is skipped for its coordinates; <0 on a NULL argument.
+ * wm_draw_boxes_u8: frames_dev [n_frames] as for wm_crop_chips_u8 (the frames are WRITTEN), boxes_dev [n][4] xyxy fp32,
+ * labels_dev [n] int32, box_frame_dev [n] (NULL: every box in frame 0), palette_dev [palette_size][3] uint8, all on the
+ * device; n a host count.  One launch, no handle, no scratch, no allocation; asynchronous on `stream`.  width in
+ * 1..WM_DRAW_MAX_WIDTH, palette_size in 1..WM_DRAW_MAX_PALETTE, n >= 0 (n == 0 returns 0 before looking at any pointer);
+ * bad arguments fail before any HIP call.
+ * wm_plot_image_u8: in_dev [batch][3][height][width] fp32 -> out_dev [batch][height][width][3] uint8, per image
+ *   out[y][x][c] = (int)(((v - mn) / mx) * 255.0f),  v = in[2 - c][y][x]  (the reference's cvtColor swaps channels 0 and 2),
+ *   mn the image's minimum over all three channels, mx the maximum of v - mn; every operation a correctly rounded fp32
+ * operation of its own, so the bytes are those of numpy's
+ *   a = x.transpose(1,2,0)[..., ::-1].copy(); a -= a.min(); a /= a.max(); np.int32(a * 255).
+ * A constant image (mx == 0; the reference divides by zero there) gives all zeros; a non-finite input gives unspecified
+ * bytes and no fault.  Two launches (a deterministic two-stage min / max, then the map); scratch_dev holds at least batch *
+ * WM_PLOT_SCRATCH_BYTES bytes, 4-byte aligned, and is the caller's: no allocation, asynchronous on `stream`.  batch == 0
+ * returns 0 before looking at any pointer; bad arguments fail before any HIP call. */
+#define WM_DRAW_MAX_WIDTH 16
+#define WM_DRAW_MAX_PALETTE 256
+#define WM_PLOT_SCRATCH_BYTES 1024
+int wm_box_outline_rect(const float box[4], int32_t out[4]);   /* host only; 0 drawn, 1 skipped */
+int wm_draw_boxes_u8(const wm_frame_desc* frames_dev, int n_frames, const float* boxes_dev /* [n][4] xyxy */,
+                     const int32_t* labels_dev /* [n] */, const int32_t* box_frame_dev /* [n], NULL = all frame 0 */, int n,
+                     const uint8_t* palette_dev /* [palette_size][3] */, int palette_size, int width, void* stream);
+int wm_plot_image_u8(const float* in_dev, int batch, int height, int width, uint8_t* out_dev, void* scratch_dev,
+                     int64_t scratch_bytes, void* stream);
 
 /* ---- intermediate taps (parity tests) -------------------------------------
  * Copies the fp32 token stream (B,64,64,embed_dim) as it stood after the patch embed + pos_embed

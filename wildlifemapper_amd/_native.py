@@ -23,7 +23,7 @@ CRITERION_MAX_TARGETS, CRITERION_SUMS, CRITERION_NONFINITE, CRITERION_UNSOLVED =
 CFG_FUSE_LN = 1
 CFG_FOLD_LN = 2
 CFG_FOLD_LN_BF16 = 4
-ABI_VERSION = 11           # include/wm_hip.h WM_ABI_VERSION this binding was written for
+ABI_VERSION = 12           # include/wm_hip.h WM_ABI_VERSION this binding was written for
 FP8_QKV, FP8_PROJ, FP8_MLP, FP8_ALL = 1, 2, 4, 7
 GEMM_W_PACKED, GEMM_A_PACKED, GEMM_OUT_PACKED, LAYOUT_PACKED = 0x1000, 0x2000, 0x4000, 0x100
 GEMM32_SPLIT = 0x100          # wm_op_gemm32: act | GEMM32_SPLIT = the fp16-split form the decoder runs (W split per K-step)
@@ -67,6 +67,9 @@ SYMBOLS = {
     "wm_scaled_size": (_I, [_I, _I, C.c_double, C.POINTER(_I), C.POINTER(_I)]),
     "wm_chip_window": (_I, [C.POINTER(_F), _F, _I, _I, C.POINTER(C.c_int32)]),
     "wm_crop_chips_u8": (_I, [_P, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P]),
+    "wm_box_outline_rect": (_I, [C.POINTER(_F), C.POINTER(C.c_int32)]),
+    "wm_draw_boxes_u8": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _I, _P]),
+    "wm_plot_image_u8": (_I, [_P, _I, _I, _I, _P, _P, _L, _P]),
     "wm_hfc_fft": (_I, [_P, _P, _P, _I, _P]),
     "wm_encoder_forward": (_I, [_P, _P, _P, _P, _I, _P]),
     "wm_decoder_forward": (_I, [_P, _P, _P, _P, _I, _P]),

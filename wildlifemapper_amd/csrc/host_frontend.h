@@ -1,10 +1,11 @@
 // Image front end: the val-transform resize (plan cache per device), the survey resampler (plan slots per stream), the
-// survey merge launcher and the review-chip launcher.
+// survey merge launcher, the review-chip launcher and the overlay launchers (box outlines, the reference's plot image).
 #pragma once
 #include "misc_kernels.h"
 #include "resample_kernels.h"
 #include "survey_kernels.h"
 #include "chip_kernels.h"
+#include "overlay_kernels.h"
 #include "host_core.h"
 
 namespace {
@@ -303,6 +304,50 @@ int launch_crop_chips(const wm_frame_desc* frames_dev, int n_frames, const float
     const int lds = chip_lds_bytes(chip, max_side);           // <= 54 KiB at chip 256, max_side 1024
     hipLaunchKernelGGL(crop_chips_kernel, dim3((unsigned)grid), dim3(256), lds, s, (const frame_desc*)frames_dev, n_frames, boxes_dev,
                        (const int*)box_frame_dev, chip, context, min_side, max_side, chips_dev, (int*)windows_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- survey overlays: box outlines drawn in place, and the reference's tile preparation ----
+static_assert(DRAW_MAX_WIDTH == WM_DRAW_MAX_WIDTH && DRAW_MAX_PALETTE == WM_DRAW_MAX_PALETTE, "WM_DRAW_*");
+static_assert(PLOT_MAX_PARTS * 2 * sizeof(float) == WM_PLOT_SCRATCH_BYTES, "WM_PLOT_SCRATCH_BYTES");
+
+// Weightless and asynchronous: no handle, no scratch, no allocation.
+int launch_draw_boxes(const wm_frame_desc* frames_dev, int n_frames, const float* boxes_dev, const int32_t* labels_dev,
+                      const int32_t* box_frame_dev, int n, const uint8_t* palette_dev, int palette_size, int width, hipStream_t s) {
+    const char* name = "wm_draw_boxes_u8";
+    if (n < 0) return fail("%s: n %d", name, n);
+    if (n == 0) return 0;
+    if (!frames_dev || !boxes_dev || !labels_dev || !palette_dev) return fail("%s: null buffer", name);
+    if (n_frames <= 0) return fail("%s: n_frames %d", name, n_frames);
+    if (width < 1 || width > WM_DRAW_MAX_WIDTH) return fail("%s: width %d outside 1..%d", name, width, WM_DRAW_MAX_WIDTH);
+    if (palette_size < 1 || palette_size > WM_DRAW_MAX_PALETTE)
+        return fail("%s: palette_size %d outside 1..%d", name, palette_size, WM_DRAW_MAX_PALETTE);
+    hipLaunchKernelGGL(draw_boxes_kernel, dim3((unsigned)n, DRAW_SLICES), dim3(256), 0, s, (const frame_desc*)frames_dev, n_frames, boxes_dev,
+                       (const int*)labels_dev, (const int*)box_frame_dev, n, palette_dev, palette_size, width);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Two launches on `s`: the partial (min, max) pairs of every image into the caller's scratch, then the map.
+int launch_plot_image(const float* in_dev, int batch, int height, int width, uint8_t* out_dev, void* scratch_dev, int64_t scratch_bytes,
+                      hipStream_t s) {
+    const char* name = "wm_plot_image_u8";
+    if (batch < 0) return fail("%s: batch %d", name, batch);
+    if (batch == 0) return 0;
+    if (!in_dev || !out_dev || !scratch_dev) return fail("%s: null buffer", name);
+    if (height <= 0 || width <= 0) return fail("%s: height %d, width %d", name, height, width);
+    if (batch > 65535) return fail("%s: batch %d exceeds one launch (65535)", name, batch);
+    if ((uintptr_t)in_dev % 4 || (uintptr_t)scratch_dev % 4) return fail("%s: in_dev or scratch_dev not 4-byte aligned", name);
+    if (scratch_bytes < (int64_t)batch * WM_PLOT_SCRATCH_BYTES)
+        return fail("%s: scratch of %lld bytes, %lld needed", name, (long long)scratch_bytes, (long long)batch * WM_PLOT_SCRATCH_BYTES);
+    const int64_t hw = (int64_t)height * width;
+    const int vec = hw % 4 == 0 && (uintptr_t)in_dev % 16 == 0 && (uintptr_t)out_dev % 4 == 0;
+    const int parts = (int)std::max<int64_t>(1, std::min<int64_t>(PLOT_MAX_PARTS, (3 * hw + 4095) / 4096));
+    hipLaunchKernelGGL(plot_minmax_kernel, dim3(parts, batch), dim3(256), 0, s, in_dev, 3 * hw, (float*)scratch_dev, vec);
+    HIP_TRY(hipGetLastError());
+    const unsigned blocks = grid_for((hw + 3) / 4, 256 * 4, 1024);
+    hipLaunchKernelGGL(plot_map_kernel, dim3(blocks, batch), dim3(256), 0, s, in_dev, hw, (const float*)scratch_dev, parts, out_dev, vec);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -225,6 +225,25 @@ extern "C" int wm_crop_chips_u8(const wm_frame_desc* frames_dev, int n_frames, c
                              (hipStream_t)stream);
 }
 
+extern "C" int wm_box_outline_rect(const float box[4], int32_t out[4]) {
+    if (!box || !out) return fail("wm_box_outline_rect: null argument");
+    const outline_rect r = box_outline_rect_of(box);
+    out[0] = r.drawn ? r.l : 0; out[1] = r.drawn ? r.t : 0; out[2] = r.drawn ? r.r : 0; out[3] = r.drawn ? r.b : 0;
+    return r.drawn ? 0 : 1;
+}
+
+extern "C" int wm_draw_boxes_u8(const wm_frame_desc* frames_dev, int n_frames, const float* boxes_dev, const int32_t* labels_dev,
+                                const int32_t* box_frame_dev, int n, const uint8_t* palette_dev, int palette_size, int width,
+                                void* stream) {
+    return launch_draw_boxes(frames_dev, n_frames, boxes_dev, labels_dev, box_frame_dev, n, palette_dev, palette_size, width,
+                             (hipStream_t)stream);
+}
+
+extern "C" int wm_plot_image_u8(const float* in_dev, int batch, int height, int width, uint8_t* out_dev, void* scratch_dev,
+                                int64_t scratch_bytes, void* stream) {
+    return launch_plot_image(in_dev, batch, height, width, out_dev, scratch_dev, scratch_bytes, (hipStream_t)stream);
+}
+
 // ---- taps / profiling / debug counters ----
 extern "C" int wm_set_tap(wm_handle* h, int which) {
     if (!h) return fail("wm_set_tap: null handle");

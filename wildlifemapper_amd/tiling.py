@@ -22,6 +22,9 @@ match: the checker is oracle/tiling_oracle.py, a numpy restatement of exactly wh
   * chips= (detect_frame, detect_frames), crop_chips, chip_windows: opt-in review chips -- one fixed-size crop per
     detection, cut from the source-resolution frame around its box (chip rule: include/wm_hip.h) and resampled with PIL's
     bilinear arithmetic, every chip of the frames a merge completed in one launch (wm_crop_chips_u8).
+  * overlay= (detect_frame, detect_frames), draw_boxes, outline_rects, DEFAULT_PALETTE: opt-in survey overlays -- the source
+    frame at a size that fits a screen (PIL-exact, wm_resample_u8) with every detection outlined in its class colour
+    (outline rule: include/wm_hip.h), the outlines of the frames a merge completed in one launch (wm_draw_boxes_u8).
 Frame coordinates are fp32: a box coordinate keeps a fractional resolution below 0.01 px up to 65536 px (ulp 2**-8).
 """
 from __future__ import annotations
@@ -258,12 +261,125 @@ def crop_chips(frames, boxes: torch.Tensor, box_frame=None, chip: int = 128, con
     return chips, windows
 
 
+# ---- overlays --------------------------------------------------------------------------------------------------------
+
+DRAW_MAX_WIDTH, DRAW_MAX_PALETTE = 16, 256          # include/wm_hip.h WM_DRAW_MAX_WIDTH, WM_DRAW_MAX_PALETTE
+OVERLAY_MIN, OVERLAY_MAX = 64, 8192                 # detect_frames(overlay=L): the long side of the picture
+
+# The project's own colours for labels 0..8, (R, G, B) for an RGB frame: the model's 0-based labels and the reference's
+# keys 1..8 are both covered.  Rows are written as they are, whatever the channel order of the frame they are drawn on.
+DEFAULT_PALETTE = np.array([(230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200), (245, 130, 48), (145, 30, 180),
+                            (70, 240, 240), (240, 50, 230), (255, 255, 255)], dtype=np.uint8)
+DEFAULT_PALETTE.setflags(write=False)
+
+
+def _check_draw_width(width, what: str) -> int:
+    if isinstance(width, bool) or not isinstance(width, (int, np.integer)):
+        raise ValueError(f"{what}: width {width!r} is not an integer")
+    if not (1 <= width <= DRAW_MAX_WIDTH):
+        raise ValueError(f"{what}: width {width!r} must be in 1..{DRAW_MAX_WIDTH}")
+    return int(width)
+
+
+def _check_palette(palette, what: str) -> np.ndarray:
+    """None -> DEFAULT_PALETTE; else a (P,3) uint8 table, P in 1..256, as a contiguous host array."""
+    if palette is None:
+        return DEFAULT_PALETTE
+    if isinstance(palette, torch.Tensor):
+        palette = palette.detach().cpu().numpy()
+    pal = np.asarray(palette)
+    if pal.dtype != np.uint8 or pal.ndim != 2 or pal.shape[1] != 3 or not (1 <= pal.shape[0] <= DRAW_MAX_PALETTE):
+        raise ValueError(f"{what}: palette must be a (P,3) uint8 table with P in 1..{DRAW_MAX_PALETTE}, got {pal.dtype} {pal.shape}")
+    return np.ascontiguousarray(pal)
+
+
+def _check_overlay(overlay, what: str) -> int:
+    """Validate an overlay size before any device work: an integer in 64..8192."""
+    if isinstance(overlay, bool) or not isinstance(overlay, (int, np.integer)):
+        raise ValueError(f"{what}: overlay size {overlay!r} is not an integer")
+    if not (OVERLAY_MIN <= overlay <= OVERLAY_MAX):
+        raise ValueError(f"{what}: overlay size {overlay!r} must be in {OVERLAY_MIN}..{OVERLAY_MAX}")
+    return int(overlay)
+
+
+def outline_rects(boxes) -> Tuple[np.ndarray, np.ndarray]:
+    """The outline rule's first step on the host (wm_box_outline_rect; no device call): boxes (n,4) xyxy -> ((n,4) int32
+    rectangles (l, t, r, b), r and b inclusive, zeros for a skipped box; (n,) bool, True where the box is drawn).  A box
+    is skipped here for a non-finite coordinate or r < l or b < t."""
+    import ctypes as C
+    if isinstance(boxes, torch.Tensor):
+        boxes = boxes.detach().cpu().numpy()
+    b = np.ascontiguousarray(np.asarray(boxes, dtype=np.float32).reshape(-1, 4))
+    out = np.zeros((b.shape[0], 4), dtype=np.int32)
+    drawn = np.zeros(b.shape[0], dtype=bool)
+    fn = N.lib().wm_box_outline_rect
+    FP, IP = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    for i in range(b.shape[0]):
+        st = fn(b[i].ctypes.data_as(FP), out[i].ctypes.data_as(IP))
+        if st < 0:
+            N.check(st)
+        drawn[i] = st == 0
+    return out, drawn
+
+
+def draw_boxes(frames, boxes: torch.Tensor, labels: torch.Tensor, box_frame=None, width: int = 2, palette=None):
+    """Outline every box on its frame, IN PLACE, all in one launch (wm_draw_boxes_u8), and return `frames`.  frames: one
+    contiguous (H,W,3) uint8 ROCm frame or a list of them; boxes (n,4) fp32 xyxy in the pixels of their frame, on the
+    frames' device; labels (n,) integers (int64 as detect_frames returns them, or int32); box_frame (n,) the frame index of
+    each box (None: all in frame 0).  palette: a (P,3) uint8 table, row `label` written as it is (None: DEFAULT_PALETTE).
+    The outline rule (include/wm_hip.h): corners truncated toward zero, right and bottom inclusive, a border of `width`
+    pixels growing inward, clipped to the frame -- PIL.ImageDraw.rectangle's pixels wherever both sides exceed `width`.
+    A box with a non-finite coordinate, an inverted box, a frame index outside the list or a label outside the palette
+    draws nothing.  The result is that of drawing the boxes in index order, later over earlier.  Runs on the current
+    stream."""
+    width = _check_draw_width(width, "draw_boxes")
+    pal = _check_palette(palette, "draw_boxes")
+    given = frames
+    frames = [frames] if isinstance(frames, torch.Tensor) else list(frames)
+    if not frames:
+        raise RuntimeError("draw_boxes: no frames")
+    for i, fr in enumerate(frames):
+        if not isinstance(fr, torch.Tensor) or not fr.is_cuda or fr.dtype != torch.uint8 or fr.dim() != 3 or fr.shape[-1] != 3:
+            raise RuntimeError(f"draw_boxes: frame {i}: expected an (H,W,3) uint8 ROCm tensor")
+        if not fr.is_contiguous():
+            raise RuntimeError(f"draw_boxes: frame {i} is not contiguous (it is drawn on in place)")
+    dev = frames[0].device
+    N.require_cuda(boxes, "draw_boxes: boxes")
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or boxes.device != dev or any(fr.device != dev for fr in frames):
+        raise RuntimeError(f"draw_boxes: boxes {tuple(boxes.shape)} on {boxes.device}, frames on {dev}: expected (n,4) on one device")
+    n = boxes.shape[0]
+    labels = torch.as_tensor(labels)
+    if tuple(labels.shape) != (n,) or labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise RuntimeError(f"draw_boxes: labels {tuple(labels.shape)} {labels.dtype} for {n} boxes: expected (n,) integers")
+    labels = labels.to(device=dev, dtype=torch.int32).contiguous()
+    if box_frame is not None:
+        box_frame = torch.as_tensor(box_frame).to(device=dev, dtype=torch.int32).contiguous()
+        if tuple(box_frame.shape) != (n,):
+            raise RuntimeError(f"draw_boxes: box_frame {tuple(box_frame.shape)} for {n} boxes")
+    if n:
+        with torch.cuda.device(dev):
+            desc = _frame_descs(frames, dev)
+            pal_d = torch.from_numpy(pal.copy()).pin_memory().to(dev, non_blocking=True)
+            N.check(N.lib().wm_draw_boxes_u8(N.ptr(desc), len(frames), N.ptr(boxes), N.ptr(labels), N.ptr(box_frame), n, N.ptr(pal_d),
+                                             pal.shape[0], width, N.stream_ptr(dev)))
+    return given
+
+
+def overlay_size(height: int, width: int, overlay: int) -> Tuple[int, int]:
+    """(oh, ow) of detect_frames(overlay=L)'s picture of a height x width frame: preprocess.scaled_size(height, width,
+    L / max(height, width)) when the long side exceeds L, else (height, width)."""
+    m = max(height, width)
+    return preprocess.scaled_size(height, width, overlay / m) if m > overlay else (height, width)
+
+
 def detect_frame(model, frame: torch.Tensor, overlap: int = 128, batch: int = 16, iou_thr: float = 0.4, scale=None,
-                 resize=None, fuse_thr=None, chips=None, chip_context: float = 1.5, chip_min_side: int = 32) -> Dict[str, torch.Tensor]:
+                 resize=None, fuse_thr=None, chips=None, chip_context: float = 1.5, chip_min_side: int = 32, overlay=None,
+                 overlay_width: int = 2, overlay_palette=None) -> Dict[str, torch.Tensor]:
     """One frame -> merged detections {'boxes' (k,4) frame xyxy, 'scores', 'labels', 'tile', 'origins', 'records'} in
     merged-NMS order: detect_frames on a survey of this one frame (a callable scale is called with index 0)."""
     return next(detect_frames(model, [frame], overlap, batch, iou_thr, scale=scale, resize=resize, fuse_thr=fuse_thr, chips=chips,
-                              chip_context=chip_context, chip_min_side=chip_min_side))
+                              chip_context=chip_context, chip_min_side=chip_min_side, overlay=overlay, overlay_width=overlay_width,
+                              overlay_palette=overlay_palette))
 
 
 # ---- survey: many frames of any size ---------------------------------------------------------------------------------
@@ -304,7 +420,7 @@ class _Frame:
 
     def __init__(self, data, height, width, origins, ready, scale_xy=None, source=None):
         self.data, self.height, self.width, self.origins, self.ready = data, height, width, origins, ready
-        self.source = source                  # chips= only: the source-resolution device frame, kept until finish()
+        self.source = source                  # chips= / overlay= only: the source-resolution device frame, kept until finish()
         self.records: List[torch.Tensor] = []
         self.origins_dev = None
         self.scale_xy = scale_xy              # resampled mode: (sx, sy) = float32(W / ow), float32(H / oh); else None
@@ -329,8 +445,8 @@ def _as_frame_array(frame, i: int, device: torch.device):
 
 @torch.no_grad()
 def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, iou_thr: float = 0.4, scale=None,
-                  resize=None, fuse_thr=None, chips=None, chip_context: float = 1.5,
-                  chip_min_side: int = 32) -> Iterator[Dict[str, torch.Tensor]]:
+                  resize=None, fuse_thr=None, chips=None, chip_context: float = 1.5, chip_min_side: int = 32, overlay=None,
+                  overlay_width: int = 2, overlay_palette=None) -> Iterator[Dict[str, torch.Tensor]]:
     """Survey of frames of any sizes ((H,W,3) uint8 ROCm tensors, CPU tensors or numpy arrays) -> one dict per frame, in
     input order, with detect_frame's keys and values.  Tiles of consecutive frames fill batches of `batch` (plan_batches);
     after each batch one wm_merge_frames_nms covers the frames it completed.  Host frames go through one pinned staging
@@ -357,7 +473,18 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
     their detection counts have reached the host (no detections: an empty tensor and no launch).  A frame is therefore
     kept until its result is yielded instead of being released at its last tile cut, and in resampled mode its source is
     kept beside its resample instead of being released once the resample is queued: one extra source-resolution frame
-    (H * W * 3 bytes, 72 MB at 6000 x 4000) of device memory per frame in flight.  chips=None: none of this."""
+    (H * W * 3 bytes, 72 MB at 6000 x 4000) of device memory per frame in flight.  chips=None: none of this.
+
+    overlay= (an integer L in 64..8192; overlay_width, overlay_palette: draw_boxes' width and palette): every frame also
+    comes with the picture a reviewer opens first, and the dict gains 'overlay' (oh,ow,3) uint8 -- the SOURCE frame at
+    (oh, ow) = overlay_size(H, W, L) with every detection outlined in its label's colour -- and 'overlay_boxes' (k,4) fp32
+    = boxes * (float32(ow / W), float32(oh / H), float32(ow / W), float32(oh / H)) in fp32, aligned with 'boxes' (the
+    union boxes when fusing, source-pixel boxes when resampling).  A frame whose long side exceeds L is resampled as
+    PIL.Image.resize((ow, oh), BILINEAR) does (wm_resample_u8), any other is copied; detections are drawn in the order
+    they are listed, the most confident first, later over earlier.  One resample (or copy) per frame and one
+    wm_draw_boxes_u8 launch for the frames a merge completed, queued where the chips' launch is queued.  The source frame
+    is kept exactly as chips= keeps it, at the same memory cost (once, when both are set).  overlay=None: no key, no
+    launch, no retained frame."""
     from .engine import split_records
     import ctypes as C
     if batch <= 0:
@@ -367,6 +494,11 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
     if chips is not None:
         chips = _check_chip(chips, "detect_frames")
         chip_context, chip_min_side, _ = _check_chip_rule(chip_context, chip_min_side, CHIP_MAX_SIDE, "detect_frames")
+    if overlay is not None:
+        overlay = _check_overlay(overlay, "detect_frames")
+        overlay_width = _check_draw_width(overlay_width, "detect_frames")
+        overlay_palette = _check_palette(overlay_palette, "detect_frames")
+    keep_source = chips is not None or overlay is not None
     device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
     staged: Dict[int, _Frame] = {}
     pinned = [None, None]                     # staging buffer, event of the last copy out of it
@@ -392,12 +524,12 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
             src = d
             ready = uploaded = torch.cuda.Event()
             uploaded.record(copy[0])
-            if resample_to is not None:       # the uploaded source goes once its resample is queued (chips= keeps it)
+            if resample_to is not None:       # the uploaded source goes once its resample is queued (chips= / overlay= keep it)
                 d = preprocess.resample_u8(d, resample_to)
                 ready = torch.cuda.Event()
                 ready.record(copy[0])
         d.record_stream(torch.cuda.current_stream(device))
-        if chips is not None:
+        if keep_source:
             src.record_stream(torch.cuda.current_stream(device))
         pinned[1] = uploaded
         return d, ready, src
@@ -422,13 +554,13 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
                 src = d
                 d, ready = (d if size is None else preprocess.resample_u8(d, size)), None
             sxy = (float(np.float32(W / ow)), float(np.float32(H / oh)))
-            staged[i] = _Frame(d, oh, ow, tile_origins(oh, ow, 1024, overlap), ready, sxy, src if chips is not None else None)
+            staged[i] = _Frame(d, oh, ow, tile_origins(oh, ow, 1024, overlap), ready, sxy, src if keep_source else None)
             return True
         org = tile_origins(H, W, 1024, overlap)
         ready = None
         if d is None:
             d, ready, _ = upload(h, H, W)
-        staged[i] = _Frame(d, H, W, org, ready, None, d if chips is not None else None)
+        staged[i] = _Frame(d, H, W, org, ready, None, d if keep_source else None)
         return True
 
     def tile_counts():
@@ -463,14 +595,20 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
                 src[:, 1::2] = b[:, 1::2] * fr.scale_xy[1]
                 res["boxes"] = src
                 res["resampled_size"] = (fr.height, fr.width)
-            if chips is None:
-                yield res
-            else:
+            if keep_source:
                 done.append((fr, res))
-        if chips is not None:
-            yield from with_chips(done)
+            else:
+                yield res
+        if done:
+            if chips is not None:
+                add_chips(done)
+            if overlay is not None:
+                add_overlays(done)
+            for fr, res in done:
+                fr.source = None
+                yield res
 
-    def with_chips(done):
+    def add_chips(done):
         """One crop launch for every detection of the frames of one merge, cut from the source frames at 'boxes'."""
         S = chips
         ks = [res["boxes"].shape[0] for _, res in done]
@@ -490,8 +628,24 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
             org = win[:, [1, 0, 1, 0]].to(torch.float32)
             res["chip_boxes"] = (res["boxes"] - org) * zoom[:, None]
             pos += k
-            fr.source = None
-            yield res
+
+    def add_overlays(done):
+        """One resample (or copy) of each source frame of one merge, then one draw launch for all their detections."""
+        pics, ks = [], []
+        for fr, res in done:
+            H, W = int(fr.source.shape[0]), int(fr.source.shape[1])
+            oh, ow = overlay_size(H, W, overlay)
+            pics.append(fr.source.clone() if (oh, ow) == (H, W) else preprocess.resample_u8(fr.source, (oh, ow)))
+            b = res["boxes"]
+            ob = torch.empty_like(b)
+            ob[:, 0::2] = b[:, 0::2] * float(np.float32(ow / W))
+            ob[:, 1::2] = b[:, 1::2] * float(np.float32(oh / H))
+            res["overlay"], res["overlay_boxes"] = pics[-1], ob
+            ks.append(b.shape[0])
+        if sum(ks):
+            idx = torch.from_numpy(np.repeat(np.arange(len(done), dtype=np.int32), ks)).pin_memory().to(device, non_blocking=True)
+            draw_boxes(pics, torch.cat([res["overlay_boxes"] for _, res in done]).contiguous(),
+                       torch.cat([res["labels"] for _, res in done]), idx, overlay_width, overlay_palette)
 
     pending = None
     main = None
