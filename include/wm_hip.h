@@ -29,7 +29,9 @@
 extern "C" {
 #endif
 
-/* 12: wm_box_outline_rect, wm_draw_boxes_u8, wm_plot_image_u8, WM_DRAW_MAX_WIDTH, WM_DRAW_MAX_PALETTE, WM_PLOT_SCRATCH_BYTES
+/* 13: wm_census_scratch_bytes, wm_census, WM_CENSUS_MAX_DETS, WM_CENSUS_SAME_CLASS, WM_CENSUS_UNSOLVED (survey census: the
+ *    detections of overlapping frames grouped into individuals on the ground); nothing else changed.
+ * 12: wm_box_outline_rect, wm_draw_boxes_u8, wm_plot_image_u8, WM_DRAW_MAX_WIDTH, WM_DRAW_MAX_PALETTE, WM_PLOT_SCRATCH_BYTES
  *    (survey overlays: detections outlined on frames and tiles, on the GPU); nothing else changed.
  * 11: wm_chip_window, wm_crop_chips_u8, WM_CHIP_MAX_SIDE (survey review chips: one PIL-exact crop per detection, cut on
  *    the GPU); nothing else changed.
@@ -50,7 +52,7 @@ extern "C" {
  * wm_profile_read no longer reports the fused-LayerNorm time-out (wm_forward / wm_encoder_forward do); precision value 2
  * (fp8), WM_FLAG_MERGED and a NULL handle in wm_postprocess_nms date from round 2.  The Python binding refuses a library
  * whose wm_abi_version() differs from the value it was written for. */
-#define WM_ABI_VERSION 12
+#define WM_ABI_VERSION 13
 
 /* operand type of the transformer blocks' MFMA GEMMs / attention (accumulation, residual stream, LayerNorm
  * statistics, softmax and the whole decoder are fp32; the stem, the HFC adaptor and the neck -- 2.9 % of the
@@ -273,6 +275,45 @@ int wm_merge_frames_fuse(const wm_box_record* records_dev, const int32_t* origin
                          int n_frames, float fuse_thr, void* scratch_dev, int64_t scratch_bytes, wm_box_record* merged_dev,
                          wm_box_record* det_dev, int32_t* det_tile_dev, int32_t* det_count_dev,
                          int32_t* det_members_dev, int32_t* slot_det_dev, void* stream);
+
+/* Survey census (tiling.census): survey frames overlap (60-80 % along a flight line, and sideways between lines), so an
+ * animal is detected in two to four frames; the census groups the detections of a whole survey into individuals.  No
+ * reference behaviour exists; this rule is the contract, and tests/test_census.py restates it sequentially.
+ * Inputs: n detections, each a box (x0, y0, x1, y1) fp32 in the pixels of its frame, a score fp32, a label int32 and a
+ * frame index f int32; georef_dev[n_frames][6] doubles (a0..a5) per frame, frame pixels -> ground metres, X east, Y north.
+ * Ground point, in double, every operation correctly rounded on its own (no contraction):
+ *     cx = ((double)x0 + (double)x1) * 0.5      cy = ((double)y0 + (double)y1) * 0.5
+ *     X  = (a0 * cx + a1 * cy) + a2             Y  = (a3 * cx + a4 * cy) + a5
+ * Invalid detections: a box coordinate or the score not finite, f outside [0, n_frames), or X or Y not finite.  An invalid
+ * detection belongs to no individual: individual -1, point (NaN, NaN).
+ * Priority: valid detections by score descending (-0 ties with +0), then by input index ascending.
+ * Association: sequential, in priority order; r2 = radius * radius once, in double, on the host.  Individual q is
+ * eligible for detection p when
+ *   1. dx * dx + dy * dy <= r2 (double, inclusive) between p's point and the point of q's KEEPER (its founder; not a mean
+ *      of the members);
+ *   2. no member of q, keeper included, comes from p's frame;
+ *   3. with WM_CENSUS_SAME_CLASS in flags: p's label equals the keeper's label.
+ * If an individual is eligible, p joins the one at the smallest squared distance, ties to the individual founded
+ * earlier; otherwise p founds a new individual and is its keeper.  Individuals are numbered in the order they are founded.
+ * Condition 2 is what keeps a herd's count right: two animals a metre apart are both seen by the same frames, and the
+ * second one's detections cannot all be absorbed by the first.
+ * Outputs (device): points_dev[n][2] every detection's ground point; individual_dev[n] its individual or -1;
+ * keeper_dev[k] the input index of individual k's keeper and members_dev[k] its member count, k < count_dev[0];
+ * count_dev[1] = status bits: WM_CENSUS_UNSOLVED if the kernel's bounded round loop (at most n rounds; a round always
+ * decides the highest-priority open detection, so it cannot happen) ended with detections undecided, which stay at -1.
+ * Argument limits: radius finite and >= 0 with r2 finite; 0 <= n <= WM_CENSUS_MAX_DETS; n_frames >= 1; scratch_dev
+ * 16-byte aligned with at least wm_census_scratch_bytes(n) bytes.  Bad arguments fail before any HIP call; n == 0
+ * returns 0 before looking at any pointer (count 0: nothing is written).  One launch of one workgroup on `stream`,
+ * asynchronous, nothing allocated.  After the call the first int32 of scratch_dev holds the rounds taken (diagnostic). */
+#define WM_CENSUS_MAX_DETS 262144
+#define WM_CENSUS_SAME_CLASS 1
+#define WM_CENSUS_UNSOLVED 1            /* status bit 0 */
+int64_t wm_census_scratch_bytes(int n);                       /* <0 on error */
+int wm_census(const float* boxes_dev, const float* scores_dev, const int32_t* labels_dev, const int32_t* box_frame_dev, int n,
+              const double* georef_dev /* [n_frames][6] */, int n_frames, double radius, int flags,
+              void* scratch_dev, int64_t scratch_bytes,
+              double* points_dev /* [n][2] */, int32_t* individual_dev /* [n] */, int32_t* keeper_dev /* [n]: input index of individual k's keeper, k < count */,
+              int32_t* members_dev /* [n]: members of individual k */, int32_t* count_dev /* [2]: individuals, status */, void* stream);
 
 /* Survey resampling (tiling.detect_frames(scale=..., resize=...)): a frame brought to the scale the checkpoint was trained
  * at (the val transform's long side of 768, dataloader_coco.py:288) before it is tiled.

@@ -20,10 +20,11 @@ GEMM_VARIANTS = ("v1_128", "v2_160", "v2_128", "v3_lockstep", "v3_conv3x3", "v5_
                  "v5_320_lnf", "v5_256_lnf", "fp8_320", "fp8_256", "v5_320_foldp", "v5_256_foldp", "v5_320_split", "v5_256_split", "v3_patch_embed", "fp8_256_planes")
 FLAG_CONF, FLAG_SCORE, FLAG_NMS, FLAG_MERGED = 1, 2, 4, 8
 CRITERION_MAX_TARGETS, CRITERION_SUMS, CRITERION_NONFINITE, CRITERION_UNSOLVED = 2048, 8, 1, 2
+CENSUS_MAX_DETS, CENSUS_SAME_CLASS, CENSUS_UNSOLVED = 262144, 1, 1
 CFG_FUSE_LN = 1
 CFG_FOLD_LN = 2
 CFG_FOLD_LN_BF16 = 4
-ABI_VERSION = 12           # include/wm_hip.h WM_ABI_VERSION this binding was written for
+ABI_VERSION = 13           # include/wm_hip.h WM_ABI_VERSION this binding was written for
 FP8_QKV, FP8_PROJ, FP8_MLP, FP8_ALL = 1, 2, 4, 7
 GEMM_W_PACKED, GEMM_A_PACKED, GEMM_OUT_PACKED, LAYOUT_PACKED = 0x1000, 0x2000, 0x4000, 0x100
 GEMM32_SPLIT = 0x100          # wm_op_gemm32: act | GEMM32_SPLIT = the fp16-split form the decoder runs (W split per K-step)
@@ -63,6 +64,8 @@ SYMBOLS = {
     "wm_merge_frames_scratch_bytes": (_L, [_I]),
     "wm_merge_frames_nms": (_I, [_P, _P, C.POINTER(C.c_int32), _I, _F, _P, _L, _P, _P, _P, _P, _P]),
     "wm_merge_frames_fuse": (_I, [_P, _P, C.POINTER(C.c_int32), _I, _F, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
+    "wm_census_scratch_bytes": (_L, [_I]),
+    "wm_census": (_I, [_P, _P, _P, _P, _I, _P, _I, C.c_double, _I, _P, _L, _P, _P, _P, _P, _P, _P]),
     "wm_resample_u8": (_I, [_P, _I, _I, _P, _I, _I, _P]),
     "wm_scaled_size": (_I, [_I, _I, C.c_double, C.POINTER(_I), C.POINTER(_I)]),
     "wm_chip_window": (_I, [C.POINTER(_F), _F, _I, _I, C.POINTER(C.c_int32)]),

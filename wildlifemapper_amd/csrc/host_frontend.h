@@ -1,9 +1,10 @@
 // Image front end: the val-transform resize (plan cache per device), the survey resampler (plan slots per stream), the
-// survey merge launcher, the review-chip launcher and the overlay launchers (box outlines, the reference's plot image).
+// survey merge launcher, the census launcher, the review-chip launcher and the overlay launchers (box outlines, the reference's plot image).
 #pragma once
 #include "misc_kernels.h"
 #include "resample_kernels.h"
 #include "survey_kernels.h"
+#include "census_kernels.h"
 #include "chip_kernels.h"
 #include "overlay_kernels.h"
 #include "host_core.h"
@@ -42,6 +43,39 @@ static int launch_merge_frames(const char* name, const char* thr_name, const wm_
                            (int*)det_tile_dev, (int*)det_count_dev, (int*)det_members_dev, (int*)slot_det_dev, f0);
         HIP_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+// Survey census: every argument is checked on the host before the first HIP call; one launch of one workgroup.
+int64_t census_scratch_bytes(int n) {
+    if (n < 0 || n > WM_CENSUS_MAX_DETS) return fail("wm_census_scratch_bytes: n %d outside 0..%d", n, WM_CENSUS_MAX_DETS);
+    return CENSUS_HEADER + (int64_t)n * CENSUS_SCRATCH_PER_DET;
+}
+
+int launch_census(const float* boxes_dev, const float* scores_dev, const int32_t* labels_dev, const int32_t* box_frame_dev, int n,
+                  const double* georef_dev, int n_frames, double radius, int flags, void* scratch_dev, int64_t scratch_bytes,
+                  double* points_dev, int32_t* individual_dev, int32_t* keeper_dev, int32_t* members_dev, int32_t* count_dev,
+                  hipStream_t s) {
+    const char* name = "wm_census";
+    if (n < 0 || n > WM_CENSUS_MAX_DETS) return fail("%s: n %d outside 0..%d", name, n, WM_CENSUS_MAX_DETS);
+    if (n == 0) return 0;
+    if (!boxes_dev || !scores_dev || !labels_dev || !box_frame_dev || !georef_dev || !scratch_dev || !points_dev || !individual_dev ||
+        !keeper_dev || !members_dev || !count_dev)
+        return fail("%s: null buffer", name);
+    if (n_frames <= 0) return fail("%s: n_frames %d", name, n_frames);
+    if (!(std::isfinite(radius) && radius >= 0.0)) return fail("%s: radius %g: need a finite radius >= 0", name, radius);
+    const double r2 = radius * radius;
+    if (!std::isfinite(r2)) return fail("%s: radius %g: its square is not finite", name, radius);
+    if (flags & ~WM_CENSUS_SAME_CLASS) return fail("%s: flags 0x%x", name, (unsigned)flags);
+    const int64_t need = census_scratch_bytes(n);
+    if (scratch_bytes < need) return fail("%s: scratch of %lld bytes, %lld needed", name, (long long)scratch_bytes, (long long)need);
+    if ((uintptr_t)scratch_dev % 16) return fail("%s: scratch not 16-byte aligned", name);
+    if ((uintptr_t)boxes_dev % 16 || (uintptr_t)points_dev % 16 || (uintptr_t)georef_dev % 8)
+        return fail("%s: boxes_dev / points_dev not 16-byte aligned, or georef_dev not 8-byte aligned", name);
+    hipLaunchKernelGGL(census_kernel, dim3(1), dim3(MF_THREADS), 0, s, (const float4*)boxes_dev, scores_dev, (const int*)labels_dev,
+                       (const int*)box_frame_dev, n, georef_dev, n_frames, radius, r2, flags & WM_CENSUS_SAME_CLASS, (char*)scratch_dev,
+                       (double2*)points_dev, (int*)individual_dev, (int*)keeper_dev, (int*)members_dev, (int*)count_dev);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

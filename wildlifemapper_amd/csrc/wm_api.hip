@@ -218,6 +218,16 @@ extern "C" int wm_chip_window(const float box[4], float context, int min_side, i
     return 0;
 }
 
+extern "C" int64_t wm_census_scratch_bytes(int n) { return census_scratch_bytes(n); }
+
+extern "C" int wm_census(const float* boxes_dev, const float* scores_dev, const int32_t* labels_dev, const int32_t* box_frame_dev, int n,
+                         const double* georef_dev, int n_frames, double radius, int flags, void* scratch_dev, int64_t scratch_bytes,
+                         double* points_dev, int32_t* individual_dev, int32_t* keeper_dev, int32_t* members_dev, int32_t* count_dev,
+                         void* stream) {
+    return launch_census(boxes_dev, scores_dev, labels_dev, box_frame_dev, n, georef_dev, n_frames, radius, flags, scratch_dev,
+                         scratch_bytes, points_dev, individual_dev, keeper_dev, members_dev, count_dev, (hipStream_t)stream);
+}
+
 extern "C" int wm_crop_chips_u8(const wm_frame_desc* frames_dev, int n_frames, const float* boxes_dev, const int32_t* box_frame_dev, int n,
                                 int chip, float context, int min_side, int max_side, uint8_t* chips_dev, int32_t* windows_dev,
                                 void* stream) {

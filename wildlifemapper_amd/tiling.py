@@ -25,6 +25,9 @@ match: the checker is oracle/tiling_oracle.py, a numpy restatement of exactly wh
   * overlay= (detect_frame, detect_frames), draw_boxes, outline_rects, DEFAULT_PALETTE: opt-in survey overlays -- the source
     frame at a size that fits a screen (PIL-exact, wm_resample_u8) with every detection outlined in its class colour
     (outline rule: include/wm_hip.h), the outlines of the frames a merge completed in one launch (wm_draw_boxes_u8).
+  * census, nadir_affine: the count a survey is flown for -- the detections of all frames (detect_frames' dicts) go to
+    ground coordinates through each frame's georeference and are grouped into individuals, at most one detection of any
+    frame per individual (census rule: include/wm_hip.h), by one wm_census launch over the whole survey.
 Frame coordinates are fp32: a box coordinate keeps a fractional resolution below 0.01 px up to 65536 px (ulp 2**-8).
 """
 from __future__ import annotations
@@ -697,3 +700,136 @@ def detect_frames(model, frames: Iterable, overlap: int = 128, batch: int = 16, 
             pending = (out, list(b.completes), offs)
     if pending is not None:
         yield from finish(pending)
+
+
+# ---- census ----------------------------------------------------------------------------------------------------------
+
+CENSUS_MAX_DETS = N.CENSUS_MAX_DETS           # include/wm_hip.h WM_CENSUS_MAX_DETS
+CENSUS_CLASSES = 7                            # 'class_counts': the model's labels 0..6 (box_decoder.py:50, 6 + 1 classes)
+
+
+def _check_radius(radius, what: str) -> float:
+    """Validate radius= before any device work: a finite number >= 0 whose square is finite in double."""
+    try:
+        r = float(radius)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: radius {radius!r} is not a number") from None
+    if not (math.isfinite(r) and r >= 0.0 and math.isfinite(r * r)):
+        raise ValueError(f"{what}: radius {radius!r} must be finite and >= 0, with a finite square")
+    return r
+
+
+def _check_georef(georef, what: str) -> np.ndarray:
+    """(F,2,3) float64, C-contiguous: rows (a0, a1, a2) and (a3, a4, a5) of every frame.  Values are not checked: a
+    georeference that is not finite makes its frame's detections invalid (the census rule)."""
+    if isinstance(georef, torch.Tensor):
+        georef = georef.detach().cpu().numpy()
+    try:
+        g = np.ascontiguousarray(np.asarray(georef, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: georef is not an array of numbers") from None
+    if g.size == 0 and g.ndim <= 1:
+        g = g.reshape(0, 2, 3)
+    if g.ndim != 3 or g.shape[1:] != (2, 3):
+        raise ValueError(f"{what}: georef of shape {g.shape}: expected (F, 2, 3)")
+    return g
+
+
+def nadir_affine(height, width, centre, gsd, yaw_deg=0.0) -> np.ndarray:
+    """Georeference of a nadir frame, (2,3) float64 for census(): [[a0, a1, a2], [a3, a4, a5]], X = a0*x + a1*y + a2 east
+    and Y = a3*x + a4*y + a5 north, in metres, of the pixel position (x, y).  centre = (E, N) is the ground position of pixel
+    (width / 2, height / 2), gsd the metres per pixel, yaw_deg the heading of the image's up direction, clockwise from
+    north: at 0 right is east and down is south, at 90 up is east.  Host only, in double."""
+    H, W, gsd, yaw = float(height), float(width), float(gsd), float(yaw_deg)
+    E, Nn = (float(v) for v in centre)
+    if not (H > 0 and W > 0 and math.isfinite(H) and math.isfinite(W)):
+        raise ValueError(f"nadir_affine: height {height!r}, width {width!r}")
+    if not (math.isfinite(gsd) and gsd > 0 and math.isfinite(yaw) and math.isfinite(E) and math.isfinite(Nn)):
+        raise ValueError(f"nadir_affine: gsd {gsd!r} must be finite and > 0, centre and yaw_deg finite")
+    psi = math.radians(yaw)
+    c, sn = math.cos(psi), math.sin(psi)
+    a0, a1 = gsd * c, -gsd * sn
+    a3, a4 = -gsd * sn, -gsd * c
+    return np.array([[a0, a1, E - (a0 * W / 2 + a1 * H / 2)],
+                     [a3, a4, Nn - (a3 * W / 2 + a4 * H / 2)]], dtype=np.float64)
+
+
+def census(results, georef, radius, same_class: bool = False) -> Dict[str, object]:
+    """Count each animal once across overlapping frames (wm_census; rule: include/wm_hip.h).  results: an iterable (a
+    generator is fine) of the dicts detect_frames yields -- 'boxes' (k,4) fp32, 'scores' (k,), 'labels' (k,) are used as
+    they come (union boxes when fusing, source-pixel boxes when resampling); georef (F,2,3) float64, an array or a
+    sequence of nadir_affine's results: result i pairs with georef[i].  radius: metres; a detection joins the nearest
+    individual within it that has no member of the detection's own frame (same_class: and whose keeper has its label),
+    else it founds one.  Everything is concatenated on the device; one wm_census launch on the current stream and one
+    small copy of the count (which waits for it).  Returns, with k individuals out of n detections:
+      'count' k (int), 'individual' (n,) int64 (-1: invalid detection), 'det_points' (n,2) float64 ground points (NaN:
+      invalid), 'det_frame' (n,) int64, 'det_offsets' host list of F + 1 (result i is detections [o[i], o[i+1]));
+      per individual, from its keeper (its highest-priority member): 'keeper' (k,) int64 index into the n detections,
+      'points' (k,2) float64, 'scores', 'labels', 'frame' (k,); 'members' (k,) int64; 'class_counts' (7,) int64, the
+      bincount of the keepers' labels 0..6."""
+    what = "census"
+    radius = _check_radius(radius, what)
+    g = _check_georef(georef, what)
+    results = list(results)
+    if len(results) != g.shape[0]:
+        raise ValueError(f"{what}: {len(results)} results for {g.shape[0]} georeferences")
+    dev = None
+    for i, res in enumerate(results):
+        try:
+            b, sc, lb = res["boxes"], res["scores"], res["labels"]
+        except (TypeError, KeyError):
+            raise ValueError(f"{what}: result {i} has no 'boxes', 'scores' and 'labels'") from None
+        if not all(isinstance(t, torch.Tensor) for t in (b, sc, lb)) or b.dim() != 2 or b.shape[1] != 4 or \
+                tuple(sc.shape) != (b.shape[0],) or tuple(lb.shape) != (b.shape[0],):
+            raise ValueError(f"{what}: result {i}: expected boxes (k,4), scores (k,) and labels (k,) tensors")
+        dev = b.device if dev is None else dev
+        if b.device != dev or sc.device != dev or lb.device != dev:
+            raise ValueError(f"{what}: result {i} is on {b.device}, earlier ones on {dev}")
+    ks = [int(res["boxes"].shape[0]) for res in results]
+    offs = [0]
+    for k in ks:
+        offs.append(offs[-1] + k)
+    n = offs[-1]
+    if n > CENSUS_MAX_DETS:
+        raise ValueError(f"{what}: {n} detections exceed {CENSUS_MAX_DETS}")
+    dev = torch.device("cpu") if dev is None else dev
+    i64 = dict(device=dev, dtype=torch.int64)
+    if n == 0:
+        return {"count": 0, "individual": torch.empty(0, **i64), "keeper": torch.empty(0, **i64),
+                "points": torch.empty((0, 2), device=dev, dtype=torch.float64),
+                "det_points": torch.empty((0, 2), device=dev, dtype=torch.float64),
+                "scores": torch.empty(0, device=dev, dtype=torch.float32), "labels": torch.empty(0, **i64),
+                "frame": torch.empty(0, **i64), "members": torch.empty(0, **i64), "det_frame": torch.empty(0, **i64),
+                "det_offsets": offs, "class_counts": torch.zeros(CENSUS_CLASSES, **i64)}
+    boxes = torch.cat([res["boxes"] for res in results]).contiguous()
+    N.require_cuda(boxes, f"{what}: boxes")
+    scores = torch.cat([res["scores"] for res in results]).contiguous()
+    N.require_cuda(scores, f"{what}: scores")
+    labels_in = torch.cat([res["labels"] for res in results])
+    labels = labels_in.to(torch.int32).contiguous()
+    with torch.cuda.device(dev):
+        frame = torch.from_numpy(np.repeat(np.arange(len(ks), dtype=np.int32), ks)).pin_memory().to(dev, non_blocking=True)
+        g_d = torch.from_numpy(g.reshape(-1, 6)).pin_memory().to(dev, non_blocking=True)
+        nbytes = N.lib().wm_census_scratch_bytes(n)
+        if nbytes < 0:
+            N.check(-1)
+        scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        points = torch.empty((n, 2), device=dev, dtype=torch.float64)
+        individual = torch.empty(n, device=dev, dtype=torch.int32)
+        keeper = torch.empty(n, device=dev, dtype=torch.int32)
+        members = torch.empty(n, device=dev, dtype=torch.int32)
+        count = torch.empty(2, device=dev, dtype=torch.int32)
+        N.check(N.lib().wm_census(N.ptr(boxes), N.ptr(scores), N.ptr(labels), N.ptr(frame), n, N.ptr(g_d), g.shape[0], radius,
+                                  N.CENSUS_SAME_CLASS if same_class else 0, N.ptr(scratch), nbytes, N.ptr(points),
+                                  N.ptr(individual), N.ptr(keeper), N.ptr(members), N.ptr(count), N.stream_ptr(dev)))
+        k, status = count.cpu().tolist()
+    if status & N.CENSUS_UNSOLVED:
+        raise RuntimeError(f"{what}: wm_census left detections undecided (status {status})")
+    keeper = keeper[:k].to(torch.int64)
+    klab = labels_in[keeper]
+    ok = (klab >= 0) & (klab < CENSUS_CLASSES)
+    det_frame = frame.to(torch.int64)
+    return {"count": k, "individual": individual.to(torch.int64), "keeper": keeper, "points": points[keeper],
+            "det_points": points, "scores": scores[keeper], "labels": klab, "frame": det_frame[keeper],
+            "members": members[:k].to(torch.int64), "det_frame": det_frame, "det_offsets": offs,
+            "class_counts": torch.bincount(klab[ok].to(torch.int64), minlength=CENSUS_CLASSES)}
