@@ -31,6 +31,10 @@ extern "C" {
 
 /* 13: wm_census_scratch_bytes, wm_census, WM_CENSUS_MAX_DETS, WM_CENSUS_SAME_CLASS, WM_CENSUS_UNSOLVED (survey census: the
  *    detections of overlapping frames grouped into individuals on the ground); nothing else changed.
+ *    13, additive: wm_coverage_raster, wm_coverage_points, WM_COVERAGE_MAX_SIDE, WM_COVERAGE_MAX_CELLS,
+ *    WM_COVERAGE_MAX_FRAMES, WM_COVERAGE_CLASSES, WM_COVERAGE_STATS (survey coverage: the ground a survey saw, its gaps and
+ *    the individuals per cell); the number stays 13 because no v13 caller is affected, and a library without the two
+ *    names is still refused by a binding that looks them up.
  * 12: wm_box_outline_rect, wm_draw_boxes_u8, wm_plot_image_u8, WM_DRAW_MAX_WIDTH, WM_DRAW_MAX_PALETTE, WM_PLOT_SCRATCH_BYTES
  *    (survey overlays: detections outlined on frames and tiles, on the GPU); nothing else changed.
  * 11: wm_chip_window, wm_crop_chips_u8, WM_CHIP_MAX_SIDE (survey review chips: one PIL-exact crop per detection, cut on
@@ -314,6 +318,56 @@ int wm_census(const float* boxes_dev, const float* scores_dev, const int32_t* la
               void* scratch_dev, int64_t scratch_bytes,
               double* points_dev /* [n][2] */, int32_t* individual_dev /* [n] */, int32_t* keeper_dev /* [n]: input index of individual k's keeper, k < count */,
               int32_t* members_dev /* [n]: members of individual k */, int32_t* count_dev /* [2]: individuals, status */, void* stream);
+
+/* Survey coverage (tiling.coverage): a count of individuals becomes a density only over the ground that was observed, and
+ * frames overlap, so that ground is the union of the frame footprints, not their sum.  A ground grid is laid over the
+ * survey; every cell gets the number of frames that saw its centre, and the census' individuals are counted into the same
+ * grid per class, each with the number of frames that could have seen it.  No reference behaviour exists; this rule is the
+ * contract, and tests/test_coverage.py restates it sequentially (coverage_oracle).  All arithmetic is IEEE double, every
+ * operation correctly rounded on its own (no contraction), in the order written.
+ * Frames: g2p_dev[n_frames][6] doubles (b0..b5), the GROUND -> PIXEL affine of each frame (the inverse of the census'
+ * georeference: tiling.ground_to_pixel); size_dev[n_frames][2] int32, (height, width) of the source frame in the pixels
+ * the georeference speaks of.
+ * Grid: (x0, y0) metres, the ground position of its south-west corner; cell metres, finite and > 0; gx cells east, gy
+ * cells north.  Row j = 0 is the SOUTHERNMOST row (a north-up picture is the raster flipped along its first axis).
+ * Predicate sees(f, X, Y):
+ *     u = (b0 * X + b1 * Y) + b2               v = (b3 * X + b4 * Y) + b5
+ *     true iff height >= 1, width >= 1, 0 <= u < width and 0 <= v < height.
+ * A NaN or an infinity anywhere makes it false, so a frame whose georeference is not finite or is singular (its inverse
+ * is NaN) sees nothing and needs no special case.  The footprint is half-open, as the pixel continuum [0, W) x [0, H) is.
+ * Raster: the centre of cell (j, i) is Xc = x0 + ((double)i + 0.5) * cell, Yc = y0 + ((double)j + 0.5) * cell;
+ * coverage_dev[gy][gx] uint16 = the number of frames f with sees(f, Xc, Yc) (n_frames <= 65535: nothing saturates);
+ * stats_dev[16] int64: stats[m], m < 15, the number of cells with coverage == m, stats[15] those with coverage >= 15.
+ * The observed area is (gx * gy - stats[0]) * cell * cell.
+ * Points (optional, an entry of their own): points_dev[n_points][2] doubles (X, Y) on the ground, labels_dev[n_points].
+ *     seen_by_dev[p] int32 = the number of frames with sees(f, X, Y), at the point itself, not at a cell centre; a point
+ *         that is not finite gets 0;
+ *     i = floor((X - x0) / cell), j = floor((Y - y0) / cell): a subtraction, a division, a floor, in double;
+ *     the point is BINNED iff it is finite, 0 <= i < gx, 0 <= j < gy and 0 <= label < 7; a binned point adds 1 to
+ *         counts_dev[label][j][i] (int32 [7][gy][gx]; NULL: nothing is binned into a raster, everything else is written);
+ *     cell_dev[p] = (j, i) int32, (-1, -1) for a point that is not binned;
+ *     pstats_dev[2] int64: [0] binned points, [1] points not binned.
+ * Both entries zero what they accumulate into (stats, pstats, counts) on `stream` and write every element of their
+ * outputs; asynchronous, nothing allocated.  The raster is gathered (a workgroup owns a block of cells and walks the
+ * frames; frames that cannot touch the block are dropped by a conservative test that changes no count), so no atomics touch
+ * it; stats and pstats take 64-bit integer atomics, counts int32 ones: integers, so the order is irrelevant.
+ * Argument limits: 1 <= gx, gy <= WM_COVERAGE_MAX_SIDE, gx * gy <= WM_COVERAGE_MAX_CELLS; 0 <= n_frames <=
+ * WM_COVERAGE_MAX_FRAMES (g2p_dev and size_dev may be NULL at 0, which gives an all-zero raster); 0 <= n_points <=
+ * WM_CENSUS_MAX_DETS; x0, y0, cell finite, cell > 0; doubles and int64 8-byte, int32 4-byte, uint16 2-byte aligned.  Bad
+ * arguments fail before any HIP call with a message that names the argument; n_points == 0 returns 0 before looking at
+ * any pointer (nothing is written). */
+#define WM_COVERAGE_MAX_SIDE 16384
+#define WM_COVERAGE_MAX_CELLS 67108864          /* 2^26 */
+#define WM_COVERAGE_MAX_FRAMES 65535
+#define WM_COVERAGE_CLASSES 7
+#define WM_COVERAGE_STATS 16
+int wm_coverage_raster(const double* g2p_dev /* [n_frames][6] */, const int32_t* size_dev /* [n_frames][2] */, int n_frames,
+                       double x0, double y0, double cell, int gx, int gy, uint16_t* coverage_dev /* [gy][gx] */,
+                       int64_t* stats_dev /* [16] */, void* stream);
+int wm_coverage_points(const double* g2p_dev, const int32_t* size_dev, int n_frames, const double* points_dev /* [n_points][2] */,
+                       const int32_t* labels_dev, int n_points, double x0, double y0, double cell, int gx, int gy,
+                       int32_t* seen_by_dev /* [n_points] */, int32_t* cell_dev /* [n_points][2] */,
+                       int32_t* counts_dev /* [7][gy][gx], may be NULL */, int64_t* pstats_dev /* [2] */, void* stream);
 
 /* Survey resampling (tiling.detect_frames(scale=..., resize=...)): a frame brought to the scale the checkpoint was trained
  * at (the val transform's long side of 768, dataloader_coco.py:288) before it is tiled.

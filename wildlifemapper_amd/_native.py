@@ -21,6 +21,7 @@ GEMM_VARIANTS = ("v1_128", "v2_160", "v2_128", "v3_lockstep", "v3_conv3x3", "v5_
 FLAG_CONF, FLAG_SCORE, FLAG_NMS, FLAG_MERGED = 1, 2, 4, 8
 CRITERION_MAX_TARGETS, CRITERION_SUMS, CRITERION_NONFINITE, CRITERION_UNSOLVED = 2048, 8, 1, 2
 CENSUS_MAX_DETS, CENSUS_SAME_CLASS, CENSUS_UNSOLVED = 262144, 1, 1
+COVERAGE_MAX_SIDE, COVERAGE_MAX_CELLS, COVERAGE_MAX_FRAMES, COVERAGE_CLASSES, COVERAGE_STATS = 16384, 1 << 26, 65535, 7, 16
 CFG_FUSE_LN = 1
 CFG_FOLD_LN = 2
 CFG_FOLD_LN_BF16 = 4
@@ -66,6 +67,8 @@ SYMBOLS = {
     "wm_merge_frames_fuse": (_I, [_P, _P, C.POINTER(C.c_int32), _I, _F, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
     "wm_census_scratch_bytes": (_L, [_I]),
     "wm_census": (_I, [_P, _P, _P, _P, _I, _P, _I, C.c_double, _I, _P, _L, _P, _P, _P, _P, _P, _P]),
+    "wm_coverage_raster": (_I, [_P, _P, _I, C.c_double, C.c_double, C.c_double, _I, _I, _P, _P, _P]),
+    "wm_coverage_points": (_I, [_P, _P, _I, _P, _P, _I, C.c_double, C.c_double, C.c_double, _I, _I, _P, _P, _P, _P, _P]),
     "wm_resample_u8": (_I, [_P, _I, _I, _P, _I, _I, _P]),
     "wm_scaled_size": (_I, [_I, _I, C.c_double, C.POINTER(_I), C.POINTER(_I)]),
     "wm_chip_window": (_I, [C.POINTER(_F), _F, _I, _I, C.POINTER(C.c_int32)]),

@@ -1,10 +1,11 @@
 // Image front end: the val-transform resize (plan cache per device), the survey resampler (plan slots per stream), the
-// survey merge launcher, the census launcher, the review-chip launcher and the overlay launchers (box outlines, the reference's plot image).
+// survey merge launcher, the census launcher, the coverage launchers, the review-chip launcher and the overlay launchers (box outlines, the reference's plot image).
 #pragma once
 #include "misc_kernels.h"
 #include "resample_kernels.h"
 #include "survey_kernels.h"
 #include "census_kernels.h"
+#include "coverage_kernels.h"
 #include "chip_kernels.h"
 #include "overlay_kernels.h"
 #include "host_core.h"
@@ -75,6 +76,61 @@ int launch_census(const float* boxes_dev, const float* scores_dev, const int32_t
     hipLaunchKernelGGL(census_kernel, dim3(1), dim3(MF_THREADS), 0, s, (const float4*)boxes_dev, scores_dev, (const int*)labels_dev,
                        (const int*)box_frame_dev, n, georef_dev, n_frames, radius, r2, flags & WM_CENSUS_SAME_CLASS, (char*)scratch_dev,
                        (double2*)points_dev, (int*)individual_dev, (int*)keeper_dev, (int*)members_dev, (int*)count_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Survey coverage: every argument is checked on the host before the first HIP call.  The grid of both entries.
+static int check_coverage_grid(const char* name, double x0, double y0, double cell, int gx, int gy) {
+    if (!std::isfinite(x0)) return fail("%s: x0 %g is not finite", name, x0);
+    if (!std::isfinite(y0)) return fail("%s: y0 %g is not finite", name, y0);
+    if (!(std::isfinite(cell) && cell > 0.0)) return fail("%s: cell %g: need a finite cell > 0", name, cell);
+    if (gx < 1 || gx > WM_COVERAGE_MAX_SIDE) return fail("%s: gx %d outside 1..%d", name, gx, WM_COVERAGE_MAX_SIDE);
+    if (gy < 1 || gy > WM_COVERAGE_MAX_SIDE) return fail("%s: gy %d outside 1..%d", name, gy, WM_COVERAGE_MAX_SIDE);
+    if ((int64_t)gx * gy > WM_COVERAGE_MAX_CELLS)
+        return fail("%s: gx * gy = %lld cells exceed %d", name, (long long)gx * gy, WM_COVERAGE_MAX_CELLS);
+    return 0;
+}
+
+static int check_coverage_frames(const char* name, const double* g2p_dev, const int32_t* size_dev, int n_frames) {
+    if (n_frames < 0 || n_frames > WM_COVERAGE_MAX_FRAMES) return fail("%s: n_frames %d outside 0..%d", name, n_frames, WM_COVERAGE_MAX_FRAMES);
+    if (n_frames > 0 && (!g2p_dev || !size_dev)) return fail("%s: null g2p_dev / size_dev with n_frames %d", name, n_frames);
+    if ((uintptr_t)g2p_dev % 8 || (uintptr_t)size_dev % 4) return fail("%s: g2p_dev not 8-byte aligned, or size_dev not 4-byte aligned", name);
+    return 0;
+}
+
+int launch_coverage_raster(const double* g2p_dev, const int32_t* size_dev, int n_frames, double x0, double y0, double cell, int gx,
+                           int gy, uint16_t* coverage_dev, int64_t* stats_dev, hipStream_t s) {
+    const char* name = "wm_coverage_raster";
+    WM_TRY(check_coverage_frames(name, g2p_dev, size_dev, n_frames));
+    WM_TRY(check_coverage_grid(name, x0, y0, cell, gx, gy));
+    if (!coverage_dev || !stats_dev) return fail("%s: null coverage_dev / stats_dev", name);
+    if ((uintptr_t)coverage_dev % 2 || (uintptr_t)stats_dev % 8) return fail("%s: coverage_dev not 2-byte aligned, or stats_dev not 8-byte aligned", name);
+    HIP_TRY(hipMemsetAsync(stats_dev, 0, COV_STATS * sizeof(int64_t), s));
+    const dim3 grid((gx + COV_BLOCK_X - 1) / COV_BLOCK_X, (gy + COV_BLOCK_Y - 1) / COV_BLOCK_Y);
+    hipLaunchKernelGGL(coverage_raster_kernel, grid, dim3(COV_THREADS), 0, s, g2p_dev, (const int*)size_dev, n_frames, x0, y0, cell, gx, gy,
+                       coverage_dev, (unsigned long long*)stats_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_coverage_points(const double* g2p_dev, const int32_t* size_dev, int n_frames, const double* points_dev,
+                           const int32_t* labels_dev, int n_points, double x0, double y0, double cell, int gx, int gy,
+                           int32_t* seen_by_dev, int32_t* cell_dev, int32_t* counts_dev, int64_t* pstats_dev, hipStream_t s) {
+    const char* name = "wm_coverage_points";
+    if (n_points < 0 || n_points > WM_CENSUS_MAX_DETS) return fail("%s: n_points %d outside 0..%d", name, n_points, WM_CENSUS_MAX_DETS);
+    if (n_points == 0) return 0;
+    WM_TRY(check_coverage_frames(name, g2p_dev, size_dev, n_frames));
+    WM_TRY(check_coverage_grid(name, x0, y0, cell, gx, gy));
+    if (!points_dev || !labels_dev || !seen_by_dev || !cell_dev || !pstats_dev) return fail("%s: null buffer", name);
+    if ((uintptr_t)points_dev % 8 || (uintptr_t)pstats_dev % 8 || (uintptr_t)labels_dev % 4 || (uintptr_t)seen_by_dev % 4 ||
+        (uintptr_t)cell_dev % 4 || (uintptr_t)counts_dev % 4)
+        return fail("%s: points_dev / pstats_dev not 8-byte aligned, or an int32 buffer not 4-byte aligned", name);
+    HIP_TRY(hipMemsetAsync(pstats_dev, 0, 2 * sizeof(int64_t), s));
+    if (counts_dev) HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)COV_CLASSES * gx * gy * sizeof(int32_t), s));
+    hipLaunchKernelGGL(coverage_points_kernel, dim3((n_points + COV_THREADS - 1) / COV_THREADS), dim3(COV_THREADS), 0, s, g2p_dev,
+                       (const int*)size_dev, n_frames, points_dev, (const int*)labels_dev, n_points, x0, y0, cell, gx, gy, (int*)seen_by_dev,
+                       (int*)cell_dev, (int*)counts_dev, (unsigned long long*)pstats_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -228,6 +228,18 @@ extern "C" int wm_census(const float* boxes_dev, const float* scores_dev, const 
                          scratch_bytes, points_dev, individual_dev, keeper_dev, members_dev, count_dev, (hipStream_t)stream);
 }
 
+extern "C" int wm_coverage_raster(const double* g2p_dev, const int32_t* size_dev, int n_frames, double x0, double y0, double cell, int gx,
+                                  int gy, uint16_t* coverage_dev, int64_t* stats_dev, void* stream) {
+    return launch_coverage_raster(g2p_dev, size_dev, n_frames, x0, y0, cell, gx, gy, coverage_dev, stats_dev, (hipStream_t)stream);
+}
+
+extern "C" int wm_coverage_points(const double* g2p_dev, const int32_t* size_dev, int n_frames, const double* points_dev,
+                                  const int32_t* labels_dev, int n_points, double x0, double y0, double cell, int gx, int gy,
+                                  int32_t* seen_by_dev, int32_t* cell_dev, int32_t* counts_dev, int64_t* pstats_dev, void* stream) {
+    return launch_coverage_points(g2p_dev, size_dev, n_frames, points_dev, labels_dev, n_points, x0, y0, cell, gx, gy, seen_by_dev,
+                                  cell_dev, counts_dev, pstats_dev, (hipStream_t)stream);
+}
+
 extern "C" int wm_crop_chips_u8(const wm_frame_desc* frames_dev, int n_frames, const float* boxes_dev, const int32_t* box_frame_dev, int n,
                                 int chip, float context, int min_side, int max_side, uint8_t* chips_dev, int32_t* windows_dev,
                                 void* stream) {

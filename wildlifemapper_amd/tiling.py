@@ -28,6 +28,10 @@ match: the checker is oracle/tiling_oracle.py, a numpy restatement of exactly wh
   * census, nadir_affine: the count a survey is flown for -- the detections of all frames (detect_frames' dicts) go to
     ground coordinates through each frame's georeference and are grouped into individuals, at most one detection of any
     frame per individual (census rule: include/wm_hip.h), by one wm_census launch over the whole survey.
+  * coverage, ground_to_pixel, footprint_bounds: the denominator of a density -- a ground grid over the survey, every
+    cell with the number of frames that saw its centre (the union of the footprints, its gaps), the census' individuals
+    per cell and class, and per individual the number of frames that could have seen it (coverage rule:
+    include/wm_hip.h), by wm_coverage_raster and wm_coverage_points.
 Frame coordinates are fp32: a box coordinate keeps a fractional resolution below 0.01 px up to 65536 px (ulp 2**-8).
 """
 from __future__ import annotations
@@ -833,3 +837,214 @@ def census(results, georef, radius, same_class: bool = False) -> Dict[str, objec
             "det_points": points, "scores": scores[keeper], "labels": klab, "frame": det_frame[keeper],
             "members": members[:k].to(torch.int64), "det_frame": det_frame, "det_offsets": offs,
             "class_counts": torch.bincount(klab[ok].to(torch.int64), minlength=CENSUS_CLASSES)}
+
+
+# ---- coverage --------------------------------------------------------------------------------------------------------
+
+COVERAGE_MAX_SIDE = N.COVERAGE_MAX_SIDE       # include/wm_hip.h WM_COVERAGE_MAX_SIDE
+COVERAGE_MAX_CELLS = N.COVERAGE_MAX_CELLS     # WM_COVERAGE_MAX_CELLS
+COVERAGE_MAX_FRAMES = N.COVERAGE_MAX_FRAMES   # WM_COVERAGE_MAX_FRAMES
+
+
+def _check_cell(cell, what: str) -> float:
+    """Validate cell= before any device work: a finite number > 0."""
+    if isinstance(cell, (str, bytes)):
+        raise ValueError(f"{what}: cell {cell!r} is not a number")
+    try:
+        c = float(cell)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: cell {cell!r} is not a number") from None
+    if not (math.isfinite(c) and c > 0.0):
+        raise ValueError(f"{what}: cell {cell!r} must be finite and > 0")
+    return c
+
+
+def _check_sizes(sizes, n_frames: int, what: str) -> np.ndarray:
+    """(F,2) int32, C-contiguous: (height, width) of every frame, one per georeference."""
+    if isinstance(sizes, torch.Tensor):
+        sizes = sizes.detach().cpu().numpy()
+    try:
+        a = np.asarray(sizes)
+        if a.size == 0 and a.ndim <= 1:
+            a = a.reshape(0, 2)
+        if a.dtype.kind not in "iu" and not (a.dtype.kind == "f" and np.all(a == np.floor(a))):
+            raise TypeError
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise TypeError
+        s = np.ascontiguousarray(a.astype(np.int32))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: sizes is not an array of whole numbers that fit int32") from None
+    if s.ndim != 2 or s.shape[1] != 2:
+        raise ValueError(f"{what}: sizes of shape {s.shape}: expected (F, 2), (height, width) per frame")
+    if s.shape[0] != n_frames:
+        raise ValueError(f"{what}: {s.shape[0]} sizes for {n_frames} georeferences")
+    return s
+
+
+def _check_grid(x0, y0, gx, gy, cell: float, what: str, name: str = "bounds"):
+    """Validate a grid against the limits of include/wm_hip.h; the message says what to do about a grid that is too large."""
+    try:
+        fx, fy = float(x0), float(y0)
+        ix, iy = int(gx), int(gy)
+        if ix != gx or iy != gy:
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: {name} {(x0, y0, gx, gy)!r}: expected (x0, y0, gx, gy), two numbers and two whole numbers") from None
+    if not (math.isfinite(fx) and math.isfinite(fy)):
+        raise ValueError(f"{what}: {name}: origin ({x0!r}, {y0!r}) is not finite")
+    if ix < 1 or iy < 1:
+        raise ValueError(f"{what}: {name}: a grid of {ix} x {iy} cells; gx and gy must be at least 1")
+    if ix > COVERAGE_MAX_SIDE or iy > COVERAGE_MAX_SIDE or ix * iy > COVERAGE_MAX_CELLS:
+        raise ValueError(f"{what}: {name}: a grid of {ix} x {iy} cells at cell {cell!r} exceeds {COVERAGE_MAX_SIDE} cells a side "
+                         f"or {COVERAGE_MAX_CELLS} cells in all: choose a larger cell")
+    return fx, fy, ix, iy
+
+
+def ground_to_pixel(georef) -> np.ndarray:
+    """The inverse of census()'s georeferences: (F,2,3) float64 [[a0, a1, a2], [a3, a4, a5]] (pixel -> ground) gives (F,2,3)
+    float64 [[b0, b1, b2], [b3, b4, b5]] (ground -> pixel), x = b0*X + b1*Y + b2, y = b3*X + b4*Y + b5; a single (2,3)
+    gives a (2,3).  Host only, in double, in this order: det = a0*a4 - a1*a3; b0 = a4/det, b1 = -a1/det, b3 = -a3/det,
+    b4 = a0/det; b2 = -(b0*a2 + b1*a5), b5 = -(b3*a2 + b4*a5).  A frame that is singular (det == 0) or not finite, in
+    its input or its inverse, gives a row of NaN: such a frame sees nothing (coverage rule: include/wm_hip.h)."""
+    g = np.asarray(georef, dtype=np.float64) if not isinstance(georef, torch.Tensor) else georef.detach().cpu().numpy().astype(np.float64)
+    single = g.ndim == 2
+    g = _check_georef(g[None] if single else g, "ground_to_pixel")
+    a0, a1, a2, a3, a4, a5 = (g[:, r, c] for r in range(2) for c in range(3))
+    out = np.empty_like(g)
+    with np.errstate(all="ignore"):
+        det = a0 * a4 - a1 * a3
+        b0, b1, b3, b4 = a4 / det, -a1 / det, -a3 / det, a0 / det
+        b2 = -(b0 * a2 + b1 * a5)
+        b5 = -(b3 * a2 + b4 * a5)
+        out[:, 0, 0], out[:, 0, 1], out[:, 0, 2] = b0, b1, b2
+        out[:, 1, 0], out[:, 1, 1], out[:, 1, 2] = b3, b4, b5
+        bad = ~(np.isfinite(g).all(axis=(1, 2)) & np.isfinite(out).all(axis=(1, 2)) & (det != 0.0))
+    out[bad] = np.nan
+    return out[0] if single else out
+
+
+def footprint_bounds(georef, sizes, cell):
+    """A grid that holds every frame's footprint: (x0, y0, gx, gy) for coverage(bounds=).  georef (F,2,3) float64 as for
+    census(), sizes (F,2) (height, width), cell metres.  The extent of the corners (0, 0), (W, 0), (0, H), (W, H) of every
+    frame whose georeference is finite and whose size is at least 1 x 1; x0 and y0 are snapped down to multiples of cell,
+    so the grids of two flights of one area line up; gx and gy are at least 1 (no usable frame: (0.0, 0.0, 1, 1)).  Host
+    only.  Raises ValueError when the grid would exceed the limits of include/wm_hip.h: choose a larger cell."""
+    what = "footprint_bounds"
+    cell = _check_cell(cell, what)
+    g = _check_georef(georef, what)
+    s = _check_sizes(sizes, g.shape[0], what)
+    ok = np.isfinite(g).all(axis=(1, 2)) & (s >= 1).all(axis=1)
+    if not ok.any():
+        return 0.0, 0.0, 1, 1
+    g, s = g[ok], s[ok].astype(np.float64)
+    cx = np.stack([np.zeros(len(g)), s[:, 1], np.zeros(len(g)), s[:, 1]], axis=1)
+    cy = np.stack([np.zeros(len(g)), np.zeros(len(g)), s[:, 0], s[:, 0]], axis=1)
+    with np.errstate(all="ignore"):
+        X = g[:, 0, 0:1] * cx + g[:, 0, 1:2] * cy + g[:, 0, 2:3]
+        Y = g[:, 1, 0:1] * cx + g[:, 1, 1:2] * cy + g[:, 1, 2:3]
+        x0, y0 = math.floor(X.min() / cell) * cell, math.floor(Y.min() / cell) * cell
+        nx, ny = math.ceil((X.max() - x0) / cell), math.ceil((Y.max() - y0) / cell)
+    if not all(math.isfinite(v) for v in (x0, y0, nx, ny)):
+        raise ValueError(f"{what}: the footprints' extent is not finite at cell {cell!r}")
+    _, _, gx, gy = _check_grid(x0, y0, max(int(nx), 1), max(int(ny), 1), cell, what, "the footprints' grid")
+    return float(x0), float(y0), gx, gy
+
+
+def coverage(georef, sizes, cell, census=None, bounds=None) -> Dict[str, object]:
+    """The ground a survey saw (wm_coverage_raster, wm_coverage_points; rule: include/wm_hip.h).  georef (F,2,3) float64 as
+    for census() (pixel -> ground; inverted on the host by ground_to_pixel), sizes (F,2) (height, width) of the frames in
+    the pixels the georeferences speak of, cell the side of a ground cell in metres, bounds (x0, y0, gx, gy) or None for
+    footprint_bounds(georef, sizes, cell), census the dict census() returned, or None.  Everything is validated before
+    any device work; the frames go up through pinned memory to the current device -- torch.cuda.current_device(), or with
+    census= the device of its tensors -- and the launches run on its current stream; one small copy of the statistics
+    waits for them.  No CPU fallback.  Returns
+      'coverage' (gy,gx) int32 on the device: frames that saw each cell's centre.  Row 0 is the SOUTHERNMOST row: a
+          north-up picture is coverage.flip(0).  The kernel writes uint16 (F <= 65535); it is widened once to int32
+          (a copy of twice the raster's bytes), the narrowest dtype torch indexes, compares and sums on the device;
+      'origin' (x0, y0), 'cell', 'shape' (gy, gx); 'multiplicity' (16,) int64 on the device: cells seen by 0, 1, ...,
+          14 and by 15 or more frames; 'gap_cells' int = multiplicity[0], the cells no frame saw;
+      'area_m2' float = (gx * gy - gap_cells) * cell * cell, the observed ground;
+    and with census=, from the individuals' keeper 'points' (k,2) and 'labels' (k,):
+      'seen_by' (k,) int64: frames whose footprint holds the individual's point (0: not finite, or seen by none);
+      'cell_index' (k,2) int64: its cell (j, i), (-1, -1) when it is not binned (outside the grid, not finite, or a
+          label outside 0..6);
+      'counts' (7,gy,gx) int32: binned individuals per class and cell; 'class_counts' (7,) int64: their sums;
+      'density_per_km2' (7,) float64 = class_counts / (area_m2 / 1e6), divided on the host in double; NaN when the area is 0;
+      'detection_rate' float = sum of 'members' / sum of 'seen_by' over the individuals with seen_by >= 1, NaN when
+          there is none: of the chances the frames had to detect an individual, the share they took.  A member's own
+          ground point differs slightly from its keeper's (the georeferencing error the census radius absorbs), so at a
+          frame's edge a member can lie in a frame whose footprint misses the keeper's point: a ratio slightly above 1
+          is possible and is not clamped."""
+    what = "coverage"
+    cell = _check_cell(cell, what)
+    g = _check_georef(georef, what)
+    s = _check_sizes(sizes, g.shape[0], what)
+    F = g.shape[0]
+    if F > COVERAGE_MAX_FRAMES:
+        raise ValueError(f"{what}: {F} frames exceed {COVERAGE_MAX_FRAMES}")
+    if bounds is None:
+        x0, y0, gx, gy = footprint_bounds(g, s, cell)
+    else:
+        try:
+            bx0, by0, bgx, bgy = bounds
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: bounds {bounds!r}: expected (x0, y0, gx, gy)") from None
+        x0, y0, gx, gy = _check_grid(bx0, by0, bgx, bgy, cell, what)
+    pts = labels = members = None
+    if census is not None:
+        try:
+            pts, labels, members = census["points"], census["labels"], census["members"]
+        except (TypeError, KeyError):
+            raise ValueError(f"{what}: census has no 'points', 'labels' and 'members': pass the dict census() returned") from None
+        if not all(isinstance(t, torch.Tensor) for t in (pts, labels, members)) or pts.dim() != 2 or pts.shape[1] != 2 or \
+                pts.dtype != torch.float64 or tuple(labels.shape) != (pts.shape[0],) or tuple(members.shape) != (pts.shape[0],):
+            raise ValueError(f"{what}: census: expected 'points' (k,2) float64, 'labels' (k,) and 'members' (k,) tensors")
+        if pts.shape[0] > CENSUS_MAX_DETS:
+            raise ValueError(f"{what}: {pts.shape[0]} individuals exceed {CENSUS_MAX_DETS}")
+        if labels.device != pts.device or members.device != pts.device:
+            raise ValueError(f"{what}: census tensors are on different devices")
+        if not pts.is_cuda:
+            raise RuntimeError(f"{what}: census['points'] is on {pts.device}; the HIP path needs a ROCm device tensor "
+                               "(there is no CPU fallback in wildlifemapper_amd)")
+        dev = pts.device
+    else:
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{what}: no GPU is present; the HIP path needs a ROCm device tensor "
+                               "(there is no CPU fallback in wildlifemapper_amd)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+    b = ground_to_pixel(g)
+    lib = N.lib()
+    with torch.cuda.device(dev):
+        g_d = s_d = None                                      # no frames: nothing to upload, an all-zero raster
+        if F:
+            g_d = torch.from_numpy(np.ascontiguousarray(b.reshape(-1, 6))).pin_memory().to(dev, non_blocking=True)
+            s_d = torch.from_numpy(s).pin_memory().to(dev, non_blocking=True)
+        cov16 = torch.empty((gy, gx), device=dev, dtype=torch.int16)
+        stats = torch.empty(N.COVERAGE_STATS, device=dev, dtype=torch.int64)
+        N.check(lib.wm_coverage_raster(N.ptr(g_d), N.ptr(s_d), F, x0, y0, cell, gx, gy, N.ptr(cov16), N.ptr(stats), N.stream_ptr(dev)))
+        out = {"coverage": cov16.to(torch.int32) & 0xFFFF, "origin": (x0, y0), "cell": cell, "shape": (gy, gx), "multiplicity": stats}
+        gap = int(stats[0].item())
+        area = float((gx * gy - gap) * cell * cell)
+        out["gap_cells"], out["area_m2"] = gap, area
+        if census is None:
+            return out
+        k = int(pts.shape[0])
+        pts = pts.contiguous()
+        lab32 = labels.to(torch.int32).contiguous()
+        alloc = torch.empty if k else torch.zeros             # k == 0: the entry returns before writing anything
+        seen = alloc(k, device=dev, dtype=torch.int32)
+        cidx = alloc((k, 2), device=dev, dtype=torch.int32)
+        counts = alloc((N.COVERAGE_CLASSES, gy, gx), device=dev, dtype=torch.int32)
+        pstats = alloc(2, device=dev, dtype=torch.int64)
+        N.check(lib.wm_coverage_points(N.ptr(g_d), N.ptr(s_d), F, N.ptr(pts), N.ptr(lab32), k, x0, y0, cell, gx, gy, N.ptr(seen),
+                                       N.ptr(cidx), N.ptr(counts), N.ptr(pstats), N.stream_ptr(dev)))
+        seen = seen.to(torch.int64)
+        class_counts = counts.sum(dim=(1, 2), dtype=torch.int64)
+        could = seen >= 1
+        n_seen, n_members = int(seen[could].sum().item()), int(members[could].sum().item())
+        # seven divisions, on the host: IEEE double there, where a device division by a scalar may be a multiplication
+        density = class_counts.cpu().numpy().astype(np.float64) / (area / 1e6) if area > 0 else np.full(N.COVERAGE_CLASSES, np.nan)
+    out.update({"seen_by": seen, "cell_index": cidx.to(torch.int64), "counts": counts, "class_counts": class_counts,
+                "density_per_km2": torch.from_numpy(density).to(dev),
+                "detection_rate": n_members / n_seen if n_seen > 0 else float("nan")})
+    return out
