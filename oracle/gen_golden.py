@@ -19,7 +19,11 @@ so they are taken out of the reference's files with `ast` (the class / function 
 executed here, nothing stored) and run on the logits / boxes the end-to-end fixtures already hold plus edge cases;
 outputs go to postprocess_ref.npz with pinned=1.  NMS (torchvision.ops.nms) and Grayscale stay unpinned.
 
-Usage:  python oracle/gen_golden.py [--only small|postprocess|vit_b|vit_l|vit_h|vit_h_tiles|vit_h_seed1|vit_h_smooth|vit_h_padded|vit_h_outlier] [--out tests/golden]
+`--only decoder` writes decoder_ref.npz: the reference's MaskDecoder / TwoWayTransformer converted to float64, on the seeded
+embeddings of tests/decoder_cases.py, with image_pe from the reference's PromptEncoder in fp32 (as the model computes it) promoted
+to float64.  Outputs only (pred_logits, pred_boxes per case), pinned=1.
+
+Usage:  python oracle/gen_golden.py [--only small|decoder|postprocess|vit_b|vit_l|vit_h|vit_h_tiles|vit_h_seed1|vit_h_smooth|vit_h_padded|vit_h_outlier] [--out tests/golden]
 """
 from __future__ import annotations
 
@@ -353,6 +357,37 @@ def gen_postprocess(out: str) -> None:
           "(oracle restatement bit-identical on all)")
 
 
+def gen_decoder(out: str) -> None:
+    """The box decoder alone in float64 (tests/decoder_cases.py: two weight profiles x the embedding cases, a second weight seed,
+    a batch of 3): the high-precision reference of tests/test_gpu_decoder.py.  The embeddings are not stored."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import decoder_cases as DC
+    M = ref_modeling()
+    fx = {"pinned": np.array(1), "cases": np.array([DC.fixture_key(p, c) for p, c in DC.TABLE])}
+    for profile, case in DC.TABLE:
+        _, _, seed = DC.CASES[case]
+        dec = M.MaskDecoder(num_multimask_outputs=50, transformer=M.TwoWayTransformer(depth=2, embedding_dim=256, mlp_dim=2048, num_heads=8),
+                            transformer_dim=256, iou_head_depth=3, iou_head_hidden_dim=256).eval()            # build_sam.py:295-306
+        pe = M.PromptEncoder(embed_dim=256, image_embedding_size=(64, 64), input_image_size=(1024, 1024), mask_in_chans=16).eval()
+        load_synth(dec, "mask_decoder.", seed, profile)
+        load_synth(pe, "prompt_encoder.", seed, profile)
+        with torch.no_grad():
+            image_pe = pe.get_dense_pe()                           # fp32, as in the model
+        assert image_pe.dtype == torch.float32
+        dec = dec.double()
+        emb = DC.case_embedding(case).double()
+        t1 = time.time()
+        with torch.no_grad():
+            res = dec(image_embeddings=emb, image_pe=image_pe.double(), sparse_prompt_embeddings=None,
+                      dense_prompt_embeddings=None, multimask_output=False, hfc_embed=None)
+        assert res["pred_logits"].dtype == torch.float64 and res["pred_boxes"].dtype == torch.float64
+        key = DC.fixture_key(profile, case)
+        fx[key + "_logits"], fx[key + "_boxes"] = res["pred_logits"].numpy(), res["pred_boxes"].numpy()
+        print(f"[decoder] {key}: float64 reference forward {time.time() - t1:.1f}s, max |logit| {res['pred_logits'].abs().max():.2f}")
+    np.savez_compressed(os.path.join(out, "decoder_ref.npz"), **fx)
+    print("wrote decoder_ref.npz", sum(v.nbytes for v in fx.values()) // 1024, "KiB")
+
+
 def gen_coco_subset(out: str, n_images: int = 8) -> None:
     """Data fixture for the COCO bbox evaluator: the first images of the reference's own annotation file
     (coco_annotations/val.json: 6 categories, xywh boxes, area, iscrowd) with their annotations, verbatim."""
@@ -402,6 +437,8 @@ def main() -> None:
         gen_small(a.out)
     if a.only in ("all", "resize"):
         gen_resize(a.out)
+    if a.only in ("all", "decoder"):
+        gen_decoder(a.out)
     if a.only in ("postprocess",):                # after the end-to-end fixtures exist (reads their logits / boxes)
         gen_postprocess(a.out)
     if a.only in ("all", "coco"):

@@ -353,15 +353,21 @@ def encoder_forward(x: Tensor, x_hfc: Tensor, W: Dict[str, Tensor], cfg: OracleC
 # ----------------------------------------------------------------------------
 # A15  dense positional encoding  (pos_encoder.py:50-70)
 # ----------------------------------------------------------------------------
-def dense_pe(gauss: Tensor, grid: int) -> Tensor:
-    """(1, 2*F, grid, grid): coords (i+0.5)/grid -> 2c-1 -> @G -> 2pi -> [sin, cos]."""
+def dense_pe(gauss: Tensor, grid: int, dtype: Optional[torch.dtype] = None) -> Tensor:
+    """(1, 2*F, grid, grid): coords (i+0.5)/grid -> 2c-1 -> @G -> 2pi -> [sin, cos].
+
+    `dtype`: evaluate in fp32 from the fp32 value of `gauss`, as the model does (the PromptEncoder stays fp32 whatever the
+    decoder runs in), then cast the table to `dtype`.  None = the table as computed from `gauss` as given."""
+    if dtype is not None:
+        gauss = gauss.to(torch.float32)
     c = (torch.arange(grid, dtype=torch.float32) + 0.5) / grid
     yy, xx = torch.meshgrid(c, c, indexing="ij")
     coords = torch.stack([xx, yy], dim=-1)          # x first, pos_encoder.py:69
     coords = 2 * coords - 1
     proj = (coords @ gauss) * (2 * np.pi)
     pe = torch.cat([proj.sin(), proj.cos()], dim=-1)
-    return pe.permute(2, 0, 1).unsqueeze(0).contiguous()
+    pe = pe.permute(2, 0, 1).unsqueeze(0).contiguous()
+    return pe if dtype is None else pe.to(dtype)
 
 
 # ----------------------------------------------------------------------------
@@ -415,10 +421,13 @@ def mlp_head(x: Tensor, W: Dict[str, Tensor], pre: str, cfg: OracleCfg) -> Tenso
 
 
 def decoder_forward(emb: Tensor, W: Dict[str, Tensor], cfg: OracleCfg) -> Dict[str, Tensor]:
-    """(B,256,64,64) -> pred_logits (B,51,8), pred_boxes (B,51,4)  (box_decoder.py:96-104, 128-147)."""
+    """(B,256,64,64) -> pred_logits (B,51,8), pred_boxes (B,51,4)  (box_decoder.py:96-104, 128-147).
+
+    Runs in the dtype of the weights (float64 weights and embedding: the high-precision reference of the GPU decoder's parity
+    tests); the dense PE is evaluated in fp32 either way, as in the model, and promoted."""
     B = emb.shape[0]
-    pe = dense_pe(W["prompt_encoder.pe_layer.positional_encoding_gaussian_matrix"], cfg.grid)
     tokens = W["mask_decoder.mask_tokens.weight"].unsqueeze(0).expand(B, -1, -1)
+    pe = dense_pe(W["prompt_encoder.pe_layer.positional_encoding_gaussian_matrix"], cfg.grid, dtype=tokens.dtype)
     hs, _ = two_way_transformer(emb, pe, tokens, W, cfg)
     hs = hs[:, :cfg.num_queries]
     logits = mlp_head(hs, W, "mask_decoder.class_embed.", cfg)

@@ -231,3 +231,32 @@ def test_postprocess_restatement_vs_reference_fixture(golden_dir):
     # the pp*_ keys inside the end-to-end fixtures (written by the oracle, pinned=0 there) equal the reference's outputs
     e = np.load(os.path.join(golden_dir, "e2e_vit_h.npz"))
     assert np.array_equal(e["pp0_scores"], fx["e2e_vit_h_pp0_scores"]) and np.array_equal(e["pp0_boxes"], fx["e2e_vit_h_pp0_boxes"])
+
+
+def test_oracle_decoder_float64_vs_reference_fixture(golden_dir):
+    """The oracle's decoder in float64 (O.decoder_forward on float64 weights; the dense PE evaluated in fp32 as in the model and
+    promoted) against tests/golden/decoder_ref.npz, which oracle/gen_golden.py --only decoder produced from the reference's own
+    MaskDecoder / TwoWayTransformer / PromptEncoder, the decoder converted to float64, on the seeded embeddings of
+    tests/decoder_cases.py.  float64 on both sides: only summation order differs.  Bars: logits 1e-9 relative L2, boxes 1e-10
+    max-abs, on every case, `large` (the peaky softmax) included: measured 1.1e-15 .. 3.4e-15 on the logits (`large`: 5.3e-15 and
+    1.1e-14) and at most 8.7e-15 on the boxes, so no case needed a wider bar.  This makes the live float64 oracle a stand-in for the fixture where
+    a GPU test changes the weights."""
+    import decoder_cases as DC
+    fx = np.load(os.path.join(golden_dir, "decoder_ref.npz"))
+    assert int(fx["pinned"]) == 1
+    assert [str(c) for c in fx["cases"]] == [DC.fixture_key(p, c) for p, c in DC.TABLE]
+    assert set(fx.files) == {"pinned", "cases"} | {f"{c}_{k}" for c in fx["cases"] for k in ("logits", "boxes")}      # outputs only
+    cfg = O.OracleCfg.from_model_type("vit_b")
+    weights = {}
+    for profile, case in DC.TABLE:
+        seed = DC.CASES[case][2]
+        if (profile, seed) not in weights:
+            weights[(profile, seed)] = {k: v.double() for k, v in DC.decoder_weights(profile, seed).items()}
+        with torch.no_grad():
+            out = O.decoder_forward(DC.case_embedding(case).double(), weights[(profile, seed)], cfg)
+        key = DC.fixture_key(profile, case)
+        lg, bx = torch.from_numpy(fx[key + "_logits"]), torch.from_numpy(fx[key + "_boxes"])
+        assert out["pred_logits"].dtype == torch.float64 and lg.dtype == torch.float64 and lg.shape == (DC.CASES[case][1], 51, 8)
+        el, eb = DC.rel_l2(out["pred_logits"], lg), DC.max_abs(out["pred_boxes"], bx)
+        print(f"decoder float64 oracle vs reference {key}: logits rel-L2 {el:.1e}, boxes max-abs {eb:.1e}")
+        assert el < 1e-9 and eb < 1e-10, (key, el, eb)

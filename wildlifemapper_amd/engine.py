@@ -197,6 +197,7 @@ class EngineHub:
         h = self.handle(emb.device, B)
         logits = torch.empty((B, N.NUM_QUERIES, N.NUM_LOGITS), device=emb.device, dtype=torch.float32)
         boxes = torch.empty((B, N.NUM_QUERIES, 4), device=emb.device, dtype=torch.float32)
+        self._warn_overflow()
         N.check(N.lib().wm_decoder_forward(h, N.ptr(emb), N.ptr(logits), N.ptr(boxes), B, N.stream_ptr(emb.device)))
         return {"pred_logits": logits, "pred_boxes": boxes}
 
