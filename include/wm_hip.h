@@ -35,6 +35,9 @@ extern "C" {
  *    WM_COVERAGE_MAX_FRAMES, WM_COVERAGE_CLASSES, WM_COVERAGE_STATS (survey coverage: the ground a survey saw, its gaps and
  *    the individuals per cell); the number stays 13 because no v13 caller is affected, and a library without the two
  *    names is still refused by a binding that looks them up.
+ *    13, additive: wm_mosaic_plan, wm_mosaic_fill_u8, WM_MOSAIC_NEAREST, WM_MOSAIC_BILINEAR, WM_MOSAIC_NORTH_UP and the
+ *    status bits WM_MOSAIC_BAD_SLOT, WM_MOSAIC_BAD_SIZE, WM_MOSAIC_BAD_SOURCE (survey mosaic: the frames laid onto the
+ *    coverage's ground grid); the number stays 13 for the same reason.
  * 12: wm_box_outline_rect, wm_draw_boxes_u8, wm_plot_image_u8, WM_DRAW_MAX_WIDTH, WM_DRAW_MAX_PALETTE, WM_PLOT_SCRATCH_BYTES
  *    (survey overlays: detections outlined on frames and tiles, on the GPU); nothing else changed.
  * 11: wm_chip_window, wm_crop_chips_u8, WM_CHIP_MAX_SIDE (survey review chips: one PIL-exact crop per detection, cut on
@@ -368,6 +371,63 @@ int wm_coverage_points(const double* g2p_dev, const int32_t* size_dev, int n_fra
                        const int32_t* labels_dev, int n_points, double x0, double y0, double cell, int gx, int gy,
                        int32_t* seen_by_dev /* [n_points] */, int32_t* cell_dev /* [n_points][2] */,
                        int32_t* counts_dev /* [7][gy][gx], may be NULL */, int64_t* pstats_dev /* [2] */, void* stream);
+
+/* Survey mosaic (tiling.mosaic, tiling.mosaic_plan): the map itself -- the frames laid onto the ground grid, one picture of
+ * the whole survey.  For every ground cell ONE frame is chosen and its pixel fetched.  No reference behaviour exists (the
+ * reference has no georeferencing); this rule is the contract, and tests/test_mosaic.py restates it sequentially
+ * (mosaic_oracle).  The grid, the cell centres, the frames and sees are those of "Survey coverage", word for word:
+ * g2p_dev[n_frames][6] doubles (b0..b5, ground -> pixel) and size_dev[n_frames][2] int32 (height, width); the centre of cell
+ * (j, i) is Xc = x0 + ((double)i + 0.5) * cell, Yc = y0 + ((double)j + 0.5) * cell, row j = 0 the SOUTHERNMOST;
+ *     u = (b0 * Xc + b1 * Yc) + b2             v = (b3 * Xc + b4 * Yc) + b5
+ * all IEEE double, every operation correctly rounded on its own (no contraction), in the order written.
+ * Seam rule: among the frames f with sees(f, Xc, Yc), the SOURCE of cell (j, i) is the one with the smallest
+ *     e = du * du + dv * dv,      du = u - 0.5 * (double)width,      dv = v - 0.5 * (double)height
+ * (two products and one sum); ties go to the lowest frame index; a cell that no frame sees has source -1.  e is the squared
+ * pixel distance from the frame's centre -- for one camera the off-nadir angle, whatever the altitude -- so every piece of
+ * ground is shown by the frame that looked at it most vertically, and the seams are the Voronoi lines between the frame
+ * centres.  A frame that is NaN, infinite, singular or smaller than 1 x 1 sees nothing: it is never a source and needs no
+ * special case.
+ * Sampling, from the source frame (HWC uint8), per channel:
+ *   WM_MOSAIC_NEAREST: the pixel ((int)floor(v), (int)floor(u)), which sees guarantees is in range.
+ *   WM_MOSAIC_BILINEAR, pixel centres at integer + 0.5: fu = u - 0.5, xf = floor(fu), tx = fu - xf, and the same for v
+ *     (fv, yf, ty); the columns (int)xf and (int)xf + 1 are each clamped to [0, width - 1], the rows (int)yf and (int)yf + 1
+ *     to [0, height - 1] (edge replicate); with p00, p10 the pixels of row yf at the two columns and p01, p11 those of row
+ *     yf + 1:  a = (1.0 - tx) * p00 + tx * p10,  b = (1.0 - tx) * p01 + tx * p11,  val = (1.0 - ty) * a + ty * b;
+ *     the output is (uint8)min(floor(val + 0.5), 255.0).
+ * A cell finer than the ground sampling distance magnifies; a coarser one point-samples and aliases: shrink the frames
+ * first (wm_resample_u8) and rescale their georeferences (tiling.resampled_georef).  There is no area filter.
+ * wm_mosaic_plan, geometry only: source_dev[gy][gx] int32; won_dev[n_frames] int32, the cells each frame is the source
+ * of; stats_dev[2] int64: [0] the cells with a source, [1] the cells without.  Every element is written; won and stats are
+ * zeroed on `stream` first.  A gather in the shape of wm_coverage_raster (no atomics touch source; won and stats take
+ * integer atomics).  n_frames == 0 (g2p_dev, size_dev and won_dev may then be NULL) gives an all -1 raster.
+ * wm_mosaic_fill_u8, the pixel gather: frames_dev[n_resident] describes the frames that are on the device in this call;
+ * slot_dev[n_frames] int32 maps a survey frame to its index in frames_dev, negative when it is not resident; g2p_dev and
+ * size_dev are the whole survey's, the grid and source_dev the plan's; mode is WM_MOSAIC_NEAREST or WM_MOSAIC_BILINEAR;
+ * flags may hold WM_MOSAIC_NORTH_UP, which stores cell row j in picture row gy - 1 - j (only the picture is flipped, never
+ * source).  mosaic_dev[gy][gx][3] uint8: a cell is written iff its source is resident, and every other byte is left as it
+ * was, so the frames of a survey may be split over any number of calls in any order with the bytes of one call.  u, v are
+ * recomputed with the expression above, which gives the plan's bits.  Nothing is read out of range: a cell is SKIPPED, and
+ * a bit ORed into status_dev[0] (int32, which the caller zeroes before its first call and reads after its last; the entry
+ * never clears it), when slot_dev[f] >= n_resident or the descriptor's data is NULL (WM_MOSAIC_BAD_SLOT), when the
+ * descriptor's (height, width) differ from size_dev[f] (WM_MOSAIC_BAD_SIZE), or when source is not the plan's: f >=
+ * n_frames, or f does not see the cell's centre (WM_MOSAIC_BAD_SOURCE).  n_frames == 0 or n_resident == 0 writes nothing.
+ * Both entries: asynchronous on `stream`, nothing allocated, plain loads and stores.  Argument limits are the coverage's:
+ * 1 <= gx, gy <= WM_COVERAGE_MAX_SIDE, gx * gy <= WM_COVERAGE_MAX_CELLS, 0 <= n_frames, n_resident <=
+ * WM_COVERAGE_MAX_FRAMES, x0, y0, cell finite, cell > 0; doubles, int64 and descriptors 8-byte, int32 4-byte aligned.  Bad
+ * arguments fail before any HIP call with a message that names the argument. */
+#define WM_MOSAIC_NEAREST 0
+#define WM_MOSAIC_BILINEAR 1
+#define WM_MOSAIC_NORTH_UP 1            /* flags bit 0 */
+#define WM_MOSAIC_BAD_SLOT 1            /* status bits */
+#define WM_MOSAIC_BAD_SIZE 2
+#define WM_MOSAIC_BAD_SOURCE 4
+int wm_mosaic_plan(const double* g2p_dev /* [n_frames][6] */, const int32_t* size_dev /* [n_frames][2] */, int n_frames,
+                   double x0, double y0, double cell, int gx, int gy, int32_t* source_dev /* [gy][gx] */,
+                   int32_t* won_dev /* [n_frames] */, int64_t* stats_dev /* [2] */, void* stream);
+int wm_mosaic_fill_u8(const wm_frame_desc* frames_dev, int n_resident, const int32_t* slot_dev /* [n_frames] */,
+                      const double* g2p_dev, const int32_t* size_dev, int n_frames, double x0, double y0, double cell, int gx,
+                      int gy, const int32_t* source_dev /* [gy][gx] */, int mode, int flags,
+                      uint8_t* mosaic_dev /* [gy][gx][3] */, int32_t* status_dev /* [1] */, void* stream);
 
 /* Survey resampling (tiling.detect_frames(scale=..., resize=...)): a frame brought to the scale the checkpoint was trained
  * at (the val transform's long side of 768, dataloader_coco.py:288) before it is tiled.

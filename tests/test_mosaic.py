@@ -1,0 +1,890 @@
+"""Survey mosaic (include/wm_hip.h "Survey mosaic", tiling.mosaic): the frames of a survey laid onto the ground grid.  The rule
+has no reference behaviour; mosaic_oracle below restates it sequentially -- one cell at a time, numpy float64, vectorised
+over the frames only, the header's operation order -- and the device result must equal it exactly: sources are integers and
+pixels are uint8 behind arithmetic that is rounded once per operation, so every comparison is assert_array_equal and there
+is no tolerance anywhere."""
+import ctypes as C
+import functools
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from wildlifemapper_amd import _native as N
+from wildlifemapper_amd import tiling
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F64 = np.float64
+NAN = float("nan")
+INF = float("inf")
+MODES = {"nearest": N.MOSAIC_NEAREST, "bilinear": N.MOSAIC_BILINEAR}
+SENTINEL = (7, 201, 77)
+
+
+def _sample(img, u, v, mode):
+    """One cell from its source frame img (H,W,3) uint8 at the pixel position (u, v), by the header's sampling rule."""
+    h, w = img.shape[:2]
+    if mode == "nearest":
+        return img[int(np.floor(v)), int(np.floor(u))]
+    fu, fv = u - F64(0.5), v - F64(0.5)
+    xf, yf = np.floor(fu), np.floor(fv)
+    tx, ty = fu - xf, fv - yf
+    xa, xb = min(max(int(xf), 0), w - 1), min(max(int(xf) + 1, 0), w - 1)
+    ya, yb = min(max(int(yf), 0), h - 1), min(max(int(yf) + 1, 0), h - 1)
+    p00, p10, p01, p11 = (img[y, x].astype(F64) for y, x in ((ya, xa), (ya, xb), (yb, xa), (yb, xb)))
+    a = (F64(1.0) - tx) * p00 + tx * p10
+    b = (F64(1.0) - tx) * p01 + tx * p11
+    val = (F64(1.0) - ty) * a + ty * b
+    return np.minimum(np.floor(val + F64(0.5)), F64(255.0)).astype(np.uint8)
+
+
+def mosaic_oracle(g2p, size, x0, y0, cell, gx, gy, frames=None, fill=SENTINEL):
+    """The mosaic rule, one cell at a time.  Returns source (gy,gx), won (F,), stats (2,), all int64, and with frames (a
+    list of (H,W,3) uint8 arrays, None for a frame without pixels) the pictures 'nearest' and 'bilinear' (gy,gx,3) uint8,
+    row 0 south, cells without a source holding `fill`.  Elementwise numpy arithmetic is one correctly rounded IEEE
+    operation per element and operator, in the order written; argmin returns the first, that is the lowest, index."""
+    b = np.asarray(g2p, dtype=F64).reshape(-1, 6)
+    size = np.asarray(size, dtype=np.int64).reshape(-1, 2)
+    h, w = size[:, 0], size[:, 1]
+    cu, cv = F64(0.5) * w.astype(F64), F64(0.5) * h.astype(F64)
+    x0, y0, cell = F64(x0), F64(y0), F64(cell)
+    nf = b.shape[0]
+    source = np.full((gy, gx), -1, dtype=np.int64)
+    pics = {m: np.empty((gy, gx, 3), dtype=np.uint8) for m in MODES} if frames is not None else {}
+    for p in pics.values():
+        p[:] = np.asarray(fill, dtype=np.uint8)
+    with np.errstate(all="ignore"):
+        for j in range(gy):
+            Yc = y0 + (F64(j) + F64(0.5)) * cell
+            for i in range(gx):
+                if not nf:
+                    continue
+                Xc = x0 + (F64(i) + F64(0.5)) * cell
+                u = (b[:, 0] * Xc + b[:, 1] * Yc) + b[:, 2]
+                v = (b[:, 3] * Xc + b[:, 4] * Yc) + b[:, 5]
+                sees = (h >= 1) & (w >= 1) & (0 <= u) & (u < w) & (0 <= v) & (v < h)
+                if not sees.any():
+                    continue
+                du, dv = u - cu, v - cv
+                e = du * du + dv * dv
+                f = int(np.argmin(np.where(sees, e, np.inf)))
+                source[j, i] = f
+                for m, p in pics.items():
+                    p[j, i] = _sample(frames[f], u[f], v[f], m)
+    seen = source >= 0
+    out = {"source": source, "won": np.bincount(source[seen], minlength=nf).astype(np.int64),
+           "stats": np.array([seen.sum(), (~seen).sum()], dtype=np.int64)}
+    out.update(pics)
+    return out
+
+
+def _sample_many(img, u, v, mode):
+    """_sample for arrays of positions: the same operations, elementwise."""
+    h, w = img.shape[:2]
+    if mode == "nearest":
+        return img[np.floor(v).astype(np.int64), np.floor(u).astype(np.int64)]
+    fu, fv = u - F64(0.5), v - F64(0.5)
+    xf, yf = np.floor(fu), np.floor(fv)
+    tx, ty = (fu - xf)[:, None], (fv - yf)[:, None]
+    xa, xb = np.clip(xf.astype(np.int64), 0, w - 1), np.clip(xf.astype(np.int64) + 1, 0, w - 1)
+    ya, yb = np.clip(yf.astype(np.int64), 0, h - 1), np.clip(yf.astype(np.int64) + 1, 0, h - 1)
+    p00, p10, p01, p11 = img[ya, xa].astype(F64), img[ya, xb].astype(F64), img[yb, xa].astype(F64), img[yb, xb].astype(F64)
+    a = (F64(1.0) - tx) * p00 + tx * p10
+    b = (F64(1.0) - tx) * p01 + tx * p11
+    val = (F64(1.0) - ty) * a + ty * b
+    return np.minimum(np.floor(val + F64(0.5)), F64(255.0)).astype(np.uint8)
+
+
+def mosaic_oracle_by_frame(g2p, size, x0, y0, cell, gx, gy, frames=None, fill=SENTINEL, modes=tuple(MODES)):
+    """The same rule one FRAME at a time over the window of cells around its footprint (the window of
+    test_coverage.coverage_oracle_by_frame), with a running best e per cell: frames in ascending order and a strict <, so
+    the lowest index keeps a tie.  The same operations per cell as mosaic_oracle, fast enough for the grids
+    tools/mosaic_time.py times.  Checked equal to mosaic_oracle below."""
+    b = np.asarray(g2p, dtype=F64).reshape(-1, 6)
+    size = np.asarray(size, dtype=np.int64).reshape(-1, 2)
+    x0, y0, cell = F64(x0), F64(y0), F64(cell)
+    Xc = x0 + (np.arange(gx, dtype=F64) + F64(0.5)) * cell
+    Yc = y0 + (np.arange(gy, dtype=F64) + F64(0.5)) * cell
+    best = np.full((gy, gx), np.inf, dtype=F64)
+    source = np.full((gy, gx), -1, dtype=np.int64)
+    windows = {}
+    with np.errstate(all="ignore"):
+        for f in range(b.shape[0]):
+            h, w = size[f]
+            if h < 1 or w < 1 or not np.isfinite(b[f]).all():
+                continue
+            i0, i1, j0, j1 = 0, gx, 0, gy
+            A = np.array([[b[f, 0], b[f, 1]], [b[f, 3], b[f, 4]]])
+            if abs(np.linalg.det(A)) > 0:
+                corners = np.array([[0, 0], [w, 0], [0, h], [w, h]], dtype=F64) - b[f, [2, 5]]
+                ground = np.linalg.solve(A, corners.T).T
+                if np.isfinite(ground).all():
+                    i0 = int(np.clip(np.floor((ground[:, 0].min() - x0) / cell) - 2, 0, gx))
+                    i1 = int(np.clip(np.ceil((ground[:, 0].max() - x0) / cell) + 2, 0, gx))
+                    j0 = int(np.clip(np.floor((ground[:, 1].min() - y0) / cell) - 2, 0, gy))
+                    j1 = int(np.clip(np.ceil((ground[:, 1].max() - y0) / cell) + 2, 0, gy))
+            windows[f] = (i0, i1, j0, j1)
+            X, Y = Xc[None, i0:i1], Yc[j0:j1, None]
+            u = (b[f, 0] * X + b[f, 1] * Y) + b[f, 2]
+            v = (b[f, 3] * X + b[f, 4] * Y) + b[f, 5]
+            du, dv = u - F64(0.5) * F64(w), v - F64(0.5) * F64(h)
+            e = du * du + dv * dv
+            better = (0 <= u) & (u < w) & (0 <= v) & (v < h) & (e < best[j0:j1, i0:i1])
+            best[j0:j1, i0:i1][better] = e[better]
+            source[j0:j1, i0:i1][better] = f
+        seen = source >= 0
+        out = {"source": source, "won": np.bincount(source[seen], minlength=b.shape[0]).astype(np.int64),
+               "stats": np.array([seen.sum(), (~seen).sum()], dtype=np.int64)}
+        if frames is None:
+            return out
+        for m in modes:
+            out[m] = np.empty((gy, gx, 3), dtype=np.uint8)
+            out[m][:] = np.asarray(fill, dtype=np.uint8)
+        for f, (i0, i1, j0, j1) in windows.items():
+            jj, ii = np.nonzero(source[j0:j1, i0:i1] == f)
+            if not len(jj):
+                continue
+            X, Y = Xc[i0 + ii], Yc[j0 + jj]
+            u = (b[f, 0] * X + b[f, 1] * Y) + b[f, 2]
+            v = (b[f, 3] * X + b[f, 4] * Y) + b[f, 5]
+            for m in modes:
+                out[m][j0 + jj, i0 + ii] = _sample_many(frames[f], u, v, m)
+    return out
+
+
+def _kernel_constants():
+    src = open(os.path.join(ROOT, "wildlifemapper_amd", "csrc", "coverage_kernels.h")).read()
+    get = lambda name: int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1))
+    threads, rows = get("COV_THREADS"), get("COV_ROWS")
+    return {"chunk": get("COV_CHUNK"), "block_x": get("COV_BLOCK_X"), "block_y": threads // 64 * rows}
+
+
+def _content(h, w, seed):
+    return np.random.default_rng(seed).integers(0, 256, (h, w, 3), dtype=np.uint8)
+
+
+def _case(frames, x0, y0, cell, gx, gy, images=None, seed=0):
+    """frames: a list of (g2p as 6 numbers or (2,3), height, width).  images: one (H,W,3) uint8 array per frame; by default
+    random content for every frame of at least 1 x 1 px and None for the others."""
+    g2p = np.array([np.asarray(f[0], dtype=F64).reshape(6) for f in frames], dtype=F64).reshape(-1, 6)
+    size = np.array([[f[1], f[2]] for f in frames], dtype=np.int32).reshape(-1, 2)
+    if images is None:
+        images = [_content(h, w, seed * 100003 + k) if h >= 1 and w >= 1 else None for k, (h, w) in enumerate(size.tolist())]
+    return {"g2p": g2p, "size": size, "x0": float(x0), "y0": float(y0), "cell": float(cell), "gx": gx, "gy": gy, "images": images}
+
+
+def _oracle(case):
+    return mosaic_oracle(case["g2p"], case["size"], case["x0"], case["y0"], case["cell"], case["gx"], case["gy"], case["images"])
+
+
+# Frame A: 8 x 4 px (W x H), 0.5 m pixels, footprint [0, 4) x (0, 2] m, u = 2 X, v = 4 - 2 Y; frame B: the same, 2 m further
+# east.  Pixel (y, x) of either holds (16 y + x, 100 + x, 200 - y).
+FRAME_A = ([2, 0, 0, 0, -2, 4], 4, 8)
+FRAME_B = ([2, 0, -4, 0, -2, 4], 4, 8)
+RAMP = np.array([[(16 * y + x, 100 + x, 200 - y) for x in range(8)] for y in range(4)], dtype=np.uint8)
+# 2 x 1 px holding 10 and 13 in every channel, 1 m pixels: u = X, v = 1 - Y
+FRAME_PAIR = ([1, 0, 0, 0, -1, 1], 1, 2)
+PAIR = np.array([[(10, 10, 10), (13, 13, 13)]], dtype=np.uint8)
+
+
+def _yawed_90():
+    a = tiling.nadir_affine(4, 8, (10.0, 20.0), 0.5, 90.0)       # up is east: 2 m east-west (9..11), 4 m north-south (18..22)
+    return (tiling.ground_to_pixel(a), 4, 8)
+
+
+def _singular():
+    return (tiling.ground_to_pixel(np.array([[1.0, 2.0, 5.0], [2.0, 4.0, 7.0]])), 4, 8)             # det == 0: a row of NaN
+
+
+# name -> (case, expected source rows from j = 0 (south) upwards)
+def _seam_cases():
+    cases = {}
+    none5 = [-1] * 5
+    one = [[0, 0, 0, 0, -1], [0, 0, 0, 0, -1], none5]
+    cases["one_frame"] = (_case([FRAME_A], 0, 0, 1, 5, 3, [RAMP]), one)
+    # centres at X = 1..6: A sees 1, 2, 3; B sees 2..5.  At X = 3 both are 2 px from their centre column (u = 6 and u = 2,
+    # centre 4) on the same row: the two e are the same number, and the lower index wins
+    cases["two_frames_2m_apart"] = (_case([FRAME_A, FRAME_B], 0.5, 0, 1, 6, 3, [RAMP, RAMP]),
+                                    [[0, 0, 0, 1, 1, -1], [0, 0, 0, 1, 1, -1], [-1] * 6])
+    cases["two_frames_2m_apart_swapped"] = (_case([FRAME_B, FRAME_A], 0.5, 0, 1, 6, 3, [RAMP, RAMP]),
+                                            [[1, 1, 0, 0, 0, -1], [1, 1, 0, 0, 0, -1], [-1] * 6])
+    cases["identical_georeferences"] = (_case([FRAME_A, FRAME_A], 0, 0, 1, 5, 3, [RAMP, RAMP[::-1].copy()]), one)
+    side = [-1, 0, 0, -1]
+    cases["yawed_90"] = (_case([_yawed_90()], 8, 17, 1, 4, 6, [RAMP]), [[-1] * 4, side, side, side, side, [-1] * 4])
+    five = [[5, 5, 5, 5, -1], [5, 5, 5, 5, -1], none5]
+    never = [([2, NAN, 0, 0, -2, 4], 4, 8), ([2, 0, 0, 0, -2, INF], 4, 8), _singular(), ([2, 0, 0, 0, -2, 4], 0, 8), ([2, 0, 0, 0, -2, 4], 4, -3)]
+    cases["never_a_source"] = (_case(never + [FRAME_A], 0, 0, 1, 5, 3, [RAMP, RAMP, RAMP, None, None, RAMP]), five)
+    return cases
+
+
+SEAM = _seam_cases()
+
+
+# name -> (case, mode or None for both, expected channel 0 rows from j = 0 upwards)
+def _pixel_cases():
+    cases = {}
+    # centres at X = 0.25 + 0.5 i, Y = 0.25 + 0.5 j: u = i + 0.5, v = 3.5 - j, every centre on a pixel centre
+    cases["on_pixel_centres"] = (_case([FRAME_A], 0, 0, 0.5, 8, 4, [RAMP]), None, RAMP[::-1, :, 0].tolist())
+    # u = 1 exactly (column 1, not 0), v = 3 exactly (row 3): cell (0, 0) of the 1 m grid
+    cases["nearest_at_integer_u"] = (_case([FRAME_A], 0, 0, 1, 5, 3, [RAMP]), "nearest",
+                                     [[49, 51, 53, 55, SENTINEL[0]], [17, 19, 21, 23, SENTINEL[0]], [SENTINEL[0]] * 5])
+    # the same cells, bilinear: half way between columns and rows, (32 + 33 + 48 + 49) / 4 = 40.5 -> 41
+    cases["bilinear_between_four"] = (_case([FRAME_A], 0, 0, 1, 5, 3, [RAMP]), "bilinear",
+                                      [[41, 43, 45, 47, SENTINEL[0]], [9, 11, 13, 15, SENTINEL[0]], [SENTINEL[0]] * 5])
+    # u = 1.0: half way between 10 and 13, 11.5 rounds up
+    cases["bilinear_half_way"] = (_case([FRAME_PAIR], 0.5, 0, 1, 1, 1, [PAIR]), "bilinear", [[12]])
+    # u = 0.25, 0.75, 1.25, 1.75: the first and the last lie within half a pixel of the edge and replicate it
+    cases["bilinear_edge_replicate"] = (_case([FRAME_PAIR], 0, 0.25, 0.5, 4, 1, [PAIR]), "bilinear", [[10, 11, 12, 13]])
+    return cases
+
+
+PIXEL = _pixel_cases()
+
+
+@pytest.mark.parametrize("name", sorted(SEAM))
+def test_oracle_seam_hand_cases(name):
+    case, rows = SEAM[name]
+    got = _oracle(case)
+    assert got["source"].tolist() == rows
+    flat = [f for r in rows for f in r]
+    assert got["won"].tolist() == [flat.count(f) for f in range(case["g2p"].shape[0])]
+    assert got["stats"].tolist() == [len(flat) - flat.count(-1), flat.count(-1)]
+
+
+def test_oracle_two_frames_tie_is_exact():
+    case, _ = SEAM["two_frames_2m_apart"]
+    b, Xc, Yc = case["g2p"], F64(3.0), F64(0.5)
+    u = (b[:, 0] * Xc + b[:, 1] * Yc) + b[:, 2]
+    v = (b[:, 3] * Xc + b[:, 4] * Yc) + b[:, 5]
+    e = (u - 4.0) * (u - 4.0) + (v - 2.0) * (v - 2.0)
+    assert u.tolist() == [6.0, 2.0] and e[0] == e[1] == 5.0
+
+
+@pytest.mark.parametrize("name", sorted(PIXEL))
+def test_oracle_pixel_hand_cases(name):
+    case, mode, rows = PIXEL[name]
+    got = _oracle(case)
+    for m in ([mode] if mode else sorted(MODES)):
+        assert got[m][:, :, 0].tolist() == rows, m
+    if name == "on_pixel_centres":
+        np.testing.assert_array_equal(got["bilinear"], RAMP[::-1])
+        np.testing.assert_array_equal(got["nearest"], RAMP[::-1])
+    if name == "nearest_at_integer_u":
+        assert got["nearest"][0, 0].tolist() == [16 * 3 + 1, 101, 197]
+
+
+@pytest.mark.parametrize("name", sorted(SEAM) + sorted(PIXEL) + ["grid_70x19", "past_one_chunk", "mixed_sizes_in_one_chunk", "random_survey"])
+def test_oracle_by_frame_equals_oracle(name):
+    if name in SEAM or name in PIXEL:
+        case = (SEAM.get(name) or PIXEL.get(name))[0]
+        want = _oracle(case)
+    else:
+        case, want = _gpu_case(name)
+    got = mosaic_oracle_by_frame(case["g2p"], case["size"], case["x0"], case["y0"], case["cell"], case["gx"], case["gy"], case["images"])
+    assert set(got) == set(want)
+    for key in want:
+        np.testing.assert_array_equal(got[key], want[key], err_msg=key)
+
+
+def test_resampled_georef():
+    H, W = 8, 16
+    a = tiling.nadir_affine(H, W, (512.0, 1024.0), 0.5, 90.0)
+    a2 = tiling.resampled_georef(a, (H, W), (H // 2, W // 2))
+    assert a2.shape == (2, 3) and a2.dtype == np.float64
+    for x, y in ((0.0, 0.0), (4.0, 2.0), (16.0, 8.0), (5.5, 1.25)):
+        np.testing.assert_array_equal(a2[:, :2] @ np.array([x / 2, y / 2]) + a2[:, 2], a[:, :2] @ np.array([x, y]) + a[:, 2])
+    g = np.array([[[0.5, 0.25, 7.0], [0.125, -0.5, 9.0]], [[2.0, 0.0, 1.0], [0.0, -2.0, 3.0]]])
+    out = tiling.resampled_georef(g, [(8, 16), (6, 4)], [(4, 4), (12, 8)])
+    np.testing.assert_array_equal(out, [[[2.0, 0.5, 7.0], [0.5, -1.0, 9.0]], [[1.0, 0.0, 1.0], [0.0, -1.0, 3.0]]])
+    np.testing.assert_array_equal(tiling.resampled_georef(torch.from_numpy(g), (8, 16), (4, 8)), g * [[[2.0, 2.0, 1.0]]])
+    np.testing.assert_array_equal(tiling.resampled_georef(g, (8, 16), (8, 16)), g)
+    with pytest.raises(ValueError, match="georef"):
+        tiling.resampled_georef(np.zeros((3, 2)), (8, 16), (4, 8))
+    with pytest.raises(ValueError, match="georef"):
+        tiling.resampled_georef("georef", (8, 16), (4, 8))
+    for bad in ((8,), (8, 16, 3), [(8, 16)] * 3, (0, 16), (8.5, 16), "size", None):
+        with pytest.raises(ValueError, match="size"):
+            tiling.resampled_georef(g, bad, (4, 8))
+        with pytest.raises(ValueError, match="new_size"):
+            tiling.resampled_georef(g, (8, 16), bad)
+
+
+class _Lazy:
+    """A sequence that is only indexed, and records what was asked of it."""
+
+    def __init__(self, items):
+        self.items, self.asked = items, []
+
+    def __len__(self):
+        return len(self.items)
+
+    def __getitem__(self, i):
+        self.asked.append(i)
+        return self.items[i]
+
+
+def test_mosaic_python_argument_errors_before_device_work():
+    g = [[[0.5, 0, 0.0], [0, -0.5, 2.0]]] * 2
+    sizes = [(4, 8), (4, 8)]
+    frames = [RAMP, RAMP]
+    lazy = _Lazy(frames)
+    for bad in ("cubic", None, 1, b"nearest"):
+        with pytest.raises(ValueError, match="sample"):
+            tiling.mosaic(frames, g, 1.0, sample=bad)
+    for bad in ((0, 0), (0, 0, 256), (0, -1, 0), (0.5, 0, 0), "red", None, 7):
+        with pytest.raises(ValueError, match="fill"):
+            tiling.mosaic(frames, g, 1.0, fill=bad)
+    for bad in (0, -1, 2.5, "8", None, True, NAN):
+        with pytest.raises(ValueError, match="chunk"):
+            tiling.mosaic(frames, g, 1.0, chunk=bad)
+    with pytest.raises(ValueError, match="marker"):
+        tiling.mosaic(frames, g, 1.0, marker=3)
+    k = 3
+    cen = {"points": torch.zeros((k, 2), dtype=torch.float64), "labels": torch.zeros(k, dtype=torch.int64)}
+    with pytest.raises(ValueError, match="marker"):
+        tiling.mosaic(frames, g, 1.0, census=cen)
+    for bad in (0, -2, 1.5, "3", True):
+        with pytest.raises(ValueError, match="marker"):
+            tiling.mosaic(frames, g, 1.0, census=cen, marker=bad)
+    with pytest.raises(ValueError, match="'points'"):
+        tiling.mosaic(frames, g, 1.0, census={"labels": cen["labels"]}, marker=3)
+    with pytest.raises(ValueError, match="census"):
+        tiling.mosaic(frames, g, 1.0, census=dict(cen, points=torch.zeros((k, 2))), marker=3)            # float32 points
+    with pytest.raises(ValueError, match="width"):
+        tiling.mosaic(frames, g, 1.0, census=cen, marker=3, width=0)
+    with pytest.raises(ValueError, match="palette"):
+        tiling.mosaic(frames, g, 1.0, census=cen, marker=3, palette=np.zeros((3, 4), dtype=np.uint8))
+    with pytest.raises(ValueError, match="sizes is required"):
+        tiling.mosaic(lazy, g, 1.0)
+    with pytest.raises(ValueError, match="sizes is required"):
+        tiling.mosaic([RAMP, "frame_0002.jpg"], g, 1.0)
+    with pytest.raises(ValueError, match="indexed"):
+        tiling.mosaic(iter(frames), g, 1.0, sizes=sizes)
+    with pytest.raises(ValueError, match="sizes for 2 georeferences"):
+        tiling.mosaic(lazy, g, 1.0, sizes=[(4, 8)])
+    with pytest.raises(ValueError, match="1 frames for 2 georeferences"):
+        tiling.mosaic(_Lazy([RAMP]), g, 1.0, sizes=sizes)
+    with pytest.raises(ValueError, match="georeferences"):
+        tiling.mosaic([RAMP], g, 1.0)
+    for bad in (0, -1.0, NAN, INF, "wide", None):
+        with pytest.raises(ValueError, match="cell"):
+            tiling.mosaic(lazy, g, bad, sizes=sizes)
+        with pytest.raises(ValueError, match="cell"):
+            tiling.mosaic_plan(g, sizes, bad)
+    with pytest.raises(ValueError, match="georef"):
+        tiling.mosaic_plan(np.zeros((2, 3, 2)), sizes, 1.0)
+    with pytest.raises(ValueError, match="sizes"):
+        tiling.mosaic_plan(g, [(4.5, 8), (4, 8)], 1.0)
+    for call in (lambda **kw: tiling.mosaic(lazy, g, 1.0, sizes=sizes, **kw), lambda **kw: tiling.mosaic_plan(g, sizes, 1.0, **kw)):
+        with pytest.raises(ValueError, match="larger cell"):
+            call(bounds=(0.0, 0.0, N.COVERAGE_MAX_SIDE + 1, 1))
+        for bad in ((0.0, 0.0, 0, 1), (NAN, 0.0, 5, 5), (0.0, 0.0, 5.5, 5), (0.0, 0.0, 5), "grid"):
+            with pytest.raises(ValueError, match="bounds"):
+                call(bounds=bad)
+    with pytest.raises(RuntimeError, match="ROCm device tensor"):              # no CPU fallback
+        tiling.mosaic(lazy, g, 1.0, sizes=sizes, census=cen, marker=3)
+    if not torch.cuda.is_available():
+        with pytest.raises(RuntimeError, match="ROCm device tensor"):
+            tiling.mosaic(lazy, g, 1.0, sizes=sizes)
+        with pytest.raises(RuntimeError, match="ROCm device tensor"):
+            tiling.mosaic_plan(g, sizes, 1.0)
+    assert lazy.asked == []                                                     # nothing was loaded on the way to an error
+
+
+def _abi_plan(n_frames=2, x0=0.0, y0=0.0, cell=1.0, gx=5, gy=3, g2p=0x2000, size=0x3000, source=0x4000, won=0x5000, stats=0x6000):
+    """wm_mosaic_plan with fake, never dereferenced device pointers: only paths that return before any HIP call."""
+    p = lambda v: C.c_void_p(v) if v else None
+    return N.lib().wm_mosaic_plan(p(g2p), p(size), n_frames, x0, y0, cell, gx, gy, p(source), p(won), p(stats), None)
+
+
+def _abi_fill(n_frames=2, n_resident=2, x0=0.0, y0=0.0, cell=1.0, gx=5, gy=3, mode=N.MOSAIC_BILINEAR, flags=0, frames=0x1000, slot=0x7000,
+              g2p=0x2000, size=0x3000, source=0x4000, mosaic=0x8000, status=0x9000):
+    p = lambda v: C.c_void_p(v) if v else None
+    return N.lib().wm_mosaic_fill_u8(p(frames), n_resident, p(slot), p(g2p), p(size), n_frames, x0, y0, cell, gx, gy, p(source), mode, flags,
+                                     p(mosaic), p(status), None)
+
+
+def test_mosaic_abi_argument_errors_without_gpu():
+    err = lambda: N.lib().wm_last_error().decode()
+    for call in (_abi_plan, _abi_fill):
+        assert call(gx=0) < 0 and "gx" in err()
+        assert call(gx=N.COVERAGE_MAX_SIDE + 1) < 0 and "gx" in err()
+        assert call(gy=0) < 0 and "gy" in err()
+        assert call(gy=-4) < 0 and "gy" in err()
+        assert call(gy=N.COVERAGE_MAX_SIDE + 1) < 0 and "gy" in err()
+        assert call(gx=16384, gy=8192) < 0 and "gx * gy" in err()
+        assert call(gx=8192, gy=8192 + 1) < 0 and "gx * gy" in err()
+        assert call(n_frames=-1) < 0 and "n_frames" in err()
+        assert call(n_frames=N.COVERAGE_MAX_FRAMES + 1) < 0 and "n_frames" in err()
+        for bad in (NAN, INF, -INF):
+            assert call(x0=bad) < 0 and "x0" in err()
+            assert call(y0=bad) < 0 and "y0" in err()
+        for bad in (0.0, -1.0, NAN, INF):
+            assert call(cell=bad) < 0 and "cell" in err()
+        assert call(g2p=0) < 0 and "g2p_dev" in err()
+        assert call(size=0) < 0 and "size_dev" in err()
+        assert call(g2p=0x2004) < 0 and "aligned" in err()
+        assert call(size=0x3002) < 0 and "aligned" in err()
+        assert call(source=0) < 0 and "source_dev" in err()
+        assert call(source=0x4002) < 0 and "aligned" in err()
+    assert _abi_plan(won=0) < 0 and "won_dev" in err()
+    assert _abi_plan(stats=0) < 0 and "stats_dev" in err()
+    assert _abi_plan(won=0x5002) < 0 and "aligned" in err()
+    assert _abi_plan(stats=0x6004) < 0 and "aligned" in err()
+    assert _abi_fill(n_resident=-1) < 0 and "n_resident" in err()
+    assert _abi_fill(n_resident=N.COVERAGE_MAX_FRAMES + 1) < 0 and "n_resident" in err()
+    for bad in (-1, 2, 7):
+        assert _abi_fill(mode=bad) < 0 and "mode" in err()
+    for bad in (2, 4, 3, -2):
+        assert _abi_fill(flags=bad) < 0 and "flags" in err()
+    assert _abi_fill(frames=0) < 0 and "frames_dev" in err()
+    assert _abi_fill(slot=0) < 0 and "slot_dev" in err()
+    assert _abi_fill(mosaic=0) < 0 and "mosaic_dev" in err()
+    assert _abi_fill(status=0) < 0 and "status_dev" in err()
+    assert _abi_fill(frames=0x1004) < 0 and "aligned" in err()
+    assert _abi_fill(slot=0x7002) < 0 and "aligned" in err()
+    assert _abi_fill(status=0x9002) < 0 and "aligned" in err()
+    # nothing can be resident: returns 0 after the checks, before any HIP call
+    assert _abi_fill(n_resident=0, frames=0, slot=0) == 0
+    assert _abi_fill(n_frames=0, g2p=0, size=0, frames=0, slot=0) == 0
+    assert _abi_fill(n_resident=0, mode=5) < 0 and "mode" in err()
+
+
+def test_mosaic_symbols_and_abi_13():
+    hdr = open(os.path.join(ROOT, "include", "wm_hip.h")).read()
+    assert int(re.search(r"#define WM_ABI_VERSION (\d+)", hdr).group(1)) == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
+    assert "Survey mosaic" in hdr and len(re.findall("13, additive", hdr)) >= 2
+    for name in ("wm_mosaic_plan", "wm_mosaic_fill_u8"):
+        assert name in N.SYMBOLS and re.search(r"\bint %s\(" % name, hdr)
+        assert getattr(N.lib(), name) is not None
+    for macro, val in (("WM_MOSAIC_NEAREST", N.MOSAIC_NEAREST), ("WM_MOSAIC_BILINEAR", N.MOSAIC_BILINEAR), ("WM_MOSAIC_NORTH_UP", N.MOSAIC_NORTH_UP),
+                       ("WM_MOSAIC_BAD_SLOT", N.MOSAIC_BAD_SLOT), ("WM_MOSAIC_BAD_SIZE", N.MOSAIC_BAD_SIZE), ("WM_MOSAIC_BAD_SOURCE", N.MOSAIC_BAD_SOURCE)):
+        assert int(re.search(r"#define %s (\d+)" % macro, hdr).group(1)) == val
+    assert N.MOSAIC_NEAREST != N.MOSAIC_BILINEAR and tiling.MOSAIC_SAMPLES == MODES
+    kern = open(os.path.join(ROOT, "wildlifemapper_amd", "csrc", "mosaic_kernels.h")).read()
+    assert '#include "coverage_kernels.h"' in kern and "cov_stage(" in kern and "cov_row_may_touch(" in kern       # shared, not copied
+    assert "cov_stage(CovFrames" not in kern and "asm" not in kern
+
+
+# ---- GPU -------------------------------------------------------------------------------------------------------------
+
+DEV = "cuda:0"
+
+
+def _up(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _plan(case):
+    """wm_mosaic_plan through the C-ABI, every output pre-filled with a poison value."""
+    F, gx, gy = case["g2p"].shape[0], case["gx"], case["gy"]
+    g = _up(case["g2p"]) if F else None
+    s = _up(case["size"]) if F else None
+    source = torch.full((gy, gx), -77, device=DEV, dtype=torch.int32)
+    won = torch.full((F,), -7, device=DEV, dtype=torch.int32) if F else None
+    stats = torch.full((2,), -7, device=DEV, dtype=torch.int64)
+    N.check(N.lib().wm_mosaic_plan(N.ptr(g), N.ptr(s), F, case["x0"], case["y0"], case["cell"], gx, gy, N.ptr(source), N.ptr(won), N.ptr(stats),
+                                   N.stream_ptr(torch.device(DEV))))
+    return {"g": g, "s": s, "source_dev": source, "source": source.cpu().numpy().astype(np.int64),
+            "won": won.cpu().numpy().astype(np.int64) if F else np.zeros(0, dtype=np.int64), "stats": stats.cpu().numpy()}
+
+
+def _fill(case, plan, mode, picture, status, resident, flags=0, descs=None, slot=None):
+    """One wm_mosaic_fill_u8 call with the frames `resident` (survey indices) on the device, in that order."""
+    F, gx, gy = case["g2p"].shape[0], case["gx"], case["gy"]
+    tensors = [_up(case["images"][f]) for f in resident]
+    if descs is None:
+        descs = tiling._frame_descs(tensors, torch.device(DEV)) if tensors else None
+    if slot is None:
+        slot = np.full(F, -1, dtype=np.int32)
+        slot[list(resident)] = np.arange(len(resident), dtype=np.int32)
+    slot_d = _up(slot) if F else None
+    N.check(N.lib().wm_mosaic_fill_u8(N.ptr(descs), len(resident), N.ptr(slot_d), N.ptr(plan["g"]), N.ptr(plan["s"]), F, case["x0"], case["y0"],
+                                      case["cell"], gx, gy, N.ptr(plan["source_dev"]), MODES[mode], flags, N.ptr(picture), N.ptr(status),
+                                      N.stream_ptr(torch.device(DEV))))
+    torch.cuda.synchronize()
+    return tensors
+
+
+def _sentinel_picture(case):
+    return _up(np.asarray(SENTINEL, dtype=np.uint8)).expand(case["gy"], case["gx"], 3).contiguous()
+
+
+def _device(case):
+    """The plan, and both pictures with every frame that has pixels resident in one call."""
+    plan = _plan(case)
+    out = {k: plan[k] for k in ("source", "won", "stats")}
+    resident = [f for f, im in enumerate(case["images"]) if im is not None]
+    for mode in MODES:
+        pic, status = _sentinel_picture(case), torch.zeros(1, device=DEV, dtype=torch.int32)
+        _fill(case, plan, mode, pic, status, resident)
+        assert status.item() == 0, mode
+        out[mode] = pic.cpu().numpy()
+    return out, plan
+
+
+def _assert_same(got, want):
+    assert set(got) == set(want)
+    for key in got:
+        assert got[key].shape == want[key].shape, key
+        np.testing.assert_array_equal(got[key], want[key], err_msg=key)
+
+
+def _run_and_check(case, want=None):
+    want = _oracle(case) if want is None else want
+    got, plan = _device(case)
+    _assert_same(got, want)
+    assert got["stats"].sum() == case["gx"] * case["gy"] and got["won"].sum() == got["stats"][0]
+    return got, want, plan
+
+
+def _axis(xw, xe, ys, yn, px):
+    """An axis-aligned frame with footprint [xw, xe) x (ys, yn] m at px pixels per metre (exact for the binary fractions used)."""
+    return ([px, 0, -px * xw, 0, -px, px * yn], int(round((yn - ys) * px)), int(round((xe - xw) * px)))
+
+
+def _yawed(centre, gsd, yaw, H, W):
+    return (tiling.ground_to_pixel(tiling.nadir_affine(H, W, centre, gsd, yaw)), H, W)
+
+
+def _some_frames(gx, gy, cell, seed, n=5):
+    """n yawed frames of different sizes spread over the grid [0, gx * cell) x [0, gy * cell), each about a third of it."""
+    rng = np.random.default_rng(seed)
+    ex, ey = gx * cell, gy * cell
+    side = max(ex, ey) / 3 + cell
+    shapes = [(30, 40), (17, 23), (40, 30), (9, 64), (33, 33)]
+    return [_yawed((rng.uniform(0, ex), rng.uniform(0, ey)), side / max(shapes[k % 5]), rng.uniform(0, 360), *shapes[k % 5]) for k in range(n)]
+
+
+@functools.lru_cache(maxsize=None)
+def _gpu_case(name):
+    """name -> (case, oracle result), computed once."""
+    k = _kernel_constants()
+    bx, by = k["block_x"], k["block_y"]
+    if name.startswith("grid_"):                                                # grid_<gx>x<gy>: none a multiple of the block
+        gx, gy = (int(v) for v in name[5:].split("x"))
+        case = _case(_some_frames(gx, gy, 0.7, gx) + [_axis(-1.0, gx * 0.7 / 2, -1.0, gy, 0.5)], 0.0, 0.0, 0.7, gx, gy, seed=1)
+    elif name == "no_frames":
+        case = _case([], 0.0, 0.0, 0.7, 70, 19)
+    elif name == "one_1x1_px_frame":                                            # one pixel of 4 m over cells of 0.7 m
+        case = _case([_axis(10.0, 14.0, 4.0, 8.0, 0.25)], 0.0, 0.0, 0.7, 70, 19, seed=2)
+    elif name == "past_one_chunk":
+        # the first COV_CHUNK frames are far away, not finite or without pixels, but for frame 10; of the frames after them,
+        # the first has frame 10's georeference (an exact tie across the chunk boundary: 10 wins), the second overlaps frame
+        # 10 and is nearer for some cells, the third lies alone
+        ch = k["chunk"]
+        ten = tiling.nadir_affine(30, 40, (16.0, 6.5), 0.5, 0.0)
+        far = [_yawed((5000.0 + 40 * f, -3000.0), 0.1, 7.0 * f, 3, 4) for f in range(ch)]
+        far[3] = ([2, NAN, 0, 0, -2, 4], 4, 8)
+        far[100] = _axis(0.0, 49.0, 0.0, 13.0, 4.0)[:1] + (0, 196)
+        far[10] = (tiling.ground_to_pixel(ten), 30, 40)
+        near = [(tiling.ground_to_pixel(ten), 30, 40), _yawed((24.0, 6.5), 0.5, 0.0, 30, 40), _yawed((42.0, 8.0), 0.25, 115.0, 30, 40)]
+        case = _case(far + near, 0.0, 0.0, 0.7, 70, 19, seed=3)
+    elif name == "mixed_sizes_in_one_chunk":
+        frames = [_axis(0.0, 32.0, 0.0, 12.0, 2.0), _axis(8.0, 40.0, 2.0, 10.0, 0.5), _axis(20.0, 49.0, 0.0, 13.0, 1.0),
+                  _axis(30.0, 34.0, 4.0, 8.0, 0.25), _yawed((25.0, 6.0), 0.3, 30.0, 7, 90)]
+        case = _case(frames, 0.0, 0.0, 0.7, 70, 19, seed=4)
+    elif name == "cull_tiny_frame":                                             # 0.5 m of footprint around one centre, inside one block
+        case = _case([_axis(100.25, 100.75, 40.25, 40.75, 8.0)], 0.0, 0.0, 1.0, 257, 65, seed=5)
+    elif name == "cull_thin_between_rows":                                      # (40.625, 40.875]: between the rows of centres 40.5 and 41.5
+        case = _case([_axis(0.0, 257.0, 40.625, 40.875, 8.0)], 0.0, 0.0, 1.0, 257, 65, seed=6)
+    elif name == "cull_thin_on_one_row":                                        # (40.375, 40.625] holds the row of centres 40.5
+        case = _case([_axis(0.0, 257.0, 40.375, 40.625, 8.0)], 0.0, 0.0, 1.0, 257, 65, seed=7)
+    elif name == "cull_yaw_45":                                                 # 1.5 m and 1 m strips across the grid's blocks
+        case = _case([_yawed((128.0, 32.0), 0.05, 45.0, 30, 3000), _yawed((60.3, 30.1), 0.05, 135.0, 3000, 20)], 0.0, 0.0, 1.0, 257, 65, seed=8)
+    elif name == "cover_all":
+        case = _case([_axis(-10.0, 300.0, -10.0, 100.0, 0.5), _yawed((128.0, 32.0), 2.0, 45.0, 300, 300)], 0.0, 0.0, 1.0, 257, 65, seed=9)
+    elif name == "block_edges":
+        # centres at multiples of 0.5 m; footprints whose edges are the centres of the first cells of blocks: the west
+        # edge is inside, the east edge outside; the north edge inside, the south edge outside
+        c = 0.5
+        frames = [_axis(bx * c, 2 * bx * c, (by - 1) * c, (2 * by - 1) * c, 2.0),            # columns bx..2bx-1, rows by..2by-1
+                  _axis(0.0, bx * c, -c, (by - 1) * c, 2.0),                                   # block (0, 0) exactly
+                  _axis(2 * bx * c, 4 * bx * c, (by - 1) * c, (2 * by - 1) * c, 2.0),          # east of the first, to the grid's edge region
+                  _axis((bx - 1) * c, (bx + 1) * c, (by - 2) * c, by * c, 2.0)]                # 2 x 2 cells across a block corner
+        case = _case(frames, -0.25, -0.25, c, 257, 65, seed=10)
+    elif name == "random_survey":
+        rng = np.random.default_rng(11)
+        x0, y0, cell, gx, gy = 500000.1, 4000000.7, 0.11, 128, 96                # 14.1 m x 10.6 m; a frame is 3.2 m x 2.4 m
+        frames = [_yawed((x0 + rng.uniform(0, 14), y0 + rng.uniform(0, 10.5)), 0.05, rng.uniform(0, 360), 48, 64) for _ in range(40)]
+        case = _case(frames, x0, y0, cell, gx, gy, seed=11)
+    else:
+        raise KeyError(name)
+    return case, _oracle(case)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(SEAM))
+def test_gpu_seam_hand_cases(name):
+    case, rows = SEAM[name]
+    got, _, _ = _run_and_check(case)
+    assert got["source"].tolist() == rows
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(PIXEL))
+def test_gpu_pixel_hand_cases(name):
+    case, mode, rows = PIXEL[name]
+    got, _, _ = _run_and_check(case)
+    for m in ([mode] if mode else sorted(MODES)):
+        assert got[m][:, :, 0].tolist() == rows, m
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["grid_1x1", "grid_70x19", "grid_257x65", "no_frames", "one_1x1_px_frame", "past_one_chunk",
+                                  "mixed_sizes_in_one_chunk"])
+def test_gpu_smallest_shapes(name):
+    case, want = _gpu_case(name)
+    got, _, _ = _run_and_check(case, want)
+    src = got["source"]
+    if name == "no_frames":
+        assert (src == -1).all() and got["stats"].tolist() == [0, 70 * 19]
+        assert (got["bilinear"] == np.asarray(SENTINEL, dtype=np.uint8)).all()
+    if name == "one_1x1_px_frame":
+        assert got["won"].tolist() == [30] and (got["bilinear"][src == 0] == case["images"][0][0, 0]).all()
+    if name == "past_one_chunk":
+        ch = _kernel_constants()["chunk"]
+        assert case["g2p"].shape[0] == ch + 3
+        np.testing.assert_array_equal(case["g2p"][ch], case["g2p"][10])            # the tie across the chunk boundary
+        assert got["won"][10] > 0 and got["won"][ch] == 0 and got["won"][ch + 1] > 0 and got["won"][ch + 2] > 0
+        both = dict(case, g2p=case["g2p"][[10, ch + 1]], size=case["size"][[10, ch + 1]], images=None)
+        o = mosaic_oracle(both["g2p"], both["size"], case["x0"], case["y0"], case["cell"], case["gx"], case["gy"])
+        assert (o["won"] > 0).all() and o["won"].sum() < (src >= 0).sum()         # frame 10 and the second chunk's frame share ground
+        assert got["won"][:ch].sum() == got["won"][10]
+    if name == "mixed_sizes_in_one_chunk":
+        assert (got["won"] > 0).all() and len({tuple(s) for s in case["size"].tolist()}) == 5
+    if name.startswith("grid_") and name != "grid_1x1":
+        assert want["stats"][1] > 0 and (want["won"] > 0).sum() >= 3
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["cull_tiny_frame", "cull_thin_between_rows", "cull_thin_on_one_row", "cull_yaw_45", "cover_all", "block_edges"])
+def test_gpu_aimed_at_the_cull(name):
+    case, want = _gpu_case(name)
+    got, _, _ = _run_and_check(case, want)
+    src = got["source"]
+    k = _kernel_constants()
+    bx, by = k["block_x"], k["block_y"]
+    if name == "cull_tiny_frame":
+        assert (src >= 0).sum() == 1 and src[40, 100] == 0
+    elif name == "cull_thin_between_rows":
+        assert (src == -1).all()
+    elif name == "cull_thin_on_one_row":
+        assert (src >= 0).sum() == 257 and (src[40] == 0).all()
+    elif name == "cull_yaw_45":
+        assert 0 < (src >= 0).sum() < 1200 and (got["won"] > 0).all()
+        blocks = {(j // by, i // bx) for j, i in zip(*np.nonzero(src >= 0))}
+        assert 2 <= len(blocks) < ((257 + bx - 1) // bx) * ((65 + by - 1) // by)
+    elif name == "cover_all":
+        assert (src >= 0).all() and (got["won"] > 0).all() and got["stats"].tolist() == [257 * 65, 0]
+    elif name == "block_edges":
+        want_src = np.full((65, 257), -1, dtype=np.int64)
+        want_src[by:2 * by, bx:2 * bx] = 0
+        want_src[0:by, 0:bx] = 1
+        want_src[by:2 * by, 2 * bx:4 * bx] = 2
+        corner = src[by - 1:by + 1, bx - 1:bx + 1]
+        want_src[by - 1:by + 1, bx - 1:bx + 1] = corner                            # decided by distance: the oracle's word
+        np.testing.assert_array_equal(src, want_src)
+        assert set(corner.ravel().tolist()) <= {0, 1, 3} and 3 in corner
+
+
+@pytest.mark.gpu
+def test_gpu_random_survey_invariants():
+    case, want = _gpu_case("random_survey")
+    got, _, plan = _run_and_check(case, want)
+    src = got["source"]
+    F, gx, gy = 40, case["gx"], case["gy"]
+    cov = torch.full((gy, gx), 0x7777, device=DEV, dtype=torch.int16)
+    cstats = torch.empty(16, device=DEV, dtype=torch.int64)
+    N.check(N.lib().wm_coverage_raster(N.ptr(plan["g"]), N.ptr(plan["s"]), F, case["x0"], case["y0"], case["cell"], gx, gy, N.ptr(cov), N.ptr(cstats),
+                                       N.stream_ptr(torch.device(DEV))))
+    cov = cov.cpu().numpy().view(np.uint16)
+    np.testing.assert_array_equal(src >= 0, cov > 0)
+    np.testing.assert_array_equal(got["won"], np.bincount(src[src >= 0], minlength=F))
+    assert got["stats"].tolist() == [int((src >= 0).sum()), int((src == -1).sum())]
+    assert got["stats"][1] > 0 and (cov >= 3).any() and (got["won"] > 0).sum() >= 30          # gaps, overlaps, many winners
+    assert (got["nearest"] != got["bilinear"]).any()
+
+
+@pytest.mark.gpu
+def test_gpu_fill_is_order_free():
+    case, want = _gpu_case("random_survey")
+    plan = _plan(case)
+    src = plan["source"]
+    sentinel = np.asarray(SENTINEL, dtype=np.uint8)
+    for mode in MODES:
+        pic, status = _sentinel_picture(case), torch.zeros(1, device=DEV, dtype=torch.int32)
+        done = np.zeros(src.shape, dtype=bool)
+        for f in range(39, -1, -1):                                               # one frame per call, descending
+            _fill(case, plan, mode, pic, status, [f])
+            done |= src == f
+            now = pic.cpu().numpy()                                               # after EVERY call
+            assert (now[~done] == sentinel).all(), f                             # every cell of a source not yet resident
+            np.testing.assert_array_equal(now[done], want[mode][done], err_msg=str(f))
+        assert status.item() == 0
+        np.testing.assert_array_equal(pic.cpu().numpy(), want[mode])
+
+
+@pytest.mark.gpu
+def test_gpu_bad_residency_is_reported_and_skipped():
+    case, want = _gpu_case("mixed_sizes_in_one_chunk")
+    plan = _plan(case)
+    src = plan["source"]
+    sentinel = np.asarray(SENTINEL, dtype=np.uint8)
+    F = case["g2p"].shape[0]
+    good = np.arange(F, dtype=np.int32)
+
+    def run(slot, images=None):
+        c = dict(case, images=images or case["images"])
+        pic, status = _sentinel_picture(case), torch.zeros(1, device=DEV, dtype=torch.int32)
+        _fill(c, plan, "bilinear", pic, status, list(range(F)), slot=slot)
+        return pic.cpu().numpy(), status.item()
+
+    # frame 2's slot points past the resident list
+    slot = good.copy()
+    slot[2] = F
+    pic, status = run(slot)
+    assert status == N.MOSAIC_BAD_SLOT
+    assert (pic[src == 2] == sentinel).all() and (src == 2).any()
+    np.testing.assert_array_equal(pic[src != 2], want["bilinear"][src != 2])
+    # frame 1's slot holds frame 3's descriptor (a smaller frame: its size is not size_dev[1]); frame 3 itself is fine
+    slot = good.copy()
+    slot[1] = 3
+    pic, status = run(slot)
+    assert status == N.MOSAIC_BAD_SIZE
+    assert (pic[src == 1] == sentinel).all() and (src == 1).any()
+    np.testing.assert_array_equal(pic[src != 1], want["bilinear"][src != 1])
+    # a resident frame one row short of what size_dev says
+    images = list(case["images"])
+    images[0] = images[0][:-1].copy()
+    pic, status = run(good, images)
+    assert status == N.MOSAIC_BAD_SIZE and (pic[src == 0] == sentinel).all()
+    # both at once; a negative slot is simply not resident
+    slot = good.copy()
+    slot[2], slot[1], slot[4] = F + 5, 3, -1
+    pic, status = run(slot)
+    assert status == N.MOSAIC_BAD_SLOT | N.MOSAIC_BAD_SIZE
+    assert (pic[(src == 1) | (src == 2) | (src == 4) | (src == -1)] == sentinel).all()
+    # a source raster that is not the plan's: a frame index past the survey, and a frame that does not see the cell
+    bogus = dict(plan, source_dev=plan["source_dev"].clone())
+    bogus["source_dev"][0, 0] = F
+    far = np.argwhere(src == -1)[0]
+    bogus["source_dev"][far[0], far[1]] = 0
+    pic2, st2 = _sentinel_picture(case), torch.zeros(1, device=DEV, dtype=torch.int32)
+    _fill(case, bogus, "nearest", pic2, st2, list(range(F)))
+    assert st2.item() == N.MOSAIC_BAD_SOURCE
+    pic2 = pic2.cpu().numpy()
+    assert (pic2[0, 0] == sentinel).all() and (pic2[far[0], far[1]] == sentinel).all()
+
+
+@pytest.mark.gpu
+def test_gpu_north_up_flips_the_picture_only():
+    case, want = _gpu_case("grid_70x19")
+    plan = _plan(case)
+    before = plan["source_dev"].clone()
+    resident = [f for f, im in enumerate(case["images"]) if im is not None]
+    for mode in MODES:
+        pic, status = _sentinel_picture(case), torch.zeros(1, device=DEV, dtype=torch.int32)
+        _fill(case, plan, mode, pic, status, resident, flags=N.MOSAIC_NORTH_UP)
+        assert status.item() == 0
+        np.testing.assert_array_equal(pic.cpu().numpy(), want[mode][::-1])
+        np.testing.assert_array_equal(pic.flip(0).cpu().numpy(), want[mode])
+    assert torch.equal(plan["source_dev"], before)
+    np.testing.assert_array_equal(before.cpu().numpy(), want["source"])
+
+
+def _python_case():
+    """Three overlapping yawed frames and a fourth off to the east, pixel -> ground georeferences."""
+    E0, N0 = 500000.0, 4000000.0
+    specs = [((E0 + 4.0, N0 + 3.0), 0.1, 10.0, 48, 64), ((E0 + 7.0, N0 + 3.5), 0.1, 40.0, 40, 56), ((E0 + 5.5, N0 + 5.0), 0.125, 200.0, 48, 64),
+             ((E0 + 16.0, N0 + 3.0), 0.1, 0.0, 24, 32)]
+    georef = np.stack([tiling.nadir_affine(H, W, c, gsd, yaw) for c, gsd, yaw, H, W in specs])
+    sizes = np.array([(H, W) for *_, H, W in specs], dtype=np.int32)
+    images = [_content(H, W, 50 + k) for k, (H, W) in enumerate(sizes.tolist())]
+    return georef, sizes, images
+
+
+PLAN_KEYS = {"source", "won", "origin", "cell", "shape", "gap_cells"}
+
+
+@pytest.mark.gpu
+def test_gpu_python_mosaic_end_to_end():
+    georef, sizes, images = _python_case()
+    cell, fill = 0.08, (9, 8, 250)
+    x0, y0, gx, gy = tiling.footprint_bounds(georef, sizes, cell)
+    g2p = tiling.ground_to_pixel(georef)
+    want = mosaic_oracle(g2p, sizes, x0, y0, cell, gx, gy, images, fill)
+    mixed = [images[0], torch.from_numpy(images[1]), torch.from_numpy(images[2]).to(DEV), images[3]]          # numpy, host, device
+    plan = tiling.mosaic_plan(georef, sizes, cell)
+    assert set(plan) == PLAN_KEYS and plan["source"].dtype == torch.int32 and plan["won"].dtype == torch.int64
+    np.testing.assert_array_equal(plan["source"].cpu().numpy(), want["source"])
+    np.testing.assert_array_equal(plan["won"].cpu().numpy(), want["won"])
+    assert plan["origin"] == (x0, y0) and plan["cell"] == cell and plan["shape"] == (gy, gx)
+    assert plan["gap_cells"] == int(want["stats"][1]) > 0 and isinstance(plan["gap_cells"], int)
+    for sample in MODES:
+        out = tiling.mosaic(mixed, georef, cell, sample=sample, fill=fill)                                      # sizes from the shapes
+        assert set(out) == PLAN_KEYS | {"mosaic", "north_up"} and out["north_up"] is True
+        assert out["mosaic"].dtype == torch.uint8 and out["mosaic"].is_cuda and tuple(out["mosaic"].shape) == (gy, gx, 3)
+        np.testing.assert_array_equal(out["mosaic"].cpu().numpy(), want[sample][::-1])
+        np.testing.assert_array_equal(out["source"].cpu().numpy(), want["source"])                             # never flipped
+        south = tiling.mosaic(mixed, georef, cell, sizes=sizes, sample=sample, fill=fill, north_up=False, chunk=1)
+        np.testing.assert_array_equal(south["mosaic"].cpu().numpy(), want[sample])
+        assert south["north_up"] is False
+    gaps = want["source"] == -1
+    assert (out["mosaic"].flip(0).cpu().numpy()[gaps] == np.asarray(fill, dtype=np.uint8)).all() and gaps.any()
+    assert tiling.mosaic(mixed, georef, cell)["mosaic"].cpu().numpy()[::-1][gaps].max() == 0                   # the default fill is black
+
+    # a lazy sequence over a corner of the survey: frame 3 (off to the east) wins nothing there and is never asked for
+    bounds = (x0, y0, 150, gy)
+    want_b = mosaic_oracle(g2p, sizes, x0, y0, cell, 150, gy, images, fill)
+    assert want_b["won"][3] == 0 and (want_b["won"][:3] > 0).all() and want["won"][3] > 0
+    for chunk in (1, 2, 8):
+        lazy = _Lazy(mixed)
+        out = tiling.mosaic(lazy, georef, cell, sizes=sizes, bounds=bounds, fill=fill, chunk=chunk)
+        assert lazy.asked == [0, 1, 2], chunk
+        np.testing.assert_array_equal(out["mosaic"].cpu().numpy(), want_b["bilinear"][::-1])
+        assert out["shape"] == (gy, 150) and out["gap_cells"] == int(want_b["stats"][1])
+    # a frame whose shape is not what sizes says is named, before its chunk is launched
+    wrong = list(mixed)
+    wrong[1] = images[1][:, :-1].copy()
+    with pytest.raises(ValueError, match="frame 1 is"):
+        tiling.mosaic(_Lazy(wrong), georef, cell, sizes=sizes, fill=fill)
+    wrong[1] = images[1].astype(np.float32)
+    with pytest.raises(RuntimeError, match="^mosaic: frame 1: expected"):
+        tiling.mosaic(_Lazy(wrong), georef, cell, sizes=sizes, fill=fill)
+    # no frames at all: a 1 x 1 grid of the fill colour
+    out = tiling.mosaic([], np.zeros((0, 2, 3)), 1.0, fill=fill)
+    assert out["shape"] == (1, 1) and out["mosaic"].cpu().tolist() == [[list(fill)]] and out["gap_cells"] == 1 and tuple(out["won"].shape) == (0,)
+
+
+@pytest.mark.gpu
+def test_gpu_python_mosaic_markers():
+    georef, sizes, images = _python_case()
+    cell = 0.08
+    x0, y0, gx, gy = tiling.footprint_bounds(georef, sizes, cell)
+    pts = np.array([[x0 + 5.0, y0 + 3.0], [x0 + 0.04, y0 + 0.04], [NAN, y0 + 1.0], [x0 - 0.5, y0 + 1.0], [x0 + 2.0, y0 + gy * cell + 0.01],
+                    [x0 + 8.26, y0 + 4.1], [x0 + 3.0, INF], [x0 + gx * cell - 0.01, y0 + gy * cell - 0.01]])
+    labels = np.array([0, 3, 1, 1, 2, 6, 2, 99])                                 # 99: outside the palette, draws nothing
+    cen = {"points": torch.from_numpy(pts).to(DEV), "labels": torch.from_numpy(labels).to(DEV)}
+    plain = tiling.mosaic(images, georef, cell)
+    for north_up in (True, False):
+        out = tiling.mosaic(images, georef, cell, north_up=north_up, census=cen, marker=9, width=2)
+        assert set(out) == PLAN_KEYS | {"mosaic", "north_up", "marker_boxes", "marker_index"}
+        assert out["marker_index"].cpu().tolist() == [0, 1, 5, 7]                   # finite and inside the grid
+        boxes = out["marker_boxes"]
+        assert boxes.dtype == torch.float32 and tuple(boxes.shape) == (4, 4) and boxes.is_cuda
+        cx, cy = (pts[[0, 1, 5, 7], 0] - x0) / cell, (pts[[0, 1, 5, 7], 1] - y0) / cell
+        cy = gy - cy if north_up else cy
+        np.testing.assert_array_equal(boxes.cpu().numpy(), np.stack([cx - 4.5, cy - 4.5, cx + 4.5, cy + 4.5], axis=1).astype(np.float32))
+        base = tiling.mosaic(images, georef, cell, north_up=north_up)["mosaic"]
+        drawn = tiling.draw_boxes(base.clone(), boxes, cen["labels"][out["marker_index"]], width=2)
+        assert torch.equal(out["mosaic"], drawn)
+        changed = (out["mosaic"] != base).any(dim=2)
+        assert 0 < int(changed.sum()) <= 3 * (100 - 36)                           # three outlines at most 10 x 10 with a 6 x 6 hole; the fourth has no colour
+    assert torch.equal(plain["mosaic"], tiling.mosaic(images, georef, cell)["mosaic"])
+    # a census without individuals in the grid draws nothing
+    none = {"points": cen["points"][[2, 3, 6]], "labels": cen["labels"][[2, 3, 6]]}
+    out = tiling.mosaic(images, georef, cell, census=none, marker=3)
+    assert tuple(out["marker_boxes"].shape) == (0, 4) and torch.equal(out["mosaic"], plain["mosaic"])

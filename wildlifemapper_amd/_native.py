@@ -22,6 +22,8 @@ FLAG_CONF, FLAG_SCORE, FLAG_NMS, FLAG_MERGED = 1, 2, 4, 8
 CRITERION_MAX_TARGETS, CRITERION_SUMS, CRITERION_NONFINITE, CRITERION_UNSOLVED = 2048, 8, 1, 2
 CENSUS_MAX_DETS, CENSUS_SAME_CLASS, CENSUS_UNSOLVED = 262144, 1, 1
 COVERAGE_MAX_SIDE, COVERAGE_MAX_CELLS, COVERAGE_MAX_FRAMES, COVERAGE_CLASSES, COVERAGE_STATS = 16384, 1 << 26, 65535, 7, 16
+MOSAIC_NEAREST, MOSAIC_BILINEAR, MOSAIC_NORTH_UP = 0, 1, 1
+MOSAIC_BAD_SLOT, MOSAIC_BAD_SIZE, MOSAIC_BAD_SOURCE = 1, 2, 4          # wm_mosaic_fill_u8's status bits
 CFG_FUSE_LN = 1
 CFG_FOLD_LN = 2
 CFG_FOLD_LN_BF16 = 4
@@ -69,6 +71,8 @@ SYMBOLS = {
     "wm_census": (_I, [_P, _P, _P, _P, _I, _P, _I, C.c_double, _I, _P, _L, _P, _P, _P, _P, _P, _P]),
     "wm_coverage_raster": (_I, [_P, _P, _I, C.c_double, C.c_double, C.c_double, _I, _I, _P, _P, _P]),
     "wm_coverage_points": (_I, [_P, _P, _I, _P, _P, _I, C.c_double, C.c_double, C.c_double, _I, _I, _P, _P, _P, _P, _P]),
+    "wm_mosaic_plan": (_I, [_P, _P, _I, C.c_double, C.c_double, C.c_double, _I, _I, _P, _P, _P, _P]),
+    "wm_mosaic_fill_u8": (_I, [_P, _I, _P, _P, _P, _I, C.c_double, C.c_double, C.c_double, _I, _I, _P, _I, _I, _P, _P, _P]),
     "wm_resample_u8": (_I, [_P, _I, _I, _P, _I, _I, _P]),
     "wm_scaled_size": (_I, [_I, _I, C.c_double, C.POINTER(_I), C.POINTER(_I)]),
     "wm_chip_window": (_I, [C.POINTER(_F), _F, _I, _I, C.POINTER(C.c_int32)]),

@@ -76,8 +76,9 @@ __device__ __forceinline__ bool cov_row_may_touch(double c0, double c1, double c
 }
 
 // Stages the frames of a chunk (one per thread: b, h, w) that pass `keep` into s, compacted by a wave ballot; returns
-// their number.  All threads call it; it syncs before its writes' slots are known and after the writes.
-__device__ __forceinline__ int cov_stage(CovFrames& s, int* s_wave, bool keep, const double (&b)[6], int h, int w) {
+// their number.  All threads call it; it syncs before its writes' slots are known and after the writes.  slot_out, when given,
+// receives the slot of a kept frame (-1 otherwise), for a caller that stages more per frame (mosaic_kernels.h: its index).
+__device__ __forceinline__ int cov_stage(CovFrames& s, int* s_wave, bool keep, const double (&b)[6], int h, int w, int* slot_out = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned long long mask = __ballot(keep);
     if (lane == 0) s_wave[wave] = __popcll(mask);
@@ -89,12 +90,14 @@ __device__ __forceinline__ int cov_stage(CovFrames& s, int* s_wave, bool keep, c
         off += k < wave ? c : 0;
         total += c;
     }
+    if (slot_out) *slot_out = -1;
     if (keep) {
         const int slot = off + __popcll(mask & ((1ull << lane) - 1ull));
 #pragma unroll
         for (int k = 0; k < 6; ++k) s.b[k][slot] = b[k];
         s.h[slot] = h;
         s.w[slot] = w;
+        if (slot_out) *slot_out = slot;
     }
     __syncthreads();
     return total;

@@ -1,11 +1,12 @@
 // Image front end: the val-transform resize (plan cache per device), the survey resampler (plan slots per stream), the
-// survey merge launcher, the census launcher, the coverage launchers, the review-chip launcher and the overlay launchers (box outlines, the reference's plot image).
+// survey merge launcher, the census launcher, the coverage launchers, the mosaic launchers, the review-chip launcher and the overlay launchers (box outlines, the reference's plot image).
 #pragma once
 #include "misc_kernels.h"
 #include "resample_kernels.h"
 #include "survey_kernels.h"
 #include "census_kernels.h"
 #include "coverage_kernels.h"
+#include "mosaic_kernels.h"
 #include "chip_kernels.h"
 #include "overlay_kernels.h"
 #include "host_core.h"
@@ -131,6 +132,55 @@ int launch_coverage_points(const double* g2p_dev, const int32_t* size_dev, int n
     hipLaunchKernelGGL(coverage_points_kernel, dim3((n_points + COV_THREADS - 1) / COV_THREADS), dim3(COV_THREADS), 0, s, g2p_dev,
                        (const int*)size_dev, n_frames, points_dev, (const int*)labels_dev, n_points, x0, y0, cell, gx, gy, (int*)seen_by_dev,
                        (int*)cell_dev, (int*)counts_dev, (unsigned long long*)pstats_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Survey mosaic: the coverage's grid and frame checks, every argument checked on the host before the first HIP call.
+int launch_mosaic_plan(const double* g2p_dev, const int32_t* size_dev, int n_frames, double x0, double y0, double cell, int gx, int gy,
+                       int32_t* source_dev, int32_t* won_dev, int64_t* stats_dev, hipStream_t s) {
+    const char* name = "wm_mosaic_plan";
+    WM_TRY(check_coverage_frames(name, g2p_dev, size_dev, n_frames));
+    WM_TRY(check_coverage_grid(name, x0, y0, cell, gx, gy));
+    if (!source_dev) return fail("%s: null source_dev", name);
+    if (!stats_dev) return fail("%s: null stats_dev", name);
+    if (n_frames > 0 && !won_dev) return fail("%s: null won_dev with n_frames %d", name, n_frames);
+    if ((uintptr_t)source_dev % 4 || (uintptr_t)won_dev % 4 || (uintptr_t)stats_dev % 8)
+        return fail("%s: source_dev / won_dev not 4-byte aligned, or stats_dev not 8-byte aligned", name);
+    HIP_TRY(hipMemsetAsync(stats_dev, 0, 2 * sizeof(int64_t), s));
+    if (n_frames > 0) HIP_TRY(hipMemsetAsync(won_dev, 0, (size_t)n_frames * sizeof(int32_t), s));
+    const dim3 grid((gx + COV_BLOCK_X - 1) / COV_BLOCK_X, (gy + COV_BLOCK_Y - 1) / COV_BLOCK_Y);
+    hipLaunchKernelGGL(mosaic_plan_kernel, grid, dim3(COV_THREADS), 0, s, g2p_dev, (const int*)size_dev, n_frames, x0, y0, cell, gx, gy,
+                       (int*)source_dev, (int*)won_dev, (unsigned long long*)stats_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_mosaic_fill(const wm_frame_desc* frames_dev, int n_resident, const int32_t* slot_dev, const double* g2p_dev,
+                       const int32_t* size_dev, int n_frames, double x0, double y0, double cell, int gx, int gy, const int32_t* source_dev,
+                       int mode, int flags, uint8_t* mosaic_dev, int32_t* status_dev, hipStream_t s) {
+    const char* name = "wm_mosaic_fill_u8";
+    WM_TRY(check_coverage_frames(name, g2p_dev, size_dev, n_frames));
+    if (n_resident < 0 || n_resident > WM_COVERAGE_MAX_FRAMES)
+        return fail("%s: n_resident %d outside 0..%d", name, n_resident, WM_COVERAGE_MAX_FRAMES);
+    WM_TRY(check_coverage_grid(name, x0, y0, cell, gx, gy));
+    if (mode != WM_MOSAIC_NEAREST && mode != WM_MOSAIC_BILINEAR) return fail("%s: mode %d is neither WM_MOSAIC_NEAREST nor WM_MOSAIC_BILINEAR", name, mode);
+    if (flags & ~WM_MOSAIC_NORTH_UP) return fail("%s: flags 0x%x", name, (unsigned)flags);
+    if (!source_dev) return fail("%s: null source_dev", name);
+    if (!mosaic_dev) return fail("%s: null mosaic_dev", name);
+    if (!status_dev) return fail("%s: null status_dev", name);
+    if (n_frames > 0 && n_resident > 0 && !frames_dev) return fail("%s: null frames_dev with n_resident %d", name, n_resident);
+    if (n_frames > 0 && n_resident > 0 && !slot_dev) return fail("%s: null slot_dev with n_frames %d", name, n_frames);
+    if ((uintptr_t)frames_dev % 8 || (uintptr_t)slot_dev % 4 || (uintptr_t)source_dev % 4 || (uintptr_t)status_dev % 4)
+        return fail("%s: frames_dev not 8-byte aligned, or slot_dev / source_dev / status_dev not 4-byte aligned", name);
+    if (n_frames == 0 || n_resident == 0) return 0;                   // no source can be resident: nothing is written
+    const dim3 grid((gx + COV_BLOCK_X - 1) / COV_BLOCK_X, (gy + MOS_FILL_BLOCK_Y - 1) / MOS_FILL_BLOCK_Y);
+    const int north_up = flags & WM_MOSAIC_NORTH_UP;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(COV_THREADS), 0, s, (const frame_desc*)frames_dev, n_resident, (const int*)slot_dev, g2p_dev,
+                           (const int*)size_dev, n_frames, x0, y0, cell, gx, gy, (const int*)source_dev, north_up, mosaic_dev, (int*)status_dev);
+    };
+    mode == WM_MOSAIC_NEAREST ? launch(mosaic_fill_kernel<WM_MOSAIC_NEAREST>) : launch(mosaic_fill_kernel<WM_MOSAIC_BILINEAR>);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -240,6 +240,18 @@ extern "C" int wm_coverage_points(const double* g2p_dev, const int32_t* size_dev
                                   cell_dev, counts_dev, pstats_dev, (hipStream_t)stream);
 }
 
+extern "C" int wm_mosaic_plan(const double* g2p_dev, const int32_t* size_dev, int n_frames, double x0, double y0, double cell, int gx, int gy,
+                              int32_t* source_dev, int32_t* won_dev, int64_t* stats_dev, void* stream) {
+    return launch_mosaic_plan(g2p_dev, size_dev, n_frames, x0, y0, cell, gx, gy, source_dev, won_dev, stats_dev, (hipStream_t)stream);
+}
+
+extern "C" int wm_mosaic_fill_u8(const wm_frame_desc* frames_dev, int n_resident, const int32_t* slot_dev, const double* g2p_dev,
+                                 const int32_t* size_dev, int n_frames, double x0, double y0, double cell, int gx, int gy,
+                                 const int32_t* source_dev, int mode, int flags, uint8_t* mosaic_dev, int32_t* status_dev, void* stream) {
+    return launch_mosaic_fill(frames_dev, n_resident, slot_dev, g2p_dev, size_dev, n_frames, x0, y0, cell, gx, gy, source_dev, mode, flags,
+                              mosaic_dev, status_dev, (hipStream_t)stream);
+}
+
 extern "C" int wm_crop_chips_u8(const wm_frame_desc* frames_dev, int n_frames, const float* boxes_dev, const int32_t* box_frame_dev, int n,
                                 int chip, float context, int min_side, int max_side, uint8_t* chips_dev, int32_t* windows_dev,
                                 void* stream) {

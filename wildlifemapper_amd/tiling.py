@@ -32,6 +32,10 @@ match: the checker is oracle/tiling_oracle.py, a numpy restatement of exactly wh
     cell with the number of frames that saw its centre (the union of the footprints, its gaps), the census' individuals
     per cell and class, and per individual the number of frames that could have seen it (coverage rule:
     include/wm_hip.h), by wm_coverage_raster and wm_coverage_points.
+  * mosaic, mosaic_plan, resampled_georef: the map -- the frames laid onto the coverage's ground grid; every cell takes its
+    pixel from the one frame that saw it most vertically (seam rule and sampling: include/wm_hip.h), chosen for all cells
+    by one wm_mosaic_plan launch and fetched by wm_mosaic_fill_u8, a chunk of resident frames per launch, so only the
+    frames that won a cell are ever loaded; the census' individuals can be outlined on it.
 Frame coordinates are fp32: a box coordinate keeps a fractional resolution below 0.01 px up to 65536 px (ulp 2**-8).
 """
 from __future__ import annotations
@@ -433,20 +437,20 @@ class _Frame:
         self.scale_xy = scale_xy              # resampled mode: (sx, sy) = float32(W / ow), float32(H / oh); else None
 
 
-def _as_frame_array(frame, i: int, device: torch.device):
+def _as_frame_array(frame, i: int, device: torch.device, who: str = "detect_frames"):
     """Validate one survey frame as frame_to_tiles does: (H,W,3) uint8.  Returns (device tensor or None, host tensor or None)."""
     if isinstance(frame, np.ndarray):
         frame = torch.from_numpy(frame)
     if not isinstance(frame, torch.Tensor) or frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[-1] != 3 \
             or frame.shape[0] <= 0 or frame.shape[1] <= 0:
         what = f"{tuple(frame.shape)} {frame.dtype} on {frame.device}" if isinstance(frame, torch.Tensor) else type(frame).__name__
-        raise RuntimeError(f"detect_frames: frame {i}: expected an (H,W,3) uint8 tensor or array, got {what}")
+        raise RuntimeError(f"{who}: frame {i}: expected an (H,W,3) uint8 tensor or array, got {what}")
     if frame.is_cuda:
         if frame.device != device:
-            raise RuntimeError(f"detect_frames: frame {i} is on {frame.device}, the survey runs on {device}")
+            raise RuntimeError(f"{who}: frame {i} is on {frame.device}, the survey runs on {device}")
         return frame.contiguous(), None
     if frame.device.type != "cpu":
-        raise RuntimeError(f"detect_frames: frame {i} is on {frame.device}")
+        raise RuntimeError(f"{who}: frame {i} is on {frame.device}")
     return None, frame.contiguous()
 
 
@@ -950,6 +954,25 @@ def footprint_bounds(georef, sizes, cell):
     return float(x0), float(y0), gx, gy
 
 
+def _survey_grid(georef, sizes, cell, bounds, what: str):
+    """The frames and the grid of coverage() and mosaic(), validated before any device work: (g (F,2,3) float64, s (F,2) int32,
+    cell, x0, y0, gx, gy); bounds None means footprint_bounds(georef, sizes, cell)."""
+    cell = _check_cell(cell, what)
+    g = _check_georef(georef, what)
+    s = _check_sizes(sizes, g.shape[0], what)
+    if g.shape[0] > COVERAGE_MAX_FRAMES:
+        raise ValueError(f"{what}: {g.shape[0]} frames exceed {COVERAGE_MAX_FRAMES}")
+    if bounds is None:
+        x0, y0, gx, gy = footprint_bounds(g, s, cell)
+    else:
+        try:
+            bx0, by0, bgx, bgy = bounds
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: bounds {bounds!r}: expected (x0, y0, gx, gy)") from None
+        x0, y0, gx, gy = _check_grid(bx0, by0, bgx, bgy, cell, what)
+    return g, s, cell, x0, y0, gx, gy
+
+
 def coverage(georef, sizes, cell, census=None, bounds=None) -> Dict[str, object]:
     """The ground a survey saw (wm_coverage_raster, wm_coverage_points; rule: include/wm_hip.h).  georef (F,2,3) float64 as
     for census() (pixel -> ground; inverted on the host by ground_to_pixel), sizes (F,2) (height, width) of the frames in
@@ -976,20 +999,8 @@ def coverage(georef, sizes, cell, census=None, bounds=None) -> Dict[str, object]
           frame's edge a member can lie in a frame whose footprint misses the keeper's point: a ratio slightly above 1
           is possible and is not clamped."""
     what = "coverage"
-    cell = _check_cell(cell, what)
-    g = _check_georef(georef, what)
-    s = _check_sizes(sizes, g.shape[0], what)
+    g, s, cell, x0, y0, gx, gy = _survey_grid(georef, sizes, cell, bounds, what)
     F = g.shape[0]
-    if F > COVERAGE_MAX_FRAMES:
-        raise ValueError(f"{what}: {F} frames exceed {COVERAGE_MAX_FRAMES}")
-    if bounds is None:
-        x0, y0, gx, gy = footprint_bounds(g, s, cell)
-    else:
-        try:
-            bx0, by0, bgx, bgy = bounds
-        except (TypeError, ValueError):
-            raise ValueError(f"{what}: bounds {bounds!r}: expected (x0, y0, gx, gy)") from None
-        x0, y0, gx, gy = _check_grid(bx0, by0, bgx, bgy, cell, what)
     pts = labels = members = None
     if census is not None:
         try:
@@ -1047,4 +1058,209 @@ def coverage(georef, sizes, cell, census=None, bounds=None) -> Dict[str, object]
     out.update({"seen_by": seen, "cell_index": cidx.to(torch.int64), "counts": counts, "class_counts": class_counts,
                 "density_per_km2": torch.from_numpy(density).to(dev),
                 "detection_rate": n_members / n_seen if n_seen > 0 else float("nan")})
+    return out
+
+
+# ---- mosaic ----------------------------------------------------------------------------------------------------------
+
+MOSAIC_SAMPLES = {"nearest": N.MOSAIC_NEAREST, "bilinear": N.MOSAIC_BILINEAR}
+
+
+def _check_whole(value, what: str, name: str, lo: int = 1) -> int:
+    """A whole number >= lo (an int, or a float without a fraction), before any device work."""
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or not math.isfinite(value) \
+            or value != int(value) or int(value) < lo:
+        raise ValueError(f"{what}: {name} {value!r} must be a whole number >= {lo}")
+    return int(value)
+
+
+def _mosaic_device(what: str, dev=None) -> torch.device:
+    if dev is not None:
+        return dev
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{what}: no GPU is present; the HIP path needs a ROCm device tensor "
+                           "(there is no CPU fallback in wildlifemapper_amd)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _mosaic_plan(g, s, cell, x0, y0, gx, gy, dev):
+    """wm_mosaic_plan on validated arguments.  Returns the plan's dict and the device copies of g2p and sizes."""
+    F = g.shape[0]
+    b = ground_to_pixel(g)
+    with torch.cuda.device(dev):
+        g_d = s_d = won = None                                # no frames: nothing to upload, an all -1 raster
+        if F:
+            g_d = torch.from_numpy(np.ascontiguousarray(b.reshape(-1, 6))).pin_memory().to(dev, non_blocking=True)
+            s_d = torch.from_numpy(s).pin_memory().to(dev, non_blocking=True)
+            won = torch.empty(F, device=dev, dtype=torch.int32)
+        source = torch.empty((gy, gx), device=dev, dtype=torch.int32)
+        stats = torch.empty(2, device=dev, dtype=torch.int64)
+        N.check(N.lib().wm_mosaic_plan(N.ptr(g_d), N.ptr(s_d), F, x0, y0, cell, gx, gy, N.ptr(source), N.ptr(won), N.ptr(stats),
+                                       N.stream_ptr(dev)))
+        gap = int(stats[1].item())
+    won = won.to(torch.int64) if F else torch.zeros(0, device=dev, dtype=torch.int64)
+    return {"source": source, "won": won, "origin": (x0, y0), "cell": cell, "shape": (gy, gx), "gap_cells": gap}, g_d, s_d
+
+
+def mosaic_plan(georef, sizes, cell, bounds=None) -> Dict[str, object]:
+    """Which frame shows each ground cell (wm_mosaic_plan; rule: include/wm_hip.h "Survey mosaic").  Geometry only, no
+    pixels: georef (F,2,3) float64 as for census() (pixel -> ground), sizes (F,2) (height, width), cell metres, bounds
+    (x0, y0, gx, gy) or None for footprint_bounds(georef, sizes, cell) -- the arguments and the validation of coverage(),
+    run before any device work.  Among the frames that see a cell's centre the source is the one whose centre pixel is
+    nearest to it (the most vertical view), ties to the lowest index.  One launch on the current device's current stream
+    and one small copy of the statistics, which waits for it.  No CPU fallback.  Returns
+      'source' (gy,gx) int32 on the device: the frame of each cell, -1 where no frame saw it; row 0 is the SOUTHERNMOST;
+      'won' (F,) int64 on the device: the cells each frame is the source of;
+      'origin' (x0, y0), 'cell', 'shape' (gy, gx); 'gap_cells' int, the cells without a source."""
+    what = "mosaic_plan"
+    g, s, cell, x0, y0, gx, gy = _survey_grid(georef, sizes, cell, bounds, what)
+    return _mosaic_plan(g, s, cell, x0, y0, gx, gy, _mosaic_device(what))[0]
+
+
+def resampled_georef(georef, size, new_size) -> np.ndarray:
+    """The georeference of a frame after resampling: georef (2,3) or (F,2,3) float64 (pixel -> ground) of frames of `size`
+    (height, width) gives that of the same frames resampled to `new_size` (H', W') -- a pixel of the new frame spans W / W'
+    old pixels across and H / H' down, and pixel (0, 0)'s corner stays where it was: a0' = a0 * (W / W'), a3' = a3 *
+    (W / W'), a1' = a1 * (H / H'), a4' = a4 * (H / H'), a2 and a5 unchanged.  size and new_size are one (height, width)
+    pair for all frames or (F,2), one pair per frame.  Host only, in double.  With preprocess.resample_u8 this is the
+    route to a map coarser than the frames: mosaic() point-samples, so shrink the frames to about the cell size first."""
+    what = "resampled_georef"
+    g = georef.detach().cpu().numpy() if isinstance(georef, torch.Tensor) else georef
+    try:
+        g = np.asarray(g, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: georef is not an array of numbers") from None
+    single = g.ndim == 2
+    g = _check_georef(g[None] if single else g, what)
+    F = g.shape[0]
+
+    def pairs(v, name):
+        try:
+            a = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
+            if a.dtype.kind not in "iuf" or a.shape not in ((2,), (F, 2)) or not np.all(np.isfinite(a)) or not np.all(a == np.floor(a)) \
+                    or not np.all(a >= 1):
+                raise TypeError
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: {name} {v!r}: expected (height, width) or ({F}, 2), whole numbers >= 1") from None
+        return np.broadcast_to(a.astype(np.float64), (F, 2))
+
+    old, new = pairs(size, "size"), pairs(new_size, "new_size")
+    sy, sx = old[:, 0] / new[:, 0], old[:, 1] / new[:, 1]
+    out = g.copy()
+    out[:, 0, 0], out[:, 1, 0] = g[:, 0, 0] * sx, g[:, 1, 0] * sx
+    out[:, 0, 1], out[:, 1, 1] = g[:, 0, 1] * sy, g[:, 1, 1] * sy
+    return out[0] if single else out
+
+
+def mosaic(frames, georef, cell, sizes=None, bounds=None, sample: str = "bilinear", fill=(0, 0, 0), north_up: bool = True,
+           chunk: int = 8, census=None, marker=None, width: int = 2, palette=None) -> Dict[str, object]:
+    """The map of a survey: its frames laid onto the ground grid (wm_mosaic_plan, wm_mosaic_fill_u8; rule: include/wm_hip.h
+    "Survey mosaic").  frames: a sequence that is only indexed (frames[i], len) -- a list of (H,W,3) uint8 ROCm tensors,
+    CPU tensors or numpy arrays as detect_frames accepts them, or a lazy sequence that loads frame i from disk when it is
+    asked for; georef (F,2,3) float64 as for census(), cell metres, bounds as for coverage().  sizes (F,2) (height, width)
+    may be None only when every item of `frames` is already a tensor or an array (a list or tuple, whose shapes cost
+    nothing); a lazy sequence needs it.  Everything is validated before any device work.
+    The plan runs first (mosaic_plan).  Only frames that are the source of at least one cell are ever indexed, each
+    exactly once, in ascending order, `chunk` at a time: host frames go up through pinned memory, one fill launch per
+    chunk, and the chunk's frames are released after it -- a lazy sequence pays for the winners only, and bounds= over a
+    corner of a survey touches a handful of frames.  A frame whose shape disagrees with sizes raises ValueError naming
+    it, before its chunk is launched.
+    sample: 'bilinear' (pixel centres at integer + 0.5, edge replicate) or 'nearest'.  A cell finer than the ground
+    sampling distance magnifies; a coarser one point-samples and aliases: for a coarse map shrink the frames first
+    (preprocess.resample_u8, PIL-exact) and rescale their georeferences (resampled_georef).  fill: the (r, g, b) of the
+    cells no frame saw.  north_up: the picture's row 0 is the NORTHERNMOST (what a viewer expects); False keeps row 0
+    south, as 'source' and coverage() always have it.
+    census= (the dict census() returned) with marker= (the side of a square in cells, a whole number >= 1): every
+    individual whose keeper point is finite and inside the grid is outlined in its class colour by one draw_boxes launch
+    on the finished mosaic (width, palette as for draw_boxes); the square is centred on ((X - x0) / cell, (Y - y0) / cell),
+    the y mirrored (gy - y) when north_up.
+    Runs on the current device's current stream (with census=, on its tensors' device).  No CPU fallback.  Returns the
+    plan's dict ('source', 'won', 'origin', 'cell', 'shape', 'gap_cells') plus 'mosaic' (gy,gx,3) uint8 on the device and
+    'north_up'; with markers also 'marker_boxes' (k',4) fp32 xyxy in picture pixels and 'marker_index' (k',) int64, the
+    individuals they belong to."""
+    what = "mosaic"
+    if not isinstance(sample, str) or sample not in MOSAIC_SAMPLES:
+        raise ValueError(f"{what}: sample {sample!r} must be 'bilinear' or 'nearest'")
+    try:
+        fill_a = np.asarray(fill)
+        if fill_a.shape != (3,) or fill_a.dtype.kind not in "iuf" or not np.all((fill_a >= 0) & (fill_a <= 255) & (fill_a == np.floor(fill_a))):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: fill {fill!r} must be three whole numbers in 0..255") from None
+    fill_a = fill_a.astype(np.uint8)
+    chunk = _check_whole(chunk, what, "chunk")
+    if (census is None) != (marker is None):
+        raise ValueError(f"{what}: marker {marker!r} and census go together: pass both (census= the dict census() returned) or neither")
+    pts = labels = None
+    if census is not None:
+        marker = _check_whole(marker, what, "marker")
+        width = _check_draw_width(width, what)
+        palette = _check_palette(palette, what)
+        try:
+            pts, labels = census["points"], census["labels"]
+        except (TypeError, KeyError):
+            raise ValueError(f"{what}: census has no 'points' and 'labels': pass the dict census() returned") from None
+        if not all(isinstance(t, torch.Tensor) for t in (pts, labels)) or pts.dim() != 2 or pts.shape[1] != 2 or \
+                pts.dtype != torch.float64 or tuple(labels.shape) != (pts.shape[0],) or labels.device != pts.device:
+            raise ValueError(f"{what}: census: expected 'points' (k,2) float64 and 'labels' (k,) tensors on one device")
+    if not (hasattr(frames, "__getitem__") and hasattr(frames, "__len__")):
+        raise ValueError(f"{what}: frames must be a sequence that can be indexed (frames[i], len), got {type(frames).__name__}")
+    n_given = len(frames)
+    if sizes is None:
+        if not isinstance(frames, (list, tuple)) or not all(isinstance(fr, (torch.Tensor, np.ndarray)) for fr in frames):
+            raise ValueError(f"{what}: sizes is required when frames is not a list of tensors or arrays (a lazy sequence is only "
+                             "indexed for the frames that won a cell)")
+        if any(fr.ndim != 3 for fr in frames):
+            raise ValueError(f"{what}: frames: expected (H,W,3) uint8 tensors or arrays")
+        sizes = np.array([tuple(fr.shape[:2]) for fr in frames], dtype=np.int64).reshape(-1, 2)
+    g, s, cell, x0, y0, gx, gy = _survey_grid(georef, sizes, cell, bounds, what)
+    F = g.shape[0]
+    if n_given != F:
+        raise ValueError(f"{what}: {n_given} frames for {F} georeferences")
+    if pts is not None and not pts.is_cuda:
+        raise RuntimeError(f"{what}: census['points'] is on {pts.device}; the HIP path needs a ROCm device tensor "
+                           "(there is no CPU fallback in wildlifemapper_amd)")
+    dev = _mosaic_device(what, None if pts is None else pts.device)
+    out, g_d, s_d = _mosaic_plan(g, s, cell, x0, y0, gx, gy, dev)
+    lib = N.lib()
+    mode, flags = MOSAIC_SAMPLES[sample], N.MOSAIC_NORTH_UP if north_up else 0
+    with torch.cuda.device(dev):
+        picture = torch.from_numpy(fill_a).to(dev).expand(gy, gx, 3).contiguous()
+        status = torch.zeros(1, device=dev, dtype=torch.int32)
+        winners = torch.nonzero(out["won"] > 0).flatten().cpu().tolist()
+        for c0 in range(0, len(winners), chunk):
+            ids = winners[c0:c0 + chunk]
+            resident = []
+            for i in ids:
+                on_dev, on_host = _as_frame_array(frames[i], i, dev, what)
+                fr = on_dev if on_dev is not None else on_host.pin_memory().to(dev, non_blocking=True)
+                if tuple(fr.shape[:2]) != tuple(int(v) for v in s[i]):
+                    raise ValueError(f"{what}: frame {i} is {tuple(fr.shape[:2])}, sizes says {tuple(int(v) for v in s[i])}")
+                resident.append(fr)
+            slot = np.full(F, -1, dtype=np.int32)
+            slot[ids] = np.arange(len(ids), dtype=np.int32)
+            slot_d = torch.from_numpy(slot).pin_memory().to(dev, non_blocking=True)
+            desc = _frame_descs(resident, dev)
+            N.check(lib.wm_mosaic_fill_u8(N.ptr(desc), len(ids), N.ptr(slot_d), N.ptr(g_d), N.ptr(s_d), F, x0, y0, cell, gx, gy,
+                                          N.ptr(out["source"]), mode, flags, N.ptr(picture), N.ptr(status), N.stream_ptr(dev)))
+            del resident, desc, slot_d                        # the stream orders their reuse after the launch
+        bad = int(status.item()) if winners else 0
+        if bad:
+            raise RuntimeError(f"{what}: wm_mosaic_fill_u8 skipped cells (status {bad}): a resident frame did not match its slot or size")
+        out.update({"mosaic": picture, "north_up": bool(north_up)})
+        if pts is not None:
+            p = pts.detach().cpu().numpy()
+            with np.errstate(all="ignore"):
+                cx, cy = (p[:, 0] - x0) / cell, (p[:, 1] - y0) / cell
+                inside = np.isfinite(p).all(axis=1) & (np.floor(cx) >= 0) & (np.floor(cx) < gx) & (np.floor(cy) >= 0) & (np.floor(cy) < gy)
+            idx = np.nonzero(inside)[0]
+            cx, cy = cx[idx], cy[idx]
+            if north_up:
+                cy = gy - cy
+            half = marker / 2.0
+            boxes = np.stack([cx - half, cy - half, cx + half, cy + half], axis=1).astype(np.float32).reshape(-1, 4)
+            boxes_d = torch.from_numpy(boxes).to(dev)
+            idx_d = torch.from_numpy(idx.astype(np.int64)).to(dev)
+            draw_boxes(picture, boxes_d, labels[idx_d], width=width, palette=palette)
+            out.update({"marker_boxes": boxes_d, "marker_index": idx_d})
     return out
