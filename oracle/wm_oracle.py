@@ -41,17 +41,19 @@ def _ident(t: Tensor) -> Tensor:
     return t
 
 
+# The rounding helpers round through the narrow type and return the dtype they were given (fp32 in, fp32 out; float64 in,
+# float64 out: the encoder's float64 oracle with emulated operand rounding, tests/encoder_cases.py).
 def bf16_round(t: Tensor) -> Tensor:
-    return t.to(torch.bfloat16).to(torch.float32)
+    return t.to(torch.bfloat16).to(t.dtype)
 
 
 def fp16_round(t: Tensor) -> Tensor:
-    return t.clamp(-65504.0, 65504.0).to(torch.float16).to(torch.float32)
+    return t.clamp(-65504.0, 65504.0).to(torch.float16).to(t.dtype)
 
 
 def e4m3_round(t: Tensor) -> Tensor:
     """OCP e4m3fn, round to nearest even, saturating at +-448 (what v_cvt_pk_fp8_f32 behind a clamp does on gfx950)."""
-    return t.clamp(-448.0, 448.0).to(torch.float8_e4m3fn).to(torch.float32)
+    return t.clamp(-448.0, 448.0).to(torch.float8_e4m3fn).to(t.dtype)
 
 
 @dataclass
@@ -259,7 +261,7 @@ def attention_rel(x: Tensor, W: Dict[str, Tensor], pre: str, heads: int, cfg: Or
     Rh = arnd(rel_pos_table(S, W[pre + "rel_pos_h"]))
     Rw = arnd(rel_pos_table(S, W[pre + "rel_pos_w"]))
     scale = hd ** -0.5
-    out = torch.empty(Bp, heads, N, hd)
+    out = torch.empty(Bp, heads, N, hd, dtype=x.dtype)
     # head-at-a-time keeps the 4096x4096 global case inside memory
     for h in range(heads):
         qh, kh, vh = q[:, h], k[:, h], v[:, h]                                 # (B',N,hd)
