@@ -38,6 +38,9 @@ extern "C" {
  *    13, additive: wm_mosaic_plan, wm_mosaic_fill_u8, WM_MOSAIC_NEAREST, WM_MOSAIC_BILINEAR, WM_MOSAIC_NORTH_UP and the
  *    status bits WM_MOSAIC_BAD_SLOT, WM_MOSAIC_BAD_SIZE, WM_MOSAIC_BAD_SOURCE (survey mosaic: the frames laid onto the
  *    coverage's ground grid); the number stays 13 for the same reason.
+ *    13, additive: wm_register_render_u8, wm_register_search, wm_register_pair, WM_REGISTER_MAX_SIDE, WM_REGISTER_MAX_SEARCH,
+ *    WM_REGISTER_MAX_PAIRS and the status bits WM_REGISTER_BAD_SLOT, WM_REGISTER_BAD_SIZE, WM_REGISTER_BAD_PAIR (survey
+ *    registration: frame georeferences corrected by image matching); the number stays 13 for the same reason.
  * 12: wm_box_outline_rect, wm_draw_boxes_u8, wm_plot_image_u8, WM_DRAW_MAX_WIDTH, WM_DRAW_MAX_PALETTE, WM_PLOT_SCRATCH_BYTES
  *    (survey overlays: detections outlined on frames and tiles, on the GPU); nothing else changed.
  * 11: wm_chip_window, wm_crop_chips_u8, WM_CHIP_MAX_SIDE (survey review chips: one PIL-exact crop per detection, cut on
@@ -428,6 +431,69 @@ int wm_mosaic_fill_u8(const wm_frame_desc* frames_dev, int n_resident, const int
                       const double* g2p_dev, const int32_t* size_dev, int n_frames, double x0, double y0, double cell, int gx,
                       int gy, const int32_t* source_dev /* [gy][gx] */, int mode, int flags,
                       uint8_t* mosaic_dev /* [gy][gx][3] */, int32_t* status_dev /* [1] */, void* stream);
+
+/* Survey registration (tiling.register): census, coverage and mosaic take each frame's georeference on trust, and one built
+ * from GPS and heading is wrong by metres from frame to frame.  Frames overlap, so every pair of neighbours shows the same
+ * ground twice: each pair is rendered onto a common ground patch and the shift at which the two agree is found by an
+ * exhaustive integer search; one translation per frame is then solved on the host (tiling.adjust).  No reference behaviour
+ * exists; this rule is the contract, and tests/test_register.py restates it sequentially (register_oracle).  The frames
+ * (g2p_dev[n_frames][6] doubles b0..b5, ground -> pixel; size_dev[n_frames][2] int32, (height, width)), the predicate sees
+ * and the cell-centre expression are those of "Survey coverage", word for word; all double arithmetic is IEEE, every
+ * operation correctly rounded on its own (no contraction), in the order written.  Everything after the render is integer.
+ * Pairs: pairs_dev[n_pairs] of wm_register_pair, 32 bytes each, 8-byte aligned.  The patch of a pair is gx x gy cells of `cell`
+ * metres with south-west corner (x0, y0); 1 <= gx, gy <= side <= WM_REGISTER_MAX_SIDE; 0 <= search <=
+ * WM_REGISTER_MAX_SEARCH; 0 <= n_pairs <= WM_REGISTER_MAX_PAIRS.
+ * Render (wm_register_render_u8): plane A of pair p is a_dev[p][side][side] uint8, of frame_a; plane B is b_dev[p][E][E],
+ * E = side + 2 * search, of frame_b.  Cell (j, i) of A has centre Xc = x0 + ((double)i + 0.5) * cell, Yc = y0 + ((double)j +
+ * 0.5) * cell; cell (j, i) of B has centre Xc = x0 + ((double)(i - search) + 0.5) * cell, Yc likewise (the subtraction in
+ * int): B is the same grid grown by `search` cells on every side, and the centre of B cell (j + search, i + search) has the
+ * bits of A cell (j, i).  A cell's value is 0 if its frame does not see the centre; else, with
+ *     u = (b0 * Xc + b1 * Yc) + b2             v = (b3 * Xc + b4 * Yc) + b5
+ * and (R, G, B) the NEAREST pixel ((int)floor(v), (int)floor(u)) of the frame (HWC uint8), it is
+ *     max(1, (77 * R + 150 * G + 29 * B + 128) >> 8)
+ * -- integer luma; 0 is reserved for "not seen".  Cells of A with i >= gx or j >= gy, and of B with i >= gx + 2 * search or
+ * j >= gy + 2 * search, are written 0.  Residency is wm_mosaic_fill_u8's: frames_dev[n_resident] describes the frames on
+ * the device in this call, slot_dev[n_frames] int32 maps a survey frame to its index there, negative when it is not
+ * resident.  A plane is written, every byte of it, iff its frame is resident, and is otherwise left untouched, so the
+ * frames of a survey may come in any number of calls in any order.  Nothing is read out of range: a plane is SKIPPED, and
+ * a bit ORed into status_dev[0] (int32, which the caller zeroes before its first call and reads after its last), when the
+ * frame's slot is >= n_resident or its descriptor's data is NULL (WM_REGISTER_BAD_SLOT), when the descriptor's (height,
+ * width) differ from size_dev[f] (WM_REGISTER_BAD_SIZE), or -- both planes of the pair -- when frame_a or frame_b is outside
+ * [0, n_frames) or gx or gy outside [1, side] (WM_REGISTER_BAD_PAIR).
+ * Search (wm_register_search): for every pair and every offset (dy, dx) in [-search, search]^2,
+ *     n(dy, dx)   = the number of cells (j, i), j < gy, i < gx, with A[j][i] != 0 and B[j + search + dy][i + search + dx] != 0;
+ *     sad(dy, dx) = the sum of |A[j][i] - B[j + search + dy][i + search + dx]| over exactly those cells;
+ * score_dev[p][2 * search + 1][2 * search + 1][2] int32 holds (sad, n) at [dy + search][dx + search] (at most 254 * 512^2 =
+ * 66 584 576: nothing overflows).  Only gx and gy of a pair are read here; a pair with gx or gy outside [1, side] keeps an
+ * all-zero score.  Offset p BEATS q iff sad_p * n_q < sad_q * n_p in int64 -- the means compared without a division -- and
+ * at equality the smaller (dy * dy + dx * dx, dy, dx) wins, lexicographically.  best_dev[p][8] int32 = (dy, dx, sad, n,
+ * dy2, dx2, sad2, n2): the first four are the offset that beats all others among those with n >= min_cells (min_cells >=
+ * 1); the last four the same among the offsets with max(|dy - dy*|, |dx - dx*|) >= 2 of the first: the runner-up outside
+ * the peak's 3 x 3, the confidence measure.  Where there is no eligible offset the four are (0, 0, -1, 0).
+ * Meaning of the sign: a best (dx, dy) says B's content appears (dx, dy) * cell metres displaced relative to A's; with t_f
+ * the translation added to (a2, a5) of frame f's georeference, the measurement is t_b - t_a = -(dx, dy) * cell.
+ * Both entries: asynchronous on `stream`, nothing allocated; the search zeroes score_dev on `stream` and accumulates into
+ * it with int32 atomics (integers: the order is irrelevant); plain vector loads and stores.  Limits beside those above:
+ * 0 <= n_frames, n_resident <= WM_COVERAGE_MAX_FRAMES, cell finite and > 0; doubles, pairs and descriptors 8-byte, int32
+ * 4-byte aligned.  Bad arguments fail before any HIP call with a message that names the argument; n_pairs == 0 returns 0
+ * before looking at any pointer. */
+#define WM_REGISTER_MAX_SIDE 512
+#define WM_REGISTER_MAX_SEARCH 64
+#define WM_REGISTER_MAX_PAIRS 65535
+#define WM_REGISTER_BAD_SLOT 1          /* status bits */
+#define WM_REGISTER_BAD_SIZE 2
+#define WM_REGISTER_BAD_PAIR 4
+typedef struct wm_register_pair {
+    int32_t frame_a, frame_b, gx, gy;
+    double x0, y0;
+} wm_register_pair;
+int wm_register_render_u8(const wm_frame_desc* frames_dev, int n_resident, const int32_t* slot_dev /* [n_frames] */,
+                          const double* g2p_dev, const int32_t* size_dev, int n_frames, const wm_register_pair* pairs_dev,
+                          int n_pairs, double cell, int search, int side, uint8_t* a_dev /* [n_pairs][side][side] */,
+                          uint8_t* b_dev /* [n_pairs][E][E] */, int32_t* status_dev /* [1] */, void* stream);
+int wm_register_search(const uint8_t* a_dev, const uint8_t* b_dev, const wm_register_pair* pairs_dev, int n_pairs, int search,
+                       int side, int min_cells, int32_t* score_dev /* [n_pairs][2S+1][2S+1][2] */,
+                       int32_t* best_dev /* [n_pairs][8] */, void* stream);
 
 /* Survey resampling (tiling.detect_frames(scale=..., resize=...)): a frame brought to the scale the checkpoint was trained
  * at (the val transform's long side of 768, dataloader_coco.py:288) before it is tiled.

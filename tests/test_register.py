@@ -1,0 +1,837 @@
+"""Survey registration (include/wm_hip.h "Survey registration", tiling.register): every overlapping pair of frames rendered
+onto a common ground patch as two luma planes, and the integer shift at which they agree.  The rule has no reference
+behaviour; register_oracle below restates it sequentially -- render, search and pick, one pair and one offset at a time,
+numpy float64 for the cell centres and int64 for everything after them, the header's operation order -- and the device
+result must equal it exactly: every device comparison is assert_array_equal and there is no tolerance on the GPU side.
+The only bound in this file is adjust()'s 1e-9 m on consistent measurements (double rounding of such a system sits near
+1e-15; the bound is slack, not measured)."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from wildlifemapper_amd import _native as N
+from wildlifemapper_amd import tiling
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F64 = np.float64
+NAN = float("nan")
+INF = float("inf")
+POISON_A, POISON_B = 0xA5, 0x5A
+
+
+def luma(px):
+    """max(1, (77 R + 150 G + 29 B + 128) >> 8) of (..., 3) uint8 pixels, in int64."""
+    p = np.asarray(px).astype(np.int64)
+    return np.maximum(1, (77 * p[..., 0] + 150 * p[..., 1] + 29 * p[..., 2] + 128) >> 8)
+
+
+def render_plane(b6, hw, img, x0, y0, cell, nx, ny, s, ext):
+    """One plane of the rule, ext x ext uint8: cell (j, i) has centre x0 + ((i - s) + 0.5) * cell; cells with i >= nx + 2 s
+    or j >= ny + 2 s are 0; a cell its frame does not see is 0; else the luma of the nearest pixel."""
+    h, w = int(hw[0]), int(hw[1])
+    b = np.asarray(b6, dtype=F64).reshape(6)
+    x0, y0, cell = F64(x0), F64(y0), F64(cell)
+    idx = np.arange(ext, dtype=np.int64)
+    with np.errstate(all="ignore"):
+        Xc = (x0 + ((idx - s).astype(F64) + F64(0.5)) * cell)[None, :]
+        Yc = (y0 + ((idx - s).astype(F64) + F64(0.5)) * cell)[:, None]
+        u = (b[0] * Xc + b[1] * Yc) + b[2]
+        v = (b[3] * Xc + b[4] * Yc) + b[5]
+        sees = (h >= 1) & (w >= 1) & (0 <= u) & (u < w) & (0 <= v) & (v < h)
+    sees = sees & (idx[None, :] < nx + 2 * s) & (idx[:, None] < ny + 2 * s)
+    out = np.zeros((ext, ext), dtype=np.uint8)
+    if sees.any():
+        out[sees] = luma(img[np.floor(v[sees]).astype(np.int64), np.floor(u[sees]).astype(np.int64)]).astype(np.uint8)
+    return out
+
+
+def search_oracle(A, B, gx, gy, S):
+    """score (2S+1, 2S+1, 2) int64 = (sad, n), one offset at a time."""
+    a = A[:gy, :gx].astype(np.int64)
+    score = np.zeros((2 * S + 1, 2 * S + 1, 2), dtype=np.int64)
+    for dy in range(-S, S + 1):
+        for dx in range(-S, S + 1):
+            bb = B[S + dy:S + dy + gy, S + dx:S + dx + gx].astype(np.int64)
+            both = (a != 0) & (bb != 0)
+            score[dy + S, dx + S] = (np.abs(a - bb)[both].sum(), both.sum())
+    return score
+
+
+def beats(p, q):
+    """Offset p = (sad, n, dy, dx) beats q: the cross products in Python integers, then (dy^2 + dx^2, dy, dx)."""
+    l, r = p[0] * q[1], q[0] * p[1]
+    if l != r:
+        return l < r
+    return (p[2] * p[2] + p[3] * p[3], p[2], p[3]) < (q[2] * q[2] + q[3] * q[3], q[2], q[3])
+
+
+def pick_oracle(score, S, min_cells):
+    """best (8,) int64 from a score table, sequentially."""
+    def top(excluded):
+        best = None
+        for dy in range(-S, S + 1):
+            for dx in range(-S, S + 1):
+                sad, n = (int(v) for v in score[dy + S, dx + S])
+                if n < min_cells or (excluded is not None and max(abs(dy - excluded[0]), abs(dx - excluded[1])) < 2):
+                    continue
+                cand = (sad, n, dy, dx)
+                if best is None or beats(cand, best):
+                    best = cand
+        return best
+    first = top(None)
+    second = top((first[2], first[3])) if first is not None else None
+    four = lambda c: [0, 0, -1, 0] if c is None else [c[2], c[3], c[0], c[1]]
+    return np.array(four(first) + four(second), dtype=np.int64)
+
+
+def register_oracle(g2p, size, images, pairs, cell, search, side, min_cells):
+    """The whole rule for a pair table: A (P,side,side), B (P,E,E) uint8, score (P,2S+1,2S+1,2) and best (P,8) int64.  A
+    pair outside the rule (a frame index out of range, gx or gy outside [1, side]) has no planes here (None)."""
+    E = side + 2 * search
+    out = {"a": [], "b": [], "score": [], "best": []}
+    nf = len(size)
+    for pr in pairs:
+        fa, fb, gx, gy = (int(pr[k]) for k in ("frame_a", "frame_b", "gx", "gy"))
+        if not (0 <= fa < nf and 0 <= fb < nf and 1 <= gx <= side and 1 <= gy <= side):
+            for k in out:
+                out[k].append(None)
+            continue
+        A = render_plane(g2p[fa], size[fa], images[fa], pr["x0"], pr["y0"], cell, gx, gy, 0, side)
+        B = render_plane(g2p[fb], size[fb], images[fb], pr["x0"], pr["y0"], cell, gx, gy, search, E)
+        score = search_oracle(A, B, gx, gy, search)
+        out["a"].append(A)
+        out["b"].append(B)
+        out["score"].append(score)
+        out["best"].append(pick_oracle(score, search, min_cells))
+    return out
+
+
+def _pairs(rows):
+    return np.array([tuple(r) for r in rows], dtype=tiling.REGISTER_PAIR).reshape(-1)
+
+
+def _axis_frame(img, x_west, y_north, gsd):
+    """A north-up frame: pixel (0, 0)'s corner at (x_west, y_north), gsd metres per pixel.  Returns (img, georef)."""
+    return img, np.array([[gsd, 0.0, x_west], [0.0, -gsd, y_north]], dtype=F64)
+
+
+def _content(h, w, seed, lo=0):
+    return np.random.default_rng(seed).integers(lo, 256, size=(h, w, 3), dtype=np.uint8)
+
+
+# ---- CPU: the oracle's hand cases ------------------------------------------------------------------------------------
+
+def test_oracle_luma_hand_cases():
+    assert luma(np.array([255, 255, 255], dtype=np.uint8)) == 255          # (256 * 255 + 128) >> 8
+    assert luma(np.array([0, 0, 0], dtype=np.uint8)) == 1                  # a black pixel is seen: clamped to 1
+    assert luma(np.array([1, 0, 0], dtype=np.uint8)) == 1                  # (77 + 128) >> 8 = 0 -> 1
+    assert luma(np.array([10, 20, 30], dtype=np.uint8)) == 18              # 770 + 3000 + 870 + 128 = 4768 >> 8
+    assert luma(np.array([40, 50, 60], dtype=np.uint8)) == 48              # 3080 + 7500 + 1740 + 128 = 12448 >> 8
+
+
+def _one_by_one():
+    """A 1 x 1 patch at search 0: two frames of one pixel each over the cell [0, 1) x [0, 1)."""
+    fa = _axis_frame(np.array([[[10, 20, 30]]], dtype=np.uint8), 0.0, 1.0, 1.0)
+    fb = _axis_frame(np.array([[[40, 50, 60]]], dtype=np.uint8), 0.0, 1.0, 1.0)
+    return _case([fa, fb], [(0, 1, 1, 1, 0.0, 0.0)], 1.0, 0, 1, 1)
+
+
+def test_oracle_one_by_one_patch_at_search_0():
+    want = _oracle(_one_by_one())
+    assert want["a"][0].tolist() == [[18]] and want["b"][0].tolist() == [[48]]
+    assert want["score"][0].tolist() == [[[30, 1]]]
+    assert want["best"][0].tolist() == [0, 0, 30, 1, 0, 0, -1, 0]
+
+
+HAND_A = np.array([[1, 2], [3, 4]], dtype=np.uint8)
+HAND_B = np.array([[0, 0, 0, 0], [0, 1, 2, 0], [0, 3, 4, 0], [0, 0, 0, 0]], dtype=np.uint8)
+# B[j + 1 + dy][i + 1 + dx] against A[j][i], only where both are not 0.  (0, 0): all four agree.  (0, 1): 2|1 and 4|3;
+# (0, -1): 1|2 and 3|4; (1, 0): 3|1 and 4|2; (-1, 0): 1|3 and 2|4; the corners meet in one cell: (1, 1) 4|1, (-1, -1) 1|4,
+# (1, -1) 3|2, (-1, 1) 2|3.
+HAND_SCORE = [[(3, 1), (4, 2), (1, 1)],
+              [(2, 2), (0, 4), (2, 2)],
+              [(1, 1), (4, 2), (3, 1)]]
+
+
+def test_oracle_3x3_score_table_at_search_1():
+    score = search_oracle(HAND_A, HAND_B, 2, 2, 1)
+    assert score.tolist() == [[list(c) for c in row] for row in HAND_SCORE]
+    assert pick_oracle(score, 1, 1).tolist() == [0, 0, 0, 4, 0, 0, -1, 0]            # nothing lies outside the peak's 3 x 3
+    assert pick_oracle(score, 1, 3).tolist() == [0, 0, 0, 4, 0, 0, -1, 0]
+    assert pick_oracle(score, 1, 5).tolist() == [0, 0, -1, 0, 0, 0, -1, 0]          # no offset has 5 cells
+
+
+def test_oracle_constant_planes_tie_to_the_centre():
+    A, B = np.full((4, 4), 9, dtype=np.uint8), np.full((8, 8), 9, dtype=np.uint8)
+    score = search_oracle(A, B, 4, 4, 2)
+    assert (score[..., 0] == 0).all() and (score[..., 1] == 16).all()
+    # every offset ties at sad 0: (0, 0) has the smallest dy^2 + dx^2; outside its 3 x 3 the smallest key is d2 = 4, dy = -2, dx = 0
+    assert pick_oracle(score, 2, 1).tolist() == [0, 0, 0, 16, -2, 0, 0, 16]
+
+
+def test_oracle_equal_cross_products_with_different_n():
+    score = np.zeros((3, 3, 2), dtype=np.int64)
+    score[2, 1] = (1, 2)                                                              # (dy, dx) = (1, 0): mean 1/2
+    score[0, 1] = (2, 4)                                                              # (-1, 0): mean 2/4, the same
+    assert not beats((1, 2, 1, 0), (2, 4, -1, 0)) and beats((2, 4, -1, 0), (1, 2, 1, 0))   # 1 * 4 == 2 * 2: dy -1 < 1
+    # (1, 0) lies two rows from the peak (-1, 0), outside its 3 x 3: it is the runner-up
+    assert pick_oracle(score, 1, 1).tolist() == [-1, 0, 2, 4, 1, 0, 1, 2]
+    score[1, 2] = (3, 6)                                                              # (0, 1): the same mean again, key (1, 0, 1) > (1, -1, 0)
+    assert pick_oracle(score, 1, 1).tolist() == [-1, 0, 2, 4, 1, 0, 1, 2]
+    score[1, 1] = (5, 10)                                                             # (0, 0): the same mean, d2 = 0 wins
+    assert pick_oracle(score, 1, 1).tolist() == [0, 0, 5, 10, 0, 0, -1, 0]
+    score[1, 1] = (5, 9)                                                              # a worse mean loses whatever its key
+    assert pick_oracle(score, 1, 1).tolist() == [-1, 0, 2, 4, 1, 0, 1, 2]
+
+
+def test_oracle_black_pixel_is_seen_and_outside_is_not():
+    black = _axis_frame(np.zeros((2, 2, 3), dtype=np.uint8), 1.0, 3.0, 1.0)          # covers [1, 3) x [1, 3)
+    plane = render_plane(tiling.ground_to_pixel(black[1]).reshape(6), (2, 2), black[0], 0.0, 0.0, 1.0, 4, 4, 0, 5)
+    want = np.zeros((5, 5), dtype=np.uint8)
+    want[1:3, 1:3] = 1
+    assert plane.tolist() == want.tolist()
+    # the B plane is the same grid grown by `search`: cell (j + s, i + s) of B is cell (j, i) of A
+    grown = render_plane(tiling.ground_to_pixel(black[1]).reshape(6), (2, 2), black[0], 0.0, 0.0, 1.0, 4, 4, 2, 9)
+    assert grown[2:7, 2:7].tolist() == want.tolist() and grown.sum() == 4
+
+
+# ---- CPU: register_pairs and adjust ----------------------------------------------------------------------------------
+
+def _north_up(x_west, y_south, w, h, gsd=1.0):
+    return np.array([[gsd, 0.0, x_west], [0.0, -gsd, y_south + h * gsd]], dtype=F64)
+
+
+def test_register_pairs_snapping_crop_and_drop():
+    # footprints [0.3, 100.3] x [0.2, 80.2] and [60.7, 160.7] x [10.6, 90.6]: intersection [60.7, 100.3] x [10.6, 80.2]
+    g = np.stack([_north_up(0.3, 0.2, 100, 80), _north_up(60.7, 10.6, 100, 80)])
+    sizes = [(80, 100), (80, 100)]
+    t = tiling.register_pairs(g, sizes, 0.5, search=4, side=512, min_cells=1)
+    assert t.dtype == tiling.REGISTER_PAIR and t.dtype.itemsize == 32 and t.shape == (1,)
+    # floor(60.7 / 0.5) = 121, ceil(100.3 / 0.5) = 201: 80 cells from 60.5; floor(10.6 / 0.5) = 21, ceil(80.2 / 0.5) = 161: 140 from 10.5
+    assert t[0].tolist() == (0, 1, 80, 140, 60.5, 10.5)
+    # centre crop to side 64: i0 += (80 - 64) // 2 = 8 -> 129, j0 += (140 - 64) // 2 = 38 -> 59
+    t = tiling.register_pairs(g, sizes, 0.5, side=64, min_cells=1)
+    assert t[0].tolist() == (0, 1, 64, 64, 64.5, 29.5)
+    # an odd surplus crops one cell more on the far side: (80 - 63) // 2 = 8
+    t = tiling.register_pairs(g, sizes, 0.5, side=63, min_cells=1)
+    assert t[0].tolist() == (0, 1, 63, 63, 64.5, 29.5)
+    # dropped below min_cells: 80 * 140 = 11200
+    assert tiling.register_pairs(g, sizes, 0.5, min_cells=11200).shape == (1,)
+    assert tiling.register_pairs(g, sizes, 0.5, min_cells=11201).shape == (0,)
+
+
+def test_register_pairs_disjoint_nan_and_order():
+    g = np.stack([_north_up(0, 0, 100, 80), _north_up(500, 0, 100, 80), _north_up(50, 40, 100, 80), _north_up(100, 0, 100, 80),
+                  _north_up(20, 20, 100, 80)])
+    sizes = [(80, 100)] * 5
+    t = tiling.register_pairs(g, sizes, 1.0, min_cells=1)
+    # frame 1 is far away; frame 3 only touches frame 0 along x = 100 (no area)
+    assert [(int(p["frame_a"]), int(p["frame_b"])) for p in t] == [(0, 2), (0, 4), (2, 3), (2, 4), (3, 4)]
+    assert t[0].tolist() == (0, 2, 50, 40, 50.0, 40.0)
+    g[4, 0, 2] = NAN
+    t = tiling.register_pairs(g, sizes, 1.0, min_cells=1)
+    assert [(int(p["frame_a"]), int(p["frame_b"])) for p in t] == [(0, 2), (2, 3)]
+    g[:] = NAN
+    assert tiling.register_pairs(g, sizes, 1.0, min_cells=1).shape == (0,)
+    assert tiling.register_pairs(np.zeros((0, 2, 3)), np.zeros((0, 2), dtype=np.int32), 1.0).shape == (0,)
+    # a frame below 1 x 1 is in no pair
+    g = np.stack([_north_up(0, 0, 100, 80), _north_up(10, 10, 100, 80)])
+    assert tiling.register_pairs(g, [(80, 100), (0, 100)], 1.0, min_cells=1).shape == (0,)
+    # a yawed frame's box is its corners' extent
+    # a yawed frame's box is its corners' extent: 100 wide and 80 high at yaw 90 covers [-40, 40] x [-50, 50]; the second
+    # frame, [-30.5, 19.5] x [-48.5, -18.5], lies inside that (and would not inside [-50, 50] x [-40, 40])
+    g = np.stack([tiling.nadir_affine(80, 100, (0.0, 0.0), 1.0, 90.0), _north_up(-30.5, -48.5, 50, 30)])
+    t = tiling.register_pairs(g, [(80, 100), (30, 50)], 1.0, min_cells=1)
+    assert t[0].tolist() == (0, 1, 51, 31, -31.0, -49.0)
+
+
+def test_adjust_consistent_measurements_are_returned():
+    true = np.array([[3.0, -2.0], [-4.0, 1.0], [2.0, 3.0], [-1.5, -2.25], [0.5, 0.25]])
+    assert np.abs(true.mean(axis=0)).max() == 0.0
+    ab = np.array([(0, 1), (1, 2), (2, 3), (3, 4), (0, 4), (1, 3)])
+    m = true[ab[:, 1]] - true[ab[:, 0]]
+    w = np.array([4096.0, 10000.0, 512.0, 7.0, 30000.0, 1.0])
+    out = tiling.adjust(5, ab, m, w)
+    assert np.abs(out["shift"] - true).max() < 1e-9
+    assert np.abs(out["residual"]).max() < 1e-9
+    assert out["component"].tolist() == [0, 0, 0, 0, 0]
+    table = _pairs([(a, b, 8, 8, 0.0, 0.0) for a, b in ab])                       # the pair table is accepted as it is
+    assert np.array_equal(tiling.adjust(5, table, m, w)["shift"], out["shift"])
+
+
+def test_adjust_components_fixed_and_isolated():
+    # frames 0-1-2 and 4-5 are two components; 3 has no pair; the pair (2, 4) has weight 0 and joins nothing
+    ab = np.array([(0, 1), (1, 2), (4, 5), (2, 4)])
+    m = np.array([[2.0, 0.0], [2.0, 2.0], [0.0, -6.0], [100.0, 100.0]])
+    w = np.array([10.0, 10.0, 5.0, 0.0])
+    out = tiling.adjust(6, ab, m, w)
+    want = np.array([[-2.0, -2.0 / 3], [0.0, -2.0 / 3], [2.0, 4.0 / 3], [0.0, 0.0], [0.0, 3.0], [0.0, -3.0]])
+    assert np.abs(out["shift"] - want).max() < 1e-9                              # each component's mean shift is 0
+    assert out["component"].tolist() == [0, 0, 0, -1, 4, 4]
+    assert np.abs(out["residual"][:3]).max() < 1e-9
+    assert np.abs(out["residual"][3] - ((want[4] - want[2]) - m[3])).max() < 1e-9    # reported for the unused pair too
+    # fixed frames stay at 0 and pin their component; the other component keeps its zero mean
+    out = tiling.adjust(6, ab, m, w, fixed=[1, 3])
+    want = np.array([[-2.0, 0.0], [0.0, 0.0], [2.0, 2.0], [0.0, 0.0], [0.0, 3.0], [0.0, -3.0]])
+    assert np.abs(out["shift"] - want).max() < 1e-9
+    assert (out["shift"][[1, 3]] == 0.0).all()
+    # nothing to solve
+    out = tiling.adjust(3, np.zeros((0, 2), dtype=np.int64), np.zeros((0, 2)), np.zeros(0))
+    assert (out["shift"] == 0).all() and out["component"].tolist() == [-1, -1, -1] and out["residual"].shape == (0, 2)
+
+
+def test_adjust_inconsistent_measurements_give_the_weighted_mean():
+    # the same pair measured twice: t1 - t0 = 1 with weight 3 and = 5 with weight 1 -> (3 * 1 + 1 * 5) / 4 = 2
+    out = tiling.adjust(2, [(0, 1), (0, 1)], [[1.0, 10.0], [5.0, 50.0]], [3.0, 1.0])
+    assert np.abs(out["shift"] - np.array([[-1.0, -10.0], [1.0, 10.0]])).max() < 1e-9
+    assert np.abs(out["residual"] - np.array([[1.0, 10.0], [-3.0, -30.0]])).max() < 1e-9
+    assert np.abs(out["residual"]).min() > 0.5
+    # a triangle that does not close: the misclosure is spread, the residuals are not 0
+    out = tiling.adjust(3, [(0, 1), (1, 2), (0, 2)], [[1.0, 0.0], [1.0, 0.0], [5.0, 0.0]], [1.0, 1.0, 1.0])
+    assert np.abs(out["residual"][:, 0] - np.array([1.0, 1.0, -1.0])).max() < 1e-9
+    assert np.abs(out["shift"].sum(axis=0)).max() < 1e-9
+
+
+class _Lazy:
+    """A sequence that is only indexed, and records what was asked of it."""
+
+    def __init__(self, items):
+        self.items, self.asked = items, []
+
+    def __len__(self):
+        return len(self.items)
+
+    def __getitem__(self, i):
+        self.asked.append(i)
+        return self.items[i]
+
+
+def test_register_python_argument_errors_before_device_work():
+    g = np.stack([_north_up(0, 0, 100, 80), _north_up(10, 10, 100, 80)])
+    sizes = [(80, 100), (80, 100)]
+    imgs = [np.zeros((80, 100, 3), dtype=np.uint8)] * 2
+    lazy = _Lazy(imgs)
+    for name, bads in (("search", (-1, 65, 2.5, "4", None, True, NAN)), ("side", (0, 513, 1.5, "64", None, True)),
+                       ("min_cells", (0, -3, 2.5, None, "1", 2 ** 31))):
+        for bad in bads:
+            with pytest.raises(ValueError, match=name):
+                tiling.register(lazy, g, 1.0, sizes=sizes, **{name: bad})
+            with pytest.raises(ValueError, match=name):
+                tiling.register_pairs(g, sizes, 1.0, **{name: bad})
+    for bad in (0, -1, 2.5, "8", None, True, 65536):
+        with pytest.raises(ValueError, match="pair_chunk"):
+            tiling.register(lazy, g, 1.0, sizes=sizes, pair_chunk=bad)
+    for bad in (-0.5, NAN, INF, "big", None):
+        with pytest.raises(ValueError, match="min_ratio"):
+            tiling.register(lazy, g, 1.0, sizes=sizes, min_ratio=bad)
+    for bad in (0, -1.0, NAN, INF, "wide", None):
+        with pytest.raises(ValueError, match="cell"):
+            tiling.register(lazy, g, bad, sizes=sizes)
+        with pytest.raises(ValueError, match="cell"):
+            tiling.register_pairs(g, sizes, bad)
+    with pytest.raises(ValueError, match="georef"):
+        tiling.register_pairs(np.zeros((2, 3, 2)), sizes, 1.0)
+    with pytest.raises(ValueError, match="sizes"):
+        tiling.register_pairs(g, [(4.5, 8), (4, 8)], 1.0)
+    with pytest.raises(ValueError, match="sizes is required"):
+        tiling.register(lazy, g, 1.0)
+    with pytest.raises(ValueError, match="indexed"):
+        tiling.register(iter(imgs), g, 1.0, sizes=sizes)
+    with pytest.raises(ValueError, match="sizes for 2 georeferences"):
+        tiling.register(lazy, g, 1.0, sizes=[(80, 100)])
+    with pytest.raises(ValueError, match="1 frames for 2 georeferences"):
+        tiling.register(_Lazy(imgs[:1]), g, 1.0, sizes=sizes)
+    good = _pairs([(0, 1, 8, 8, 0.0, 0.0)])
+    for bad in ([(0, 1, 8, 8, 0.0, 0.0)], np.zeros((1, 6)), good.reshape(1, 1), _pairs([(0, 2, 8, 8, 0.0, 0.0)]), _pairs([(-1, 1, 8, 8, 0.0, 0.0)]),
+                _pairs([(1, 1, 8, 8, 0.0, 0.0)]), _pairs([(0, 1, 0, 8, 0.0, 0.0)]), _pairs([(0, 1, 8, 65, 0.0, 0.0)]), _pairs([(0, 1, 8, 8, NAN, 0.0)])):
+        with pytest.raises(ValueError, match="pairs"):
+            tiling.register(lazy, g, 1.0, sizes=sizes, side=64, pairs=bad)
+    for bad in ([2], [-1], [0.5], "0", 7):
+        with pytest.raises(ValueError, match="fixed"):
+            tiling.register(lazy, g, 1.0, sizes=sizes, fixed=bad)
+        with pytest.raises(ValueError, match="fixed"):
+            tiling.adjust(2, [(0, 1)], [[0.0, 0.0]], [1.0], fixed=bad)
+    with pytest.raises(ValueError, match="n_frames"):
+        tiling.adjust(-1, [(0, 1)], [[0.0, 0.0]], [1.0])
+    for bad in ([(0, 2)], [(0, 0)], [(0.5, 1)], [(0, 1, 2)]):
+        with pytest.raises(ValueError, match="pairs"):
+            tiling.adjust(2, bad, [[0.0, 0.0]], [1.0])
+    with pytest.raises(ValueError, match="measured"):
+        tiling.adjust(2, [(0, 1)], [[0.0, 0.0], [1.0, 1.0]], [1.0])
+    with pytest.raises(ValueError, match="measured"):
+        tiling.adjust(2, [(0, 1)], [[NAN, 0.0]], [1.0])
+    for bad in ([-1.0], [NAN], [INF]):
+        with pytest.raises(ValueError, match="weights"):
+            tiling.adjust(2, [(0, 1)], [[0.0, 0.0]], bad)
+    if not torch.cuda.is_available():
+        with pytest.raises(RuntimeError, match="ROCm device tensor"):              # no CPU fallback
+            tiling.register(lazy, g, 1.0, sizes=sizes, min_cells=1)
+    assert lazy.asked == []                                                     # nothing was loaded on the way to an error
+    # no pair at all needs no device: every frame keeps its georeference
+    far = np.stack([_north_up(0, 0, 100, 80), _north_up(1000, 0, 100, 80)])
+    out = tiling.register(lazy, far, 1.0, sizes=sizes)
+    assert out["pairs"].shape == (0,) and (out["shift"] == 0).all() and np.array_equal(out["georef"], far) and lazy.asked == []
+    assert out["component"].tolist() == [-1, -1] and out["accepted"].shape == (0,) and out["offset"].shape == (0, 2)
+
+
+def _abi_render(n_frames=2, n_resident=2, n_pairs=3, cell=1.0, search=4, side=64, frames=0x1000, slot=0x7000, g2p=0x2000, size=0x3000,
+                pairs=0x4000, a=0x5001, b=0x6001, status=0x9000):
+    """wm_register_render_u8 with fake, never dereferenced device pointers: only paths that return before any HIP call."""
+    p = lambda v: C.c_void_p(v) if v else None
+    return N.lib().wm_register_render_u8(p(frames), n_resident, p(slot), p(g2p), p(size), n_frames, p(pairs), n_pairs, cell, search, side,
+                                         p(a), p(b), p(status), None)
+
+
+def _abi_search(n_pairs=3, search=4, side=64, min_cells=1, a=0x5001, b=0x6001, pairs=0x4000, score=0x8000, best=0xa000):
+    p = lambda v: C.c_void_p(v) if v else None
+    return N.lib().wm_register_search(p(a), p(b), p(pairs), n_pairs, search, side, min_cells, p(score), p(best), None)
+
+
+def test_register_abi_argument_errors_without_gpu():
+    err = lambda: N.lib().wm_last_error().decode()
+    for call in (_abi_render, _abi_search):
+        assert call(n_pairs=-1) < 0 and "n_pairs" in err()
+        assert call(n_pairs=N.REGISTER_MAX_PAIRS + 1) < 0 and "n_pairs" in err()
+        assert call(search=-1) < 0 and "search" in err()
+        assert call(search=N.REGISTER_MAX_SEARCH + 1) < 0 and "search" in err()
+        assert call(side=0) < 0 and "side" in err()
+        assert call(side=N.REGISTER_MAX_SIDE + 1) < 0 and "side" in err()
+        assert call(pairs=0) < 0 and "pairs_dev" in err()
+        assert call(pairs=0x4004) < 0 and "pairs_dev" in err() and "aligned" in err()
+        assert call(a=0) < 0 and "a_dev" in err()
+        assert call(b=0) < 0 and "b_dev" in err()
+        # n_pairs == 0 returns 0 before looking at any pointer or any other argument
+        assert call(n_pairs=0, pairs=0, a=0, b=0, search=-5, side=0) == 0
+    assert _abi_render(n_frames=-1) < 0 and "n_frames" in err()
+    assert _abi_render(n_frames=N.COVERAGE_MAX_FRAMES + 1) < 0 and "n_frames" in err()
+    assert _abi_render(n_resident=-1) < 0 and "n_resident" in err()
+    assert _abi_render(n_resident=N.COVERAGE_MAX_FRAMES + 1) < 0 and "n_resident" in err()
+    for bad in (0.0, -1.0, NAN, INF):
+        assert _abi_render(cell=bad) < 0 and "cell" in err()
+    assert _abi_render(g2p=0) < 0 and "g2p_dev" in err()
+    assert _abi_render(size=0) < 0 and "size_dev" in err()
+    assert _abi_render(g2p=0x2004) < 0 and "aligned" in err()
+    assert _abi_render(size=0x3002) < 0 and "aligned" in err()
+    assert _abi_render(frames=0) < 0 and "frames_dev" in err()
+    assert _abi_render(slot=0) < 0 and "slot_dev" in err()
+    assert _abi_render(status=0) < 0 and "status_dev" in err()
+    assert _abi_render(frames=0x1004) < 0 and "aligned" in err()
+    assert _abi_render(slot=0x7002) < 0 and "aligned" in err()
+    assert _abi_render(status=0x9002) < 0 and "aligned" in err()
+    for bad in (0, -1, -2 ** 31):
+        assert _abi_search(min_cells=bad) < 0 and "min_cells" in err()
+    assert _abi_search(score=0) < 0 and "score_dev" in err()
+    assert _abi_search(best=0) < 0 and "best_dev" in err()
+    assert _abi_search(score=0x8002) < 0 and "aligned" in err()
+    assert _abi_search(best=0xa002) < 0 and "aligned" in err()
+
+
+def test_register_symbols_and_abi_13():
+    hdr = open(os.path.join(ROOT, "include", "wm_hip.h")).read()
+    assert int(re.search(r"#define WM_ABI_VERSION (\d+)", hdr).group(1)) == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
+    assert "Survey registration" in hdr and len(re.findall("13, additive", hdr)) >= 3
+    for name in ("wm_register_render_u8", "wm_register_search"):
+        assert name in N.SYMBOLS and re.search(r"\bint %s\(" % name, hdr)
+        assert getattr(N.lib(), name) is not None
+    for macro, val in (("WM_REGISTER_MAX_SIDE", N.REGISTER_MAX_SIDE), ("WM_REGISTER_MAX_SEARCH", N.REGISTER_MAX_SEARCH),
+                       ("WM_REGISTER_MAX_PAIRS", N.REGISTER_MAX_PAIRS), ("WM_REGISTER_BAD_SLOT", N.REGISTER_BAD_SLOT),
+                       ("WM_REGISTER_BAD_SIZE", N.REGISTER_BAD_SIZE), ("WM_REGISTER_BAD_PAIR", N.REGISTER_BAD_PAIR)):
+        assert int(re.search(r"#define %s (\d+)" % macro, hdr).group(1)) == val
+    assert (N.REGISTER_MAX_SIDE, N.REGISTER_MAX_SEARCH, N.REGISTER_MAX_PAIRS) == (512, 64, 65535)
+    assert tiling.REGISTER_PAIR.itemsize == 32 and [tiling.REGISTER_PAIR.fields[k][1] for k in tiling.REGISTER_PAIR.names] == [0, 4, 8, 12, 16, 24]
+    kern = open(os.path.join(ROOT, "wildlifemapper_amd", "csrc", "register_kernels.h")).read()
+    assert "__builtin_amdgcn_sad_u8(" in kern and "asm" not in kern
+
+
+# ---- cases -----------------------------------------------------------------------------------------------------------
+
+def _case(frames, pairs, cell, search, side, min_cells):
+    """frames: a list of (img (H,W,3) uint8, georef (2,3)); pairs: rows of (frame_a, frame_b, gx, gy, x0, y0)."""
+    georef = np.stack([f[1] for f in frames])
+    return {"images": [f[0] for f in frames], "g2p": tiling.ground_to_pixel(georef).reshape(-1, 6),
+            "size": np.array([f[0].shape[:2] for f in frames], dtype=np.int32), "pairs": _pairs(pairs), "cell": cell, "search": search,
+            "side": side, "min_cells": min_cells}
+
+
+def _oracle(case):
+    return register_oracle(case["g2p"], case["size"], case["images"], case["pairs"], case["cell"], case["search"], case["side"],
+                           case["min_cells"])
+
+
+def _cover(gx, gy, search, x0, y0, cell, seed, gsd_cells=1.5, yaw=0.0, margin=2):
+    """A frame of random pixels that sees the whole patch and its search margin: gsd = gsd_cells * cell."""
+    gsd = gsd_cells * cell
+    span = max(gx, gy) + 2 * search + 2 * margin
+    n = int(np.ceil(span / gsd_cells * (1.5 if yaw else 1.0))) + 2
+    centre = (x0 + 0.5 * gx * cell, y0 + 0.5 * gy * cell)
+    return _content(n, n + 1, seed), tiling.nadir_affine(n, n + 1, centre, gsd, yaw)
+
+
+def _shape_case(gx, gy, search, side, seed=0, min_cells=1):
+    x0, y0, cell = 500000.0 + 0.25 * seed, 6000000.0 - 0.5 * seed, 0.25
+    fa = _cover(gx, gy, search, x0, y0, cell, 2 * seed)
+    fb = _cover(gx, gy, search, x0, y0, cell, 2 * seed + 1, gsd_cells=1.25)
+    return _case([fa, fb], [(0, 1, gx, gy, x0, y0)], cell, search, side, min_cells)
+
+
+SHAPES = {  # gx, gy, search, side
+    "1x1_s0": (1, 1, 0, 1), "1x1_s1_side4": (1, 1, 1, 4), "3x5_s1": (3, 5, 1, 8), "4x4_s5": (4, 4, 5, 4), "5x3_s5": (5, 3, 5, 16),
+    "63x65_s5": (63, 65, 5, 65), "64x64_s1": (64, 64, 1, 64), "65x63_s5": (65, 63, 5, 80), "1x65_s5": (1, 65, 5, 65),
+    "64x1_s0": (64, 1, 0, 64), "70x19_s5": (70, 19, 5, 70), "257x65_s5": (257, 65, 5, 300), "96x80_s64": (96, 80, 64, 96),
+    "512x512_s4": (512, 512, 4, 512), "65x33_s16": (65, 33, 16, 67), "40x40_s33": (40, 40, 33, 41),
+    "33x37_s62": (33, 37, 62, 40), "33x37_s63": (33, 37, 63, 40)}             # the last search with 32-row tiles, the first with 16
+
+
+def _several_pairs():
+    """Pairs of different sizes in one launch, sharing frames, patches at different places, one yawed 45 degrees."""
+    x0, y0, cell = 1000.0, 2000.0, 0.5
+    diamond = _content(90, 90, 13), tiling.nadir_affine(90, 90, (x0 + 17.5, y0 + 17.5), 0.5, 45.0)       # 45 m a side, yawed
+    frames = [_cover(70, 70, 6, x0, y0, cell, 11), _cover(70, 70, 6, x0, y0, cell, 12, gsd_cells=1.25), diamond,
+              _cover(30, 30, 6, x0 + 10.0, y0 + 10.0, cell, 14, gsd_cells=0.75)]
+    pairs = [(0, 1, 70, 19, x0, y0), (1, 2, 5, 66, x0 + 3.0, y0 + 1.5), (0, 3, 33, 30, x0 + 9.5, y0 + 8.0), (2, 3, 72, 72, x0 - 4.0, y0 - 4.0),
+             (0, 2, 1, 1, x0 + 7.0, y0 + 7.0)]
+    return _case(frames, pairs, cell, 6, 72, 40)
+
+
+# ---- GPU -------------------------------------------------------------------------------------------------------------
+
+DEV = "cuda:0"
+
+
+def _up(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _planes(case):
+    n, side, E = len(case["pairs"]), case["side"], case["side"] + 2 * case["search"]
+    return (torch.full((n, side, side), POISON_A, device=DEV, dtype=torch.uint8), torch.full((n, E, E), POISON_B, device=DEV, dtype=torch.uint8))
+
+
+def _render(case, a, b, status, resident, slot=None, images=None):
+    """One wm_register_render_u8 call with the frames `resident` (survey indices) on the device, in that order."""
+    F = case["g2p"].shape[0]
+    images = case["images"] if images is None else images
+    tensors = [_up(images[f]) for f in resident]
+    descs = tiling._frame_descs(tensors, torch.device(DEV)) if tensors else None
+    if slot is None:
+        slot = np.full(F, -1, dtype=np.int32)
+        slot[list(resident)] = np.arange(len(resident), dtype=np.int32)
+    pairs = _up(case["pairs"].view(np.uint8).reshape(len(case["pairs"]), 32))
+    slot_d, g_d, s_d = _up(slot), _up(case["g2p"]), _up(case["size"])                # held until the launch has run
+    N.check(N.lib().wm_register_render_u8(N.ptr(descs), len(resident), N.ptr(slot_d), N.ptr(g_d), N.ptr(s_d), F,
+                                          N.ptr(pairs), len(case["pairs"]), case["cell"], case["search"], case["side"], N.ptr(a), N.ptr(b),
+                                          N.ptr(status), N.stream_ptr(torch.device(DEV))))
+    torch.cuda.synchronize()
+
+
+def _search(case, a, b, min_cells=None):
+    """wm_register_search on device planes, both outputs pre-filled with a poison value.  Returns (score, best) int64."""
+    n, w1 = len(case["pairs"]), 2 * case["search"] + 1
+    pairs = _up(case["pairs"].view(np.uint8).reshape(n, 32))
+    score = torch.full((n, w1, w1, 2), -77, device=DEV, dtype=torch.int32)
+    best = torch.full((n, 8), -77, device=DEV, dtype=torch.int32)
+    N.check(N.lib().wm_register_search(N.ptr(a), N.ptr(b), N.ptr(pairs), n, case["search"], case["side"],
+                                       case["min_cells"] if min_cells is None else min_cells, N.ptr(score), N.ptr(best),
+                                       N.stream_ptr(torch.device(DEV))))
+    torch.cuda.synchronize()
+    return score.cpu().numpy().astype(np.int64), best.cpu().numpy().astype(np.int64)
+
+
+def _run_and_check(case, want=None):
+    """Render with every frame resident, search, and compare planes, score and best with the oracle."""
+    want = _oracle(case) if want is None else want
+    a, b = _planes(case)
+    status = torch.zeros(1, device=DEV, dtype=torch.int32)
+    _render(case, a, b, status, list(range(len(case["images"]))))
+    assert status.item() == 0
+    score, best = _search(case, a, b)
+    a, b = a.cpu().numpy(), b.cpu().numpy()
+    for p in range(len(case["pairs"])):
+        np.testing.assert_array_equal(a[p], want["a"][p], err_msg=f"A of pair {p}")
+        np.testing.assert_array_equal(b[p], want["b"][p], err_msg=f"B of pair {p}")
+        np.testing.assert_array_equal(score[p], want["score"][p], err_msg=f"score of pair {p}")
+        np.testing.assert_array_equal(best[p], want["best"][p], err_msg=f"best of pair {p}")
+    return want, score, best
+
+
+@pytest.mark.gpu
+def test_gpu_one_by_one_hand_case():
+    _, score, best = _run_and_check(_one_by_one())
+    assert score.tolist() == [[[[30, 1]]]] and best.tolist() == [[0, 0, 30, 1, 0, 0, -1, 0]]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(SHAPES))
+def test_gpu_smallest_shapes(name):
+    gx, gy, search, side = SHAPES[name]
+    want, score, best = _run_and_check(_shape_case(gx, gy, search, side, seed=sorted(SHAPES).index(name)))
+    assert (score[0, :, :, 1] == gx * gy).all()                                       # both frames see everything
+    assert (want["a"][0][gy:] == 0).all() and (want["a"][0][:, gx:] == 0).all()       # the zero padding up to side
+    assert best[0, 2] >= 0
+
+
+@pytest.mark.gpu
+def test_gpu_several_pairs_in_one_launch():
+    want, score, best = _run_and_check(_several_pairs())
+    assert best[4].tolist() == [0, 0, -1, 0, 0, 0, -1, 0]                              # 1 cell < min_cells 40
+    assert (best[:4, 2] >= 0).all() and (best[:4, 6] >= 0).all()
+    diagonal = want["a"][3]                                                           # pair 3's A is the frame yawed 45 degrees
+    assert 0 < (diagonal[:72, :72] != 0).sum() < 72 * 72
+
+
+@pytest.mark.gpu
+def test_gpu_diagonal_mask_edge_and_a_frame_that_sees_nothing():
+    x0, y0, cell = 300.0, 400.0, 1.0
+    small = _content(40, 40, 21), tiling.nadir_affine(40, 40, (x0 + 30.0, y0 + 30.0), 1.0, 45.0)     # a diamond inside the patch
+    full = _cover(60, 60, 5, x0, y0, cell, 22)
+    away = _content(30, 30, 23), tiling.nadir_affine(30, 30, (x0 + 5000.0, y0), 1.0, 0.0)
+    nan = _content(30, 30, 24), np.full((2, 3), NAN)
+    case = _case([small, full, away, nan], [(0, 1, 60, 60, x0, y0), (1, 0, 60, 60, x0, y0), (1, 2, 60, 60, x0, y0), (1, 3, 60, 60, x0, y0)],
+                 cell, 5, 64, 100)
+    want, score, best = _run_and_check(case)
+    seen = want["a"][0] != 0
+    assert 0 < seen.sum() < 60 * 60 and not seen[0, 0] and seen[30, 30]               # the mask's edge is diagonal
+    assert len(set(score[0, :, :, 1].reshape(-1).tolist())) == 1                      # A's mask alone decides n
+    assert len(set(score[1, :, :, 1].reshape(-1).tolist())) > 1                       # B's mask moves with the offset
+    for p in (2, 3):                                                                  # B never sees the patch
+        assert (want["b"][p] == 0).all() and (score[p] == 0).all()
+        assert best[p].tolist() == [0, 0, -1, 0, 0, 0, -1, 0]
+
+
+def _plane_case(A, B, gx, gy, search, min_cells=1):
+    """Hand-built planes, for the search alone: a list of (A (side,side), B (E,E)) per pair."""
+    side = A[0].shape[0]
+    pairs = _pairs([(0, 1, gx, gy, 0.0, 0.0)] * len(A))
+    return {"pairs": pairs, "search": search, "side": side, "min_cells": min_cells}, _up(np.stack(A)), _up(np.stack(B))
+
+
+@pytest.mark.gpu
+def test_gpu_hand_score_table_and_ties():
+    case, a, b = _plane_case([HAND_A], [HAND_B], 2, 2, 1)
+    score, best = _search(case, a, b)
+    assert score[0].tolist() == [[list(c) for c in row] for row in HAND_SCORE]
+    assert best[0].tolist() == [0, 0, 0, 4, 0, 0, -1, 0]
+    # constant planes: every offset ties at sad 0, the pick is (0, 0), the runner-up (-2, 0)
+    case, a, b = _plane_case([np.full((4, 4), 9, dtype=np.uint8)], [np.full((8, 8), 9, dtype=np.uint8)], 4, 4, 2)
+    score, best = _search(case, a, b)
+    assert (score[0, :, :, 0] == 0).all() and (score[0, :, :, 1] == 16).all()
+    assert best[0].tolist() == [0, 0, 0, 16, -2, 0, 0, 16]
+    # equal cross products with different n.  A's only seen cells are rows 1, 2 x columns 0, 1 = (10, 200); they meet B's
+    # columns 1, 2 at dx = 0 and rows (j + 1 + dy): (-1, 0) rows 1, 2: 0 + 2 over 4 cells; (0, 0) rows 2, 3: 2 + 1 over 4;
+    # (1, 0) rows 3, 4: 1 over 2 (row 4 is not seen).  2 * 2 == 1 * 4, and dy = -1 < 1 decides; dx = +-1 pairs 10 with 200.
+    A = np.zeros((4, 4), dtype=np.uint8)
+    A[1:3, 0], A[1:3, 1] = 10, 200
+    B = np.zeros((6, 6), dtype=np.uint8)
+    B[1, 1:3], B[2, 1:3], B[3, 1:3] = (10, 200), (12, 200), (10, 201)
+    want = search_oracle(A, B, 4, 4, 1)
+    assert want[0, 1].tolist() == [2, 4] and want[1, 1].tolist() == [3, 4] and want[2, 1].tolist() == [1, 2]
+    case, a, b = _plane_case([A], [B], 4, 4, 1, min_cells=2)
+    score, best = _search(case, a, b)
+    np.testing.assert_array_equal(score[0], want)
+    assert best[0].tolist() == [-1, 0, 2, 4, 1, 0, 1, 2] == pick_oracle(want, 1, 2).tolist()       # (1, 0): the runner-up
+
+
+@pytest.mark.gpu
+def test_gpu_min_cells_boundary_on_a_hand_built_mask():
+    rng = np.random.default_rng(5)
+    A = np.zeros((70, 70), dtype=np.uint8)
+    cells = rng.permutation(66 * 67)[:1234]
+    A[cells // 66, cells % 66] = rng.integers(1, 256, size=1234)                    # gx = 66, gy = 67: exactly 1234 seen cells
+    A[:, 66:] = 200                                                                 # beyond gx: must not count
+    A[67:, :] = 200
+    B = rng.integers(1, 256, size=(70, 70), dtype=np.uint8)                         # search 0: E = side; B sees everything
+    case, a, b = _plane_case([A], [B], 66, 67, 0)
+    want = search_oracle(A, B, 66, 67, 0)
+    assert want[0, 0, 1] == 1234
+    score, best = _search(case, a, b, min_cells=1234)
+    np.testing.assert_array_equal(score[0], want)
+    assert best[0].tolist() == [0, 0, int(want[0, 0, 0]), 1234, 0, 0, -1, 0]          # n == min_cells is eligible
+    score, best = _search(case, a, b, min_cells=1235)
+    np.testing.assert_array_equal(score[0], want)
+    assert best[0].tolist() == [0, 0, -1, 0, 0, 0, -1, 0]                            # n == min_cells - 1 is not
+
+
+@pytest.mark.gpu
+def test_gpu_extremes_white_against_black_and_sprinkled_zeros():
+    white = _axis_frame(np.full((8, 8, 3), 255, dtype=np.uint8), -100.0, 700.0, 100.0)      # covers [-100, 700)^2
+    black = _axis_frame(np.zeros((8, 8, 3), dtype=np.uint8), -100.0, 700.0, 100.0)
+    case = _case([white, black], [(0, 1, 512, 512, 0.0, 0.0)], 1.0, 0, 512, 1)
+    a, b = _planes(case)
+    status = torch.zeros(1, device=DEV, dtype=torch.int32)
+    _render(case, a, b, status, [0, 1])
+    assert status.item() == 0 and (a == 255).all().item() and (b == 1).all().item()
+    score, best = _search(case, a, b)
+    assert score.tolist() == [[[[66584576, 512 * 512]]]] and 254 * 512 * 512 == 66584576
+    assert best.tolist() == [[0, 0, 66584576, 262144, 0, 0, -1, 0]]
+    # random content with not-seen cells sprinkled into both planes, two pairs of one launch
+    rng = np.random.default_rng(9)
+    A = [np.where(rng.random((72, 72)) < 0.2, 0, rng.integers(1, 256, size=(72, 72))).astype(np.uint8) for _ in range(2)]
+    B = [np.where(rng.random((82, 82)) < 0.3, 0, rng.integers(1, 256, size=(82, 82))).astype(np.uint8) for _ in range(2)]
+    case, a, b = _plane_case(A, B, 70, 45, 5, min_cells=300)
+    score, best = _search(case, a, b)
+    for p in range(2):
+        want = search_oracle(A[p], B[p], 70, 45, 5)
+        np.testing.assert_array_equal(score[p], want)
+        np.testing.assert_array_equal(best[p], pick_oracle(want, 5, 300))
+
+
+@pytest.mark.gpu
+def test_gpu_render_is_order_free():
+    case = _several_pairs()
+    want = _oracle(case)
+    for order in ([[0, 1], [2, 3]], [[3, 2], [1, 0]], [[2], [0], [3], [1]]):
+        a, b = _planes(case)
+        status = torch.zeros(1, device=DEV, dtype=torch.int32)
+        done = set()
+        for resident in order:
+            _render(case, a, b, status, resident)
+            done |= set(resident)
+            now_a, now_b = a.cpu().numpy(), b.cpu().numpy()
+            for p, pr in enumerate(case["pairs"]):                                    # after EVERY call
+                np.testing.assert_array_equal(now_a[p], want["a"][p] if int(pr["frame_a"]) in done else POISON_A)
+                np.testing.assert_array_equal(now_b[p], want["b"][p] if int(pr["frame_b"]) in done else POISON_B)
+        assert status.item() == 0
+
+
+@pytest.mark.gpu
+def test_gpu_bad_residency_is_reported_and_skipped():
+    case = _several_pairs()
+    want = _oracle(case)
+    F = len(case["images"])
+    good = np.arange(F, dtype=np.int32)
+
+    def run(c, slot, images=None):
+        a, b = _planes(c)
+        status = torch.zeros(1, device=DEV, dtype=torch.int32)
+        _render(c, a, b, status, list(range(F)), slot=slot, images=images)
+        return a, b, status.item()
+
+    def check(c, w, a, b, skipped_frames=(), skipped_pairs=()):
+        score, best = _search(c, a, b)
+        a, b = a.cpu().numpy(), b.cpu().numpy()
+        for p, pr in enumerate(c["pairs"]):
+            a_ok = p not in skipped_pairs and int(pr["frame_a"]) not in skipped_frames
+            b_ok = p not in skipped_pairs and int(pr["frame_b"]) not in skipped_frames
+            np.testing.assert_array_equal(a[p], w["a"][p] if a_ok else POISON_A, err_msg=f"A {p}")
+            np.testing.assert_array_equal(b[p], w["b"][p] if b_ok else POISON_B, err_msg=f"B {p}")
+            if a_ok and b_ok:                                                         # the other pairs of the launch are still exact
+                np.testing.assert_array_equal(score[p], w["score"][p], err_msg=f"score {p}")
+                np.testing.assert_array_equal(best[p], w["best"][p], err_msg=f"best {p}")
+        return score, best
+
+    slot = good.copy()
+    slot[2] = F                                                                       # frame 2's slot points past the resident list
+    a, b, status = run(case, slot)
+    assert status == N.REGISTER_BAD_SLOT
+    check(case, want, a, b, skipped_frames={2})
+    slot = good.copy()
+    slot[1] = 3                                                                       # frame 1's slot holds frame 3's descriptor
+    a, b, status = run(case, slot)
+    assert status == N.REGISTER_BAD_SIZE
+    check(case, want, a, b, skipped_frames={1})
+    images = list(case["images"])
+    images[0] = images[0][:-1].copy()                                                 # a resident frame one row short of size_dev
+    a, b, status = run(case, good, images)
+    assert status == N.REGISTER_BAD_SIZE
+    check(case, want, a, b, skipped_frames={0})
+    # bad pairs: a frame index outside the survey, gx = 0, gy past side; the others still exact
+    bad = dict(case, pairs=case["pairs"].copy())
+    bad["pairs"]["frame_b"][0] = F
+    bad["pairs"]["gx"][2] = 0
+    bad["pairs"]["gy"][3] = case["side"] + 1
+    a, b, status = run(bad, good)
+    assert status == N.REGISTER_BAD_PAIR
+    score, best = check(bad, want, a, b, skipped_pairs={0, 2, 3})
+    for p in (2, 3):                                                                  # the search skips them too: score 0, no best
+        assert (score[p] == 0).all() and best[p].tolist() == [0, 0, -1, 0, 0, 0, -1, 0]
+    bad["pairs"]["frame_a"][1] = -1
+    slot = good.copy()
+    slot[0], slot[3] = F + 5, -1                                                      # with a bad slot; a negative slot is not resident
+    a, b, status = run(bad, slot)
+    assert status == N.REGISTER_BAD_PAIR | N.REGISTER_BAD_SLOT
+    check(bad, want, a, b, skipped_frames={0, 3}, skipped_pairs={0, 1, 2, 3})
+
+
+# ---- end to end ------------------------------------------------------------------------------------------------------
+
+SCENE_H, SCENE_W = 400, 500
+DISPLACED = np.array([(3, -2), (-4, 1), (2, 3), (-1, -2)], dtype=F64)                  # whole cells (east, north), zero mean
+ANIMALS = np.array([(x, y) for y in (150.0, 180.0, 210.0) for x in (190.0, 215.0, 240.0, 265.0)])   # 12, >= 25 m apart
+
+
+def _scene(seed=3):
+    """A multi-scale texture: independent uniform fields at 1, 4 and 16 px, mixed per channel."""
+    rng = np.random.default_rng(seed)
+    out = np.zeros((SCENE_H, SCENE_W, 3), dtype=F64)
+    for k, wt in ((1, 0.3), (4, 0.3), (16, 0.4)):
+        field = rng.random((SCENE_H // k + 1, SCENE_W // k + 1, 3))
+        out += wt * np.kron(field, np.ones((k, k, 1)))[:SCENE_H, :SCENE_W]
+    return np.clip(out * 255.0, 0, 255).astype(np.uint8)
+
+
+def _survey():
+    """Four 160 x 200 frames cut from the scene (1 m per pixel; scene pixel (r, c) is the ground [c, c + 1) x [399 - r, 400 - r))
+    through their TRUE georeferences, at yaw 0 / 0 / 180 / 90.  Returns frames, true georef, displaced georef."""
+    scene = _scene()
+    true = np.stack([tiling.nadir_affine(160, 200, c, 1.0, yaw) for c, yaw in
+                     (((200.0, 200.0), 0.0), ((280.0, 220.0), 0.0), ((240.0, 170.0), 180.0), ((250.0, 210.0), 90.0))])
+    yy, xx = np.meshgrid(np.arange(160) + 0.5, np.arange(200) + 0.5, indexing="ij")
+    frames = []
+    for g in true:
+        X = g[0, 0] * xx + g[0, 1] * yy + g[0, 2]
+        Y = g[1, 0] * xx + g[1, 1] * yy + g[1, 2]
+        frames.append(scene[SCENE_H - 1 - np.floor(Y).astype(np.int64), np.floor(X).astype(np.int64)].copy())
+    displaced = true.copy()
+    displaced[:, 0, 2] += DISPLACED[:, 0]
+    displaced[:, 1, 2] += DISPLACED[:, 1]
+    return frames, true, displaced
+
+
+def _detections(true):
+    """Every animal boxed in each frame that sees it through the TRUE georeference."""
+    g2p = tiling.ground_to_pixel(true)
+    out = []
+    for f in range(len(true)):
+        u = g2p[f, 0, 0] * ANIMALS[:, 0] + g2p[f, 0, 1] * ANIMALS[:, 1] + g2p[f, 0, 2]
+        v = g2p[f, 1, 0] * ANIMALS[:, 0] + g2p[f, 1, 1] * ANIMALS[:, 1] + g2p[f, 1, 2]
+        ok = (u >= 4) & (u < 196) & (v >= 4) & (v < 156)
+        boxes = np.stack([u - 3, v - 3, u + 3, v + 3], axis=1)[ok].astype(np.float32)
+        out.append({"boxes": _up(boxes), "scores": _up(np.linspace(0.9, 0.5, ok.sum()).astype(np.float32)),
+                    "labels": torch.ones(int(ok.sum()), device=DEV, dtype=torch.int64)})
+    return out
+
+
+@pytest.mark.gpu
+def test_gpu_register_end_to_end_corrects_the_census():
+    frames, true, displaced = _survey()
+    out = tiling.register(frames, displaced, 1.0, search=8, side=256, min_cells=4096)
+    ab = [(int(p["frame_a"]), int(p["frame_b"])) for p in out["pairs"]]
+    assert ab == [(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)]
+    want = np.array([DISPLACED[b] - DISPLACED[a] for a, b in ab], dtype=np.int64)
+    np.testing.assert_array_equal(out["offset"], want)
+    assert out["accepted"].all() and (out["mean"] == 0.0).all() and (out["runner_up"] > 0).all()
+    assert np.abs(out["shift"] + DISPLACED).max() < 1e-9
+    assert np.abs(out["georef"] - true).max() < 1e-9 and np.abs(out["residual"]).max() < 1e-9
+    assert out["component"].tolist() == [0, 0, 0, 0] and (out["cells"] >= 4096).all()
+    # the device's best equals the oracle's on this input, planes and all
+    case = {"images": frames, "g2p": tiling.ground_to_pixel(displaced).reshape(-1, 6), "size": np.array([(160, 200)] * 4, dtype=np.int32),
+            "pairs": out["pairs"][:2], "cell": 1.0, "search": 8, "side": 256, "min_cells": 4096}
+    _run_and_check(case)
+    # the census: the true count with the corrected georeferences, a larger one with the displaced ones
+    dets = _detections(true)
+    assert sum(len(d["boxes"]) for d in dets) >= 2 * len(ANIMALS)
+    assert tiling.census(dets, out["georef"], 1.5)["count"] == len(ANIMALS) == 12
+    assert tiling.census(dets, displaced, 1.5)["count"] > len(ANIMALS)
+    # a lazy sequence, two pairs at a time: the same result, every frame asked for only while a chunk needs it
+    lazy = _Lazy(frames)
+    again = tiling.register(lazy, displaced, 1.0, sizes=[(160, 200)] * 4, search=8, side=256, min_cells=4096, pair_chunk=2)
+    for key in out:
+        np.testing.assert_array_equal(again[key], out[key], err_msg=key)
+    assert lazy.asked == [0, 1, 2, 0, 1, 2, 3, 1, 2, 3]                              # chunks (0,1)(0,2) | (0,3)(1,2) | (1,3)(2,3)
+    # fixed= pins the gauge: frame 0 stays, the others move relative to it
+    pinned = tiling.register(frames, displaced, 1.0, search=8, side=256, pairs=out["pairs"], fixed=[0])
+    assert np.abs(pinned["shift"] - (DISPLACED[0] - DISPLACED)).max() < 1e-9

@@ -1,0 +1,152 @@
+"""Times of the survey registration (wm_register_render_u8, wm_register_search) against the host route a caller had before.
+
+  python tools/register_time.py [--reps 20] [--oracle-pairs 4] [--only NAME]
+      HIP-event min and median over --reps repetitions of one wm_register_render_u8 call with every frame of the chunk
+      resident (one launch) and of one wm_register_search call (one memset, the search launch, the pick launch) on ONE
+      CHUNK of pairs, as tiling.register issues them (pair_chunk pairs at a time; buffers and frames are allocated once,
+      outside the timed region), and -- for the first --oracle-pairs pairs of the chunk -- the wall clock of the numpy
+      restatement of the rule on the same input (tests/test_register.py: register_oracle), whose planes, score table
+      and best the device's must equal.  The restatement costs seconds per pair at the survey setting, so it runs on a
+      sample and its time for the survey is the sample's mean per byte difference times the survey's byte differences.
+      Two settings, nadir frames of 400 x 600 px (20 x 30 m at 0.05 m) of random content at UTM-sized coordinates on
+      flight lines with 55 % forward overlap and 30 % sidelap, a little jitter in position and heading, cell = 0.05 m:
+        f40      F = 40 (4 lines of 10), side 256, search 16, pair_chunk 64;
+        f1000    F = 1 000 (25 lines of 40), side 512, search 32, pair_chunk 256: about 4 pairs per frame.
+      The search's work is counted from the shapes: (2 S + 1)^2 * gx * gy byte differences per pair.  With the minimum
+      time that is a rate, printed against the VALU bound of the kernel's inner loop: 7 vector instructions per 4 cells
+      and offset (two v_alignbyte_b32, three v_and_b32, v_sad_u8, v_bcnt_u32_b32), 256 CUs x 4 SIMDs x 32 lanes per
+      clock at 2.4 GHz = 78.6e12 lane-instructions per second (MI355X_MICROARCH: a wave64 VALU instruction issues over
+      2 cycles on a SIMD-32), so 44.9e12 byte differences per second.
+      The search is also timed with each of the offsets-per-thread variants K = 1, 2, 4 (WM_REGISTER_K; the result does
+      not depend on K), alternating, next to the default choice.
+      Prints one JSON line.  No figure is a pass mark: the numbers are records.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from wildlifemapper_amd import _native as N  # noqa: E402
+from wildlifemapper_amd import tiling  # noqa: E402
+
+H, W, GSD = 400, 600, 0.05
+VALU_LANE_OPS = 256 * 4 * 32 * 2.4e9          # lane-instructions per second
+LOOP_VALU_PER_4_CELLS = 7
+
+
+def make(lines, per_line, seed):
+    rng = np.random.default_rng(seed)
+    x0, y0 = 500000.1, 6000000.7
+    dx, dy = W * GSD * 0.7, H * GSD * 0.45
+    georef = np.stack([tiling.nadir_affine(H, W, (x0 + l * dx + rng.uniform(-0.5, 0.5), y0 + k * dy + rng.uniform(-0.5, 0.5)), GSD,
+                                           rng.uniform(-3.0, 3.0)) for l in range(lines) for k in range(per_line)])
+    return georef, np.tile(np.array([[H, W]], dtype=np.int32), (lines * per_line, 1))
+
+
+def timed(call, reps):
+    call()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return round(float(np.min(ms)), 4), round(float(np.median(ms)), 4)
+
+
+def run(lines, per_line, side, search, pair_chunk, seed, reps, oracle_pairs):
+    dev = torch.device("cuda:0")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    georef, size = make(lines, per_line, seed)
+    F = georef.shape[0]
+    table = tiling.register_pairs(georef, size, GSD, search, side, 4096)
+    w1 = 2 * search + 1
+    diffs_all = int((table["gx"].astype(np.int64) * table["gy"]).sum()) * w1 * w1
+    chunk = table[:pair_chunk]
+    n = chunk.shape[0]
+    diffs = int((chunk["gx"].astype(np.int64) * chunk["gy"]).sum()) * w1 * w1
+    needed = sorted(set(chunk["frame_a"].tolist()) | set(chunk["frame_b"].tolist()))
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    pixels = torch.randint(0, 256, (len(needed), H, W, 3), device=dev, dtype=torch.uint8, generator=gen)
+    frames = [pixels[k] for k in range(len(needed))]
+    desc = tiling._frame_descs(frames, dev)
+    slot = np.full(F, -1, dtype=np.int32)
+    slot[needed] = np.arange(len(needed), dtype=np.int32)
+    g2p = tiling.ground_to_pixel(georef).reshape(-1, 6)
+    g_d, s_d, slot_d = up(g2p), up(size), up(slot)
+    pairs_d = up(chunk.view(np.uint8).reshape(n, 32))
+    E = side + 2 * search
+    a = torch.zeros((n, side, side), device=dev, dtype=torch.uint8)
+    b = torch.zeros((n, E, E), device=dev, dtype=torch.uint8)
+    status = torch.zeros(1, device=dev, dtype=torch.int32)
+    score = torch.empty((n, w1, w1, 2), device=dev, dtype=torch.int32)
+    best = torch.empty((n, 8), device=dev, dtype=torch.int32)
+    lib, st = N.lib(), N.stream_ptr(dev)
+    render = lambda: N.check(lib.wm_register_render_u8(N.ptr(desc), len(needed), N.ptr(slot_d), N.ptr(g_d), N.ptr(s_d), F, N.ptr(pairs_d), n, GSD,
+                                                       search, side, N.ptr(a), N.ptr(b), N.ptr(status), st))
+    find = lambda: N.check(lib.wm_register_search(N.ptr(a), N.ptr(b), N.ptr(pairs_d), n, search, side, 4096, N.ptr(score), N.ptr(best), st))
+    r_min, r_med = timed(render, reps)
+    s_min, s_med = timed(find, reps)
+    rate = diffs / (s_min * 1e-3)
+    bound = VALU_LANE_OPS / LOOP_VALU_PER_4_CELLS * 4
+    out = {"frames": F, "pairs": int(table.shape[0]), "pairs_per_frame": round(table.shape[0] / F, 2), "side": side, "search": search,
+           "chunk_pairs": n, "chunk_frames": len(needed), "mean_patch_cells": int((chunk["gx"].astype(np.int64) * chunk["gy"]).mean()),
+           "render_ms_min": r_min, "render_ms_median": r_med, "render_cells": n * (side * side + E * E),
+           "search_ms_min": s_min, "search_ms_median": s_med, "search_byte_differences": diffs,
+           "search_byte_differences_per_s": float(f"{rate:.4g}"), "valu_bound_byte_differences_per_s": float(f"{bound:.4g}"),
+           "search_fraction_of_valu_bound": round(rate / bound, 4), "survey_byte_differences": diffs_all,
+           "survey_search_s_at_this_rate": round(diffs_all / rate, 4), "render_status": int(status.item())}
+    by_k = {}
+    for rnd in range(2):                                      # K = 1, 2, 4 alternating, twice
+        for k in (1, 2, 4):
+            os.environ["WM_REGISTER_K"] = str(k)
+            by_k.setdefault(f"k{k}", []).append(timed(find, reps)[0])
+    del os.environ["WM_REGISTER_K"]
+    out["search_ms_min_by_offsets_per_thread"] = by_k
+    find()
+    if oracle_pairs > 0:
+        from test_register import register_oracle
+        m = min(oracle_pairs, n)
+        host = pixels.cpu().numpy()
+        images = {f: host[k] for k, f in enumerate(needed)}
+        t = time.perf_counter()
+        want = register_oracle(g2p, size, images, chunk[:m], GSD, search, side, 4096)
+        took = time.perf_counter() - t
+        sample = int((chunk["gx"][:m].astype(np.int64) * chunk["gy"][:m]).sum()) * w1 * w1
+        out["oracle_pairs"], out["oracle_host_s"] = m, round(took, 2)
+        out["oracle_host_s_for_the_survey_extrapolated"] = round(took / sample * diffs_all, 1)
+        got_a, got_b = a[:m].cpu().numpy(), b[:m].cpu().numpy()
+        got_s, got_best = score[:m].cpu().numpy(), best[:m].cpu().numpy()
+        equal = all(np.array_equal(got_a[p], want["a"][p]) and np.array_equal(got_b[p], want["b"][p]) and
+                    np.array_equal(got_s[p], want["score"][p]) and np.array_equal(got_best[p], want["best"][p]) for p in range(m))
+        out["equals_oracle"] = bool(equal)
+        assert equal, "the device result differs from register_oracle"
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--oracle-pairs", type=int, default=4)
+    ap.add_argument("--only", default=None)
+    a = ap.parse_args()
+    settings = {"f40": (4, 10, 256, 16, 64), "f1000": (25, 40, 512, 32, 256)}
+    out = {"reps": a.reps}
+    for i, (name, (lines, per_line, side, search, chunk)) in enumerate(settings.items()):
+        if a.only in (None, name):
+            out[name] = run(lines, per_line, side, search, chunk, i, a.reps, a.oracle_pairs)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,5 +1,5 @@
 // Image front end: the val-transform resize (plan cache per device), the survey resampler (plan slots per stream), the
-// survey merge launcher, the census launcher, the coverage launchers, the mosaic launchers, the review-chip launcher and the overlay launchers (box outlines, the reference's plot image).
+// survey merge launcher, the census launcher, the coverage launchers, the mosaic launchers, the registration launchers, the review-chip launcher and the overlay launchers (box outlines, the reference's plot image).
 #pragma once
 #include "misc_kernels.h"
 #include "resample_kernels.h"
@@ -7,6 +7,7 @@
 #include "census_kernels.h"
 #include "coverage_kernels.h"
 #include "mosaic_kernels.h"
+#include "register_kernels.h"
 #include "chip_kernels.h"
 #include "overlay_kernels.h"
 #include "host_core.h"
@@ -181,6 +182,89 @@ int launch_mosaic_fill(const wm_frame_desc* frames_dev, int n_resident, const in
                            (const int*)size_dev, n_frames, x0, y0, cell, gx, gy, (const int*)source_dev, north_up, mosaic_dev, (int*)status_dev);
     };
     mode == WM_MOSAIC_NEAREST ? launch(mosaic_fill_kernel<WM_MOSAIC_NEAREST>) : launch(mosaic_fill_kernel<WM_MOSAIC_BILINEAR>);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Survey registration: every argument checked on the host before the first HIP call.  What both entries share.
+static int check_register_shape(const char* name, const wm_register_pair* pairs_dev, int search, int side) {
+    if (search < 0 || search > WM_REGISTER_MAX_SEARCH) return fail("%s: search %d outside 0..%d", name, search, WM_REGISTER_MAX_SEARCH);
+    if (side < 1 || side > WM_REGISTER_MAX_SIDE) return fail("%s: side %d outside 1..%d", name, side, WM_REGISTER_MAX_SIDE);
+    if (!pairs_dev) return fail("%s: null pairs_dev", name);
+    if ((uintptr_t)pairs_dev % 8) return fail("%s: pairs_dev not 8-byte aligned", name);
+    return 0;
+}
+
+int launch_register_render(const wm_frame_desc* frames_dev, int n_resident, const int32_t* slot_dev, const double* g2p_dev,
+                           const int32_t* size_dev, int n_frames, const wm_register_pair* pairs_dev, int n_pairs, double cell, int search,
+                           int side, uint8_t* a_dev, uint8_t* b_dev, int32_t* status_dev, hipStream_t s) {
+    const char* name = "wm_register_render_u8";
+    if (n_pairs < 0 || n_pairs > WM_REGISTER_MAX_PAIRS) return fail("%s: n_pairs %d outside 0..%d", name, n_pairs, WM_REGISTER_MAX_PAIRS);
+    if (n_pairs == 0) return 0;
+    WM_TRY(check_coverage_frames(name, g2p_dev, size_dev, n_frames));
+    if (n_resident < 0 || n_resident > WM_COVERAGE_MAX_FRAMES)
+        return fail("%s: n_resident %d outside 0..%d", name, n_resident, WM_COVERAGE_MAX_FRAMES);
+    if (!(std::isfinite(cell) && cell > 0.0)) return fail("%s: cell %g: need a finite cell > 0", name, cell);
+    WM_TRY(check_register_shape(name, pairs_dev, search, side));
+    if (!a_dev) return fail("%s: null a_dev", name);
+    if (!b_dev) return fail("%s: null b_dev", name);
+    if (!status_dev) return fail("%s: null status_dev", name);
+    if (n_resident > 0 && !frames_dev) return fail("%s: null frames_dev with n_resident %d", name, n_resident);
+    if (n_frames > 0 && !slot_dev) return fail("%s: null slot_dev with n_frames %d", name, n_frames);
+    if ((uintptr_t)frames_dev % 8 || (uintptr_t)slot_dev % 4 || (uintptr_t)status_dev % 4)
+        return fail("%s: frames_dev not 8-byte aligned, or slot_dev / status_dev not 4-byte aligned", name);
+    const int ext = side + 2 * search;
+    const int row_blocks = (ext + REG_RENDER_BLOCK_Y - 1) / REG_RENDER_BLOCK_Y;
+    const dim3 grid((ext + 63) / 64, 2 * row_blocks, n_pairs);                    // y: plane A's blocks of rows, then plane B's
+    hipLaunchKernelGGL(register_render_kernel, grid, dim3(REG_THREADS), 0, s, (const frame_desc*)frames_dev, n_resident, (const int*)slot_dev,
+                       g2p_dev, (const int*)size_dev, n_frames, pairs_dev, cell, search, side, row_blocks, a_dev, b_dev, (int*)status_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Offsets per thread of the search: the largest K of {4, 2, 1} whose blocks of 256 * K offsets leave at most a tenth of
+// their threads without an offset on (2S + 1)^2 offsets (a larger K shares each read of A among more offsets), else 1.
+// WM_REGISTER_K = 1 | 2 | 4 overrides it (tools/register_time.py's A/B; the result does not depend on K).
+static int register_offsets_per_thread(int n_off) {
+    if (const char* e = getenv("WM_REGISTER_K")) {
+        const int k = atoi(e);
+        if (k == 1 || k == 2 || k == 4) return k;
+    }
+    for (int k : {4, 2}) {
+        const int per = REG_THREADS * k, padded = (n_off + per - 1) / per * per;
+        if ((padded - n_off) * 10 <= padded) return k;
+    }
+    return 1;
+}
+
+int launch_register_search(const uint8_t* a_dev, const uint8_t* b_dev, const wm_register_pair* pairs_dev, int n_pairs, int search, int side,
+                           int min_cells, int32_t* score_dev, int32_t* best_dev, hipStream_t s) {
+    const char* name = "wm_register_search";
+    if (n_pairs < 0 || n_pairs > WM_REGISTER_MAX_PAIRS) return fail("%s: n_pairs %d outside 0..%d", name, n_pairs, WM_REGISTER_MAX_PAIRS);
+    if (n_pairs == 0) return 0;
+    WM_TRY(check_register_shape(name, pairs_dev, search, side));
+    if (min_cells < 1) return fail("%s: min_cells %d: need at least 1", name, min_cells);
+    if (!a_dev) return fail("%s: null a_dev", name);
+    if (!b_dev) return fail("%s: null b_dev", name);
+    if (!score_dev) return fail("%s: null score_dev", name);
+    if (!best_dev) return fail("%s: null best_dev", name);
+    if ((uintptr_t)score_dev % 4 || (uintptr_t)best_dev % 4) return fail("%s: score_dev / best_dev not 4-byte aligned", name);
+    const int w1 = 2 * search + 1, n_off = w1 * w1;
+    HIP_TRY(hipMemsetAsync(score_dev, 0, (size_t)n_pairs * n_off * 2 * sizeof(int32_t), s));
+    const int tile_rows = reg_search_lds(search, 32) <= REG_LDS_MAX ? 32 : 16;   // 16 rows fit at every search <= 64
+    static_assert(reg_search_lds(WM_REGISTER_MAX_SEARCH, 16) <= REG_LDS_MAX, "the search's LDS");
+    const int lds = reg_search_lds(search, tile_rows);
+    const int tiles_x = (side + REG_TILE_X - 1) / REG_TILE_X, tiles_y = (side + tile_rows - 1) / tile_rows;
+    const int k = register_offsets_per_thread(n_off);
+    const int off_blocks = (n_off + REG_THREADS * k - 1) / (REG_THREADS * k);
+    const dim3 grid(tiles_x * tiles_y * off_blocks, n_pairs);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(REG_THREADS), lds, s, a_dev, b_dev, pairs_dev, search, side, tile_rows, tiles_x, off_blocks,
+                           (int*)score_dev);
+    };
+    k == 4 ? launch(register_search_kernel<4>) : k == 2 ? launch(register_search_kernel<2>) : launch(register_search_kernel<1>);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(register_best_kernel, dim3(n_pairs), dim3(REG_THREADS), 0, s, (const int*)score_dev, search, min_cells, (int*)best_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -1,0 +1,245 @@
+// Survey registration (include/wm_hip.h, "Survey registration"): every overlapping pair of frames is rendered onto a common
+// ground patch as two uint8 luma planes, and the shift at which they agree is found by an exhaustive integer search.  No
+// reference behaviour exists; the rule is the header's, and the checker is its sequential restatement register_oracle in
+// tests/test_register.py.  The render's arithmetic is the coverage's (IEEE double, one rounding per operation, no
+// contraction); everything after it is integer, so all three kernels equal the oracle bit for bit.
+//
+// register_render_kernel: lane = column, a thread owns REG_RENDER_ROWS cells of one column, blockIdx.z = pair, blockIdx.y =
+// (plane, block of rows).  A plane is written whole or not at all: the pair's and the frame's checks are uniform over the
+// workgroup and come before the first store.  What bounds every read: 0 <= frame < n_frames, 0 <= slot < n_resident, a
+// non-null data pointer, the descriptor's (height, width) equal to size[f], and 0 <= u < width, 0 <= v < height from sees.
+//
+// register_search_kernel, the hot path: (2S+1)^2 * gx * gy byte differences per pair.  A workgroup owns one tile of
+// REG_TILE_X x tile_rows cells of A, the matching tile of B grown by 2S in both axes, and 256 * K consecutive offsets (o =
+// (dy + S) * (2S+1) + (dx + S), lane = consecutive o, so the lanes of a wave read consecutive bytes of one or two B rows).
+// Both tiles sit in LDS as (value dword, mask dword) pairs -- mask byte 0xff where the cell is seen -- so one ds_read_b64
+// fetches four cells with their mask.  A thread walks the tile four cells at a time: the A pair is a broadcast read shared
+// by its K offsets; per offset one new B pair (the previous one is kept: a row is walked with a sliding dword window), two
+// v_alignbyte_b32 to bring B and its mask to A's byte phase, three ANDs (both operands and the mask by (a != 0) & (b != 0),
+// so a cell that either frame does not see adds 0), one v_sad_u8 and one v_bcnt_u32_b32 (8 bits per counted cell).  Tile
+// partials go to score by int32 atomics: two per (tile, offset), against tile_rows * 16 steps of work.
+//
+// register_best_kernel: one workgroup per pair scans score twice with the header's order, which is total (the cross products
+// decide, then the unique key (dy^2 + dx^2, dy, dx)), so the reduction's order is irrelevant.
+#pragma once
+
+#include "mosaic_kernels.h"
+#include "survey_kernels.h"
+
+namespace wm {
+
+constexpr int REG_THREADS = 256;
+constexpr int REG_TILE_X = 64;                    // cells east per tile of the search = 16 dwords
+constexpr int REG_TILE_DW = REG_TILE_X / 4;
+constexpr int REG_RENDER_ROWS = 4;                // cells per thread of the render, consecutive rows of one column
+constexpr int REG_RENDER_BLOCK_Y = (REG_THREADS / 64) * REG_RENDER_ROWS;
+constexpr int REG_LDS_MAX = 64 * 1024;
+
+static_assert(sizeof(wm_register_pair) == 32, "wm_register_pair layout");
+
+__host__ __device__ inline bool reg_pair_ok(const wm_register_pair& pr, int n_frames, int side) {
+    return pr.frame_a >= 0 && pr.frame_a < n_frames && pr.frame_b >= 0 && pr.frame_b < n_frames && pr.gx >= 1 && pr.gx <= side &&
+           pr.gy >= 1 && pr.gy <= side;
+}
+
+// dwords of one staged B row: the tile, 2S cells of halo, and one more dword for the window's look-ahead
+__host__ __device__ constexpr int reg_b_stride(int search) { return (REG_TILE_X + 2 * search + 3) / 4 + 1; }
+__host__ __device__ constexpr int reg_search_lds(int search, int tile_rows) {
+    return (tile_rows * REG_TILE_DW + (tile_rows + 2 * search) * reg_b_stride(search)) * (int)sizeof(uint2);
+}
+
+__global__ __launch_bounds__(REG_THREADS) void register_render_kernel(
+        const frame_desc* __restrict__ frames, int n_resident, const int* __restrict__ slot, const double* __restrict__ g2p,
+        const int* __restrict__ size, int n_frames, const wm_register_pair* __restrict__ pairs, double cell, int search, int side,
+        int row_blocks, unsigned char* __restrict__ a, unsigned char* __restrict__ b, int* __restrict__ status) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p = blockIdx.z;
+    const int plane_b = (int)blockIdx.y >= row_blocks ? 1 : 0;
+    const int rb = (int)blockIdx.y - plane_b * row_blocks;
+    const int s = plane_b ? search : 0;
+    const int ext = side + 2 * s;                                // the plane is ext x ext
+    const int i = blockIdx.x * 64 + lane, j0 = rb * REG_RENDER_BLOCK_Y + wave * REG_RENDER_ROWS;
+    if ((int)blockIdx.x * 64 >= ext || rb * REG_RENDER_BLOCK_Y >= ext) return;
+    const bool reporter = blockIdx.x == 0 && rb == 0 && tid == 0;
+    const wm_register_pair pr = pairs[p];
+    if (!reg_pair_ok(pr, n_frames, side)) { if (reporter) atomicOr(status, WM_REGISTER_BAD_PAIR); return; }
+    const int f = plane_b ? pr.frame_b : pr.frame_a;
+    const int sl = slot[f];
+    if (sl < 0) return;                                          // its frame is not resident in this call
+    if (sl >= n_resident) { if (reporter) atomicOr(status, WM_REGISTER_BAD_SLOT); return; }
+    const frame_desc fd = frames[sl];
+    const int h = size[(size_t)f * 2], w = size[(size_t)f * 2 + 1];
+    if (!fd.data) { if (reporter) atomicOr(status, WM_REGISTER_BAD_SLOT); return; }
+    if (fd.height != h || fd.width != w) { if (reporter) atomicOr(status, WM_REGISTER_BAD_SIZE); return; }
+    if (i >= ext) return;
+    const double* bb = g2p + (size_t)f * 6;
+    const double b1 = bb[1], b2 = bb[2], b4 = bb[4], b5 = bb[5];
+    const double Xc = pr.x0 + ((double)(i - s) + 0.5) * cell;
+    const double bu = bb[0] * Xc, bv = bb[3] * Xc;
+    const double fw = (double)w, fh = (double)h;
+    unsigned char* plane = (plane_b ? b : a) + (size_t)p * ext * ext;
+    const int lim_x = pr.gx + 2 * s, lim_y = pr.gy + 2 * s;
+#pragma unroll
+    for (int r = 0; r < REG_RENDER_ROWS; ++r) {
+        const int j = j0 + r;
+        if (j >= ext) break;
+        unsigned char val = 0;
+        if (i < lim_x && j < lim_y && h >= 1 && w >= 1) {
+            const double Yc = pr.y0 + ((double)(j - s) + 0.5) * cell;
+            double u, v;
+            mos_uv(bu, bv, b1, b2, b4, b5, Yc, u, v);
+            if (0.0 <= u && u < fw && 0.0 <= v && v < fh) {
+                const unsigned char* px = fd.data + ((size_t)(int)floor(v) * w + (int)floor(u)) * 3;
+                const int y = (77 * (int)px[0] + 150 * (int)px[1] + 29 * (int)px[2] + 128) >> 8;
+                val = (unsigned char)max(1, y);                   // 0 is kept for "not seen"
+            }
+        }
+        plane[(size_t)j * ext + i] = val;
+    }
+}
+
+// 0xff in every byte of v that is not 0
+__device__ __forceinline__ unsigned int reg_nonzero_mask(unsigned int v) {
+    unsigned int m = (((v & 0x7f7f7f7fu) + 0x7f7f7f7fu) | v) & 0x80808080u;
+    return (m - (m >> 7)) | m;
+}
+
+// four cells of a plane row starting at column c (bytes of a dword, lowest first); columns >= lim read as 0
+__device__ __forceinline__ unsigned int reg_load4(const unsigned char* __restrict__ row, int c, int lim) {
+    if (c + 3 < lim && (((uintptr_t)(row + c)) & 3) == 0) return *(const unsigned int*)(row + c);
+    unsigned int v = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (c + k < lim) v |= (unsigned int)row[c + k] << (8 * k);
+    return v;
+}
+
+template <int K>
+__global__ __launch_bounds__(REG_THREADS) void register_search_kernel(
+        const unsigned char* __restrict__ a, const unsigned char* __restrict__ b, const wm_register_pair* __restrict__ pairs, int search,
+        int side, int tile_rows, int tiles_x, int off_blocks, int* __restrict__ score) {
+    extern __shared__ uint2 reg_lds[];
+    const int tid = threadIdx.x;
+    const int p = blockIdx.y;
+    const wm_register_pair pr = pairs[p];
+    if (pr.gx < 1 || pr.gx > side || pr.gy < 1 || pr.gy > side) return;      // a bad pair keeps its zeroed score
+    const int ob = (int)blockIdx.x % off_blocks, tile = (int)blockIdx.x / off_blocks;
+    const int i0 = (tile % tiles_x) * REG_TILE_X, j0 = (tile / tiles_x) * tile_rows;
+    if (i0 >= pr.gx || j0 >= pr.gy) return;
+    const int ext = side + 2 * search, w1 = 2 * search + 1, n_off = w1 * w1;
+    const int bs = reg_b_stride(search), b_rows = tile_rows + 2 * search;
+    uint2* sA = reg_lds;                                         // [tile_rows][REG_TILE_DW]
+    uint2* sB = reg_lds + tile_rows * REG_TILE_DW;               // [b_rows][bs]
+    const unsigned char* pa = a + (size_t)p * side * side;
+    const unsigned char* pb = b + (size_t)p * ext * ext;
+
+    for (int e = tid; e < tile_rows * REG_TILE_DW; e += REG_THREADS) {
+        const int r = e / REG_TILE_DW, c = i0 + (e % REG_TILE_DW) * 4, j = j0 + r;
+        const unsigned int v = j < pr.gy ? reg_load4(pa + (size_t)j * side, c, pr.gx) : 0u;       // only cells j < gy, i < gx count
+        sA[e] = make_uint2(v, reg_nonzero_mask(v));
+    }
+    for (int e = tid; e < b_rows * bs; e += REG_THREADS) {
+        const int r = e / bs, c = i0 + (e % bs) * 4, j = j0 + r;
+        const unsigned int v = j < ext ? reg_load4(pb + (size_t)j * ext, c, ext) : 0u;
+        sB[e] = make_uint2(v, reg_nonzero_mask(v));
+    }
+    __syncthreads();
+
+    int o[K], sh[K], sad[K], cnt[K], row_b[K];                   // row_b: an index into sB, so every read stays an LDS read
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        o[k] = (ob * K + k) * REG_THREADS + tid;
+        const int oc = min(o[k], n_off - 1);                     // a thread past the last offset walks the last one and drops it
+        const int dyi = oc / w1, dxi = oc - dyi * w1;
+        sh[k] = dxi & 3;
+        row_b[k] = dyi * bs + (dxi >> 2);
+        sad[k] = 0;
+        cnt[k] = 0;
+    }
+    for (int r = 0; r < tile_rows; ++r) {
+        uint2 lo[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) lo[k] = sB[row_b[k]];
+#pragma unroll
+        for (int c = 0; c < REG_TILE_DW; ++c) {
+            const uint2 av = sA[r * REG_TILE_DW + c];
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const uint2 hi = sB[row_b[k] + c + 1];
+                const unsigned int bv = __builtin_amdgcn_alignbyte(hi.x, lo[k].x, sh[k]);
+                const unsigned int bm = __builtin_amdgcn_alignbyte(hi.y, lo[k].y, sh[k]);
+                sad[k] = (int)__builtin_amdgcn_sad_u8(av.x & bm, bv & av.y, (unsigned int)sad[k]);
+                cnt[k] += __popc(av.y & bm);
+                lo[k] = hi;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) row_b[k] += bs;
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        if (o[k] < n_off && cnt[k]) {
+            int* out = score + ((size_t)p * n_off + o[k]) * 2;
+            if (sad[k]) atomicAdd(out, sad[k]);
+            atomicAdd(out + 1, cnt[k] >> 3);
+        }
+}
+
+struct reg_cand { int sad, n, dy, dx; };                         // n < 0: no candidate
+
+// the header's order: p beats q
+__device__ __forceinline__ bool reg_beats(const reg_cand& p, const reg_cand& q) {
+    if (p.n < 0) return false;
+    if (q.n < 0) return true;
+    const long long l = (long long)p.sad * q.n, r = (long long)q.sad * p.n;
+    if (l != r) return l < r;
+    const int dp = p.dy * p.dy + p.dx * p.dx, dq = q.dy * q.dy + q.dx * q.dx;
+    if (dp != dq) return dp < dq;
+    if (p.dy != q.dy) return p.dy < q.dy;
+    return p.dx < q.dx;
+}
+
+__global__ __launch_bounds__(REG_THREADS) void register_best_kernel(const int* __restrict__ score, int search, int min_cells,
+                                                                     int* __restrict__ best) {
+    __shared__ reg_cand s_wave[REG_THREADS / 64];
+    __shared__ reg_cand s_first;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p = blockIdx.x, w1 = 2 * search + 1, n_off = w1 * w1;
+    const int* sc = score + (size_t)p * n_off * 2;
+    for (int pass = 0; pass < 2; ++pass) {
+        reg_cand first = {-1, -1, 0, 0};
+        if (pass) first = s_first;
+        reg_cand mine = {-1, -1, 0, 0};
+        if (!pass || first.n >= 0)
+            for (int o = tid; o < n_off; o += REG_THREADS) {
+                const reg_cand c = {sc[o * 2], sc[o * 2 + 1], o / w1 - search, o % w1 - search};
+                if (c.n < min_cells) continue;
+                if (pass && max(abs(c.dy - first.dy), abs(c.dx - first.dx)) < 2) continue;
+                if (reg_beats(c, mine)) mine = c;
+            }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const reg_cand other = {__shfl_xor(mine.sad, d), __shfl_xor(mine.n, d), __shfl_xor(mine.dy, d), __shfl_xor(mine.dx, d)};
+            if (reg_beats(other, mine)) mine = other;
+        }
+        if (lane == 0) s_wave[wave] = mine;
+        __syncthreads();
+        if (tid == 0) {
+            reg_cand top = s_wave[0];
+#pragma unroll
+            for (int k = 1; k < REG_THREADS / 64; ++k)
+                if (reg_beats(s_wave[k], top)) top = s_wave[k];
+            int* out = best + (size_t)p * 8 + pass * 4;
+            const bool has = top.n >= 0;
+            out[0] = has ? top.dy : 0;
+            out[1] = has ? top.dx : 0;
+            out[2] = has ? top.sad : -1;
+            out[3] = has ? top.n : 0;
+            s_first = top;
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace wm

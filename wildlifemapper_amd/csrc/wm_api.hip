@@ -252,6 +252,18 @@ extern "C" int wm_mosaic_fill_u8(const wm_frame_desc* frames_dev, int n_resident
                               mosaic_dev, status_dev, (hipStream_t)stream);
 }
 
+extern "C" int wm_register_render_u8(const wm_frame_desc* frames_dev, int n_resident, const int32_t* slot_dev, const double* g2p_dev,
+                                     const int32_t* size_dev, int n_frames, const wm_register_pair* pairs_dev, int n_pairs, double cell,
+                                     int search, int side, uint8_t* a_dev, uint8_t* b_dev, int32_t* status_dev, void* stream) {
+    return launch_register_render(frames_dev, n_resident, slot_dev, g2p_dev, size_dev, n_frames, pairs_dev, n_pairs, cell, search, side,
+                                  a_dev, b_dev, status_dev, (hipStream_t)stream);
+}
+
+extern "C" int wm_register_search(const uint8_t* a_dev, const uint8_t* b_dev, const wm_register_pair* pairs_dev, int n_pairs, int search,
+                                  int side, int min_cells, int32_t* score_dev, int32_t* best_dev, void* stream) {
+    return launch_register_search(a_dev, b_dev, pairs_dev, n_pairs, search, side, min_cells, score_dev, best_dev, (hipStream_t)stream);
+}
+
 extern "C" int wm_crop_chips_u8(const wm_frame_desc* frames_dev, int n_frames, const float* boxes_dev, const int32_t* box_frame_dev, int n,
                                 int chip, float context, int min_side, int max_side, uint8_t* chips_dev, int32_t* windows_dev,
                                 void* stream) {
