@@ -464,8 +464,12 @@ def test_mosaic_symbols_and_abi_13():
         assert int(re.search(r"#define %s (\d+)" % macro, hdr).group(1)) == val
     assert N.MOSAIC_NEAREST != N.MOSAIC_BILINEAR and tiling.MOSAIC_SAMPLES == MODES
     kern = open(os.path.join(ROOT, "wildlifemapper_amd", "csrc", "mosaic_kernels.h")).read()
-    assert '#include "coverage_kernels.h"' in kern and "cov_stage(" in kern and "cov_row_may_touch(" in kern       # shared, not copied
-    assert "cov_stage(CovFrames" not in kern and "asm" not in kern
+    shared = ("cov_stage(", "cov_load_frame(", ".may_touch(", "cov_uv(", "cov_inside(")        # the cull is behind CovBlock::may_touch
+    assert '#include "coverage_kernels.h"' in kern and "CovBlock blk(" in kern and all(call in kern for call in shared)    # shared, not copied
+    assert "cov_stage(CovFrames" not in kern and "struct CovBlock" not in kern and "asm" not in kern
+    assert not re.search(r"(int|bool|void|double)\s+(cov_\w+|may_touch)\s*\(", kern)               # none of them is defined here
+    reg = open(os.path.join(ROOT, "wildlifemapper_amd", "csrc", "register_kernels.h")).read()
+    assert not any(re.search(r"\+\s*b1\s*\*\s*\w+\s*\)\s*\+\s*b2", src) for src in (kern, reg))    # the (u, v) expression lives in coverage_kernels.h only
 
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------

@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "../../include/wm_hip.h"
+#include "survey_kernels.h"                      // frame_desc
 
 namespace wm {
 
@@ -51,7 +52,26 @@ __device__ __forceinline__ bool cov_finite(double d) {
     return ((uint64_t)__double_as_longlong(d) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
 }
 
-// sees(f, X, Y) with the X products given: bu = b0 * X, bv = b3 * X.
+// The centre of cell `index` of one axis of the grid.
+__device__ __forceinline__ double cov_centre(double origin, int index, double cell) {
+#pragma clang fp contract(off)
+    return origin + ((double)index + 0.5) * cell;
+}
+
+// u, v of the rule with the X products given: bu = b0 * X, bv = b3 * X.
+__device__ __forceinline__ void cov_uv(double bu, double bv, double b1, double b2, double b4, double b5, double Y, double& u, double& v) {
+#pragma clang fp contract(off)
+    u = (bu + b1 * Y) + b2;
+    v = (bv + b4 * Y) + b5;
+}
+
+__device__ __forceinline__ bool cov_inside(double u, double v, double w, double h) {
+#pragma clang fp contract(off)
+    return 0.0 <= u && u < w && 0.0 <= v && v < h;
+}
+
+// sees(f, X, Y) with the X products given.  Mirrors cov_uv and cov_inside, statement for statement: built from the two
+// calls, the frame loop of coverage_points_kernel measured slower (profiles/ground_family/).
 __device__ __forceinline__ bool cov_sees(double bu, double bv, double b1, double b2, double b4, double b5, double Y, double w, double h) {
 #pragma clang fp contract(off)
     const double u = (bu + b1 * Y) + b2;
@@ -73,6 +93,60 @@ __device__ __forceinline__ bool cov_row_may_touch(double c0, double c1, double c
     const double lo = cov_min4(p00, p10, p01, p11) - m, hi = cov_max4(p00, p10, p01, p11) + m;
     if (!(cov_finite(p00) && cov_finite(p10) && cov_finite(p01) && cov_finite(p11) && cov_finite(lo) && cov_finite(hi))) return true;
     return !(hi < 0.0 || lo >= extent);
+}
+
+// What a thread of a raster / plan workgroup knows of its block of COV_BLOCK_X x COV_BLOCK_Y cells: its own column i, first
+// row j0 and their centres, and the block's ground rectangle, the centres of its extreme cells by cov_centre itself.
+struct CovBlock {
+    int i, j0;
+    double xl, xh, yl, yh, xm, ym;
+    double Xc, Yc[COV_ROWS];
+
+    __device__ __forceinline__ CovBlock(int lane, int wave, double x0, double y0, double cell, int gx, int gy) {
+#pragma clang fp contract(off)
+        const int i_first = blockIdx.x * COV_BLOCK_X, j_first = blockIdx.y * COV_BLOCK_Y;
+        const int i_last = min(i_first + COV_BLOCK_X, gx) - 1, j_last = min(j_first + COV_BLOCK_Y, gy) - 1;
+        i = i_first + lane, j0 = j_first + wave * COV_ROWS;
+        xl = cov_centre(x0, i_first, cell), xh = cov_centre(x0, i_last, cell);
+        yl = cov_centre(y0, j_first, cell), yh = cov_centre(y0, j_last, cell);
+        xm = fmax(fabs(xl), fabs(xh)), ym = fmax(fabs(yl), fabs(yh));
+        Xc = cov_centre(x0, i, cell);
+#pragma unroll
+        for (int r = 0; r < COV_ROWS; ++r) Yc[r] = cov_centre(y0, j0 + r, cell);
+    }
+
+    // The cull: false only when frame (b, h, w) provably sees no centre of the block.
+    __device__ __forceinline__ bool may_touch(const double (&b)[6], int h, int w) const {
+#pragma clang fp contract(off)
+        return h >= 1 && w >= 1 && cov_row_may_touch(b[0], b[1], b[2], xl, xh, yl, yh, xm, ym, (double)w) &&
+               cov_row_may_touch(b[3], b[4], b[5], xl, xh, yl, yh, xm, ym, (double)h);
+    }
+};
+
+// Frame f's b[6] and (height, width); zeros and false past n_frames.  size is indexed in int on purpose: with (size_t)f * 2
+// the helper's address arithmetic is formed in another order than the kernels' own text gave, and coverage_points_kernel's
+// bytes change (profiles/ground_family/); f < n_frames <= WM_COVERAGE_MAX_FRAMES keeps f * 2 + 1 far inside int.
+static_assert(WM_COVERAGE_MAX_FRAMES <= (1 << 29), "cov_load_frame indexes size[f * 2 + 1] in int");
+__device__ __forceinline__ bool cov_load_frame(const double* __restrict__ g2p, const int* __restrict__ size, int f, int n_frames,
+                                               double (&b)[6], int& h, int& w) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) b[k] = 0.0;
+    h = w = 0;
+    const bool in_range = f < n_frames;
+    if (in_range) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) b[k] = g2p[(size_t)f * 6 + k];
+        h = size[f * 2];
+        w = size[f * 2 + 1];
+    }
+    return in_range;
+}
+
+// The pixel that holds (u, v), for 0 <= u < w, 0 <= v < height.
+__device__ __forceinline__ const unsigned char* cov_nearest_pixel(const frame_desc& fd, int w, double u, double v) {
+#pragma clang fp contract(off)
+    return fd.data + ((size_t)(int)floor(v) * w + (int)floor(u)) * 3;
 }
 
 // Stages the frames of a chunk (one per thread: b, h, w) that pass `keep` into s, compacted by a wave ballot; returns
@@ -111,46 +185,25 @@ __global__ __launch_bounds__(COV_THREADS) void coverage_raster_kernel(
     __shared__ int s_wave[COV_THREADS / 64];
     __shared__ int s_hist[COV_STATS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i_first = blockIdx.x * COV_BLOCK_X, j_first = blockIdx.y * COV_BLOCK_Y;
-    const int i_last = min(i_first + COV_BLOCK_X, gx) - 1, j_last = min(j_first + COV_BLOCK_Y, gy) - 1;
-    const int i = i_first + lane, j0 = j_first + wave * COV_ROWS;
+    const CovBlock blk(lane, wave, x0, y0, cell, gx, gy);
+    const int i = blk.i, j0 = blk.j0;
     if (tid < COV_STATS) s_hist[tid] = 0;
-
-    // the block's ground rectangle: the centres of its extreme cells, by the centre formula itself
-    const double xl = x0 + ((double)i_first + 0.5) * cell, xh = x0 + ((double)i_last + 0.5) * cell;
-    const double yl = y0 + ((double)j_first + 0.5) * cell, yh = y0 + ((double)j_last + 0.5) * cell;
-    const double xm = fmax(fabs(xl), fabs(xh)), ym = fmax(fabs(yl), fabs(yh));
-
-    const double Xc = x0 + ((double)i + 0.5) * cell;
-    double Yc[COV_ROWS];
     int cnt[COV_ROWS];
 #pragma unroll
-    for (int r = 0; r < COV_ROWS; ++r) {
-        Yc[r] = y0 + ((double)(j0 + r) + 0.5) * cell;
-        cnt[r] = 0;
-    }
+    for (int r = 0; r < COV_ROWS; ++r) cnt[r] = 0;
 
     for (int base = 0; base < n_frames; base += COV_CHUNK) {
-        const int f = base + tid;
-        const bool in_range = f < n_frames;
-        double b[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        int h = 0, w = 0;
+        double b[6];
+        int h, w;
         bool keep = false;
-        if (in_range) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) b[k] = g2p[(size_t)f * 6 + k];
-            h = size[(size_t)f * 2];
-            w = size[(size_t)f * 2 + 1];
-            keep = h >= 1 && w >= 1 && cov_row_may_touch(b[0], b[1], b[2], xl, xh, yl, yh, xm, ym, (double)w) &&
-                   cov_row_may_touch(b[3], b[4], b[5], xl, xh, yl, yh, xm, ym, (double)h);
-        }
+        if (cov_load_frame(g2p, size, base + tid, n_frames, b, h, w)) keep = blk.may_touch(b, h, w);
         const int n_s = cov_stage(s, s_wave, keep, b, h, w);
         for (int q = 0; q < n_s; ++q) {
             const double b1 = s.b[1][q], b2 = s.b[2][q], b4 = s.b[4][q], b5 = s.b[5][q];
             const double fw = (double)s.w[q], fh = (double)s.h[q];
-            const double bu = s.b[0][q] * Xc, bv = s.b[3][q] * Xc;
+            const double bu = s.b[0][q] * blk.Xc, bv = s.b[3][q] * blk.Xc;
 #pragma unroll
-            for (int r = 0; r < COV_ROWS; ++r) cnt[r] += cov_sees(bu, bv, b1, b2, b4, b5, Yc[r], fw, fh) ? 1 : 0;
+            for (int r = 0; r < COV_ROWS; ++r) cnt[r] += cov_sees(bu, bv, b1, b2, b4, b5, blk.Yc[r], fw, fh) ? 1 : 0;
         }
         __syncthreads();                                     // the chunk is read before the next one overwrites it
     }
@@ -185,16 +238,9 @@ __global__ __launch_bounds__(COV_THREADS) void coverage_points_kernel(
     const bool finite = cov_finite(X) && cov_finite(Y);
     int seen = 0;
     for (int base = 0; base < n_frames; base += COV_CHUNK) {
-        const int f = base + tid;
-        const bool in_range = f < n_frames;
-        double b[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        int h = 0, w = 0;
-        if (in_range) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) b[k] = g2p[(size_t)f * 6 + k];
-            h = size[(size_t)f * 2];
-            w = size[(size_t)f * 2 + 1];
-        }
+        double b[6];
+        int h, w;
+        const bool in_range = cov_load_frame(g2p, size, base + tid, n_frames, b, h, w);
         const int n_s = cov_stage(s, s_wave, in_range && h >= 1 && w >= 1, b, h, w);
         if (finite)
             for (int q = 0; q < n_s; ++q)

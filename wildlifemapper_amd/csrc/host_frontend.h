@@ -1,273 +1,11 @@
-// Image front end: the val-transform resize (plan cache per device), the survey resampler (plan slots per stream), the
-// survey merge launcher, the census launcher, the coverage launchers, the mosaic launchers, the registration launchers, the review-chip launcher and the overlay launchers (box outlines, the reference's plot image).
+// Image front end: the val-transform resize (plan cache per device) and the survey resampler (plan slots per stream).
+// The survey launchers are in host_survey.h.
 #pragma once
 #include "misc_kernels.h"
 #include "resample_kernels.h"
-#include "survey_kernels.h"
-#include "census_kernels.h"
-#include "coverage_kernels.h"
-#include "mosaic_kernels.h"
-#include "register_kernels.h"
-#include "chip_kernels.h"
-#include "overlay_kernels.h"
 #include "host_core.h"
 
 namespace {
-
-static_assert(sizeof(wm_frame_desc) == sizeof(frame_desc), "wm_frame_desc layout");
-
-// Argument checks and launches of both merge modes; `thr_name` is the threshold's name in error messages.
-template <int MODE>
-static int launch_merge_frames(const char* name, const char* thr_name, const wm_box_record* records_dev, const int32_t* origins_dev,
-                               const int32_t* frame_tile_offsets, int n_frames, float thr, void* scratch_dev, int64_t scratch_bytes,
-                               wm_box_record* merged_dev, wm_box_record* det_dev, int32_t* det_tile_dev, int32_t* det_count_dev,
-                               int32_t* det_members_dev, int32_t* slot_det_dev, void* stream) {
-    if (!records_dev || !origins_dev || !frame_tile_offsets || !scratch_dev || !merged_dev || !det_dev || !det_tile_dev || !det_count_dev)
-        return fail("%s: null buffer", name);
-    if (MODE == MF_FUSE && (!det_members_dev || !slot_det_dev)) return fail("%s: null buffer", name);
-    if (n_frames <= 0) return fail("%s: n_frames %d", name, n_frames);
-    if (!(thr >= 0.f && thr < 1.f)) return fail("%s: %s %g outside [0, 1)", name, thr_name, (double)thr);
-    if (frame_tile_offsets[0] != 0) return fail("%s: frame_tile_offsets[0] = %d, not 0", name, frame_tile_offsets[0]);
-    for (int f = 0; f < n_frames; ++f)
-        if (frame_tile_offsets[f + 1] <= frame_tile_offsets[f])
-            return fail("%s: frame_tile_offsets not strictly increasing at frame %d (%d -> %d)", name, f, frame_tile_offsets[f],
-                        frame_tile_offsets[f + 1]);
-    const int n_tiles = frame_tile_offsets[n_frames];
-    const int64_t need = wm_merge_frames_scratch_bytes(n_tiles);
-    if (need < 0) return -1;
-    if (scratch_bytes < need) return fail("%s: scratch of %lld bytes, %lld needed", name, (long long)scratch_bytes, (long long)need);
-    if ((uintptr_t)scratch_dev % 16) return fail("%s: scratch not 16-byte aligned", name);
-    for (int f0 = 0; f0 < n_frames; f0 += MF_MAX_FRAMES) {
-        const int nf = std::min(MF_MAX_FRAMES, n_frames - f0);
-        mf_offsets offs;
-        for (int f = 0; f <= nf; ++f) offs.tile[f] = frame_tile_offsets[f0 + f];
-        hipLaunchKernelGGL(merge_frames_nms_kernel<MODE>, dim3(nf), dim3(MF_THREADS), 0, (hipStream_t)stream, records_dev,
-                           (const int*)origins_dev, offs, thr, (char*)scratch_dev, n_tiles * WM_NUM_QUERIES, merged_dev, det_dev,
-                           (int*)det_tile_dev, (int*)det_count_dev, (int*)det_members_dev, (int*)slot_det_dev, f0);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
-}
-
-// Survey census: every argument is checked on the host before the first HIP call; one launch of one workgroup.
-int64_t census_scratch_bytes(int n) {
-    if (n < 0 || n > WM_CENSUS_MAX_DETS) return fail("wm_census_scratch_bytes: n %d outside 0..%d", n, WM_CENSUS_MAX_DETS);
-    return CENSUS_HEADER + (int64_t)n * CENSUS_SCRATCH_PER_DET;
-}
-
-int launch_census(const float* boxes_dev, const float* scores_dev, const int32_t* labels_dev, const int32_t* box_frame_dev, int n,
-                  const double* georef_dev, int n_frames, double radius, int flags, void* scratch_dev, int64_t scratch_bytes,
-                  double* points_dev, int32_t* individual_dev, int32_t* keeper_dev, int32_t* members_dev, int32_t* count_dev,
-                  hipStream_t s) {
-    const char* name = "wm_census";
-    if (n < 0 || n > WM_CENSUS_MAX_DETS) return fail("%s: n %d outside 0..%d", name, n, WM_CENSUS_MAX_DETS);
-    if (n == 0) return 0;
-    if (!boxes_dev || !scores_dev || !labels_dev || !box_frame_dev || !georef_dev || !scratch_dev || !points_dev || !individual_dev ||
-        !keeper_dev || !members_dev || !count_dev)
-        return fail("%s: null buffer", name);
-    if (n_frames <= 0) return fail("%s: n_frames %d", name, n_frames);
-    if (!(std::isfinite(radius) && radius >= 0.0)) return fail("%s: radius %g: need a finite radius >= 0", name, radius);
-    const double r2 = radius * radius;
-    if (!std::isfinite(r2)) return fail("%s: radius %g: its square is not finite", name, radius);
-    if (flags & ~WM_CENSUS_SAME_CLASS) return fail("%s: flags 0x%x", name, (unsigned)flags);
-    const int64_t need = census_scratch_bytes(n);
-    if (scratch_bytes < need) return fail("%s: scratch of %lld bytes, %lld needed", name, (long long)scratch_bytes, (long long)need);
-    if ((uintptr_t)scratch_dev % 16) return fail("%s: scratch not 16-byte aligned", name);
-    if ((uintptr_t)boxes_dev % 16 || (uintptr_t)points_dev % 16 || (uintptr_t)georef_dev % 8)
-        return fail("%s: boxes_dev / points_dev not 16-byte aligned, or georef_dev not 8-byte aligned", name);
-    hipLaunchKernelGGL(census_kernel, dim3(1), dim3(MF_THREADS), 0, s, (const float4*)boxes_dev, scores_dev, (const int*)labels_dev,
-                       (const int*)box_frame_dev, n, georef_dev, n_frames, radius, r2, flags & WM_CENSUS_SAME_CLASS, (char*)scratch_dev,
-                       (double2*)points_dev, (int*)individual_dev, (int*)keeper_dev, (int*)members_dev, (int*)count_dev);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// Survey coverage: every argument is checked on the host before the first HIP call.  The grid of both entries.
-static int check_coverage_grid(const char* name, double x0, double y0, double cell, int gx, int gy) {
-    if (!std::isfinite(x0)) return fail("%s: x0 %g is not finite", name, x0);
-    if (!std::isfinite(y0)) return fail("%s: y0 %g is not finite", name, y0);
-    if (!(std::isfinite(cell) && cell > 0.0)) return fail("%s: cell %g: need a finite cell > 0", name, cell);
-    if (gx < 1 || gx > WM_COVERAGE_MAX_SIDE) return fail("%s: gx %d outside 1..%d", name, gx, WM_COVERAGE_MAX_SIDE);
-    if (gy < 1 || gy > WM_COVERAGE_MAX_SIDE) return fail("%s: gy %d outside 1..%d", name, gy, WM_COVERAGE_MAX_SIDE);
-    if ((int64_t)gx * gy > WM_COVERAGE_MAX_CELLS)
-        return fail("%s: gx * gy = %lld cells exceed %d", name, (long long)gx * gy, WM_COVERAGE_MAX_CELLS);
-    return 0;
-}
-
-static int check_coverage_frames(const char* name, const double* g2p_dev, const int32_t* size_dev, int n_frames) {
-    if (n_frames < 0 || n_frames > WM_COVERAGE_MAX_FRAMES) return fail("%s: n_frames %d outside 0..%d", name, n_frames, WM_COVERAGE_MAX_FRAMES);
-    if (n_frames > 0 && (!g2p_dev || !size_dev)) return fail("%s: null g2p_dev / size_dev with n_frames %d", name, n_frames);
-    if ((uintptr_t)g2p_dev % 8 || (uintptr_t)size_dev % 4) return fail("%s: g2p_dev not 8-byte aligned, or size_dev not 4-byte aligned", name);
-    return 0;
-}
-
-int launch_coverage_raster(const double* g2p_dev, const int32_t* size_dev, int n_frames, double x0, double y0, double cell, int gx,
-                           int gy, uint16_t* coverage_dev, int64_t* stats_dev, hipStream_t s) {
-    const char* name = "wm_coverage_raster";
-    WM_TRY(check_coverage_frames(name, g2p_dev, size_dev, n_frames));
-    WM_TRY(check_coverage_grid(name, x0, y0, cell, gx, gy));
-    if (!coverage_dev || !stats_dev) return fail("%s: null coverage_dev / stats_dev", name);
-    if ((uintptr_t)coverage_dev % 2 || (uintptr_t)stats_dev % 8) return fail("%s: coverage_dev not 2-byte aligned, or stats_dev not 8-byte aligned", name);
-    HIP_TRY(hipMemsetAsync(stats_dev, 0, COV_STATS * sizeof(int64_t), s));
-    const dim3 grid((gx + COV_BLOCK_X - 1) / COV_BLOCK_X, (gy + COV_BLOCK_Y - 1) / COV_BLOCK_Y);
-    hipLaunchKernelGGL(coverage_raster_kernel, grid, dim3(COV_THREADS), 0, s, g2p_dev, (const int*)size_dev, n_frames, x0, y0, cell, gx, gy,
-                       coverage_dev, (unsigned long long*)stats_dev);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int launch_coverage_points(const double* g2p_dev, const int32_t* size_dev, int n_frames, const double* points_dev,
-                           const int32_t* labels_dev, int n_points, double x0, double y0, double cell, int gx, int gy,
-                           int32_t* seen_by_dev, int32_t* cell_dev, int32_t* counts_dev, int64_t* pstats_dev, hipStream_t s) {
-    const char* name = "wm_coverage_points";
-    if (n_points < 0 || n_points > WM_CENSUS_MAX_DETS) return fail("%s: n_points %d outside 0..%d", name, n_points, WM_CENSUS_MAX_DETS);
-    if (n_points == 0) return 0;
-    WM_TRY(check_coverage_frames(name, g2p_dev, size_dev, n_frames));
-    WM_TRY(check_coverage_grid(name, x0, y0, cell, gx, gy));
-    if (!points_dev || !labels_dev || !seen_by_dev || !cell_dev || !pstats_dev) return fail("%s: null buffer", name);
-    if ((uintptr_t)points_dev % 8 || (uintptr_t)pstats_dev % 8 || (uintptr_t)labels_dev % 4 || (uintptr_t)seen_by_dev % 4 ||
-        (uintptr_t)cell_dev % 4 || (uintptr_t)counts_dev % 4)
-        return fail("%s: points_dev / pstats_dev not 8-byte aligned, or an int32 buffer not 4-byte aligned", name);
-    HIP_TRY(hipMemsetAsync(pstats_dev, 0, 2 * sizeof(int64_t), s));
-    if (counts_dev) HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)COV_CLASSES * gx * gy * sizeof(int32_t), s));
-    hipLaunchKernelGGL(coverage_points_kernel, dim3((n_points + COV_THREADS - 1) / COV_THREADS), dim3(COV_THREADS), 0, s, g2p_dev,
-                       (const int*)size_dev, n_frames, points_dev, (const int*)labels_dev, n_points, x0, y0, cell, gx, gy, (int*)seen_by_dev,
-                       (int*)cell_dev, (int*)counts_dev, (unsigned long long*)pstats_dev);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// Survey mosaic: the coverage's grid and frame checks, every argument checked on the host before the first HIP call.
-int launch_mosaic_plan(const double* g2p_dev, const int32_t* size_dev, int n_frames, double x0, double y0, double cell, int gx, int gy,
-                       int32_t* source_dev, int32_t* won_dev, int64_t* stats_dev, hipStream_t s) {
-    const char* name = "wm_mosaic_plan";
-    WM_TRY(check_coverage_frames(name, g2p_dev, size_dev, n_frames));
-    WM_TRY(check_coverage_grid(name, x0, y0, cell, gx, gy));
-    if (!source_dev) return fail("%s: null source_dev", name);
-    if (!stats_dev) return fail("%s: null stats_dev", name);
-    if (n_frames > 0 && !won_dev) return fail("%s: null won_dev with n_frames %d", name, n_frames);
-    if ((uintptr_t)source_dev % 4 || (uintptr_t)won_dev % 4 || (uintptr_t)stats_dev % 8)
-        return fail("%s: source_dev / won_dev not 4-byte aligned, or stats_dev not 8-byte aligned", name);
-    HIP_TRY(hipMemsetAsync(stats_dev, 0, 2 * sizeof(int64_t), s));
-    if (n_frames > 0) HIP_TRY(hipMemsetAsync(won_dev, 0, (size_t)n_frames * sizeof(int32_t), s));
-    const dim3 grid((gx + COV_BLOCK_X - 1) / COV_BLOCK_X, (gy + COV_BLOCK_Y - 1) / COV_BLOCK_Y);
-    hipLaunchKernelGGL(mosaic_plan_kernel, grid, dim3(COV_THREADS), 0, s, g2p_dev, (const int*)size_dev, n_frames, x0, y0, cell, gx, gy,
-                       (int*)source_dev, (int*)won_dev, (unsigned long long*)stats_dev);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int launch_mosaic_fill(const wm_frame_desc* frames_dev, int n_resident, const int32_t* slot_dev, const double* g2p_dev,
-                       const int32_t* size_dev, int n_frames, double x0, double y0, double cell, int gx, int gy, const int32_t* source_dev,
-                       int mode, int flags, uint8_t* mosaic_dev, int32_t* status_dev, hipStream_t s) {
-    const char* name = "wm_mosaic_fill_u8";
-    WM_TRY(check_coverage_frames(name, g2p_dev, size_dev, n_frames));
-    if (n_resident < 0 || n_resident > WM_COVERAGE_MAX_FRAMES)
-        return fail("%s: n_resident %d outside 0..%d", name, n_resident, WM_COVERAGE_MAX_FRAMES);
-    WM_TRY(check_coverage_grid(name, x0, y0, cell, gx, gy));
-    if (mode != WM_MOSAIC_NEAREST && mode != WM_MOSAIC_BILINEAR) return fail("%s: mode %d is neither WM_MOSAIC_NEAREST nor WM_MOSAIC_BILINEAR", name, mode);
-    if (flags & ~WM_MOSAIC_NORTH_UP) return fail("%s: flags 0x%x", name, (unsigned)flags);
-    if (!source_dev) return fail("%s: null source_dev", name);
-    if (!mosaic_dev) return fail("%s: null mosaic_dev", name);
-    if (!status_dev) return fail("%s: null status_dev", name);
-    if (n_frames > 0 && n_resident > 0 && !frames_dev) return fail("%s: null frames_dev with n_resident %d", name, n_resident);
-    if (n_frames > 0 && n_resident > 0 && !slot_dev) return fail("%s: null slot_dev with n_frames %d", name, n_frames);
-    if ((uintptr_t)frames_dev % 8 || (uintptr_t)slot_dev % 4 || (uintptr_t)source_dev % 4 || (uintptr_t)status_dev % 4)
-        return fail("%s: frames_dev not 8-byte aligned, or slot_dev / source_dev / status_dev not 4-byte aligned", name);
-    if (n_frames == 0 || n_resident == 0) return 0;                   // no source can be resident: nothing is written
-    const dim3 grid((gx + COV_BLOCK_X - 1) / COV_BLOCK_X, (gy + MOS_FILL_BLOCK_Y - 1) / MOS_FILL_BLOCK_Y);
-    const int north_up = flags & WM_MOSAIC_NORTH_UP;
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(COV_THREADS), 0, s, (const frame_desc*)frames_dev, n_resident, (const int*)slot_dev, g2p_dev,
-                           (const int*)size_dev, n_frames, x0, y0, cell, gx, gy, (const int*)source_dev, north_up, mosaic_dev, (int*)status_dev);
-    };
-    mode == WM_MOSAIC_NEAREST ? launch(mosaic_fill_kernel<WM_MOSAIC_NEAREST>) : launch(mosaic_fill_kernel<WM_MOSAIC_BILINEAR>);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// Survey registration: every argument checked on the host before the first HIP call.  What both entries share.
-static int check_register_shape(const char* name, const wm_register_pair* pairs_dev, int search, int side) {
-    if (search < 0 || search > WM_REGISTER_MAX_SEARCH) return fail("%s: search %d outside 0..%d", name, search, WM_REGISTER_MAX_SEARCH);
-    if (side < 1 || side > WM_REGISTER_MAX_SIDE) return fail("%s: side %d outside 1..%d", name, side, WM_REGISTER_MAX_SIDE);
-    if (!pairs_dev) return fail("%s: null pairs_dev", name);
-    if ((uintptr_t)pairs_dev % 8) return fail("%s: pairs_dev not 8-byte aligned", name);
-    return 0;
-}
-
-int launch_register_render(const wm_frame_desc* frames_dev, int n_resident, const int32_t* slot_dev, const double* g2p_dev,
-                           const int32_t* size_dev, int n_frames, const wm_register_pair* pairs_dev, int n_pairs, double cell, int search,
-                           int side, uint8_t* a_dev, uint8_t* b_dev, int32_t* status_dev, hipStream_t s) {
-    const char* name = "wm_register_render_u8";
-    if (n_pairs < 0 || n_pairs > WM_REGISTER_MAX_PAIRS) return fail("%s: n_pairs %d outside 0..%d", name, n_pairs, WM_REGISTER_MAX_PAIRS);
-    if (n_pairs == 0) return 0;
-    WM_TRY(check_coverage_frames(name, g2p_dev, size_dev, n_frames));
-    if (n_resident < 0 || n_resident > WM_COVERAGE_MAX_FRAMES)
-        return fail("%s: n_resident %d outside 0..%d", name, n_resident, WM_COVERAGE_MAX_FRAMES);
-    if (!(std::isfinite(cell) && cell > 0.0)) return fail("%s: cell %g: need a finite cell > 0", name, cell);
-    WM_TRY(check_register_shape(name, pairs_dev, search, side));
-    if (!a_dev) return fail("%s: null a_dev", name);
-    if (!b_dev) return fail("%s: null b_dev", name);
-    if (!status_dev) return fail("%s: null status_dev", name);
-    if (n_resident > 0 && !frames_dev) return fail("%s: null frames_dev with n_resident %d", name, n_resident);
-    if (n_frames > 0 && !slot_dev) return fail("%s: null slot_dev with n_frames %d", name, n_frames);
-    if ((uintptr_t)frames_dev % 8 || (uintptr_t)slot_dev % 4 || (uintptr_t)status_dev % 4)
-        return fail("%s: frames_dev not 8-byte aligned, or slot_dev / status_dev not 4-byte aligned", name);
-    const int ext = side + 2 * search;
-    const int row_blocks = (ext + REG_RENDER_BLOCK_Y - 1) / REG_RENDER_BLOCK_Y;
-    const dim3 grid((ext + 63) / 64, 2 * row_blocks, n_pairs);                    // y: plane A's blocks of rows, then plane B's
-    hipLaunchKernelGGL(register_render_kernel, grid, dim3(REG_THREADS), 0, s, (const frame_desc*)frames_dev, n_resident, (const int*)slot_dev,
-                       g2p_dev, (const int*)size_dev, n_frames, pairs_dev, cell, search, side, row_blocks, a_dev, b_dev, (int*)status_dev);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// Offsets per thread of the search: the largest K of {4, 2, 1} whose blocks of 256 * K offsets leave at most a tenth of
-// their threads without an offset on (2S + 1)^2 offsets (a larger K shares each read of A among more offsets), else 1.
-// WM_REGISTER_K = 1 | 2 | 4 overrides it (tools/register_time.py's A/B; the result does not depend on K).
-static int register_offsets_per_thread(int n_off) {
-    if (const char* e = getenv("WM_REGISTER_K")) {
-        const int k = atoi(e);
-        if (k == 1 || k == 2 || k == 4) return k;
-    }
-    for (int k : {4, 2}) {
-        const int per = REG_THREADS * k, padded = (n_off + per - 1) / per * per;
-        if ((padded - n_off) * 10 <= padded) return k;
-    }
-    return 1;
-}
-
-int launch_register_search(const uint8_t* a_dev, const uint8_t* b_dev, const wm_register_pair* pairs_dev, int n_pairs, int search, int side,
-                           int min_cells, int32_t* score_dev, int32_t* best_dev, hipStream_t s) {
-    const char* name = "wm_register_search";
-    if (n_pairs < 0 || n_pairs > WM_REGISTER_MAX_PAIRS) return fail("%s: n_pairs %d outside 0..%d", name, n_pairs, WM_REGISTER_MAX_PAIRS);
-    if (n_pairs == 0) return 0;
-    WM_TRY(check_register_shape(name, pairs_dev, search, side));
-    if (min_cells < 1) return fail("%s: min_cells %d: need at least 1", name, min_cells);
-    if (!a_dev) return fail("%s: null a_dev", name);
-    if (!b_dev) return fail("%s: null b_dev", name);
-    if (!score_dev) return fail("%s: null score_dev", name);
-    if (!best_dev) return fail("%s: null best_dev", name);
-    if ((uintptr_t)score_dev % 4 || (uintptr_t)best_dev % 4) return fail("%s: score_dev / best_dev not 4-byte aligned", name);
-    const int w1 = 2 * search + 1, n_off = w1 * w1;
-    HIP_TRY(hipMemsetAsync(score_dev, 0, (size_t)n_pairs * n_off * 2 * sizeof(int32_t), s));
-    const int tile_rows = reg_search_lds(search, 32) <= REG_LDS_MAX ? 32 : 16;   // 16 rows fit at every search <= 64
-    static_assert(reg_search_lds(WM_REGISTER_MAX_SEARCH, 16) <= REG_LDS_MAX, "the search's LDS");
-    const int lds = reg_search_lds(search, tile_rows);
-    const int tiles_x = (side + REG_TILE_X - 1) / REG_TILE_X, tiles_y = (side + tile_rows - 1) / tile_rows;
-    const int k = register_offsets_per_thread(n_off);
-    const int off_blocks = (n_off + REG_THREADS * k - 1) / (REG_THREADS * k);
-    const dim3 grid(tiles_x * tiles_y * off_blocks, n_pairs);
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(REG_THREADS), lds, s, a_dev, b_dev, pairs_dev, search, side, tile_rows, tiles_x, off_blocks,
-                           (int*)score_dev);
-    };
-    k == 4 ? launch(register_search_kernel<4>) : k == 2 ? launch(register_search_kernel<2>) : launch(register_search_kernel<1>);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(register_best_kernel, dim3(n_pairs), dim3(REG_THREADS), 0, s, (const int*)score_dev, search, min_cells, (int*)best_dev);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
 
 // ---- N1: val transform resize (PIL bilinear semantics) + normalise + pad ----
 // augmentation.py:80-99 (get_size_with_aspect_ratio): (w, h), size, max_size -> (oh, ow)
@@ -498,81 +236,6 @@ int resample_impl(const uint8_t* in_dev, int height, int width, uint8_t* out_dev
                            (const int*)(pl->dev + pl->off_ky), pl->ksy, (int64_t)out_width * 3);
         HIP_TRY(hipGetLastError());
     }
-    return 0;
-}
-
-// ---- survey review chips: one PIL-exact crop per detection, windows and coefficients derived on the device ----
-static_assert(CHIP_MAX_SIDE == WM_CHIP_MAX_SIDE, "WM_CHIP_MAX_SIDE");
-
-// the arguments wm_chip_window and wm_crop_chips_u8 share
-int check_chip_rule(const char* name, float context, int min_side, int max_side) {
-    if (!(context >= 1.f && context <= 8.f)) return fail("%s: context %g outside [1, 8]", name, (double)context);
-    if (min_side < 1 || min_side > max_side || max_side > WM_CHIP_MAX_SIDE)
-        return fail("%s: min_side %d, max_side %d: need 1 <= min_side <= max_side <= %d", name, min_side, max_side, WM_CHIP_MAX_SIDE);
-    return 0;
-}
-
-// Weightless and asynchronous: no handle, no scratch, no allocation, no table upload.
-int launch_crop_chips(const wm_frame_desc* frames_dev, int n_frames, const float* boxes_dev, const int32_t* box_frame_dev, int n, int chip,
-                      float context, int min_side, int max_side, uint8_t* chips_dev, int32_t* windows_dev, hipStream_t s) {
-    const char* name = "wm_crop_chips_u8";
-    if (n < 0) return fail("%s: n %d", name, n);
-    if (n == 0) return 0;
-    if (!frames_dev || !boxes_dev || !chips_dev) return fail("%s: null buffer", name);
-    if (n_frames <= 0) return fail("%s: n_frames %d", name, n_frames);
-    if (chip < 16 || chip > 256 || chip % 4) return fail("%s: chip %d: need a multiple of 4 in 16..256", name, chip);
-    if ((uintptr_t)chips_dev % 4) return fail("%s: chips_dev not 4-byte aligned", name);
-    WM_TRY(check_chip_rule(name, context, min_side, max_side));
-    const int64_t grid = (int64_t)n * ((chip + CHIP_BAND_ROWS - 1) / CHIP_BAND_ROWS);
-    if (grid > INT32_MAX) return fail("%s: n %d chips of %d rows exceed one launch", name, n, chip);
-    const int lds = chip_lds_bytes(chip, max_side);           // <= 54 KiB at chip 256, max_side 1024
-    hipLaunchKernelGGL(crop_chips_kernel, dim3((unsigned)grid), dim3(256), lds, s, (const frame_desc*)frames_dev, n_frames, boxes_dev,
-                       (const int*)box_frame_dev, chip, context, min_side, max_side, chips_dev, (int*)windows_dev);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// ---- survey overlays: box outlines drawn in place, and the reference's tile preparation ----
-static_assert(DRAW_MAX_WIDTH == WM_DRAW_MAX_WIDTH && DRAW_MAX_PALETTE == WM_DRAW_MAX_PALETTE, "WM_DRAW_*");
-static_assert(PLOT_MAX_PARTS * 2 * sizeof(float) == WM_PLOT_SCRATCH_BYTES, "WM_PLOT_SCRATCH_BYTES");
-
-// Weightless and asynchronous: no handle, no scratch, no allocation.
-int launch_draw_boxes(const wm_frame_desc* frames_dev, int n_frames, const float* boxes_dev, const int32_t* labels_dev,
-                      const int32_t* box_frame_dev, int n, const uint8_t* palette_dev, int palette_size, int width, hipStream_t s) {
-    const char* name = "wm_draw_boxes_u8";
-    if (n < 0) return fail("%s: n %d", name, n);
-    if (n == 0) return 0;
-    if (!frames_dev || !boxes_dev || !labels_dev || !palette_dev) return fail("%s: null buffer", name);
-    if (n_frames <= 0) return fail("%s: n_frames %d", name, n_frames);
-    if (width < 1 || width > WM_DRAW_MAX_WIDTH) return fail("%s: width %d outside 1..%d", name, width, WM_DRAW_MAX_WIDTH);
-    if (palette_size < 1 || palette_size > WM_DRAW_MAX_PALETTE)
-        return fail("%s: palette_size %d outside 1..%d", name, palette_size, WM_DRAW_MAX_PALETTE);
-    hipLaunchKernelGGL(draw_boxes_kernel, dim3((unsigned)n, DRAW_SLICES), dim3(256), 0, s, (const frame_desc*)frames_dev, n_frames, boxes_dev,
-                       (const int*)labels_dev, (const int*)box_frame_dev, n, palette_dev, palette_size, width);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// Two launches on `s`: the partial (min, max) pairs of every image into the caller's scratch, then the map.
-int launch_plot_image(const float* in_dev, int batch, int height, int width, uint8_t* out_dev, void* scratch_dev, int64_t scratch_bytes,
-                      hipStream_t s) {
-    const char* name = "wm_plot_image_u8";
-    if (batch < 0) return fail("%s: batch %d", name, batch);
-    if (batch == 0) return 0;
-    if (!in_dev || !out_dev || !scratch_dev) return fail("%s: null buffer", name);
-    if (height <= 0 || width <= 0) return fail("%s: height %d, width %d", name, height, width);
-    if (batch > 65535) return fail("%s: batch %d exceeds one launch (65535)", name, batch);
-    if ((uintptr_t)in_dev % 4 || (uintptr_t)scratch_dev % 4) return fail("%s: in_dev or scratch_dev not 4-byte aligned", name);
-    if (scratch_bytes < (int64_t)batch * WM_PLOT_SCRATCH_BYTES)
-        return fail("%s: scratch of %lld bytes, %lld needed", name, (long long)scratch_bytes, (long long)batch * WM_PLOT_SCRATCH_BYTES);
-    const int64_t hw = (int64_t)height * width;
-    const int vec = hw % 4 == 0 && (uintptr_t)in_dev % 16 == 0 && (uintptr_t)out_dev % 4 == 0;
-    const int parts = (int)std::max<int64_t>(1, std::min<int64_t>(PLOT_MAX_PARTS, (3 * hw + 4095) / 4096));
-    hipLaunchKernelGGL(plot_minmax_kernel, dim3(parts, batch), dim3(256), 0, s, in_dev, 3 * hw, (float*)scratch_dev, vec);
-    HIP_TRY(hipGetLastError());
-    const unsigned blocks = grid_for((hw + 3) / 4, 256 * 4, 1024);
-    hipLaunchKernelGGL(plot_map_kernel, dim3(blocks, batch), dim3(256), 0, s, in_dev, hw, (const float*)scratch_dev, parts, out_dev, vec);
-    HIP_TRY(hipGetLastError());
     return 0;
 }
 

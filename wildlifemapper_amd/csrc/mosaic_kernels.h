@@ -3,7 +3,8 @@
 // index -- and fetches that frame's pixel.  No reference behaviour exists; the rule is the header's, and the checker is its
 // sequential restatement mosaic_oracle in tests/test_mosaic.py.  All arithmetic is IEEE double with one rounding per
 // operation (no contraction), so both kernels equal the oracle bit for bit.  The grid, the centres, the staging and the
-// cull are the coverage's (coverage_kernels.h: cov_row_may_touch, cov_stage, CovFrames), included, not copied.
+// cull are the coverage's (coverage_kernels.h: CovBlock, whose may_touch is the two cov_row_may_touch() calls, cov_load_frame,
+// cov_stage, cov_uv, cov_inside), included, not copied.
 //
 // mosaic_plan_kernel, geometry only: the shape of coverage_raster_kernel.  A workgroup of COV_THREADS owns COV_BLOCK_X x
 // COV_BLOCK_Y cells, lane = column, a thread owns COV_ROWS cells of one column; the frames are staged through LDS in
@@ -34,13 +35,6 @@ namespace wm {
 constexpr int MOS_FILL_ROWS = 4;                                  // cells per thread of the fill, consecutive rows of one column
 constexpr int MOS_FILL_BLOCK_Y = (COV_THREADS / 64) * MOS_FILL_ROWS;
 
-// u, v of the rule with the X products given (bu = b0 * X, bv = b3 * X), as cov_sees forms them.
-__device__ __forceinline__ void mos_uv(double bu, double bv, double b1, double b2, double b4, double b5, double Y, double& u, double& v) {
-#pragma clang fp contract(off)
-    u = (bu + b1 * Y) + b2;
-    v = (bv + b4 * Y) + b5;
-}
-
 __global__ __launch_bounds__(COV_THREADS) void mosaic_plan_kernel(
         const double* __restrict__ g2p, const int* __restrict__ size, int n_frames, double x0, double y0, double cell, int gx, int gy,
         int* __restrict__ source, int* __restrict__ won, unsigned long long* __restrict__ stats) {
@@ -50,38 +44,22 @@ __global__ __launch_bounds__(COV_THREADS) void mosaic_plan_kernel(
     __shared__ int s_wave[COV_THREADS / 64];
     __shared__ int s_with[COV_THREADS / 64], s_without[COV_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i_first = blockIdx.x * COV_BLOCK_X, j_first = blockIdx.y * COV_BLOCK_Y;
-    const int i_last = min(i_first + COV_BLOCK_X, gx) - 1, j_last = min(j_first + COV_BLOCK_Y, gy) - 1;
-    const int i = i_first + lane, j0 = j_first + wave * COV_ROWS;
-
-    // the block's ground rectangle: the centres of its extreme cells, by the centre formula itself
-    const double xl = x0 + ((double)i_first + 0.5) * cell, xh = x0 + ((double)i_last + 0.5) * cell;
-    const double yl = y0 + ((double)j_first + 0.5) * cell, yh = y0 + ((double)j_last + 0.5) * cell;
-    const double xm = fmax(fabs(xl), fabs(xh)), ym = fmax(fabs(yl), fabs(yh));
-
-    const double Xc = x0 + ((double)i + 0.5) * cell;
-    double Yc[COV_ROWS], best[COV_ROWS];
+    const CovBlock blk(lane, wave, x0, y0, cell, gx, gy);
+    const int i = blk.i, j0 = blk.j0;
+    double best[COV_ROWS];
     int src[COV_ROWS];
 #pragma unroll
     for (int r = 0; r < COV_ROWS; ++r) {
-        Yc[r] = y0 + ((double)(j0 + r) + 0.5) * cell;
         best[r] = __longlong_as_double(0x7ff0000000000000ll);    // +inf: the first frame that sees the cell is smaller
         src[r] = -1;
     }
 
     for (int base = 0; base < n_frames; base += COV_CHUNK) {
         const int f = base + tid;
-        double b[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        int h = 0, w = 0;
+        double b[6];
+        int h, w;
         bool keep = false;
-        if (f < n_frames) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) b[k] = g2p[(size_t)f * 6 + k];
-            h = size[(size_t)f * 2];
-            w = size[(size_t)f * 2 + 1];
-            keep = h >= 1 && w >= 1 && cov_row_may_touch(b[0], b[1], b[2], xl, xh, yl, yh, xm, ym, (double)w) &&
-                   cov_row_may_touch(b[3], b[4], b[5], xl, xh, yl, yh, xm, ym, (double)h);
-        }
+        if (cov_load_frame(g2p, size, f, n_frames, b, h, w)) keep = blk.may_touch(b, h, w);
         int slot_f = -1;
         const int n_s = cov_stage(s, s_wave, keep, b, h, w, &slot_f);
         if (slot_f >= 0) s_idx[slot_f] = f;                  // the frame's index beside it, in the slot cov_stage gave it
@@ -90,15 +68,15 @@ __global__ __launch_bounds__(COV_THREADS) void mosaic_plan_kernel(
             const double b1 = s.b[1][q], b2 = s.b[2][q], b4 = s.b[4][q], b5 = s.b[5][q];
             const double fw = (double)s.w[q], fh = (double)s.h[q];
             const double cu = 0.5 * fw, cv = 0.5 * fh;
-            const double bu = s.b[0][q] * Xc, bv = s.b[3][q] * Xc;
+            const double bu = s.b[0][q] * blk.Xc, bv = s.b[3][q] * blk.Xc;
             const int fq = s_idx[q];
 #pragma unroll
             for (int r = 0; r < COV_ROWS; ++r) {
                 double u, v;
-                mos_uv(bu, bv, b1, b2, b4, b5, Yc[r], u, v);
+                cov_uv(bu, bv, b1, b2, b4, b5, blk.Yc[r], u, v);
                 const double du = u - cu, dv = v - cv;
                 const double e = du * du + dv * dv;
-                if (0.0 <= u && u < fw && 0.0 <= v && v < fh && e < best[r]) {
+                if (0.0 <= u && u < fw && 0.0 <= v && v < fh && e < best[r]) {     // mirrors cov_inside (coverage_kernels.h)
                     best[r] = e;
                     src[r] = fq;
                 }
@@ -166,7 +144,7 @@ __device__ __forceinline__ bool mos_cell(const frame_desc* __restrict__ frames, 
 #pragma clang fp contract(off)
     if (f < 0) return false;                                 // no frame saw the cell
     if (f >= n_frames) { bad |= WM_MOSAIC_BAD_SOURCE; return false; }
-    const int sl = slot[f];
+    const int sl = slot[f];                                  // the residency chain: register_render_kernel mirrors it, statement for statement
     if (sl < 0) return false;                                // its frame is not resident in this call
     if (sl >= n_resident) { bad |= WM_MOSAIC_BAD_SLOT; return false; }
     const frame_desc fd = frames[sl];
@@ -175,10 +153,10 @@ __device__ __forceinline__ bool mos_cell(const frame_desc* __restrict__ frames, 
     if (fd.height != h || fd.width != w) { bad |= WM_MOSAIC_BAD_SIZE; return false; }
     const double* b = g2p + (size_t)f * 6;
     double u, v;
-    mos_uv(b[0] * Xc, b[3] * Xc, b[1], b[2], b[4], b[5], Y, u, v);
-    if (!(0.0 <= u && u < (double)w && 0.0 <= v && v < (double)h)) { bad |= WM_MOSAIC_BAD_SOURCE; return false; }   // not the plan's source
+    cov_uv(b[0] * Xc, b[3] * Xc, b[1], b[2], b[4], b[5], Y, u, v);
+    if (!cov_inside(u, v, (double)w, (double)h)) { bad |= WM_MOSAIC_BAD_SOURCE; return false; }   // not the plan's source
     if (MODE == WM_MOSAIC_NEAREST) {
-        const unsigned char* p = fd.data + ((size_t)(int)floor(v) * w + (int)floor(u)) * 3;
+        const unsigned char* p = cov_nearest_pixel(fd, w, u, v);
         px[0] = p[0];
         px[1] = p[1];
         px[2] = p[2];
@@ -212,7 +190,7 @@ __global__ __launch_bounds__(COV_THREADS) void mosaic_fill_kernel(
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i_first = blockIdx.x * COV_BLOCK_X;
     const int i = i_first + lane, j0 = blockIdx.y * MOS_FILL_BLOCK_Y + wave * MOS_FILL_ROWS;
-    const double Xc = x0 + ((double)i + 0.5) * cell;
+    const double Xc = cov_centre(x0, i, cell);
     int bad = 0;
 #pragma unroll
     for (int r = 0; r < MOS_FILL_ROWS; ++r) {
@@ -220,7 +198,7 @@ __global__ __launch_bounds__(COV_THREADS) void mosaic_fill_kernel(
         if (j >= gy) break;                                  // wave-uniform
         unsigned char px[3] = {0, 0, 0};
         const bool wr = i < gx && mos_cell<MODE>(frames, n_resident, slot, g2p, size, n_frames, source[(size_t)j * gx + i], Xc,
-                                                 y0 + ((double)j + 0.5) * cell, bad, px);
+                                                 cov_centre(y0, j, cell), bad, px);
         unsigned char* row = mosaic + ((size_t)(north_up ? gy - 1 - j : j) * gx + i_first) * 3;
         if (__ballot(wr) == ~0ull && ((uintptr_t)row & 3) == 0) {
             unsigned char* sb = (unsigned char*)s_row[wave];

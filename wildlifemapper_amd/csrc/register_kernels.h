@@ -36,6 +36,7 @@ constexpr int REG_RENDER_BLOCK_Y = (REG_THREADS / 64) * REG_RENDER_ROWS;
 constexpr int REG_LDS_MAX = 64 * 1024;
 
 static_assert(sizeof(wm_register_pair) == 32, "wm_register_pair layout");
+static_assert(WM_REGISTER_BAD_SLOT == WM_MOSAIC_BAD_SLOT && WM_REGISTER_BAD_SIZE == WM_MOSAIC_BAD_SIZE, "the two residency chains set the same bits");
 
 __host__ __device__ inline bool reg_pair_ok(const wm_register_pair& pr, int n_frames, int side) {
     return pr.frame_a >= 0 && pr.frame_a < n_frames && pr.frame_b >= 0 && pr.frame_b < n_frames && pr.gx >= 1 && pr.gx <= side &&
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(REG_THREADS) void register_render_kernel(
     const wm_register_pair pr = pairs[p];
     if (!reg_pair_ok(pr, n_frames, side)) { if (reporter) atomicOr(status, WM_REGISTER_BAD_PAIR); return; }
     const int f = plane_b ? pr.frame_b : pr.frame_a;
-    const int sl = slot[f];
+    const int sl = slot[f];                                      // the residency chain: mirrors mos_cell (mosaic_kernels.h), statement for statement
     if (sl < 0) return;                                          // its frame is not resident in this call
     if (sl >= n_resident) { if (reporter) atomicOr(status, WM_REGISTER_BAD_SLOT); return; }
     const frame_desc fd = frames[sl];
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(REG_THREADS) void register_render_kernel(
     if (i >= ext) return;
     const double* bb = g2p + (size_t)f * 6;
     const double b1 = bb[1], b2 = bb[2], b4 = bb[4], b5 = bb[5];
-    const double Xc = pr.x0 + ((double)(i - s) + 0.5) * cell;
+    const double Xc = cov_centre(pr.x0, i - s, cell);
     const double bu = bb[0] * Xc, bv = bb[3] * Xc;
     const double fw = (double)w, fh = (double)h;
     unsigned char* plane = (plane_b ? b : a) + (size_t)p * ext * ext;
@@ -86,11 +87,10 @@ __global__ __launch_bounds__(REG_THREADS) void register_render_kernel(
         if (j >= ext) break;
         unsigned char val = 0;
         if (i < lim_x && j < lim_y && h >= 1 && w >= 1) {
-            const double Yc = pr.y0 + ((double)(j - s) + 0.5) * cell;
             double u, v;
-            mos_uv(bu, bv, b1, b2, b4, b5, Yc, u, v);
-            if (0.0 <= u && u < fw && 0.0 <= v && v < fh) {
-                const unsigned char* px = fd.data + ((size_t)(int)floor(v) * w + (int)floor(u)) * 3;
+            cov_uv(bu, bv, b1, b2, b4, b5, cov_centre(pr.y0, j - s, cell), u, v);
+            if (cov_inside(u, v, fw, fh)) {
+                const unsigned char* px = cov_nearest_pixel(fd, w, u, v);
                 const int y = (77 * (int)px[0] + 150 * (int)px[1] + 29 * (int)px[2] + 128) >> 8;
                 val = (unsigned char)max(1, y);                   // 0 is kept for "not seen"
             }

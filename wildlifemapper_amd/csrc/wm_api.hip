@@ -12,6 +12,7 @@
 #include "host_encoder.h"
 #include "host_decoder.h"
 #include "host_frontend.h"
+#include "host_survey.h"
 #include "host_criterion.h"
 
 extern "C" const char* wm_last_error(void) { return g_err; }

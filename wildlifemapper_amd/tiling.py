@@ -973,6 +973,61 @@ def _survey_grid(georef, sizes, cell, bounds, what: str):
     return g, s, cell, x0, y0, gx, gy
 
 
+def _survey_device(what: str, pts=None) -> torch.device:
+    """The device of coverage(), mosaic() and register(): that of the census' points when they are given, else the current one."""
+    if pts is not None:
+        if not pts.is_cuda:
+            raise RuntimeError(f"{what}: census['points'] is on {pts.device}; the HIP path needs a ROCm device tensor "
+                               "(there is no CPU fallback in wildlifemapper_amd)")
+        return pts.device
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{what}: no GPU is present; the HIP path needs a ROCm device tensor "
+                           "(there is no CPU fallback in wildlifemapper_amd)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _pinned_upload(a: np.ndarray, dev: torch.device) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(dev, non_blocking=True)
+
+
+def _frame_tables(g: np.ndarray, s: np.ndarray, dev: torch.device):
+    """The kernels' g2p (F,6) float64 and sizes (F,2) int32 on dev, through pinned memory; (None, None) when there is no frame."""
+    if not g.shape[0]:
+        return None, None
+    return _pinned_upload(ground_to_pixel(g).reshape(-1, 6), dev), _pinned_upload(s, dev)
+
+
+def _frame_sequence(frames, sizes, what: str, indexed_for: str):
+    """The frames of mosaic() and register(): a sequence that is only indexed.  Returns (len(frames), sizes); sizes None is
+    inferred only from a list or tuple of tensors or arrays, whose shapes cost nothing."""
+    if not (hasattr(frames, "__getitem__") and hasattr(frames, "__len__")):
+        raise ValueError(f"{what}: frames must be a sequence that can be indexed (frames[i], len), got {type(frames).__name__}")
+    if sizes is None:
+        if not isinstance(frames, (list, tuple)) or not all(isinstance(fr, (torch.Tensor, np.ndarray)) for fr in frames):
+            raise ValueError(f"{what}: sizes is required when frames is not a list of tensors or arrays (a lazy sequence is only "
+                             f"indexed for {indexed_for})")
+        if any(fr.ndim != 3 for fr in frames):
+            raise ValueError(f"{what}: frames: expected (H,W,3) uint8 tensors or arrays")
+        sizes = np.array([tuple(fr.shape[:2]) for fr in frames], dtype=np.int64).reshape(-1, 2)
+    return len(frames), sizes
+
+
+def _resident_chunk(frames, ids, s: np.ndarray, dev: torch.device, what: str):
+    """Makes the frames `ids` (ascending) resident for one fill or render launch: frames[i] is indexed once each, in that
+    order, host frames go up through pinned memory, and a shape that disagrees with s raises ValueError naming the frame.
+    Returns (descriptors, the (F,) slot table, the frames), all on dev; the caller drops them after its launch."""
+    resident = []
+    for i in ids:
+        on_dev, on_host = _as_frame_array(frames[i], i, dev, what)
+        fr = on_dev if on_dev is not None else on_host.pin_memory().to(dev, non_blocking=True)
+        if tuple(fr.shape[:2]) != tuple(int(v) for v in s[i]):
+            raise ValueError(f"{what}: frame {i} is {tuple(fr.shape[:2])}, sizes says {tuple(int(v) for v in s[i])}")
+        resident.append(fr)
+    slot = np.full(s.shape[0], -1, dtype=np.int32)
+    slot[ids] = np.arange(len(ids), dtype=np.int32)
+    return _frame_descs(resident, dev), _pinned_upload(slot, dev), resident
+
+
 def coverage(georef, sizes, cell, census=None, bounds=None) -> Dict[str, object]:
     """The ground a survey saw (wm_coverage_raster, wm_coverage_points; rule: include/wm_hip.h).  georef (F,2,3) float64 as
     for census() (pixel -> ground; inverted on the host by ground_to_pixel), sizes (F,2) (height, width) of the frames in
@@ -1014,22 +1069,10 @@ def coverage(georef, sizes, cell, census=None, bounds=None) -> Dict[str, object]
             raise ValueError(f"{what}: {pts.shape[0]} individuals exceed {CENSUS_MAX_DETS}")
         if labels.device != pts.device or members.device != pts.device:
             raise ValueError(f"{what}: census tensors are on different devices")
-        if not pts.is_cuda:
-            raise RuntimeError(f"{what}: census['points'] is on {pts.device}; the HIP path needs a ROCm device tensor "
-                               "(there is no CPU fallback in wildlifemapper_amd)")
-        dev = pts.device
-    else:
-        if not torch.cuda.is_available():
-            raise RuntimeError(f"{what}: no GPU is present; the HIP path needs a ROCm device tensor "
-                               "(there is no CPU fallback in wildlifemapper_amd)")
-        dev = torch.device("cuda", torch.cuda.current_device())
-    b = ground_to_pixel(g)
+    dev = _survey_device(what, pts)
     lib = N.lib()
     with torch.cuda.device(dev):
-        g_d = s_d = None                                      # no frames: nothing to upload, an all-zero raster
-        if F:
-            g_d = torch.from_numpy(np.ascontiguousarray(b.reshape(-1, 6))).pin_memory().to(dev, non_blocking=True)
-            s_d = torch.from_numpy(s).pin_memory().to(dev, non_blocking=True)
+        g_d, s_d = _frame_tables(g, s, dev)                   # no frames: nothing to upload, an all-zero raster
         cov16 = torch.empty((gy, gx), device=dev, dtype=torch.int16)
         stats = torch.empty(N.COVERAGE_STATS, device=dev, dtype=torch.int64)
         N.check(lib.wm_coverage_raster(N.ptr(g_d), N.ptr(s_d), F, x0, y0, cell, gx, gy, N.ptr(cov16), N.ptr(stats), N.stream_ptr(dev)))
@@ -1074,25 +1117,12 @@ def _check_whole(value, what: str, name: str, lo: int = 1) -> int:
     return int(value)
 
 
-def _mosaic_device(what: str, dev=None) -> torch.device:
-    if dev is not None:
-        return dev
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{what}: no GPU is present; the HIP path needs a ROCm device tensor "
-                           "(there is no CPU fallback in wildlifemapper_amd)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _mosaic_plan(g, s, cell, x0, y0, gx, gy, dev):
     """wm_mosaic_plan on validated arguments.  Returns the plan's dict and the device copies of g2p and sizes."""
     F = g.shape[0]
-    b = ground_to_pixel(g)
     with torch.cuda.device(dev):
-        g_d = s_d = won = None                                # no frames: nothing to upload, an all -1 raster
-        if F:
-            g_d = torch.from_numpy(np.ascontiguousarray(b.reshape(-1, 6))).pin_memory().to(dev, non_blocking=True)
-            s_d = torch.from_numpy(s).pin_memory().to(dev, non_blocking=True)
-            won = torch.empty(F, device=dev, dtype=torch.int32)
+        g_d, s_d = _frame_tables(g, s, dev)                   # no frames: nothing to upload, an all -1 raster
+        won = torch.empty(F, device=dev, dtype=torch.int32) if F else None
         source = torch.empty((gy, gx), device=dev, dtype=torch.int32)
         stats = torch.empty(2, device=dev, dtype=torch.int64)
         N.check(N.lib().wm_mosaic_plan(N.ptr(g_d), N.ptr(s_d), F, x0, y0, cell, gx, gy, N.ptr(source), N.ptr(won), N.ptr(stats),
@@ -1114,7 +1144,7 @@ def mosaic_plan(georef, sizes, cell, bounds=None) -> Dict[str, object]:
       'origin' (x0, y0), 'cell', 'shape' (gy, gx); 'gap_cells' int, the cells without a source."""
     what = "mosaic_plan"
     g, s, cell, x0, y0, gx, gy = _survey_grid(georef, sizes, cell, bounds, what)
-    return _mosaic_plan(g, s, cell, x0, y0, gx, gy, _mosaic_device(what))[0]
+    return _mosaic_plan(g, s, cell, x0, y0, gx, gy, _survey_device(what))[0]
 
 
 def resampled_georef(georef, size, new_size) -> np.ndarray:
@@ -1203,24 +1233,12 @@ def mosaic(frames, georef, cell, sizes=None, bounds=None, sample: str = "bilinea
         if not all(isinstance(t, torch.Tensor) for t in (pts, labels)) or pts.dim() != 2 or pts.shape[1] != 2 or \
                 pts.dtype != torch.float64 or tuple(labels.shape) != (pts.shape[0],) or labels.device != pts.device:
             raise ValueError(f"{what}: census: expected 'points' (k,2) float64 and 'labels' (k,) tensors on one device")
-    if not (hasattr(frames, "__getitem__") and hasattr(frames, "__len__")):
-        raise ValueError(f"{what}: frames must be a sequence that can be indexed (frames[i], len), got {type(frames).__name__}")
-    n_given = len(frames)
-    if sizes is None:
-        if not isinstance(frames, (list, tuple)) or not all(isinstance(fr, (torch.Tensor, np.ndarray)) for fr in frames):
-            raise ValueError(f"{what}: sizes is required when frames is not a list of tensors or arrays (a lazy sequence is only "
-                             "indexed for the frames that won a cell)")
-        if any(fr.ndim != 3 for fr in frames):
-            raise ValueError(f"{what}: frames: expected (H,W,3) uint8 tensors or arrays")
-        sizes = np.array([tuple(fr.shape[:2]) for fr in frames], dtype=np.int64).reshape(-1, 2)
+    n_given, sizes = _frame_sequence(frames, sizes, what, "the frames that won a cell")
     g, s, cell, x0, y0, gx, gy = _survey_grid(georef, sizes, cell, bounds, what)
     F = g.shape[0]
     if n_given != F:
         raise ValueError(f"{what}: {n_given} frames for {F} georeferences")
-    if pts is not None and not pts.is_cuda:
-        raise RuntimeError(f"{what}: census['points'] is on {pts.device}; the HIP path needs a ROCm device tensor "
-                           "(there is no CPU fallback in wildlifemapper_amd)")
-    dev = _mosaic_device(what, None if pts is None else pts.device)
+    dev = _survey_device(what, pts)
     out, g_d, s_d = _mosaic_plan(g, s, cell, x0, y0, gx, gy, dev)
     lib = N.lib()
     mode, flags = MOSAIC_SAMPLES[sample], N.MOSAIC_NORTH_UP if north_up else 0
@@ -1230,17 +1248,7 @@ def mosaic(frames, georef, cell, sizes=None, bounds=None, sample: str = "bilinea
         winners = torch.nonzero(out["won"] > 0).flatten().cpu().tolist()
         for c0 in range(0, len(winners), chunk):
             ids = winners[c0:c0 + chunk]
-            resident = []
-            for i in ids:
-                on_dev, on_host = _as_frame_array(frames[i], i, dev, what)
-                fr = on_dev if on_dev is not None else on_host.pin_memory().to(dev, non_blocking=True)
-                if tuple(fr.shape[:2]) != tuple(int(v) for v in s[i]):
-                    raise ValueError(f"{what}: frame {i} is {tuple(fr.shape[:2])}, sizes says {tuple(int(v) for v in s[i])}")
-                resident.append(fr)
-            slot = np.full(F, -1, dtype=np.int32)
-            slot[ids] = np.arange(len(ids), dtype=np.int32)
-            slot_d = torch.from_numpy(slot).pin_memory().to(dev, non_blocking=True)
-            desc = _frame_descs(resident, dev)
+            desc, slot_d, resident = _resident_chunk(frames, ids, s, dev, what)
             N.check(lib.wm_mosaic_fill_u8(N.ptr(desc), len(ids), N.ptr(slot_d), N.ptr(g_d), N.ptr(s_d), F, x0, y0, cell, gx, gy,
                                           N.ptr(out["source"]), mode, flags, N.ptr(picture), N.ptr(status), N.stream_ptr(dev)))
             del resident, desc, slot_d                        # the stream orders their reuse after the launch
@@ -1466,16 +1474,7 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
             raise TypeError
     except (TypeError, ValueError):
         raise ValueError(f"{what}: min_ratio {min_ratio!r} must be a finite number >= 0") from None
-    if not (hasattr(frames, "__getitem__") and hasattr(frames, "__len__")):
-        raise ValueError(f"{what}: frames must be a sequence that can be indexed (frames[i], len), got {type(frames).__name__}")
-    n_given = len(frames)
-    if sizes is None:
-        if not isinstance(frames, (list, tuple)) or not all(isinstance(fr, (torch.Tensor, np.ndarray)) for fr in frames):
-            raise ValueError(f"{what}: sizes is required when frames is not a list of tensors or arrays (a lazy sequence is only "
-                             "indexed for the frames of the current chunk of pairs)")
-        if any(fr.ndim != 3 for fr in frames):
-            raise ValueError(f"{what}: frames: expected (H,W,3) uint8 tensors or arrays")
-        sizes = np.array([tuple(fr.shape[:2]) for fr in frames], dtype=np.int64).reshape(-1, 2)
+    n_given, sizes = _frame_sequence(frames, sizes, what, "the frames of the current chunk of pairs")
     cell = _check_cell(cell, what)
     g = _check_georef(georef, what)
     s = _check_sizes(sizes, g.shape[0], what)
@@ -1490,34 +1489,22 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
     best = np.zeros((P, 8), dtype=np.int32)
     best[:, 2] = best[:, 6] = -1
     if P:
-        dev = _mosaic_device(what)
+        dev = _survey_device(what)
         lib = N.lib()
-        b = ground_to_pixel(g)
         E = side + 2 * search
         with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(dev, non_blocking=True)
-            g_d, s_d = up(b.reshape(-1, 6)), up(s)
+            g_d, s_d = _frame_tables(g, s, dev)
             status = torch.zeros(1, device=dev, dtype=torch.int32)
             for c0 in range(0, P, pair_chunk):
                 chunk = table[c0:c0 + pair_chunk]
                 n = chunk.shape[0]
-                pairs_d = up(chunk.view(np.uint8).reshape(n, REGISTER_PAIR.itemsize))
+                pairs_d = _pinned_upload(chunk.view(np.uint8).reshape(n, REGISTER_PAIR.itemsize), dev)
                 plane_a = torch.empty((n, side, side), device=dev, dtype=torch.uint8)
                 plane_b = torch.empty((n, E, E), device=dev, dtype=torch.uint8)
                 needed = sorted(set(chunk["frame_a"].tolist()) | set(chunk["frame_b"].tolist()))
                 for f0 in range(0, len(needed), _REGISTER_FRAMES_RESIDENT):
                     ids = needed[f0:f0 + _REGISTER_FRAMES_RESIDENT]
-                    resident = []
-                    for i in ids:
-                        on_dev, on_host = _as_frame_array(frames[i], i, dev, what)
-                        fr = on_dev if on_dev is not None else on_host.pin_memory().to(dev, non_blocking=True)
-                        if tuple(fr.shape[:2]) != tuple(int(v) for v in s[i]):
-                            raise ValueError(f"{what}: frame {i} is {tuple(fr.shape[:2])}, sizes says {tuple(int(v) for v in s[i])}")
-                        resident.append(fr)
-                    slot = np.full(F, -1, dtype=np.int32)
-                    slot[ids] = np.arange(len(ids), dtype=np.int32)
-                    slot_d = up(slot)
-                    desc = _frame_descs(resident, dev)
+                    desc, slot_d, resident = _resident_chunk(frames, ids, s, dev, what)
                     N.check(lib.wm_register_render_u8(N.ptr(desc), len(ids), N.ptr(slot_d), N.ptr(g_d), N.ptr(s_d), F, N.ptr(pairs_d), n,
                                                       cell, search, side, N.ptr(plane_a), N.ptr(plane_b), N.ptr(status), N.stream_ptr(dev)))
                     del resident, desc, slot_d                    # the stream orders their reuse after the launch
