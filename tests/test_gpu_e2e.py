@@ -952,6 +952,111 @@ def test_input_pipeline_resize_bit_exact_vs_pil(golden_dir):
         tiles_from_u8(torch.zeros(1, 2000, 2000, 3, dtype=torch.uint8, device=G.dev()), resize=(1100, 0))
 
 
+# N1 on the column-blocked horizontal kernel and the resampler's plan slots: (h, w, size, max_size) -> (oh, ow) and what the
+# shape is there for.  Three frames per shape, so the horizontal pass sees rows of more than one image.
+N1_SHAPES = [((150, 225, 43, 64), (43, 64)),        # 9 taps, row bytes % 4 = 3
+             ((23, 771, 11, None), (11, 368)),      # 7 taps, row bytes % 4 = 1, OPT = 2
+             ((30, 1050, 20, None), (20, 700)),     # 5 taps, row bytes % 4 = 2, OPT = 3
+             ((16, 4096, 4, None), (4, 1024)),      # 9 taps, OPT = 4: the widest N1 output
+             ((114, 171, 16, 24), (16, 24)),        # 17 taps: KMAX = 20
+             ((40, 600, 4, None), (4, 60)),         # 21 taps: the generic horizontal kernel
+             ((30, 1049, 20, None), (20, 699)),     # ow % 4 = 3: the generic vertical kernel
+             ((21, 37, 30, None), (30, 52)),        # upsampling
+             ((64, 64, 64, None), (64, 64))]        # both passes skipped: preprocess_u8_kernel alone
+_n1_cache = {}
+
+
+def _n1_case(i):
+    """(frames uint8 [3, h, w, 3], expected canvas fp32 [3, 3, 1024, 1024]) of N1_SHAPES[i]: frames 0 and 2 random, frame 1
+    structured; expected from the oracle's restatement of Pillow and the bit-exact normalise twin.  Computed once."""
+    if i not in _n1_cache:
+        from oracle import pil_resize as R
+        (h, w, size, mx), (oh, ow) = N1_SHAPES[i]
+        frames = np.random.default_rng(100 + i).integers(0, 256, (3, h, w, 3), dtype=np.uint8)
+        yy, xx = np.mgrid[0:h, 0:w]
+        frames[1] = np.stack([(yy * 5 + xx * 3) % 256, ((yy // 4 + xx // 4) % 2) * 255, 255 - (xx * 7) % 256], axis=-1).astype(np.uint8)
+        want = np.zeros((3, 3, 1024, 1024), np.float32)
+        for b in range(3):
+            u8 = R.val_transform_u8(frames[b], size, mx)
+            assert u8.shape == (oh, ow, 3), (i, u8.shape)
+            want[b, :, :oh, :ow] = synth.normalize_tile(u8)
+        frames.setflags(write=False); want.setflags(write=False)
+        _n1_cache[i] = (frames, want)
+    return _n1_cache[i]
+
+
+def test_input_pipeline_resize_batched_frames_odd_row_lengths():
+    """Batches of three frames whose rows are not dword multiples, at every OPT and KMAX of the column-blocked horizontal
+    kernel, both generic fallbacks, upsampling and the no-filter path: the whole canvas, zeros included, bit for bit."""
+    from wildlifemapper_amd.preprocess import tiles_from_u8, resized_size
+    for i, ((h, w, size, mx), (oh, ow)) in enumerate(N1_SHAPES):
+        assert resized_size(h, w, size, mx or 0) == (oh, ow), i
+        frames, want = _n1_case(i)
+        got = tiles_from_u8(torch.tensor(frames).to(G.dev()), resize=(size, mx)).cpu().numpy()
+        assert np.array_equal(got, want), N1_SHAPES[i]
+
+
+def test_input_pipeline_resize_unaligned_input_start():
+    """The same batches starting 1, 2 and 3 bytes past an aligned allocation (a view: tiles_from_u8 passes its pointer on)."""
+    from wildlifemapper_amd.preprocess import tiles_from_u8
+    for i in (0, 2):
+        (h, w, size, mx), _ = N1_SHAPES[i]
+        frames, want = _n1_case(i)
+        for off in (1, 2, 3):
+            buf = torch.zeros(frames.size + 8, dtype=torch.uint8, device=G.dev())
+            buf[off:off + frames.size] = torch.tensor(frames.reshape(-1)).to(G.dev())
+            view = buf[off:off + frames.size].view(3, h, w, 3)
+            assert view.is_contiguous() and view.data_ptr() % 4 == off
+            got = tiles_from_u8(view, resize=(size, mx)).cpu().numpy()
+            assert np.array_equal(got, want), (N1_SHAPES[i], off)
+
+
+def test_input_pipeline_plan_slots_shared_with_resampler():
+    """More N1 geometries on one stream than it has plan slots, then the first again; then the survey resampler and N1
+    alternately on that stream, whose slots and intermediate image they share."""
+    from oracle import pil_resize as R
+    from wildlifemapper_amd.preprocess import tiles_from_u8, resample_u8
+    rng = np.random.default_rng(77)
+
+    def n1(frame, size):
+        got = tiles_from_u8(torch.from_numpy(frame[None]).to(G.dev()), resize=(size, None)).cpu().numpy()[0]
+        u8 = R.val_transform_u8(frame, size, None)
+        want = np.zeros((3, 1024, 1024), np.float32)
+        want[:, :u8.shape[0], :u8.shape[1]] = synth.normalize_tile(u8)
+        assert np.array_equal(got, want), (frame.shape, size)
+        return got
+
+    geoms = [(rng.integers(0, 256, (24 + k, 41 + 2 * k, 3), dtype=np.uint8), 10 + k) for k in range(12)]
+    first = [n1(f, s) for f, s in geoms][0]
+    assert np.array_equal(n1(*geoms[0]), first)
+    big = rng.integers(0, 256, (90, 301, 3), dtype=np.uint8)
+    for k in range(3):
+        oh, ow = 33 + k, 77 + 3 * k
+        got = resample_u8(torch.from_numpy(big).to(G.dev()), (oh, ow)).cpu().numpy()
+        assert np.array_equal(got, R.resize_bilinear_u8(big, oh, ow)), k
+        n1(*geoms[k])
+        n1(big, 50 + k)
+    torch.cuda.synchronize()
+
+
+def test_input_pipeline_resize_generic_switch_same_bits():
+    """WM_RESIZE_GENERIC=1 (read at call time) puts N1 on the generic horizontal and vertical kernels: the same bits."""
+    from wildlifemapper_amd.preprocess import tiles_from_u8
+    was = os.environ.get("WM_RESIZE_GENERIC")
+    os.environ["WM_RESIZE_GENERIC"] = "1"
+    try:
+        for i in range(3):
+            (h, w, size, mx), _ = N1_SHAPES[i]
+            frames, want = _n1_case(i)
+            got = tiles_from_u8(torch.tensor(frames).to(G.dev()), resize=(size, mx)).cpu().numpy()
+            assert np.array_equal(got, want), N1_SHAPES[i]
+    finally:
+        if was is None:
+            del os.environ["WM_RESIZE_GENERIC"]
+        else:
+            os.environ["WM_RESIZE_GENERIC"] = was
+
+
 def test_bench_two_ranks_on_one_gpu_rehearsal():
     """The N > 1 path of bench.py (self-launch through torch.distributed.run, tile sharding, the per-step all-gather of box
     records, max-over-ranks timing, one JSON line on rank 0) rehearsed with two ranks sharing this box's single GPU.  The

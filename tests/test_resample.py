@@ -3,6 +3,7 @@ CPU; bit-exactness against Pillow (tests/golden/resample_pil.npz, tools/gen_resa
 resize path on the GPU."""
 import ctypes as C
 import os
+import re
 
 import numpy as np
 import pytest
@@ -75,6 +76,27 @@ def test_detect_frames_rejects_bad_scale_before_device_work():
         tiling.detect_frame(None, torch.from_numpy(frame), scale=float("nan"))
     with pytest.raises(ValueError):
         tiling.detect_frame(None, torch.from_numpy(frame), scale=1.0, resize=(768, 768))
+
+
+def test_resample_family_has_one_definition_of_what_it_shares():
+    """From the sources: one horizontal streaming kernel, one plan cache, one home for the family, one spelling of the clip."""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "wildlifemapper_amd", "csrc")
+    src = {n: open(os.path.join(csrc, n)).read() for n in sorted(os.listdir(csrc)) if n.endswith((".h", ".hip"))}
+    everything = "\n".join(src.values())
+    for gone in ("resize_h_rows_kernel", "g_resize", "ResizePlan", "ResizeDevState", "upload_ints"):
+        assert not re.search(r"\b%s\b" % gone, everything), gone
+    kern = src["resample_kernels.h"]
+    assert re.search(r"constexpr int RESIZE_PREC_BITS\s*=", kern)
+    assert len(re.findall(r"constexpr int RESIZE_PREC_BITS\s*=", everything)) == 1
+    assert re.findall(r'#include "(\w+\.h)"', kern) == ["wm_common.h"]
+    for k in ("preprocess_u8_kernel", "resize_h_u8_kernel", "resample_h_cols_kernel", "resample_v_u8_kernel", "resize_v_normalize_kernel",
+              "resize_v_normalize4_kernel"):
+        assert [n for n, s in src.items() if re.search(r"__global__[^;{]*\b%s\(" % k, s)] == ["resample_kernels.h"], k
+    assert "RESIZE_PREC_BITS" not in src["misc_kernels.h"] and "resiz" not in src["misc_kernels.h"].lower()
+    assert everything.count(">> RESIZE_PREC_BITS, 0), 255)") == 1                  # resample_clip8
+    assert everything.count("1 << (RESIZE_PREC_BITS - 1)") == 1                    # RESAMPLE_ACC0
+    assert '#include "resample_kernels.h"' in src["chip_kernels.h"] and "resample_clip8(" in src["chip_kernels.h"]
+    assert everything.count('getenv("WM_RESIZE_GENERIC")') == 1
 
 
 # ---- GPU --------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Dev tool (round 4): N1 input pipeline (wm_preprocess_u8_resized) on resident 3648 x 5472 uint8 frames: us per frame and the
-algorithmic GB/s (frame read once + tile written once), streaming kernels vs the generic ones (WM_RESIZE_GENERIC=1), bit-compared."""
+algorithmic GB/s (frame read once + tile written once), streaming kernels (resample_h_cols_kernel, resize_v_normalize4_kernel)
+vs the generic ones (resize_h_u8_kernel, resize_v_normalize_kernel: WM_RESIZE_GENERIC=1), bit-compared."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

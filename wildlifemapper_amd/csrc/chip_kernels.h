@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void crop_chips_kernel(const frame_desc* __res
         for (int i = tid; i < ng * S; i += 256) {
             const int rl = i / S, xx = i - rl * S;
             const int fy = w.y0 + y_first + g0 + rl;
-            int a0 = 1 << (RESIZE_PREC_BITS - 1), a1 = a0, a2 = a0;
+            int a0 = RESAMPLE_ACC0, a1 = a0, a2 = a0;
             if (fy >= 0 && fy < fd.height) {       // a row outside the frame is a row of zeros
                 const int shift = (int)((uintptr_t)(fd.data + ((int64_t)fy * fd.width + cx0) * 3) & 3);
                 const unsigned char* sb = (const unsigned char*)(s_stage + rl * rs_dw) + shift;
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void crop_chips_kernel(const frame_desc* __res
         const unsigned* hp = hrows + (s_bounds[2 * r] - y_first) * row_dw + j;
         int acc[4];
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc[b] = 1 << (RESIZE_PREC_BITS - 1);
+        for (int b = 0; b < 4; ++b) acc[b] = RESAMPLE_ACC0;
         for (int y = 0; y < n; ++y) {
             const unsigned v = hp[y * row_dw];
             const int c = k[y];

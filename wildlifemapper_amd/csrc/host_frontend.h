@@ -1,13 +1,13 @@
-// Image front end: the val-transform resize (plan cache per device) and the survey resampler (plan slots per stream).
-// The survey launchers are in host_survey.h.
+// Image front end: the val-transform resize (N1) and the survey resampler, two clients of one plan cache (slots per
+// device and stream) and one horizontal launch.  The survey launchers are in host_survey.h.
 #pragma once
-#include "misc_kernels.h"
+#include <climits>
+
 #include "resample_kernels.h"
 #include "host_core.h"
 
 namespace {
 
-// ---- N1: val transform resize (PIL bilinear semantics) + normalise + pad ----
 // augmentation.py:80-99 (get_size_with_aspect_ratio): (w, h), size, max_size -> (oh, ow)
 void resized_size(int w, int h, int size, int max_size, int* oh, int* ow) {
     if (max_size > 0) {
@@ -30,88 +30,15 @@ void resize_coeffs(int in_size, int out_size, std::vector<int>& bounds, std::vec
         resize_coeff_row(ax, in_size, xx, &bounds[(size_t)xx * 2], &bounds[(size_t)xx * 2 + 1], &kk[(size_t)xx * ksize]);
 }
 
-// the row / column-blocked horizontal kernels' instance: KMAX taps (4 | 12 | 20, the caller has checked ks <= 20), 256 * (1..4) columns per workgroup
-template <class F>
-void by_taps_cols(int ks, int opt, F&& f) {
-    auto cols = [&](auto km) { opt <= 1 ? f(km, int_c<1>{}) : opt <= 2 ? f(km, int_c<2>{}) : opt <= 3 ? f(km, int_c<3>{}) : f(km, int_c<4>{}); };
-    ks <= 4 ? cols(int_c<4>{}) : ks <= 12 ? cols(int_c<12>{}) : cols(int_c<20>{});
-}
-
-struct ResizePlan {          // device tables of one geometry; owned by the library for the life of the process
-    int oh = 0, ow = 0, ksx = 0, ksy = 0;
-    int *bx = nullptr, *kx = nullptr, *by = nullptr, *ky = nullptr;
-};
-struct ResizeTmp { unsigned char* p = nullptr; size_t bytes = 0; };
-struct ResizeDevState {
-    std::map<std::array<int, 4>, ResizePlan> plans;      // (h, w, size, max_size); read-only once built
-    // the intermediate (horizontally resampled) image, one per STREAM: calls on different streams of a device may overlap
-    // on the GPU (a loader thread's side stream), and a shared buffer would be overwritten under the first call's kernels
-    std::map<hipStream_t, ResizeTmp> tmp;
-};
-std::map<int, ResizeDevState> g_resize;
-
-int upload_ints(const std::vector<int>& v, int** out) {
-    HIP_TRY(hipMalloc((void**)out, v.size() * 4));
-    HIP_TRY(hipMemcpy(*out, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-    return 0;
-}
-
-int preprocess_resized_impl(const uint8_t* img_dev, float* out_dev, int batch, int height, int width, int size, int max_size, int oh, int ow,
-                            hipStream_t s) {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_dev_mu);
-    ResizeDevState& st = g_resize[dev];
-    const std::array<int, 4> key{height, width, size, max_size};
-    auto it = st.plans.find(key);
-    if (it == st.plans.end()) {
-        ResizePlan pl;
-        pl.oh = oh; pl.ow = ow;
-        std::vector<int> b, k;
-        resize_coeffs(width, ow, b, k, pl.ksx);
-        WM_TRY(upload_ints(b, &pl.bx)); WM_TRY(upload_ints(k, &pl.kx));
-        resize_coeffs(height, oh, b, k, pl.ksy);
-        WM_TRY(upload_ints(b, &pl.by)); WM_TRY(upload_ints(k, &pl.ky));
-        it = st.plans.emplace(key, pl).first;
-    }
-    const ResizePlan& pl = it->second;
-    const size_t need = (size_t)batch * height * ow * 3;
-    ResizeTmp& tmp = st.tmp[s];
-    if (need > tmp.bytes) {
-        if (tmp.p) HIP_TRY(hipFree(tmp.p));              // hipFree synchronises the device: no kernel still reads the old buffer
-        tmp.p = nullptr; tmp.bytes = 0;
-        HIP_TRY(hipMalloc((void**)&tmp.p, need));
-        tmp.bytes = need;
-    }
-    // horizontal pass: the row-staged kernel where its geometry holds (<= 20 taps, <= 1024 output columns, a row fits LDS), else the generic one
-    const int64_t rows_total = (int64_t)batch * height;
-    const int lds_h = ((width * 3 + 3 + 3) / 4 + 1) * 4 + 64;      // row + alignment shift, + slack for the zero-coefficient taps (KMAX * 3 bytes)
-    const bool fast_h = pl.ksx <= 20 && ow <= 1024 && lds_h <= 64 * 1024 && !(getenv("WM_RESIZE_GENERIC") && atoi(getenv("WM_RESIZE_GENERIC")));
-    if (fast_h) {
-        const int rpb = (int)std::max<int64_t>(4, std::min<int64_t>(16, rows_total / (256 * 8)));     // rows per workgroup: the coefficient registers are loaded once per workgroup
-        const dim3 grid((unsigned)((rows_total + rpb - 1) / rpb));
-        const int64_t in_bytes = rows_total * width * 3;
-        by_taps_cols(pl.ksx, (ow + 255) / 256, [&](auto km, auto op) {
-            hipLaunchKernelGGL((resize_h_rows_kernel<decltype(km)::value, decltype(op)::value>), grid, dim3(256), lds_h, s, img_dev, tmp.p, (const int*)pl.bx,
-                               (const int*)pl.kx, pl.ksx, rows_total, width, ow, rpb, in_bytes);
-        });
-    } else {
-        hipLaunchKernelGGL(resize_h_u8_kernel, dim3(grid_for((int64_t)batch * height * ow)), dim3(256), 0, s, img_dev, tmp.p, (const int*)pl.bx,
-                           (const int*)pl.kx, pl.ksx, batch, height, width, ow);
-    }
-    if (ow % 4 == 0 && !(getenv("WM_RESIZE_GENERIC") && atoi(getenv("WM_RESIZE_GENERIC"))))
-        hipLaunchKernelGGL(resize_v_normalize4_kernel, dim3((unsigned)batch * 1024u), dim3(256), 0, s, (const unsigned char*)tmp.p, out_dev,
-                           (const int*)pl.by, (const int*)pl.ky, pl.ksy, height, ow, oh);
-    else
-        hipLaunchKernelGGL(resize_v_normalize_kernel, dim3(grid_for((int64_t)batch * 1024 * 1024)), dim3(256), 0, s, (const unsigned char*)tmp.p, out_dev,
-                           (const int*)pl.by, (const int*)pl.ky, pl.ksy, batch, height, ow, oh);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// ---- survey resampling: any size -> any size, uint8 HWC (PIL bilinear semantics) ----
+// ---- what both callers share: the plan slots of a stream, its intermediate image, the horizontal launch ----
 constexpr int RESAMPLE_MAX_SIDE = 65536;       // the merge's fp32 frame coordinates keep sub-0.01 px resolution up to here
 constexpr int RESAMPLE_PLAN_SLOTS = 8;         // coefficient tables cached per (device, stream), least recently used evicted
+
+// how the horizontal pass of one geometry runs (resample_h_geometry)
+struct ResampleHGeometry {
+    bool fast_h = false;                       // on resample_h_cols_kernel
+    int opt = 1, lds_h = 0;                    // 256 * opt columns per workgroup, its LDS bytes
+};
 
 // One geometry's tables, both axes in one device buffer (bx, kx, by, ky; an unchanged axis has none), uploaded on the
 // caller's stream from a pinned copy, so a new geometry neither allocates nor blocks the host: a slot is refilled only
@@ -125,31 +52,69 @@ struct ResampleSlot {
     int* host = nullptr;
     size_t cap = 0;                            // ints of dev and host
     hipEvent_t copied = nullptr;               // recorded after the upload out of `host`
-    bool fast_h = false;                       // horizontal pass on resample_h_cols_kernel
-    int opt = 1, lds_h = 0;
+    ResampleHGeometry hg;
     uint64_t used = 0;
 };
+// The intermediate (horizontally resampled) image, one per STREAM: calls on different streams of a device may overlap
+// on the GPU (a loader thread's side stream), and a shared buffer would be overwritten under the first call's kernels.
+struct ResampleTmp { unsigned char* p = nullptr; size_t bytes = 0; };
 struct ResampleStreamState {
     ResampleSlot slot[RESAMPLE_PLAN_SLOTS];
-    ResizeTmp tmp;                             // the horizontally resampled image
+    ResampleTmp tmp;
     uint64_t clock = 0;
 };
 std::map<std::pair<int, hipStream_t>, ResampleStreamState> g_resample;
 
+int resample_tmp_grow(ResampleTmp& tmp, size_t need) {
+    if (need <= tmp.bytes) return 0;
+    if (tmp.p) HIP_TRY(hipFree(tmp.p));                // hipFree synchronises the device: no kernel still reads the old buffer
+    tmp.p = nullptr; tmp.bytes = 0;
+    HIP_TRY(hipMalloc((void**)&tmp.p, need));
+    tmp.bytes = need;
+    return 0;
+}
+
 // the column-blocked horizontal kernel: <= 20 taps, and the input span of the widest block of 256 * opt columns fits LDS
-void resample_h_geometry(const std::vector<int>& b, int ow, int ks, ResampleSlot& sl) {
-    sl.opt = std::min(4, (ow + 255) / 256);
-    sl.fast_h = false;
+void resample_h_geometry(const std::vector<int>& b, int ow, int ks, ResampleHGeometry& g) {
+    g.opt = std::min(4, (ow + 255) / 256);
+    g.fast_h = false;
     if (ks > 20) return;
     for (int x = 1; x < ow; ++x)
         if (b[2 * x] < b[2 * x - 2] || b[2 * x] + b[2 * x + 1] < b[2 * x - 2] + b[2 * x - 1]) return;
     int span = 0;
-    for (int c0 = 0; c0 < ow; c0 += 256 * sl.opt) {
-        const int c1 = std::min(c0 + 256 * sl.opt, ow) - 1;
+    for (int c0 = 0; c0 < ow; c0 += 256 * g.opt) {
+        const int c1 = std::min(c0 + 256 * g.opt, ow) - 1;
         span = std::max(span, b[2 * c1] + b[2 * c1 + 1] - b[2 * c0]);
     }
-    sl.lds_h = (span * 3 + 3 + 3) / 4 * 4 + 64;     // span + alignment shift, + slack for the zero-coefficient taps (KMAX * 3 bytes)
-    sl.fast_h = sl.lds_h <= 64 * 1024;
+    g.lds_h = (span * 3 + 3 + 3) / 4 * 4 + 64;      // span + alignment shift, + slack for the zero-coefficient taps (KMAX * 3 bytes)
+    g.fast_h = g.lds_h <= 64 * 1024;
+}
+
+// rows per workgroup of the column-blocked kernel: its coefficient registers are loaded once per workgroup
+int resample_rows_per_block(int rows) { return std::max(4, std::min(16, rows / (256 * 8))); }
+
+// the column-blocked kernel's instance: KMAX taps (4 | 12 | 20, the caller has checked ks <= 20), 256 * (1..4) columns per workgroup
+template <class F>
+void by_taps_cols(int ks, int opt, F&& f) {
+    auto cols = [&](auto km) { opt <= 1 ? f(km, int_c<1>{}) : opt <= 2 ? f(km, int_c<2>{}) : opt <= 3 ? f(km, int_c<3>{}) : f(km, int_c<4>{}); };
+    ks <= 4 ? cols(int_c<4>{}) : ks <= 12 ? cols(int_c<12>{}) : cols(int_c<20>{});
+}
+
+// The horizontal pass of both callers: in [rows, w, 3] -> out [rows, ow, 3], rows = the rows of one frame or of a batch.
+int resample_h_launch(const unsigned char* in, unsigned char* out, int rows, int w, int ow, const int* bx, const int* kx, int ksx,
+                      const ResampleHGeometry& g, hipStream_t s) {
+    if (g.fast_h) {
+        const int rpb = resample_rows_per_block(rows);
+        const dim3 grid((unsigned)((rows + rpb - 1) / rpb), (unsigned)((ow + 256 * g.opt - 1) / (256 * g.opt)));
+        by_taps_cols(ksx, g.opt, [&](auto km, auto op) {
+            hipLaunchKernelGGL((resample_h_cols_kernel<decltype(km)::value, decltype(op)::value>), grid, dim3(256), g.lds_h, s, in, out, bx, kx, ksx,
+                               rows, w, ow, rpb);
+        });
+    } else {                                                           // > 20 taps (scale below ~0.1): one thread per output pixel
+        hipLaunchKernelGGL(resize_h_u8_kernel, dim3(grid_for((int64_t)rows * ow)), dim3(256), 0, s, in, out, bx, kx, ksx, 1, rows, w, ow);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 int resample_plan(ResampleStreamState& st, int h, int w, int oh, int ow, hipStream_t s, ResampleSlot** out) {
@@ -184,13 +149,60 @@ int resample_plan(ResampleStreamState& st, int h, int w, int oh, int ow, hipStre
     if (!ky.empty()) memcpy(sl->host + sl->off_ky, ky.data(), ky.size() * 4);
     if (total) HIP_TRY(hipMemcpyAsync(sl->dev, sl->host, total * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(sl->copied, s));
-    if (ow != w) resample_h_geometry(bx, ow, sl->ksx, *sl);
+    if (ow != w) resample_h_geometry(bx, ow, sl->ksx, sl->hg);
     sl->key = key;
     sl->used = ++st.clock;
     *out = sl;
     return 0;
 }
 
+// ---- N1: val transform resize (PIL bilinear semantics) + normalise + pad ----
+// A client of the resampler's state: its tables live in the plan slots of (device, stream), 8 geometries with the least
+// recently used evicted, are uploaded on the caller's stream from pinned memory, and a new geometry no longer blocks the
+// host (N1 used to keep every geometry for the life of the process, per device, uploaded by a synchronous copy).
+// As Pillow does, an unchanged axis has no table and no pass: without a horizontal pass the vertical kernel reads the
+// input; without a vertical pass preprocess_u8_kernel normalises and pads the rows it is given.  The bits are those of
+// the identity table (coefficients 2^22, 0): clip8((2^21 + 2^22 v) >> 22) = v.  (The val transform's size rule keeps the
+// aspect ratio, so it changes both axes or neither; the one-axis cases follow resample_plan's rule all the same.)
+// WM_RESIZE_GENERIC=1 (read per call): the generic horizontal and vertical kernels.
+int preprocess_resized_impl(const uint8_t* img_dev, float* out_dev, int batch, int height, int width, int oh, int ow, hipStream_t s) {
+    if ((int64_t)batch * height > INT_MAX) return fail("wm_preprocess_u8_resized: batch %d x height %d is more than 2^31 - 1 rows", batch, height);
+    const int rows = batch * height;
+    const char* env = getenv("WM_RESIZE_GENERIC");
+    const bool generic = env && atoi(env);
+    const unsigned char* src = img_dev;
+    ResampleSlot* pl = nullptr;
+    std::lock_guard<std::mutex> lk(g_dev_mu);
+    if (ow != width || oh != height) {
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        ResampleStreamState& st = g_resample[{dev, s}];
+        WM_TRY(resample_plan(st, height, width, oh, ow, s, &pl));
+        if (ow != width) {
+            WM_TRY(resample_tmp_grow(st.tmp, (size_t)batch * height * ow * 3));
+            ResampleHGeometry g = pl->hg;
+            g.fast_h = g.fast_h && !generic;
+            WM_TRY(resample_h_launch(src, st.tmp.p, rows, width, ow, pl->dev, pl->dev + pl->off_kx, pl->ksx, g, s));
+            src = st.tmp.p;
+        }
+    }
+    if (oh == height) {
+        hipLaunchKernelGGL(preprocess_u8_kernel, dim3(grid_for((int64_t)batch * 1024 * 256)), dim3(256), 0, s, src, out_dev, batch, oh, ow);
+    } else {
+        const int* by = pl->dev + pl->off_by;
+        const int* ky = pl->dev + pl->off_ky;
+        // four pixels per thread by dword loads: the intermediate image is an allocation of its own; the caller's input may start anywhere
+        if (ow % 4 == 0 && !generic && ((uintptr_t)src & 3) == 0)
+            hipLaunchKernelGGL(resize_v_normalize4_kernel, dim3((unsigned)batch * 1024u), dim3(256), 0, s, src, out_dev, by, ky, pl->ksy, height, ow, oh);
+        else
+            hipLaunchKernelGGL(resize_v_normalize_kernel, dim3(grid_for((int64_t)batch * 1024 * 1024)), dim3(256), 0, s, src, out_dev, by, ky, pl->ksy,
+                               batch, height, ow, oh);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- survey resampling: any size -> any size, uint8 HWC (PIL bilinear semantics) ----
 int resample_impl(const uint8_t* in_dev, int height, int width, uint8_t* out_dev, int out_height, int out_width, hipStream_t s) {
     if (height == out_height && width == out_width) {                  // both of Pillow's passes skipped
         HIP_TRY(hipMemcpyAsync(out_dev, in_dev, (size_t)height * width * 3, hipMemcpyDeviceToDevice, s));
@@ -206,29 +218,10 @@ int resample_impl(const uint8_t* in_dev, int height, int width, uint8_t* out_dev
     if (out_width != width) {
         unsigned char* dst = out_dev;                                  // no vertical pass: straight into the output
         if (out_height != height) {
-            const size_t need = (size_t)height * out_width * 3;
-            if (need > st.tmp.bytes) {
-                if (st.tmp.p) HIP_TRY(hipFree(st.tmp.p));              // hipFree synchronises the device
-                st.tmp.p = nullptr; st.tmp.bytes = 0;
-                HIP_TRY(hipMalloc((void**)&st.tmp.p, need));
-                st.tmp.bytes = need;
-            }
+            WM_TRY(resample_tmp_grow(st.tmp, (size_t)height * out_width * 3));
             dst = st.tmp.p;
         }
-        const int* bx = pl->dev;
-        const int* kx = pl->dev + pl->off_kx;
-        if (pl->fast_h) {
-            const int rpb = std::max(4, std::min(16, height / (256 * 8)));
-            const dim3 grid((unsigned)((height + rpb - 1) / rpb), (unsigned)((out_width + 256 * pl->opt - 1) / (256 * pl->opt)));
-            by_taps_cols(pl->ksx, pl->opt, [&](auto km, auto op) {
-                hipLaunchKernelGGL((resample_h_cols_kernel<decltype(km)::value, decltype(op)::value>), grid, dim3(256), pl->lds_h, s, in_dev, dst, bx, kx, pl->ksx,
-                                   height, width, out_width, rpb);
-            });
-        } else {                                                       // > 20 taps (scale below ~0.1): one thread per output pixel
-            hipLaunchKernelGGL(resize_h_u8_kernel, dim3(grid_for((int64_t)height * out_width)), dim3(256), 0, s, in_dev, dst, bx, kx, pl->ksx,
-                               1, height, width, out_width);
-        }
-        HIP_TRY(hipGetLastError());
+        WM_TRY(resample_h_launch(in_dev, dst, height, width, out_width, pl->dev, pl->dev + pl->off_kx, pl->ksx, pl->hg, s));
         src = dst;
     }
     if (out_height != height) {

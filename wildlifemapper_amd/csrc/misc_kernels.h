@@ -493,193 +493,4 @@ __global__ __launch_bounds__(256) void cvt_16_to_f32_kernel(const u16* __restric
     }
 }
 
-// ---------------------------------------------------------------------------
-// Input pipeline: uint8 HWC image (h, w <= 1024) -> fp32 CHW tile on the zero 1024 x 1024
-// canvas, top-left aligned: ToTensor (/255), Normalize(ImageNet mean/std) (dataloader_coco.py:286-292,
-// augmentation.py:229-249) and the fixed-1024 zero padding of nested_tensor_from_tensor_list
-// (utils/misc.py:46-67) in one pass.  in [B,h,w,3] u8, out [B,3,1024,1024] fp32.  One thread per 4 pixels.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void preprocess_u8_kernel(const unsigned char* __restrict__ in, float* __restrict__ out,
-                                                            int B, int h, int w) {
-    const int64_t total = (int64_t)B * 1024 * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int x4 = (int)(i & 255) * 4;
-        const int y = (int)((i >> 8) & 1023);
-        const int64_t b = i >> 18;
-        f32x4 v[3] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-        if (y < h) {
-            const unsigned char* row = in + ((b * h + y) * (int64_t)w) * 3;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int x = x4 + j;
-                if (x < w) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) v[c][j] = normalize_u8(row[x * 3 + c], c);
-                }
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) *(f32x4*)(out + ((b * 3 + c) * 1024 + y) * (int64_t)1024 + x4) = v[c];
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Input pipeline with the val transform's resize (dataloader_coco.py:286-292 -> augmentation.py:77-133
-// -> torchvision F.resize on a PIL image = PIL bilinear resample).  The arithmetic is Pillow's 8-bit ImagingResample:
-// separable antialiased triangle filter, 22-bit fixed-point coefficients (computed on the host in double exactly as
-// Resample.c does, host_frontend.h: resize_coeffs), horizontal pass into an 8-bit image, then the vertical pass, each output
-// clip8((sum + 2^21) >> 22) -- integer work, bit-exact with PIL.  The second kernel fuses the vertical pass with ToTensor,
-// Normalize and the zero padding to 1024 x 1024 (utils/misc.py:46-67).
-// ---------------------------------------------------------------------------
-constexpr int RESIZE_PREC_BITS = 22;
-
-// in [B,h,w,3] u8 -> tmp [B,h,ow,3] u8; bounds [ow][2] = (first input column, taps), kk [ow][ksize]
-__global__ __launch_bounds__(256) void resize_h_u8_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ tmp,
-                                                          const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
-                                                          int B, int h, int w, int ow) {
-    const int64_t total = (int64_t)B * h * ow;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int xx = (int)(i % ow);
-        const int64_t by = i / ow;                                   // b * h + y
-        const int x0 = bounds[2 * xx], n = bounds[2 * xx + 1];
-        const unsigned char* src = in + (by * w + x0) * 3;
-        const int* k = kk + (int64_t)xx * ksize;
-        int a0 = 1 << (RESIZE_PREC_BITS - 1), a1 = a0, a2 = a0;
-        for (int x = 0; x < n; ++x) {
-            const int c = k[x];
-            a0 += src[3 * x] * c; a1 += src[3 * x + 1] * c; a2 += src[3 * x + 2] * c;
-        }
-        unsigned char* dst = tmp + i * 3;
-        dst[0] = (unsigned char)min(max(a0 >> RESIZE_PREC_BITS, 0), 255);
-        dst[1] = (unsigned char)min(max(a1 >> RESIZE_PREC_BITS, 0), 255);
-        dst[2] = (unsigned char)min(max(a2 >> RESIZE_PREC_BITS, 0), 255);
-    }
-}
-
-// tmp [B,h,ow,3] u8 -> out [B,3,1024,1024] fp32: vertical pass to oh rows, /255, ImageNet normalise, zero canvas outside
-__global__ __launch_bounds__(256) void resize_v_normalize_kernel(const unsigned char* __restrict__ tmp, float* __restrict__ out,
-                                                                 const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
-                                                                 int B, int h, int ow, int oh) {
-    const int64_t total = (int64_t)B * 1024 * 1024;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int xx = (int)(i & 1023), yy = (int)((i >> 10) & 1023);
-        const int64_t b = i >> 20;
-        float v[3] = {0.f, 0.f, 0.f};
-        if (yy < oh && xx < ow) {
-            const int y0 = bounds[2 * yy], n = bounds[2 * yy + 1];
-            const unsigned char* src = tmp + ((b * h + y0) * (int64_t)ow + xx) * 3;
-            const int* k = kk + (int64_t)yy * ksize;
-            int a[3] = {1 << (RESIZE_PREC_BITS - 1), 1 << (RESIZE_PREC_BITS - 1), 1 << (RESIZE_PREC_BITS - 1)};
-            for (int y = 0; y < n; ++y) {
-                const int c = k[y];
-                const unsigned char* p = src + (int64_t)y * ow * 3;
-                a[0] += p[0] * c; a[1] += p[1] * c; a[2] += p[2] * c;
-            }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[c] = normalize_u8(min(max(a[c] >> RESIZE_PREC_BITS, 0), 255), c);
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) out[((b * 3 + c) * 1024 + yy) * (int64_t)1024 + xx] = v[c];
-    }
-}
-
-// ---- round 4: the two resize passes at streaming rate (the generic kernels above: one thread per output pixel, byte loads from
-// global memory, 110 us per 3648 x 5472 frame = 0.08 of the HBM rate for 72 MB of algorithmic traffic) -------------------------
-// Horizontal pass, row-staged: a workgroup walks input rows; a row (w * 3 bytes) is staged in LDS by coalesced dword loads, each
-// thread owns up to OPT output columns and keeps their taps' coefficients in registers for all its rows (KMAX taps, zero beyond
-// the column's count: a zero coefficient times any staged byte adds nothing, and the LDS row has KMAX * 3 bytes of slack).
-// Same integer arithmetic as resize_h_u8_kernel: bit-identical.
-template <int KMAX, int OPT>
-__global__ __launch_bounds__(256) void resize_h_rows_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ tmp,
-                                                            const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
-                                                            int64_t rows_total, int w, int ow, int rows_per_block, int64_t in_bytes) {
-    extern __shared__ __attribute__((aligned(16))) unsigned srow[];
-    const int tid = threadIdx.x;
-    int x0[OPT], coef[OPT][KMAX];
-    bool valid[OPT];
-#pragma unroll
-    for (int o = 0; o < OPT; ++o) {
-        const int xx = tid + 256 * o;
-        valid[o] = xx < ow;
-        const int n = valid[o] ? bounds[2 * xx + 1] : 0;
-        x0[o] = valid[o] ? bounds[2 * xx] : 0;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) coef[o][k] = k < n ? kk[(int64_t)xx * ksize + k] : 0;
-    }
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r1 = r0 + rows_per_block < rows_total ? r0 + rows_per_block : rows_total;
-    const int row_bytes = w * 3;
-    for (int64_t row = r0; row < r1; ++row) {
-        const int64_t byte0 = row * row_bytes, a0 = byte0 & ~(int64_t)3;
-        const int shift = (int)(byte0 - a0), ndw = (shift + row_bytes + 3) >> 2;
-        for (int i = tid; i < ndw; i += 256) {
-            const int64_t off = a0 + 4 * (int64_t)i;
-            unsigned v;
-            if (off + 4 <= in_bytes) v = *(const unsigned*)(in + off);
-            else {                                            // the last dword of the whole buffer: byte by byte
-                v = 0;
-                for (int j = 0; j < 4; ++j)
-                    if (off + j < in_bytes) v |= (unsigned)in[off + j] << (8 * j);
-            }
-            srow[i] = v;
-        }
-        __syncthreads();
-        const unsigned char* sb = (const unsigned char*)srow + shift;
-#pragma unroll
-        for (int o = 0; o < OPT; ++o) {
-            if (!valid[o]) continue;
-            const unsigned char* src = sb + x0[o] * 3;
-            int a0c = 1 << (RESIZE_PREC_BITS - 1), a1c = a0c, a2c = a0c;
-#pragma unroll
-            for (int k = 0; k < KMAX; ++k) {
-                const int c = coef[o][k];
-                a0c += src[3 * k] * c; a1c += src[3 * k + 1] * c; a2c += src[3 * k + 2] * c;
-            }
-            unsigned char* dst = tmp + (row * ow + tid + 256 * o) * 3;
-            dst[0] = (unsigned char)min(max(a0c >> RESIZE_PREC_BITS, 0), 255);
-            dst[1] = (unsigned char)min(max(a1c >> RESIZE_PREC_BITS, 0), 255);
-            dst[2] = (unsigned char)min(max(a2c >> RESIZE_PREC_BITS, 0), 255);
-        }
-        __syncthreads();
-    }
-}
-
-// Vertical pass + ToTensor + Normalize + zero canvas, four output pixels per thread: a workgroup is one output row (its taps'
-// coefficients are wave-uniform), a thread reads 12 contiguous bytes (3 dwords) per tap row and writes one 16-byte chunk per
-// channel.  ow % 4 == 0.  Same arithmetic as resize_v_normalize_kernel: bit-identical.
-__global__ __launch_bounds__(256) void resize_v_normalize4_kernel(const unsigned char* __restrict__ tmp, float* __restrict__ out,
-                                                                  const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
-                                                                  int h, int ow, int oh) {
-    const int yy = blockIdx.x & 1023;
-    const int64_t b = blockIdx.x >> 10;
-    const int xx4 = threadIdx.x * 4;
-    f32x4 v[3] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-    if (yy < oh && xx4 < ow) {
-        const int y0 = bounds[2 * yy], n = bounds[2 * yy + 1];
-        const unsigned* src = (const unsigned*)(tmp + ((b * h + y0) * (int64_t)ow + xx4) * 3);
-        const int* k = kk + (int64_t)yy * ksize;
-        int a[12];
-#pragma unroll
-        for (int j = 0; j < 12; ++j) a[j] = 1 << (RESIZE_PREC_BITS - 1);
-        const int64_t stride_dw = (int64_t)ow * 3 / 4;
-        for (int y = 0; y < n; ++y) {
-            const int c = k[y];
-            const unsigned d0 = src[0], d1 = src[1], d2 = src[2];
-            src += stride_dw;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                a[j] += (int)((d0 >> (8 * j)) & 255u) * c;
-                a[4 + j] += (int)((d1 >> (8 * j)) & 255u) * c;
-                a[8 + j] += (int)((d2 >> (8 * j)) & 255u) * c;
-            }
-        }
-#pragma unroll
-        for (int px = 0; px < 4; ++px)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[c][px] = normalize_u8(min(max(a[px * 3 + c] >> RESIZE_PREC_BITS, 0), 255), c);
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) *(f32x4*)(out + ((b * 3 + c) * 1024 + yy) * (int64_t)1024 + xx4) = v[c];
-}
-
 }  // namespace wm

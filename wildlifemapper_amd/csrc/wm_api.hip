@@ -84,7 +84,7 @@ extern "C" int wm_preprocess_u8_resized(const uint8_t* img_dev, float* out_dev, 
     resized_size(width, height, size, max_size, &oh, &ow);
     if (oh > 1024 || ow > 1024 || oh <= 0 || ow <= 0)
         return fail("wm_preprocess_u8_resized: %dx%d resizes to %dx%d, outside the 1024x1024 canvas (utils/misc.py:57-60 crops; not built)", height, width, oh, ow);
-    return preprocess_resized_impl(img_dev, out_dev, batch, height, width, size, max_size, oh, ow, (hipStream_t)stream);
+    return preprocess_resized_impl(img_dev, out_dev, batch, height, width, oh, ow, (hipStream_t)stream);
 }
 
 extern "C" int wm_resized_size(int height, int width, int size, int max_size, int* out_h, int* out_w) {
