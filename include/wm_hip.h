@@ -41,6 +41,8 @@ extern "C" {
  *    13, additive: wm_register_render_u8, wm_register_search, wm_register_pair, WM_REGISTER_MAX_SIDE, WM_REGISTER_MAX_SEARCH,
  *    WM_REGISTER_MAX_PAIRS and the status bits WM_REGISTER_BAD_SLOT, WM_REGISTER_BAD_SIZE, WM_REGISTER_BAD_PAIR (survey
  *    registration: frame georeferences corrected by image matching); the number stays 13 for the same reason.
+ *    13, additive: wm_register_search_zncc (survey registration, correlation search: a score that a gain and an offset
+ *    between the two frames of a pair do not change); the number stays 13 for the same reason.
  * 12: wm_box_outline_rect, wm_draw_boxes_u8, wm_plot_image_u8, WM_DRAW_MAX_WIDTH, WM_DRAW_MAX_PALETTE, WM_PLOT_SCRATCH_BYTES
  *    (survey overlays: detections outlined on frames and tiles, on the GPU); nothing else changed.
  * 11: wm_chip_window, wm_crop_chips_u8, WM_CHIP_MAX_SIDE (survey review chips: one PIL-exact crop per detection, cut on
@@ -494,6 +496,36 @@ int wm_register_render_u8(const wm_frame_desc* frames_dev, int n_resident, const
 int wm_register_search(const uint8_t* a_dev, const uint8_t* b_dev, const wm_register_pair* pairs_dev, int n_pairs, int search,
                        int side, int min_cells, int32_t* score_dev /* [n_pairs][2S+1][2S+1][2] */,
                        int32_t* best_dev /* [n_pairs][8] */, void* stream);
+
+/* Survey registration, correlation search (tiling.register(metric="zncc")): the search above compares grey levels as they
+ * are, so a pair whose frames differ in exposure -- b -> g * b + o, g > 0 -- moves its minimum or flattens it.  This search
+ * scores an offset by the zero-mean normalised correlation of the two planes, which no such change alters.  Planes, pairs,
+ * limits, the offset convention and the meaning of the sign are those of "Survey registration", word for word; the planes
+ * are wm_register_render_u8's.
+ * Search (wm_register_search_zncc): for every pair and every offset (dy, dx) in [-search, search]^2, over exactly the cells
+ * that wm_register_search counts -- (j, i), j < gy, i < gx, with a = A[j][i] != 0 and b = B[j + search + dy][i + search + dx]
+ * != 0 -- six integers:
+ *     n = their number, Sa = sum a, Sb = sum b, Saa = sum a * a, Sbb = sum b * b, Sab = sum a * b      (a, b in 1..255)
+ * moments_dev[p][2 * search + 1][2 * search + 1][6] int64 holds (n, Sa, Sb, Saa, Sbb, Sab) at [dy + search][dx + search]
+ * (Sab is at most 255^2 * 512^2 = 1.7e10: int64 is required).  Only gx and gy of a pair are read here; a pair with gx or gy
+ * outside [1, side] keeps all-zero moments.  From the moments, all exact in int64 and every product below 2^53,
+ *     c = n * Sab - Sa * Sb          va = n * Saa - Sa * Sa          vb = n * Sbb - Sb * Sb
+ * An offset is ELIGIBLE iff n >= min_cells (min_cells >= 1), va > 0 and vb > 0: a flat plane has no correlation.  Its score
+ * is the signed squared correlation in IEEE double,
+ *     q = ((double)c * fabs((double)c)) / ((double)va * (double)vb)
+ * -- two multiplications and one division, each correctly rounded on its own, no contraction, no square root; the
+ * conversions are exact.  Offset p BEATS q iff q_p > q_q as doubles, and at equality the smaller (dy * dy + dx * dx, dy,
+ * dx) wins, lexicographically: the tie key above.  best_dev[p][8] int32 = (dy, dx, ok, n, dy2, dx2, ok2, n2): the first
+ * four are the eligible offset that beats all others, with ok = 1; the last four the same among the eligible offsets with
+ * max(|dy - dy*|, |dx - dx*|) >= 2 of the first, the runner-up outside the peak's 3 x 3.  Where there is no eligible offset
+ * the four are (0, 0, 0, 0).  peak_dev[p][2] double = (q, q2) of the two, NaN where ok (ok2) is 0.
+ * Asynchronous on `stream`, nothing allocated; moments_dev is zeroed on `stream` and accumulated into with 64-bit integer
+ * vector atomics (integers: the order is irrelevant); plain vector loads and stores.  Arguments as for wm_register_search;
+ * moments_dev and peak_dev 8-byte, best_dev 4-byte aligned.  Bad arguments fail before any HIP call with a message that names
+ * the argument; n_pairs == 0 returns 0 before looking at any pointer. */
+int wm_register_search_zncc(const uint8_t* a_dev, const uint8_t* b_dev, const wm_register_pair* pairs_dev, int n_pairs, int search,
+                            int side, int min_cells, int64_t* moments_dev /* [n_pairs][2S+1][2S+1][6] */,
+                            int32_t* best_dev /* [n_pairs][8] */, double* peak_dev /* [n_pairs][2] */, void* stream);
 
 /* Survey resampling (tiling.detect_frames(scale=..., resize=...)): a frame brought to the scale the checkpoint was trained
  * at (the val transform's long side of 768, dataloader_coco.py:288) before it is tiled.

@@ -77,6 +77,7 @@ SYMBOLS = {
     "wm_mosaic_fill_u8": (_I, [_P, _I, _P, _P, _P, _I, C.c_double, C.c_double, C.c_double, _I, _I, _P, _I, _I, _P, _P, _P]),
     "wm_register_render_u8": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, C.c_double, _I, _I, _P, _P, _P, _P]),
     "wm_register_search": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "wm_register_search_zncc": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "wm_resample_u8": (_I, [_P, _I, _I, _P, _I, _I, _P]),
     "wm_scaled_size": (_I, [_I, _I, C.c_double, C.POINTER(_I), C.POINTER(_I)]),
     "wm_chip_window": (_I, [C.POINTER(_F), _F, _I, _I, C.POINTER(C.c_int32)]),

@@ -21,6 +21,18 @@
 //
 // register_best_kernel: one workgroup per pair scans score twice with the header's order, which is total (the cross products
 // decide, then the unique key (dy^2 + dx^2, dy, dx)), so the reduction's order is irrelevant.
+//
+// Correlation search (include/wm_hip.h, "Survey registration, correlation search"; checker: zncc_search_oracle and
+// zncc_pick_oracle in tests/test_register_zncc.py).  register_zncc_kernel is register_search_kernel's sibling: the same
+// decomposition, tiles, staging and sliding window, with six integer sums per offset where that one has two.  It shares
+// reg_load4, reg_nonzero_mask, reg_b_stride, reg_search_lds and the tie key; the staging loops and the walk are restated,
+// because moving them into a function the two kernels call changed the register allocation of the SAD instances
+// (profiles/register_zncc/README.md), and those stay byte for byte what they were.
+// Per 4 cells and offset: two v_alignbyte_b32, three v_and_b32, two v_sad_u8 against 0 (the byte sums), three
+// v_dot4_u32_u8 (sum a^2, sum b^2, sum ab) and one v_bcnt_u32_b32.  A tile's partials fit 32 bits (the static_assert beside
+// REG_TILE_ROWS_MAX); they go to moments by six 64-bit vector atomics per (tile, offset).  register_zncc_best_kernel: the
+// score q of an offset is three IEEE double operations on exact integers (no contraction, no sqrt), the order is total
+// (q decides, then the key), so the reduction's shape is free here too.
 #pragma once
 
 #include "mosaic_kernels.h"
@@ -34,6 +46,9 @@ constexpr int REG_TILE_DW = REG_TILE_X / 4;
 constexpr int REG_RENDER_ROWS = 4;                // cells per thread of the render, consecutive rows of one column
 constexpr int REG_RENDER_BLOCK_Y = (REG_THREADS / 64) * REG_RENDER_ROWS;
 constexpr int REG_LDS_MAX = 64 * 1024;
+constexpr int REG_TILE_ROWS_MAX = 32;             // rows of A per tile of either search: 32, or 16 where 32 do not fit the LDS
+// the correlation search keeps a tile's partial sums in 32 bits: at most 64 x 32 cells of 255 * 255 = 133 171 200
+static_assert(255LL * 255 * REG_TILE_X * REG_TILE_ROWS_MAX < (1LL << 31), "a tile's sum of products fits 32 bits");
 
 static_assert(sizeof(wm_register_pair) == 32, "wm_register_pair layout");
 static_assert(WM_REGISTER_BAD_SLOT == WM_MOSAIC_BAD_SLOT && WM_REGISTER_BAD_SIZE == WM_MOSAIC_BAD_SIZE, "the two residency chains set the same bits");
@@ -188,16 +203,21 @@ __global__ __launch_bounds__(REG_THREADS) void register_search_kernel(
 
 struct reg_cand { int sad, n, dy, dx; };                         // n < 0: no candidate
 
+// the tie key of both searches: the smaller (dy^2 + dx^2, dy, dx)
+__device__ __forceinline__ bool reg_key_less(int pdy, int pdx, int qdy, int qdx) {
+    const int dp = pdy * pdy + pdx * pdx, dq = qdy * qdy + qdx * qdx;
+    if (dp != dq) return dp < dq;
+    if (pdy != qdy) return pdy < qdy;
+    return pdx < qdx;
+}
+
 // the header's order: p beats q
 __device__ __forceinline__ bool reg_beats(const reg_cand& p, const reg_cand& q) {
     if (p.n < 0) return false;
     if (q.n < 0) return true;
     const long long l = (long long)p.sad * q.n, r = (long long)q.sad * p.n;
     if (l != r) return l < r;
-    const int dp = p.dy * p.dy + p.dx * p.dx, dq = q.dy * q.dy + q.dx * q.dx;
-    if (dp != dq) return dp < dq;
-    if (p.dy != q.dy) return p.dy < q.dy;
-    return p.dx < q.dx;
+    return reg_key_less(p.dy, p.dx, q.dy, q.dx);
 }
 
 __global__ __launch_bounds__(REG_THREADS) void register_best_kernel(const int* __restrict__ score, int search, int min_cells,
@@ -236,6 +256,151 @@ __global__ __launch_bounds__(REG_THREADS) void register_best_kernel(const int* _
             out[1] = has ? top.dx : 0;
             out[2] = has ? top.sad : -1;
             out[3] = has ? top.n : 0;
+            s_first = top;
+        }
+        __syncthreads();
+    }
+}
+
+// ---- correlation search: six integer moments per offset, then the signed squared correlation in double ----
+
+constexpr int REG_MOMENTS = 6;                                   // n, sum a, sum b, sum a^2, sum b^2, sum ab
+
+template <int K>
+__global__ __launch_bounds__(REG_THREADS) void register_zncc_kernel(
+        const unsigned char* __restrict__ a, const unsigned char* __restrict__ b, const wm_register_pair* __restrict__ pairs, int search,
+        int side, int tile_rows, int tiles_x, int off_blocks, unsigned long long* __restrict__ moments) {
+    extern __shared__ uint2 reg_lds[];
+    const int tid = threadIdx.x;
+    const int p = blockIdx.y;
+    const wm_register_pair pr = pairs[p];
+    if (pr.gx < 1 || pr.gx > side || pr.gy < 1 || pr.gy > side) return;      // a bad pair keeps its zeroed moments
+    const int ob = (int)blockIdx.x % off_blocks, tile = (int)blockIdx.x / off_blocks;
+    const int i0 = (tile % tiles_x) * REG_TILE_X, j0 = (tile / tiles_x) * tile_rows;
+    if (i0 >= pr.gx || j0 >= pr.gy) return;
+    const int ext = side + 2 * search, w1 = 2 * search + 1, n_off = w1 * w1;
+    const int bs = reg_b_stride(search), b_rows = tile_rows + 2 * search;
+    uint2* sA = reg_lds;                                         // [tile_rows][REG_TILE_DW]
+    uint2* sB = reg_lds + tile_rows * REG_TILE_DW;               // [b_rows][bs]
+    const unsigned char* pa = a + (size_t)p * side * side;
+    const unsigned char* pb = b + (size_t)p * ext * ext;
+
+    for (int e = tid; e < tile_rows * REG_TILE_DW; e += REG_THREADS) {
+        const int r = e / REG_TILE_DW, c = i0 + (e % REG_TILE_DW) * 4, j = j0 + r;
+        const unsigned int v = j < pr.gy ? reg_load4(pa + (size_t)j * side, c, pr.gx) : 0u;       // only cells j < gy, i < gx count
+        sA[e] = make_uint2(v, reg_nonzero_mask(v));
+    }
+    for (int e = tid; e < b_rows * bs; e += REG_THREADS) {
+        const int r = e / bs, c = i0 + (e % bs) * 4, j = j0 + r;
+        const unsigned int v = j < ext ? reg_load4(pb + (size_t)j * ext, c, ext) : 0u;
+        sB[e] = make_uint2(v, reg_nonzero_mask(v));
+    }
+    __syncthreads();
+
+    int o[K], sh[K], row_b[K];                                   // row_b: an index into sB, so every read stays an LDS read
+    unsigned int cnt[K], sa[K], sb[K], saa[K], sbb[K], sab[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        o[k] = (ob * K + k) * REG_THREADS + tid;
+        const int oc = min(o[k], n_off - 1);                     // a thread past the last offset walks the last one and drops it
+        const int dyi = oc / w1, dxi = oc - dyi * w1;
+        sh[k] = dxi & 3;
+        row_b[k] = dyi * bs + (dxi >> 2);
+        cnt[k] = sa[k] = sb[k] = saa[k] = sbb[k] = sab[k] = 0u;
+    }
+    for (int r = 0; r < tile_rows; ++r) {
+        uint2 lo[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) lo[k] = sB[row_b[k]];
+#pragma unroll
+        for (int c = 0; c < REG_TILE_DW; ++c) {
+            const uint2 av = sA[r * REG_TILE_DW + c];
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const uint2 hi = sB[row_b[k] + c + 1];
+                const unsigned int bv = __builtin_amdgcn_alignbyte(hi.x, lo[k].x, sh[k]);
+                const unsigned int bm = __builtin_amdgcn_alignbyte(hi.y, lo[k].y, sh[k]);
+                const unsigned int am = av.x & bm, bmv = bv & av.y;              // a cell that either frame does not see adds 0 to every sum
+                sa[k] = __builtin_amdgcn_sad_u8(am, 0u, sa[k]);
+                sb[k] = __builtin_amdgcn_sad_u8(bmv, 0u, sb[k]);
+                saa[k] = __builtin_amdgcn_udot4(am, am, saa[k], false);
+                sbb[k] = __builtin_amdgcn_udot4(bmv, bmv, sbb[k], false);
+                sab[k] = __builtin_amdgcn_udot4(am, bmv, sab[k], false);
+                cnt[k] += __popc(av.y & bm);
+                lo[k] = hi;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) row_b[k] += bs;
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        if (o[k] < n_off && cnt[k]) {                            // a counted cell has a, b >= 1: all six partials are positive
+            unsigned long long* out = moments + ((size_t)p * n_off + o[k]) * REG_MOMENTS;
+            atomicAdd(out, (unsigned long long)(cnt[k] >> 3));
+            atomicAdd(out + 1, (unsigned long long)sa[k]);
+            atomicAdd(out + 2, (unsigned long long)sb[k]);
+            atomicAdd(out + 3, (unsigned long long)saa[k]);
+            atomicAdd(out + 4, (unsigned long long)sbb[k]);
+            atomicAdd(out + 5, (unsigned long long)sab[k]);
+        }
+}
+
+struct zncc_cand { double q; int n, dy, dx; };                   // n < 0: no candidate
+
+// the header's order: p beats q
+__device__ __forceinline__ bool zncc_beats(const zncc_cand& p, const zncc_cand& q) {
+    if (p.n < 0) return false;
+    if (q.n < 0) return true;
+    if (p.q != q.q) return p.q > q.q;
+    return reg_key_less(p.dy, p.dx, q.dy, q.dx);
+}
+
+__global__ __launch_bounds__(REG_THREADS) void register_zncc_best_kernel(const long long* __restrict__ moments, int search, int min_cells,
+                                                                          int* __restrict__ best, double* __restrict__ peak) {
+#pragma clang fp contract(off)
+    __shared__ zncc_cand s_wave[REG_THREADS / 64];
+    __shared__ zncc_cand s_first;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p = blockIdx.x, w1 = 2 * search + 1, n_off = w1 * w1;
+    const long long* mo = moments + (size_t)p * n_off * REG_MOMENTS;
+    for (int pass = 0; pass < 2; ++pass) {
+        zncc_cand first = {0.0, -1, 0, 0};
+        if (pass) first = s_first;
+        zncc_cand mine = {0.0, -1, 0, 0};
+        if (!pass || first.n >= 0)
+            for (int o = tid; o < n_off; o += REG_THREADS) {
+                const long long* m = mo + (size_t)o * REG_MOMENTS;
+                const long long n = m[0];
+                if (n < min_cells) continue;
+                const int dy = o / w1 - search, dx = o % w1 - search;
+                if (pass && max(abs(dy - first.dy), abs(dx - first.dx)) < 2) continue;
+                const long long sa = m[1], sb = m[2];
+                const long long va = n * m[3] - sa * sa, vb = n * m[4] - sb * sb;      // exact: every product is below 2^53
+                if (va <= 0 || vb <= 0) continue;                                       // a flat plane has no correlation
+                const double c = (double)(n * m[5] - sa * sb);
+                const zncc_cand cand = {(c * fabs(c)) / ((double)va * (double)vb), (int)n, dy, dx};
+                if (zncc_beats(cand, mine)) mine = cand;
+            }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const zncc_cand other = {__shfl_xor(mine.q, d), __shfl_xor(mine.n, d), __shfl_xor(mine.dy, d), __shfl_xor(mine.dx, d)};
+            if (zncc_beats(other, mine)) mine = other;
+        }
+        if (lane == 0) s_wave[wave] = mine;
+        __syncthreads();
+        if (tid == 0) {
+            zncc_cand top = s_wave[0];
+#pragma unroll
+            for (int k = 1; k < REG_THREADS / 64; ++k)
+                if (zncc_beats(s_wave[k], top)) top = s_wave[k];
+            int* out = best + (size_t)p * 8 + pass * 4;
+            const bool has = top.n >= 0;
+            out[0] = has ? top.dy : 0;
+            out[1] = has ? top.dx : 0;
+            out[2] = has ? 1 : 0;
+            out[3] = has ? top.n : 0;
+            peak[(size_t)p * 2 + pass] = has ? top.q : __builtin_nan("");
             s_first = top;
         }
         __syncthreads();

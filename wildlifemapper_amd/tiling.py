@@ -1441,10 +1441,14 @@ def adjust(n_frames, pairs, measured, weights, fixed=None) -> Dict[str, np.ndarr
     return {"shift": shift, "residual": residual, "component": component}
 
 
+REGISTER_METRICS = ("sad", "zncc")
+
+
 def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512, min_cells: int = 4096, min_ratio: float = 1.25,
-             pairs=None, fixed=None, pair_chunk: int = 256) -> Dict[str, object]:
+             pairs=None, fixed=None, pair_chunk: int = 256, metric: str = "sad", min_corr: float = 0.0) -> Dict[str, object]:
     """Correct the georeferences of a survey by matching the pixels of its overlapping frames (wm_register_render_u8,
-    wm_register_search; rule: include/wm_hip.h "Survey registration").  frames as mosaic() takes them: a sequence that is
+    wm_register_search or wm_register_search_zncc; rule: include/wm_hip.h "Survey registration" and "Survey registration,
+    correlation search").  frames as mosaic() takes them: a sequence that is
     only indexed -- tensors, arrays, or a lazy sequence that loads frame i when asked; georef (F,2,3) float64 as for
     census(); cell metres; sizes (F,2) may be None only for a list of tensors or arrays.  pairs: the table to use, None for
     register_pairs(georef, sizes, cell, search, side, min_cells).  Everything is validated before any device work.
@@ -1455,15 +1459,34 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
     on the window's edge is not a peak), and the runner-up outside the peak's 3 x 3 has a mean absolute difference of at
     least min_ratio times the peak's (sad2 / n2 >= min_ratio * (sad / n), in double); a runner-up that does not exist also
     accepts.  The accepted pairs, each measuring t_b - t_a = -(dx, dy) * cell with weight n, go to adjust(fixed=fixed).
-    SAD assumes the same exposure in both frames of a pair (no gain or offset is fitted); a cell coarser than the ground
+    metric: "sad" (the default) is the rule above, masked sums of absolute differences; it assumes the same exposure in
+    both frames of a pair (no gain or offset is fitted).  Where exposure changes between frames -- auto-exposure, cloud
+    shadow -- use metric="zncc": the offsets are scored by the zero-mean normalised correlation, which a gain and an offset
+    between the two frames do not change.  With r = sign(q) * sqrt(|q|) of the device's signed squared correlation q, a
+    pair is then accepted iff a best offset exists (n >= min_cells and neither plane flat), |dy| < search and |dx| <
+    search, r > min_corr (finite, in [-1, 1)), and the runner-up does not exist or 1 - r2 >= min_ratio * (1 - r): 1 - r
+    takes the part of the mean absolute difference, so min_ratio keeps its meaning.  Both defaults are policy, not
+    measurements on real imagery.  A cell coarser than the ground
     sampling distance point-samples, so shrink the frames first (preprocess.resample_u8, resampled_georef); only a
     translation is corrected, not yaw or scale; the resolution is one cell -- a second register() at a finer cell on the
     corrected georef refines it.  Runs on the current device's current stream.  No CPU fallback.  Returns host arrays:
       'georef' (F,2,3) float64 corrected (shift added to a2, a5), 'shift' (F,2) metres, 'pairs' the table,
       'offset' (P,2) int64 cells (dx, dy), 'cells' (P,) int64 n at the best offset (0: none), 'mean' (P,) float64 sad / n
       (NaN: none), 'runner_up' (P,) float64 sad2 / n2 (NaN: none), 'accepted' (P,) bool, 'residual' (P,2) metres after
-      the adjustment, 'component' (F,) int64 as adjust() gives it."""
+      the adjustment, 'component' (F,) int64 as adjust() gives it, 'corr' (P,) float64 NaN.  Under metric="zncc" 'mean'
+      is 1 - r and 'runner_up' 1 - r2 (NaN: none), and 'corr' is r (NaN: none)."""
     what = "register"
+    if not isinstance(metric, str) or metric not in REGISTER_METRICS:
+        raise ValueError(f"{what}: metric {metric!r} must be one of {REGISTER_METRICS}")
+    try:
+        if isinstance(min_corr, bool):
+            raise TypeError
+        min_corr = float(min_corr)
+        if not (math.isfinite(min_corr) and -1.0 <= min_corr < 1.0):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: min_corr {min_corr!r} must be a finite number in [-1, 1)") from None
+    zncc = metric == "zncc"
     search, side, min_cells = _check_register_shape(search, side, min_cells, what)
     pair_chunk = _check_whole(pair_chunk, what, "pair_chunk")
     if pair_chunk > REGISTER_MAX_PAIRS:
@@ -1487,7 +1510,9 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
     adjust(F, np.zeros((0, 2), dtype=np.int64), np.zeros((0, 2)), np.zeros(0), fixed)         # fixed= validated before device work
     P = table.shape[0]
     best = np.zeros((P, 8), dtype=np.int32)
-    best[:, 2] = best[:, 6] = -1
+    peak = np.full((P, 2), np.nan, dtype=np.float64)                 # (q, q2) of the correlation search
+    if not zncc:
+        best[:, 2] = best[:, 6] = -1
     if P:
         dev = _survey_device(what)
         lib = N.lib()
@@ -1508,10 +1533,18 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
                     N.check(lib.wm_register_render_u8(N.ptr(desc), len(ids), N.ptr(slot_d), N.ptr(g_d), N.ptr(s_d), F, N.ptr(pairs_d), n,
                                                       cell, search, side, N.ptr(plane_a), N.ptr(plane_b), N.ptr(status), N.stream_ptr(dev)))
                     del resident, desc, slot_d                    # the stream orders their reuse after the launch
-                score = torch.empty((n, 2 * search + 1, 2 * search + 1, 2), device=dev, dtype=torch.int32)
                 best_d = torch.empty((n, 8), device=dev, dtype=torch.int32)
-                N.check(lib.wm_register_search(N.ptr(plane_a), N.ptr(plane_b), N.ptr(pairs_d), n, search, side, min_cells, N.ptr(score),
-                                               N.ptr(best_d), N.stream_ptr(dev)))
+                if zncc:
+                    score = torch.empty((n, 2 * search + 1, 2 * search + 1, 6), device=dev, dtype=torch.int64)
+                    peak_d = torch.empty((n, 2), device=dev, dtype=torch.float64)
+                    N.check(lib.wm_register_search_zncc(N.ptr(plane_a), N.ptr(plane_b), N.ptr(pairs_d), n, search, side, min_cells,
+                                                        N.ptr(score), N.ptr(best_d), N.ptr(peak_d), N.stream_ptr(dev)))
+                    peak[c0:c0 + n] = peak_d.cpu().numpy()
+                    del peak_d
+                else:
+                    score = torch.empty((n, 2 * search + 1, 2 * search + 1, 2), device=dev, dtype=torch.int32)
+                    N.check(lib.wm_register_search(N.ptr(plane_a), N.ptr(plane_b), N.ptr(pairs_d), n, search, side, min_cells, N.ptr(score),
+                                                   N.ptr(best_d), N.stream_ptr(dev)))
                 best[c0:c0 + n] = best_d.cpu().numpy()
                 del plane_a, plane_b, score, best_d, pairs_d
             bad = int(status.item())
@@ -1519,15 +1552,25 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
             raise RuntimeError(f"{what}: wm_register_render_u8 skipped planes (status {bad}): a resident frame did not match its slot or size")
     dy, dx, sad, n1 = (best[:, k].astype(np.int64) for k in range(4))
     sad2, n2 = best[:, 6].astype(np.int64), best[:, 7].astype(np.int64)
-    has, has2 = sad >= 0, sad2 >= 0
     with np.errstate(all="ignore"):
-        mean = np.where(has, sad / np.maximum(n1, 1), np.nan)
-        runner = np.where(has2, sad2 / np.maximum(n2, 1), np.nan)
-        accepted = has & (np.abs(dy) < search) & (np.abs(dx) < search) & (~has2 | (runner >= min_ratio * mean))
+        if zncc:                                                     # best's third of four is ok (1 / 0), peak holds q (NaN: none)
+            has, has2 = sad == 1, sad2 == 1
+            r = np.sign(peak) * np.sqrt(np.abs(peak))
+            corr = np.where(has, r[:, 0], np.nan)
+            mean = np.where(has, 1.0 - r[:, 0], np.nan)
+            runner = np.where(has2, 1.0 - r[:, 1], np.nan)
+            confident = has & (corr > min_corr)
+        else:
+            confident = has = sad >= 0
+            has2 = sad2 >= 0
+            corr = np.full(P, np.nan)
+            mean = np.where(has, sad / np.maximum(n1, 1), np.nan)
+            runner = np.where(has2, sad2 / np.maximum(n2, 1), np.nan)
+        accepted = confident & (np.abs(dy) < search) & (np.abs(dx) < search) & (~has2 | (runner >= min_ratio * mean))
     offset = np.stack([dx, dy], axis=1).reshape(P, 2)
     adj = adjust(F, table, -offset.astype(np.float64) * cell, np.where(accepted, n1, 0).astype(np.float64), fixed)
     out_g = g.copy()
     out_g[:, 0, 2] += adj["shift"][:, 0]
     out_g[:, 1, 2] += adj["shift"][:, 1]
     return {"georef": out_g, "shift": adj["shift"], "pairs": table, "offset": offset, "cells": np.where(has, n1, 0), "mean": mean,
-            "runner_up": runner, "accepted": accepted, "residual": adj["residual"], "component": adj["component"]}
+            "runner_up": runner, "accepted": accepted, "residual": adj["residual"], "component": adj["component"], "corr": corr}
