@@ -69,21 +69,29 @@ def beats(p, q):
     return (p[2] * p[2] + p[3] * p[3], p[2], p[3]) < (q[2] * q[2] + q[3] * q[3], q[2], q[3])
 
 
-def pick_oracle(score, S, min_cells):
-    """best (8,) int64 from a score table, sequentially."""
+def pick_two(S, candidate, beats):
+    """The pick of both searches, sequentially: the best offset, then the best outside its 3 x 3 (None where there is none).
+    candidate(dy, dx) is the offset's (score, n, dy, dx) or None; beats(p, q) the metric's order."""
     def top(excluded):
         best = None
         for dy in range(-S, S + 1):
             for dx in range(-S, S + 1):
-                sad, n = (int(v) for v in score[dy + S, dx + S])
-                if n < min_cells or (excluded is not None and max(abs(dy - excluded[0]), abs(dx - excluded[1])) < 2):
+                if excluded is not None and max(abs(dy - excluded[2]), abs(dx - excluded[3])) < 2:
                     continue
-                cand = (sad, n, dy, dx)
-                if best is None or beats(cand, best):
+                cand = candidate(dy, dx)
+                if cand is not None and (best is None or beats(cand, best)):
                     best = cand
         return best
     first = top(None)
-    second = top((first[2], first[3])) if first is not None else None
+    return first, (top(first) if first is not None else None)
+
+
+def pick_oracle(score, S, min_cells):
+    """best (8,) int64 from a score table, sequentially."""
+    def candidate(dy, dx):
+        sad, n = (int(v) for v in score[dy + S, dx + S])
+        return (sad, n, dy, dx) if n >= min_cells else None
+    first, second = pick_two(S, candidate, beats)
     four = lambda c: [0, 0, -1, 0] if c is None else [c[2], c[3], c[0], c[1]]
     return np.array(four(first) + four(second), dtype=np.int64)
 
@@ -528,17 +536,26 @@ def _render(case, a, b, status, resident, slot=None, images=None):
     torch.cuda.synchronize()
 
 
-def _search(case, a, b, min_cells=None):
-    """wm_register_search on device planes, both outputs pre-filled with a poison value.  Returns (score, best) int64."""
-    n, w1 = len(case["pairs"]), 2 * case["search"] + 1
-    pairs = _up(case["pairs"].view(np.uint8).reshape(n, 32))
-    score = torch.full((n, w1, w1, 2), -77, device=DEV, dtype=torch.int32)
+def device_search(metric, a, b, table, S, side, min_cells):
+    """wm_register_search ("sad") or wm_register_search_zncc ("zncc") on device planes a (P, side, side), b (P, E, E) and a
+    pair table, every output pre-filled with a poison value.  Returns the offsets' table (P, 2S+1, 2S+1, 2 or 6) and best
+    (P, 8) as int64, and peak (P, 2) float64 (None for "sad")."""
+    zncc = metric == "zncc"
+    n, w1 = len(table), 2 * S + 1
+    pairs = _up(table.view(np.uint8).reshape(n, 32))
+    score = torch.full((n, w1, w1, 6 if zncc else 2), -77, device=DEV, dtype=torch.int64 if zncc else torch.int32)
     best = torch.full((n, 8), -77, device=DEV, dtype=torch.int32)
-    N.check(N.lib().wm_register_search(N.ptr(a), N.ptr(b), N.ptr(pairs), n, case["search"], case["side"],
-                                       case["min_cells"] if min_cells is None else min_cells, N.ptr(score), N.ptr(best),
-                                       N.stream_ptr(torch.device(DEV))))
+    peak = torch.full((n, 2), 123.0, device=DEV, dtype=torch.float64) if zncc else None
+    entry = N.lib().wm_register_search_zncc if zncc else N.lib().wm_register_search
+    N.check(entry(N.ptr(a), N.ptr(b), N.ptr(pairs), n, S, side, min_cells, N.ptr(score), N.ptr(best), *([N.ptr(peak)] if zncc else []),
+                  N.stream_ptr(torch.device(DEV))))
     torch.cuda.synchronize()
-    return score.cpu().numpy().astype(np.int64), best.cpu().numpy().astype(np.int64)
+    return score.cpu().numpy().astype(np.int64), best.cpu().numpy().astype(np.int64), peak.cpu().numpy() if zncc else None
+
+
+def _search(case, a, b, min_cells=None):
+    """The SAD search of a case on device planes.  Returns (score, best) int64."""
+    return device_search("sad", a, b, case["pairs"], case["search"], case["side"], case["min_cells"] if min_cells is None else min_cells)[:2]
 
 
 def _run_and_check(case, want=None):
@@ -677,6 +694,46 @@ def test_gpu_extremes_white_against_black_and_sprinkled_zeros():
         want = search_oracle(A[p], B[p], 70, 45, 5)
         np.testing.assert_array_equal(score[p], want)
         np.testing.assert_array_equal(best[p], pick_oracle(want, 5, 300))
+
+
+def per_k_planes():
+    """The planes of the offsets-per-thread tests of both searches: 72 x 72 against 82 x 82 (search 5), 20 % / 30 % not seen."""
+    rng = np.random.default_rng(17)
+    A = np.where(rng.random((72, 72)) < 0.2, 0, rng.integers(1, 256, size=(72, 72))).astype(np.uint8)
+    B = np.where(rng.random((82, 82)) < 0.3, 0, rng.integers(1, 256, size=(82, 82))).astype(np.uint8)
+    return A, B
+
+
+_PER_K_WANT = []
+
+
+def _per_k_want():
+    """(score, best) of the oracle on per_k_planes() at size (70, 45), min_cells 300; computed once for the three K."""
+    if not _PER_K_WANT:
+        A, B = per_k_planes()
+        score = search_oracle(A, B, 70, 45, 5)
+        _PER_K_WANT.append((score, pick_oracle(score, 5, 300)))
+    return _PER_K_WANT[0]
+
+
+def test_oracle_per_k_case_has_a_best_and_a_runner_up():
+    score, best = _per_k_want()                                                      # about 56 % of 3150 cells at the central offsets
+    assert best[2] >= 0 and best[6] >= 0 and best[3] >= 300 and best[7] >= 300
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", (1, 2, 4))
+def test_gpu_every_offsets_per_thread_instance(k, monkeypatch):
+    """WM_REGISTER_K forces the instance (the launcher reads it per call); the result does not depend on it.  At search 5
+    the 121 offsets leave most threads of a K = 4 block without one: they walk the last offset and drop it."""
+    monkeypatch.setenv("WM_REGISTER_K", str(k))
+    A, B = per_k_planes()
+    want_score, want_best = _per_k_want()
+    assert want_best[2] >= 0 and want_best[6] >= 0                                    # the case cannot pass by having nothing eligible
+    case, a, b = _plane_case([A], [B], 70, 45, 5, min_cells=300)
+    score, best = _search(case, a, b)
+    np.testing.assert_array_equal(score[0], want_score)
+    np.testing.assert_array_equal(best[0], want_best)
 
 
 @pytest.mark.gpu

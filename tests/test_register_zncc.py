@@ -57,22 +57,11 @@ def zncc_beats(p, q):
 
 def zncc_pick_oracle(moments, S, min_cells):
     """(best (8,) int64, peak (2,) float64) from a moments table, sequentially."""
-    def top(excluded):
-        best = None
-        for dy in range(-S, S + 1):
-            for dx in range(-S, S + 1):
-                m = moments[dy + S, dx + S]
-                if int(m[0]) < min_cells or (excluded is not None and max(abs(dy - excluded[0]), abs(dx - excluded[1])) < 2):
-                    continue
-                q = zncc_q(m)
-                if q is None:
-                    continue
-                cand = (q, int(m[0]), dy, dx)
-                if best is None or zncc_beats(cand, best):
-                    best = cand
-        return best
-    first = top(None)
-    second = top((first[2], first[3])) if first is not None else None
+    def candidate(dy, dx):
+        m = moments[dy + S, dx + S]
+        q = zncc_q(m) if int(m[0]) >= min_cells else None
+        return None if q is None else (q, int(m[0]), dy, dx)
+    first, second = T.pick_two(S, candidate, zncc_beats)
     four = lambda c: [0, 0, 0, 0] if c is None else [c[2], c[3], 1, c[1]]
     peak = np.array([NAN if c is None else c[0] for c in (first, second)], dtype=F64)
     return np.array(four(first) + four(second), dtype=np.int64), peak
@@ -285,18 +274,10 @@ def test_register_metric_and_min_corr_errors_before_device_work():
 def _zncc(A, B, sizes, S, min_cells):
     """wm_register_search_zncc on hand-built planes: A a list of (side, side), B of (E, E) uint8, sizes a list of (gx, gy).
     Every output is pre-filled with a poison value.  Returns moments (P, 2S+1, 2S+1, 6) int64, best (P, 8) int64, peak (P, 2)."""
-    n, w1, side = len(A), 2 * S + 1, A[0].shape[0]
+    side = A[0].shape[0]
     assert all(x.shape == (side, side) for x in A) and all(x.shape == (side + 2 * S, side + 2 * S) for x in B)
     table = T._pairs([(0, 1, gx, gy, 0.0, 0.0) for gx, gy in sizes])
-    pairs = T._up(table.view(np.uint8).reshape(n, 32))
-    a, b = T._up(np.stack(A)), T._up(np.stack(B))
-    moments = torch.full((n, w1, w1, 6), -77, device=DEV, dtype=torch.int64)
-    best = torch.full((n, 8), -77, device=DEV, dtype=torch.int32)
-    peak = torch.full((n, 2), 123.0, device=DEV, dtype=torch.float64)
-    N.check(N.lib().wm_register_search_zncc(N.ptr(a), N.ptr(b), N.ptr(pairs), n, S, side, min_cells, N.ptr(moments), N.ptr(best), N.ptr(peak),
-                                            N.stream_ptr(torch.device(DEV))))
-    torch.cuda.synchronize()
-    return moments.cpu().numpy(), best.cpu().numpy().astype(np.int64), peak.cpu().numpy()
+    return T.device_search("zncc", T._up(np.stack(A)), T._up(np.stack(B)), table, S, side, min_cells)
 
 
 def _check(A, B, sizes, S, min_cells, want=None):
@@ -415,9 +396,7 @@ def test_gpu_zncc_every_offsets_per_thread_instance(k, monkeypatch):
     """WM_REGISTER_K forces the instance (the launcher reads it per call); the result does not depend on it.  At search 5
     the 121 offsets leave most threads of a K = 4 block without one: they walk the last offset and drop it."""
     monkeypatch.setenv("WM_REGISTER_K", str(k))
-    rng = np.random.default_rng(17)
-    A = np.where(rng.random((72, 72)) < 0.2, 0, rng.integers(1, 256, size=(72, 72))).astype(np.uint8)
-    B = np.where(rng.random((82, 82)) < 0.3, 0, rng.integers(1, 256, size=(82, 82))).astype(np.uint8)
+    A, B = T.per_k_planes()
     _check([A], [B], [(70, 45)], 5, 300)
 
 

@@ -1,24 +1,32 @@
-"""Times of the survey registration (wm_register_render_u8, wm_register_search) against the host route a caller had before.
+"""Times of the survey registration: the render (wm_register_render_u8) and both searches (wm_register_search, SAD, and
+wm_register_search_zncc, the correlation) on the same planes, against the host route a caller had before.
 
-  python tools/register_time.py [--reps 20] [--oracle-pairs 4] [--only NAME]
+  python tools/register_time.py [--reps 20] [--oracle-pairs 4] [--zncc-oracle-pairs 2] [--only NAME]
       HIP-event min and median over --reps repetitions of one wm_register_render_u8 call with every frame of the chunk
-      resident (one launch) and of one wm_register_search call (one memset, the search launch, the pick launch) on ONE
-      CHUNK of pairs, as tiling.register issues them (pair_chunk pairs at a time; buffers and frames are allocated once,
-      outside the timed region), and -- for the first --oracle-pairs pairs of the chunk -- the wall clock of the numpy
-      restatement of the rule on the same input (tests/test_register.py: register_oracle), whose planes, score table
-      and best the device's must equal.  The restatement costs seconds per pair at the survey setting, so it runs on a
-      sample and its time for the survey is the sample's mean per byte difference times the survey's byte differences.
+      resident (one launch) and of one search call (one memset, the search launch, the pick launch) on ONE CHUNK of
+      pairs, as tiling.register issues them (pair_chunk pairs at a time; buffers and frames are allocated once, outside
+      the timed region).  The SAD search is timed in a run of its own (search_ms_*), and then, in the same process,
+      --reps rounds of one SAD call and one correlation call, alternating, each between two HIP events (sad_ms_*,
+      zncc_ms_*, and the ratio zncc / sad of the minima and of the medians).
       Two settings, nadir frames of 400 x 600 px (20 x 30 m at 0.05 m) of random content at UTM-sized coordinates on
       flight lines with 55 % forward overlap and 30 % sidelap, a little jitter in position and heading, cell = 0.05 m:
         f40      F = 40 (4 lines of 10), side 256, search 16, pair_chunk 64;
         f1000    F = 1 000 (25 lines of 40), side 512, search 32, pair_chunk 256: about 4 pairs per frame.
-      The search's work is counted from the shapes: (2 S + 1)^2 * gx * gy byte differences per pair.  With the minimum
-      time that is a rate, printed against the VALU bound of the kernel's inner loop: 7 vector instructions per 4 cells
-      and offset (two v_alignbyte_b32, three v_and_b32, v_sad_u8, v_bcnt_u32_b32), 256 CUs x 4 SIMDs x 32 lanes per
-      clock at 2.4 GHz = 78.6e12 lane-instructions per second (MI355X_MICROARCH: a wave64 VALU instruction issues over
-      2 cycles on a SIMD-32), so 44.9e12 byte differences per second.
-      The search is also timed with each of the offsets-per-thread variants K = 1, 2, 4 (WM_REGISTER_K; the result does
-      not depend on K), alternating, next to the default choice.
+      The searches' work is counted from the shapes: (2 S + 1)^2 * gx * gy cell pairs (byte differences) per pair of
+      frames.  With the minimum time that is a rate, printed against the VALU bound of each inner loop: per 4 cells and
+      offset SAD issues 7 vector instructions (two v_alignbyte_b32, three v_and_b32, v_sad_u8, v_bcnt_u32_b32), the
+      correlation 11 (two v_alignbyte_b32, three v_and_b32, two v_sad_u8, three v_dot4_u32_u8, v_bcnt_u32_b32); 256 CUs
+      x 4 SIMDs x 32 lanes per clock at 2.4 GHz = 78.6e12 lane-instructions per second (MI355X_MICROARCH: a wave64
+      VALU instruction issues over 2 cycles on a SIMD-32), so 44.9e12 and 28.6e12 cell pairs per second.
+      Each search is also timed with each of the offsets-per-thread variants K = 1, 2, 4 (WM_REGISTER_K; the result does
+      not depend on K), alternating, twice, next to the default choice.
+      For the first --oracle-pairs pairs of the chunk the wall clock of the numpy restatement of the SAD rule on the same
+      input (tests/test_register.py: register_oracle), whose planes, score table and best the device's must equal; it
+      costs seconds per pair at the survey setting, so it runs on a sample and its time for the survey is the sample's
+      mean per byte difference times the survey's byte differences.  For the first --zncc-oracle-pairs pairs the device's
+      moments, best and peak must equal the restatement of the correlation rule (tests/test_register_zncc.py:
+      zncc_search_oracle, zncc_pick_oracle) on the device's planes, peak by its bytes.  The tool asserts both;
+      equals_oracle is true where every comparison that ran held.
       Prints one JSON line.  No figure is a pass mark: the numbers are records.
 """
 import argparse
@@ -37,8 +45,9 @@ from wildlifemapper_amd import _native as N  # noqa: E402
 from wildlifemapper_amd import tiling  # noqa: E402
 
 H, W, GSD = 400, 600, 0.05
+MIN_CELLS = 4096
 VALU_LANE_OPS = 256 * 4 * 32 * 2.4e9          # lane-instructions per second
-LOOP_VALU_PER_4_CELLS = 7
+LOOP_VALU_PER_4_CELLS = {"sad": 7, "zncc": 11}
 
 
 def make(lines, per_line, seed):
@@ -50,26 +59,39 @@ def make(lines, per_line, seed):
     return georef, np.tile(np.array([[H, W]], dtype=np.int32), (lines * per_line, 1))
 
 
+def once(call):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    call()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
 def timed(call, reps):
     call()
     torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
+    ms = [once(call) for _ in range(reps)]
     return round(float(np.min(ms)), 4), round(float(np.median(ms)), 4)
 
 
-def run(lines, per_line, side, search, pair_chunk, seed, reps, oracle_pairs):
+def by_offsets_per_thread(call, reps):
+    """Minimum time of `call` with K = 1, 2, 4 forced through WM_REGISTER_K, alternating, twice."""
+    by_k = {}
+    for rnd in range(2):
+        for k in (1, 2, 4):
+            os.environ["WM_REGISTER_K"] = str(k)
+            by_k.setdefault(f"k{k}", []).append(timed(call, reps)[0])
+    del os.environ["WM_REGISTER_K"]
+    return by_k
+
+
+def run(lines, per_line, side, search, pair_chunk, seed, reps, oracle_pairs, zncc_oracle_pairs):
     dev = torch.device("cuda:0")
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     georef, size = make(lines, per_line, seed)
     F = georef.shape[0]
-    table = tiling.register_pairs(georef, size, GSD, search, side, 4096)
+    table = tiling.register_pairs(georef, size, GSD, search, side, MIN_CELLS)
     w1 = 2 * search + 1
     diffs_all = int((table["gx"].astype(np.int64) * table["gy"]).sum()) * w1 * w1
     chunk = table[:pair_chunk]
@@ -90,47 +112,78 @@ def run(lines, per_line, side, search, pair_chunk, seed, reps, oracle_pairs):
     b = torch.zeros((n, E, E), device=dev, dtype=torch.uint8)
     status = torch.zeros(1, device=dev, dtype=torch.int32)
     score = torch.empty((n, w1, w1, 2), device=dev, dtype=torch.int32)
+    best_sad = torch.empty((n, 8), device=dev, dtype=torch.int32)
+    moments = torch.empty((n, w1, w1, 6), device=dev, dtype=torch.int64)
     best = torch.empty((n, 8), device=dev, dtype=torch.int32)
+    peak = torch.empty((n, 2), device=dev, dtype=torch.float64)
     lib, st = N.lib(), N.stream_ptr(dev)
     render = lambda: N.check(lib.wm_register_render_u8(N.ptr(desc), len(needed), N.ptr(slot_d), N.ptr(g_d), N.ptr(s_d), F, N.ptr(pairs_d), n, GSD,
                                                        search, side, N.ptr(a), N.ptr(b), N.ptr(status), st))
-    find = lambda: N.check(lib.wm_register_search(N.ptr(a), N.ptr(b), N.ptr(pairs_d), n, search, side, 4096, N.ptr(score), N.ptr(best), st))
+    sad = lambda: N.check(lib.wm_register_search(N.ptr(a), N.ptr(b), N.ptr(pairs_d), n, search, side, MIN_CELLS, N.ptr(score), N.ptr(best_sad), st))
+    zncc = lambda: N.check(lib.wm_register_search_zncc(N.ptr(a), N.ptr(b), N.ptr(pairs_d), n, search, side, MIN_CELLS, N.ptr(moments),
+                                                       N.ptr(best), N.ptr(peak), st))
     r_min, r_med = timed(render, reps)
-    s_min, s_med = timed(find, reps)
+    s_min, s_med = timed(sad, reps)
     rate = diffs / (s_min * 1e-3)
-    bound = VALU_LANE_OPS / LOOP_VALU_PER_4_CELLS * 4
+    bound = VALU_LANE_OPS / LOOP_VALU_PER_4_CELLS["sad"] * 4
     out = {"frames": F, "pairs": int(table.shape[0]), "pairs_per_frame": round(table.shape[0] / F, 2), "side": side, "search": search,
            "chunk_pairs": n, "chunk_frames": len(needed), "mean_patch_cells": int((chunk["gx"].astype(np.int64) * chunk["gy"]).mean()),
            "render_ms_min": r_min, "render_ms_median": r_med, "render_cells": n * (side * side + E * E),
            "search_ms_min": s_min, "search_ms_median": s_med, "search_byte_differences": diffs,
            "search_byte_differences_per_s": float(f"{rate:.4g}"), "valu_bound_byte_differences_per_s": float(f"{bound:.4g}"),
            "search_fraction_of_valu_bound": round(rate / bound, 4), "survey_byte_differences": diffs_all,
-           "survey_search_s_at_this_rate": round(diffs_all / rate, 4), "render_status": int(status.item())}
-    by_k = {}
-    for rnd in range(2):                                      # K = 1, 2, 4 alternating, twice
-        for k in (1, 2, 4):
-            os.environ["WM_REGISTER_K"] = str(k)
-            by_k.setdefault(f"k{k}", []).append(timed(find, reps)[0])
-    del os.environ["WM_REGISTER_K"]
-    out["search_ms_min_by_offsets_per_thread"] = by_k
-    find()
+           "survey_search_s_at_this_rate": round(diffs_all / rate, 4), "render_status": int(status.item()), "cell_pairs": diffs}
+    sad(), zncc()
+    torch.cuda.synchronize()
+    ms = {"sad": [], "zncc": []}
+    for _ in range(reps):                                     # alternating, in one process
+        ms["sad"].append(once(sad))
+        ms["zncc"].append(once(zncc))
+    a_min, a_med = float(np.min(ms["sad"])), float(np.median(ms["sad"]))
+    z_min, z_med = float(np.min(ms["zncc"])), float(np.median(ms["zncc"]))
+    rate, bound = diffs / (z_min * 1e-3), VALU_LANE_OPS / LOOP_VALU_PER_4_CELLS["zncc"] * 4
+    out.update({"sad_ms_min": round(a_min, 4), "sad_ms_median": round(a_med, 4), "zncc_ms_min": round(z_min, 4), "zncc_ms_median": round(z_med, 4),
+                "zncc_over_sad_min": round(z_min / a_min, 3), "zncc_over_sad_median": round(z_med / a_med, 3),
+                "zncc_cell_pairs_per_s": float(f"{rate:.4g}"), "valu_bound_cell_pairs_per_s": float(f"{bound:.4g}"),
+                "zncc_fraction_of_valu_bound": round(rate / bound, 4)})
+    out["search_ms_min_by_offsets_per_thread"] = by_offsets_per_thread(sad, reps)
+    out["zncc_ms_min_by_offsets_per_thread"] = by_offsets_per_thread(zncc, reps)
+    sad(), zncc()
+    torch.cuda.synchronize()
+    equal = []
     if oracle_pairs > 0:
         from test_register import register_oracle
         m = min(oracle_pairs, n)
         host = pixels.cpu().numpy()
         images = {f: host[k] for k, f in enumerate(needed)}
         t = time.perf_counter()
-        want = register_oracle(g2p, size, images, chunk[:m], GSD, search, side, 4096)
+        want = register_oracle(g2p, size, images, chunk[:m], GSD, search, side, MIN_CELLS)
         took = time.perf_counter() - t
         sample = int((chunk["gx"][:m].astype(np.int64) * chunk["gy"][:m]).sum()) * w1 * w1
         out["oracle_pairs"], out["oracle_host_s"] = m, round(took, 2)
         out["oracle_host_s_for_the_survey_extrapolated"] = round(took / sample * diffs_all, 1)
         got_a, got_b = a[:m].cpu().numpy(), b[:m].cpu().numpy()
-        got_s, got_best = score[:m].cpu().numpy(), best[:m].cpu().numpy()
-        equal = all(np.array_equal(got_a[p], want["a"][p]) and np.array_equal(got_b[p], want["b"][p]) and
-                    np.array_equal(got_s[p], want["score"][p]) and np.array_equal(got_best[p], want["best"][p]) for p in range(m))
-        out["equals_oracle"] = bool(equal)
-        assert equal, "the device result differs from register_oracle"
+        got_s, got_best = score[:m].cpu().numpy(), best_sad[:m].cpu().numpy()
+        equal.append(all(np.array_equal(got_a[p], want["a"][p]) and np.array_equal(got_b[p], want["b"][p]) and
+                         np.array_equal(got_s[p], want["score"][p]) and np.array_equal(got_best[p], want["best"][p]) for p in range(m)))
+        out["sad_equals_oracle"] = bool(equal[-1])
+    if zncc_oracle_pairs > 0:
+        from test_register_zncc import same_bytes, zncc_pick_oracle, zncc_search_oracle
+        m = min(zncc_oracle_pairs, n)
+        A, B = a[:m].cpu().numpy(), b[:m].cpu().numpy()
+        got_m, got_b, got_p = moments[:m].cpu().numpy(), best[:m].cpu().numpy(), peak[:m].cpu().numpy()
+        t = time.perf_counter()
+        ok = True
+        for p in range(m):
+            mo = zncc_search_oracle(A[p], B[p], int(chunk["gx"][p]), int(chunk["gy"][p]), search)
+            wb, wp = zncc_pick_oracle(mo, search, MIN_CELLS)
+            ok = ok and np.array_equal(got_m[p], mo) and np.array_equal(got_b[p], wb) and same_bytes(got_p[p], wp)
+        equal.append(ok)
+        out["zncc_oracle_pairs"], out["zncc_oracle_host_s"], out["zncc_equals_oracle"] = m, round(time.perf_counter() - t, 2), bool(ok)
+        out["sampled_peaks_r"] = [round(float(np.sign(q) * np.sqrt(abs(q))), 4) for q in got_p[:, 0]]
+    if equal:
+        out["equals_oracle"] = bool(all(equal))
+        assert all(equal), "the device result differs from the oracle: sad %s, zncc %s" % (out.get("sad_equals_oracle"), out.get("zncc_equals_oracle"))
     return out
 
 
@@ -138,13 +191,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--oracle-pairs", type=int, default=4)
+    ap.add_argument("--zncc-oracle-pairs", type=int, default=2)
     ap.add_argument("--only", default=None)
     a = ap.parse_args()
     settings = {"f40": (4, 10, 256, 16, 64), "f1000": (25, 40, 512, 32, 256)}
     out = {"reps": a.reps}
     for i, (name, (lines, per_line, side, search, chunk)) in enumerate(settings.items()):
         if a.only in (None, name):
-            out[name] = run(lines, per_line, side, search, chunk, i, a.reps, a.oracle_pairs)
+            out[name] = run(lines, per_line, side, search, chunk, i, a.reps, a.oracle_pairs, a.zncc_oracle_pairs)
     print(json.dumps(out))
 
 

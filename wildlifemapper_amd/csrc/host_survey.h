@@ -247,20 +247,36 @@ static int register_tile_rows(int search) {
     return reg_search_lds(search, REG_TILE_ROWS_MAX) <= REG_LDS_MAX ? REG_TILE_ROWS_MAX : REG_TILE_ROWS_MAX / 2;
 }
 
-int launch_register_search(const uint8_t* a_dev, const uint8_t* b_dev, const wm_register_pair* pairs_dev, int n_pairs, int search, int side,
-                           int min_cells, int32_t* score_dev, int32_t* best_dev, hipStream_t s) {
-    const char* name = "wm_register_search";
+// Both searches: the shared checks, the metric's own pointer checks, the table's memset, the tiles, the K rule, the search
+// launch and the pick launch.  SAD keeps two int32 per offset in score_dev; the correlation six int64 in moments_dev and
+// the picks' q in peak_dev.  The K rule was measured for both kernels (profiles/register/README.md,
+// profiles/register_zncc/README.md): for the correlation it picks the fastest K at search 16; at search 32 it picks K = 2
+// where K = 4 measured 1.7 % faster, too little and too few points for a second rule.
+template <bool ZNCC>
+static int launch_register_search_as(const char* name, const uint8_t* a_dev, const uint8_t* b_dev, const wm_register_pair* pairs_dev,
+                                     int n_pairs, int search, int side, int min_cells, std::conditional_t<ZNCC, int64_t, int32_t>* table_dev,
+                                     int32_t* best_dev, double* peak_dev, hipStream_t s) {
     if (n_pairs < 0 || n_pairs > WM_REGISTER_MAX_PAIRS) return fail("%s: n_pairs %d outside 0..%d", name, n_pairs, WM_REGISTER_MAX_PAIRS);
     if (n_pairs == 0) return 0;
     WM_TRY(check_register_shape(name, pairs_dev, search, side));
     if (min_cells < 1) return fail("%s: min_cells %d: need at least 1", name, min_cells);
     if (!a_dev) return fail("%s: null a_dev", name);
     if (!b_dev) return fail("%s: null b_dev", name);
-    if (!score_dev) return fail("%s: null score_dev", name);
-    if (!best_dev) return fail("%s: null best_dev", name);
-    if ((uintptr_t)score_dev % 4 || (uintptr_t)best_dev % 4) return fail("%s: score_dev / best_dev not 4-byte aligned", name);
+    if constexpr (ZNCC) {
+        if (!table_dev) return fail("%s: null moments_dev", name);
+        if (!best_dev) return fail("%s: null best_dev", name);
+        if (!peak_dev) return fail("%s: null peak_dev", name);
+        if ((uintptr_t)table_dev % 8) return fail("%s: moments_dev not 8-byte aligned", name);
+        if ((uintptr_t)peak_dev % 8) return fail("%s: peak_dev not 8-byte aligned", name);
+        if ((uintptr_t)best_dev % 4) return fail("%s: best_dev not 4-byte aligned", name);
+    } else {
+        if (!table_dev) return fail("%s: null score_dev", name);
+        if (!best_dev) return fail("%s: null best_dev", name);
+        if ((uintptr_t)table_dev % 4 || (uintptr_t)best_dev % 4) return fail("%s: score_dev / best_dev not 4-byte aligned", name);
+    }
+    using table = reg_table<ZNCC>;
     const int w1 = 2 * search + 1, n_off = w1 * w1;
-    HIP_TRY(hipMemsetAsync(score_dev, 0, (size_t)n_pairs * n_off * 2 * sizeof(int32_t), s));
+    HIP_TRY(hipMemsetAsync(table_dev, 0, (size_t)n_pairs * n_off * table::entries * sizeof(*table_dev), s));
     const int tile_rows = register_tile_rows(search);
     const int lds = reg_search_lds(search, tile_rows);
     const int tiles_x = (side + REG_TILE_X - 1) / REG_TILE_X, tiles_y = (side + tile_rows - 1) / tile_rows;
@@ -269,51 +285,29 @@ int launch_register_search(const uint8_t* a_dev, const uint8_t* b_dev, const wm_
     const dim3 grid(tiles_x * tiles_y * off_blocks, n_pairs);
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, grid, dim3(REG_THREADS), lds, s, a_dev, b_dev, pairs_dev, search, side, tile_rows, tiles_x, off_blocks,
-                           (int*)score_dev);
+                           (typename table::elem*)table_dev);
     };
-    k == 4 ? launch(register_search_kernel<4>) : k == 2 ? launch(register_search_kernel<2>) : launch(register_search_kernel<1>);
+    k == 4 ? launch(register_search_kernel<4, ZNCC>) : k == 2 ? launch(register_search_kernel<2, ZNCC>) : launch(register_search_kernel<1, ZNCC>);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(register_best_kernel, dim3(n_pairs), dim3(REG_THREADS), 0, s, (const int*)score_dev, search, min_cells, (int*)best_dev);
+    if constexpr (ZNCC)
+        hipLaunchKernelGGL(register_zncc_best_kernel, dim3(n_pairs), dim3(REG_THREADS), 0, s, (const long long*)table_dev, search, min_cells,
+                           (int*)best_dev, peak_dev);
+    else
+        hipLaunchKernelGGL(register_best_kernel, dim3(n_pairs), dim3(REG_THREADS), 0, s, (const int*)table_dev, search, min_cells, (int*)best_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// The correlation search: the SAD launcher's checks, tiles and K rule, six int64 moments per offset where that one has two
-// int32.  The K rule was measured for this kernel too (profiles/register_zncc/README.md): it picks the fastest K at search
-// 16; at search 32 it picks K = 2 where K = 4 measured 1.7 % faster, too little and too few points for a second rule.
+int launch_register_search(const uint8_t* a_dev, const uint8_t* b_dev, const wm_register_pair* pairs_dev, int n_pairs, int search, int side,
+                           int min_cells, int32_t* score_dev, int32_t* best_dev, hipStream_t s) {
+    return launch_register_search_as<false>("wm_register_search", a_dev, b_dev, pairs_dev, n_pairs, search, side, min_cells, score_dev, best_dev,
+                                            nullptr, s);
+}
+
 int launch_register_search_zncc(const uint8_t* a_dev, const uint8_t* b_dev, const wm_register_pair* pairs_dev, int n_pairs, int search,
                                 int side, int min_cells, int64_t* moments_dev, int32_t* best_dev, double* peak_dev, hipStream_t s) {
-    const char* name = "wm_register_search_zncc";
-    if (n_pairs < 0 || n_pairs > WM_REGISTER_MAX_PAIRS) return fail("%s: n_pairs %d outside 0..%d", name, n_pairs, WM_REGISTER_MAX_PAIRS);
-    if (n_pairs == 0) return 0;
-    WM_TRY(check_register_shape(name, pairs_dev, search, side));
-    if (min_cells < 1) return fail("%s: min_cells %d: need at least 1", name, min_cells);
-    if (!a_dev) return fail("%s: null a_dev", name);
-    if (!b_dev) return fail("%s: null b_dev", name);
-    if (!moments_dev) return fail("%s: null moments_dev", name);
-    if (!best_dev) return fail("%s: null best_dev", name);
-    if (!peak_dev) return fail("%s: null peak_dev", name);
-    if ((uintptr_t)moments_dev % 8) return fail("%s: moments_dev not 8-byte aligned", name);
-    if ((uintptr_t)peak_dev % 8) return fail("%s: peak_dev not 8-byte aligned", name);
-    if ((uintptr_t)best_dev % 4) return fail("%s: best_dev not 4-byte aligned", name);
-    const int w1 = 2 * search + 1, n_off = w1 * w1;
-    HIP_TRY(hipMemsetAsync(moments_dev, 0, (size_t)n_pairs * n_off * REG_MOMENTS * sizeof(int64_t), s));
-    const int tile_rows = register_tile_rows(search);
-    const int lds = reg_search_lds(search, tile_rows);
-    const int tiles_x = (side + REG_TILE_X - 1) / REG_TILE_X, tiles_y = (side + tile_rows - 1) / tile_rows;
-    const int k = register_offsets_per_thread(n_off);
-    const int off_blocks = (n_off + REG_THREADS * k - 1) / (REG_THREADS * k);
-    const dim3 grid(tiles_x * tiles_y * off_blocks, n_pairs);
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(REG_THREADS), lds, s, a_dev, b_dev, pairs_dev, search, side, tile_rows, tiles_x, off_blocks,
-                           (unsigned long long*)moments_dev);
-    };
-    k == 4 ? launch(register_zncc_kernel<4>) : k == 2 ? launch(register_zncc_kernel<2>) : launch(register_zncc_kernel<1>);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(register_zncc_best_kernel, dim3(n_pairs), dim3(REG_THREADS), 0, s, (const long long*)moments_dev, search, min_cells,
-                       (int*)best_dev, peak_dev);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_register_search_as<true>("wm_register_search_zncc", a_dev, b_dev, pairs_dev, n_pairs, search, side, min_cells, moments_dev,
+                                           best_dev, peak_dev, s);
 }
 
 // ---- survey review chips: one PIL-exact crop per detection, windows and coefficients derived on the device ----

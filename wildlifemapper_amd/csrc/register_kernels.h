@@ -9,30 +9,29 @@
 // workgroup and come before the first store.  What bounds every read: 0 <= frame < n_frames, 0 <= slot < n_resident, a
 // non-null data pointer, the descriptor's (height, width) equal to size[f], and 0 <= u < width, 0 <= v < height from sees.
 //
-// register_search_kernel, the hot path: (2S+1)^2 * gx * gy byte differences per pair.  A workgroup owns one tile of
-// REG_TILE_X x tile_rows cells of A, the matching tile of B grown by 2S in both axes, and 256 * K consecutive offsets (o =
-// (dy + S) * (2S+1) + (dx + S), lane = consecutive o, so the lanes of a wave read consecutive bytes of one or two B rows).
-// Both tiles sit in LDS as (value dword, mask dword) pairs -- mask byte 0xff where the cell is seen -- so one ds_read_b64
-// fetches four cells with their mask.  A thread walks the tile four cells at a time: the A pair is a broadcast read shared
-// by its K offsets; per offset one new B pair (the previous one is kept: a row is walked with a sliding dword window), two
-// v_alignbyte_b32 to bring B and its mask to A's byte phase, three ANDs (both operands and the mask by (a != 0) & (b != 0),
-// so a cell that either frame does not see adds 0), one v_sad_u8 and one v_bcnt_u32_b32 (8 bits per counted cell).  Tile
-// partials go to score by int32 atomics: two per (tile, offset), against tile_rows * 16 steps of work.
+// register_search_kernel<K, ZNCC>, the hot path of both searches: (2S+1)^2 * gx * gy cell pairs per pair of frames.  A
+// workgroup owns one tile of REG_TILE_X x tile_rows cells of A, the matching tile of B grown by 2S in both axes, and 256 * K
+// consecutive offsets (o = (dy + S) * (2S+1) + (dx + S), lane = consecutive o, so the lanes of a wave read consecutive
+// bytes of one or two B rows).  Both tiles sit in LDS as (value dword, mask dword) pairs -- mask byte 0xff where the cell is
+// seen -- so one ds_read_b64 fetches four cells with their mask.  A thread walks the tile four cells at a time: the A pair
+// is a broadcast read shared by its K offsets; per offset one new B pair (the previous one is kept: a row is walked with a
+// sliding dword window), two v_alignbyte_b32 to bring B and its mask to A's byte phase, three ANDs (both operands and the
+// mask by (a != 0) & (b != 0), so a cell that either frame does not see adds 0) and one v_bcnt_u32_b32 (8 bits per counted
+// cell).  The decomposition, the pair check, the staging, the offset setup, the walk and the flush guard are the same text
+// for both metrics; the metric decides three spots under `if constexpr`:
+//   SAD (include/wm_hip.h, "Survey registration"; checker: search_oracle in tests/test_register.py): one v_sad_u8 per 4
+//     cells and offset; tile partials go to score by int32 atomics, two per (tile, offset), against tile_rows * 16 steps.
+//   correlation (include/wm_hip.h, "Survey registration, correlation search"; checker: zncc_search_oracle in
+//     tests/test_register_zncc.py): two v_sad_u8 against 0 (the byte sums) and three v_dot4_u32_u8 (sum a^2, sum b^2, sum
+//     ab).  A tile's partials fit 32 bits (the static_assert beside REG_TILE_ROWS_MAX); they go to moments by six 64-bit
+//     vector atomics per (tile, offset).
+// What keeps every instance at the registers and bytes it had as two kernels: profiles/register_family/README.md.
 //
-// register_best_kernel: one workgroup per pair scans score twice with the header's order, which is total (the cross products
-// decide, then the unique key (dy^2 + dx^2, dy, dx)), so the reduction's order is irrelevant.
-//
-// Correlation search (include/wm_hip.h, "Survey registration, correlation search"; checker: zncc_search_oracle and
-// zncc_pick_oracle in tests/test_register_zncc.py).  register_zncc_kernel is register_search_kernel's sibling: the same
-// decomposition, tiles, staging and sliding window, with six integer sums per offset where that one has two.  It shares
-// reg_load4, reg_nonzero_mask, reg_b_stride, reg_search_lds and the tie key; the staging loops and the walk are restated,
-// because moving them into a function the two kernels call changed the register allocation of the SAD instances
-// (profiles/register_zncc/README.md), and those stay byte for byte what they were.
-// Per 4 cells and offset: two v_alignbyte_b32, three v_and_b32, two v_sad_u8 against 0 (the byte sums), three
-// v_dot4_u32_u8 (sum a^2, sum b^2, sum ab) and one v_bcnt_u32_b32.  A tile's partials fit 32 bits (the static_assert beside
-// REG_TILE_ROWS_MAX); they go to moments by six 64-bit vector atomics per (tile, offset).  register_zncc_best_kernel: the
-// score q of an offset is three IEEE double operations on exact integers (no contraction, no sqrt), the order is total
-// (q decides, then the key), so the reduction's shape is free here too.
+// register_best_kernel, register_zncc_best_kernel: one workgroup per pair scans the table twice -- the best offset, then the
+// best outside its 3 x 3 -- in reg_pick, with the metric's candidate, order and output from reg_pick_sad / reg_pick_zncc.
+// SAD's order is the header's cross products, the correlation's the score q, three IEEE double operations on exact integers
+// (no contraction, no sqrt); both then fall to the unique key (dy^2 + dx^2, dy, dx), so the order is total and the
+// reduction's shape is free.
 #pragma once
 
 #include "mosaic_kernels.h"
@@ -130,15 +129,21 @@ __device__ __forceinline__ unsigned int reg_load4(const unsigned char* __restric
     return v;
 }
 
-template <int K>
+constexpr int REG_MOMENTS = 6;                                   // n, sum a, sum b, sum a^2, sum b^2, sum ab
+
+// what a search keeps per offset: SAD two int32 (sad, n), the correlation REG_MOMENTS 64-bit sums
+template <bool ZNCC> struct reg_table { using elem = int; static constexpr int entries = 2; };
+template <> struct reg_table<true> { using elem = unsigned long long; static constexpr int entries = REG_MOMENTS; };
+
+template <int K, bool ZNCC>
 __global__ __launch_bounds__(REG_THREADS) void register_search_kernel(
         const unsigned char* __restrict__ a, const unsigned char* __restrict__ b, const wm_register_pair* __restrict__ pairs, int search,
-        int side, int tile_rows, int tiles_x, int off_blocks, int* __restrict__ score) {
+        int side, int tile_rows, int tiles_x, int off_blocks, typename reg_table<ZNCC>::elem* __restrict__ table) {
     extern __shared__ uint2 reg_lds[];
     const int tid = threadIdx.x;
     const int p = blockIdx.y;
     const wm_register_pair pr = pairs[p];
-    if (pr.gx < 1 || pr.gx > side || pr.gy < 1 || pr.gy > side) return;      // a bad pair keeps its zeroed score
+    if (pr.gx < 1 || pr.gx > side || pr.gy < 1 || pr.gy > side) return;      // a bad pair keeps its zeroed table
     const int ob = (int)blockIdx.x % off_blocks, tile = (int)blockIdx.x / off_blocks;
     const int i0 = (tile % tiles_x) * REG_TILE_X, j0 = (tile / tiles_x) * tile_rows;
     if (i0 >= pr.gx || j0 >= pr.gy) return;
@@ -161,7 +166,10 @@ __global__ __launch_bounds__(REG_THREADS) void register_search_kernel(
     }
     __syncthreads();
 
-    int o[K], sh[K], sad[K], cnt[K], row_b[K];                   // row_b: an index into sB, so every read stays an LDS read
+    // plain local arrays, in this order: accumulators held in a struct or a policy object cost every K > 1 instance an
+    // address add per LDS read, and another order renumbers the registers (profiles/register_family/README.md)
+    int o[K], sh[K], sad[K], row_b[K];                           // row_b: an index into sB, so every read stays an LDS read
+    unsigned int cnt[K], sa[K], sb[K], saa[K], sbb[K], sab[K];   // sad: SAD alone; sa .. sab: the correlation alone
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         o[k] = (ob * K + k) * REG_THREADS + tid;
@@ -170,142 +178,6 @@ __global__ __launch_bounds__(REG_THREADS) void register_search_kernel(
         sh[k] = dxi & 3;
         row_b[k] = dyi * bs + (dxi >> 2);
         sad[k] = 0;
-        cnt[k] = 0;
-    }
-    for (int r = 0; r < tile_rows; ++r) {
-        uint2 lo[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) lo[k] = sB[row_b[k]];
-#pragma unroll
-        for (int c = 0; c < REG_TILE_DW; ++c) {
-            const uint2 av = sA[r * REG_TILE_DW + c];
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const uint2 hi = sB[row_b[k] + c + 1];
-                const unsigned int bv = __builtin_amdgcn_alignbyte(hi.x, lo[k].x, sh[k]);
-                const unsigned int bm = __builtin_amdgcn_alignbyte(hi.y, lo[k].y, sh[k]);
-                sad[k] = (int)__builtin_amdgcn_sad_u8(av.x & bm, bv & av.y, (unsigned int)sad[k]);
-                cnt[k] += __popc(av.y & bm);
-                lo[k] = hi;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < K; ++k) row_b[k] += bs;
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-        if (o[k] < n_off && cnt[k]) {
-            int* out = score + ((size_t)p * n_off + o[k]) * 2;
-            if (sad[k]) atomicAdd(out, sad[k]);
-            atomicAdd(out + 1, cnt[k] >> 3);
-        }
-}
-
-struct reg_cand { int sad, n, dy, dx; };                         // n < 0: no candidate
-
-// the tie key of both searches: the smaller (dy^2 + dx^2, dy, dx)
-__device__ __forceinline__ bool reg_key_less(int pdy, int pdx, int qdy, int qdx) {
-    const int dp = pdy * pdy + pdx * pdx, dq = qdy * qdy + qdx * qdx;
-    if (dp != dq) return dp < dq;
-    if (pdy != qdy) return pdy < qdy;
-    return pdx < qdx;
-}
-
-// the header's order: p beats q
-__device__ __forceinline__ bool reg_beats(const reg_cand& p, const reg_cand& q) {
-    if (p.n < 0) return false;
-    if (q.n < 0) return true;
-    const long long l = (long long)p.sad * q.n, r = (long long)q.sad * p.n;
-    if (l != r) return l < r;
-    return reg_key_less(p.dy, p.dx, q.dy, q.dx);
-}
-
-__global__ __launch_bounds__(REG_THREADS) void register_best_kernel(const int* __restrict__ score, int search, int min_cells,
-                                                                     int* __restrict__ best) {
-    __shared__ reg_cand s_wave[REG_THREADS / 64];
-    __shared__ reg_cand s_first;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int p = blockIdx.x, w1 = 2 * search + 1, n_off = w1 * w1;
-    const int* sc = score + (size_t)p * n_off * 2;
-    for (int pass = 0; pass < 2; ++pass) {
-        reg_cand first = {-1, -1, 0, 0};
-        if (pass) first = s_first;
-        reg_cand mine = {-1, -1, 0, 0};
-        if (!pass || first.n >= 0)
-            for (int o = tid; o < n_off; o += REG_THREADS) {
-                const reg_cand c = {sc[o * 2], sc[o * 2 + 1], o / w1 - search, o % w1 - search};
-                if (c.n < min_cells) continue;
-                if (pass && max(abs(c.dy - first.dy), abs(c.dx - first.dx)) < 2) continue;
-                if (reg_beats(c, mine)) mine = c;
-            }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const reg_cand other = {__shfl_xor(mine.sad, d), __shfl_xor(mine.n, d), __shfl_xor(mine.dy, d), __shfl_xor(mine.dx, d)};
-            if (reg_beats(other, mine)) mine = other;
-        }
-        if (lane == 0) s_wave[wave] = mine;
-        __syncthreads();
-        if (tid == 0) {
-            reg_cand top = s_wave[0];
-#pragma unroll
-            for (int k = 1; k < REG_THREADS / 64; ++k)
-                if (reg_beats(s_wave[k], top)) top = s_wave[k];
-            int* out = best + (size_t)p * 8 + pass * 4;
-            const bool has = top.n >= 0;
-            out[0] = has ? top.dy : 0;
-            out[1] = has ? top.dx : 0;
-            out[2] = has ? top.sad : -1;
-            out[3] = has ? top.n : 0;
-            s_first = top;
-        }
-        __syncthreads();
-    }
-}
-
-// ---- correlation search: six integer moments per offset, then the signed squared correlation in double ----
-
-constexpr int REG_MOMENTS = 6;                                   // n, sum a, sum b, sum a^2, sum b^2, sum ab
-
-template <int K>
-__global__ __launch_bounds__(REG_THREADS) void register_zncc_kernel(
-        const unsigned char* __restrict__ a, const unsigned char* __restrict__ b, const wm_register_pair* __restrict__ pairs, int search,
-        int side, int tile_rows, int tiles_x, int off_blocks, unsigned long long* __restrict__ moments) {
-    extern __shared__ uint2 reg_lds[];
-    const int tid = threadIdx.x;
-    const int p = blockIdx.y;
-    const wm_register_pair pr = pairs[p];
-    if (pr.gx < 1 || pr.gx > side || pr.gy < 1 || pr.gy > side) return;      // a bad pair keeps its zeroed moments
-    const int ob = (int)blockIdx.x % off_blocks, tile = (int)blockIdx.x / off_blocks;
-    const int i0 = (tile % tiles_x) * REG_TILE_X, j0 = (tile / tiles_x) * tile_rows;
-    if (i0 >= pr.gx || j0 >= pr.gy) return;
-    const int ext = side + 2 * search, w1 = 2 * search + 1, n_off = w1 * w1;
-    const int bs = reg_b_stride(search), b_rows = tile_rows + 2 * search;
-    uint2* sA = reg_lds;                                         // [tile_rows][REG_TILE_DW]
-    uint2* sB = reg_lds + tile_rows * REG_TILE_DW;               // [b_rows][bs]
-    const unsigned char* pa = a + (size_t)p * side * side;
-    const unsigned char* pb = b + (size_t)p * ext * ext;
-
-    for (int e = tid; e < tile_rows * REG_TILE_DW; e += REG_THREADS) {
-        const int r = e / REG_TILE_DW, c = i0 + (e % REG_TILE_DW) * 4, j = j0 + r;
-        const unsigned int v = j < pr.gy ? reg_load4(pa + (size_t)j * side, c, pr.gx) : 0u;       // only cells j < gy, i < gx count
-        sA[e] = make_uint2(v, reg_nonzero_mask(v));
-    }
-    for (int e = tid; e < b_rows * bs; e += REG_THREADS) {
-        const int r = e / bs, c = i0 + (e % bs) * 4, j = j0 + r;
-        const unsigned int v = j < ext ? reg_load4(pb + (size_t)j * ext, c, ext) : 0u;
-        sB[e] = make_uint2(v, reg_nonzero_mask(v));
-    }
-    __syncthreads();
-
-    int o[K], sh[K], row_b[K];                                   // row_b: an index into sB, so every read stays an LDS read
-    unsigned int cnt[K], sa[K], sb[K], saa[K], sbb[K], sab[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        o[k] = (ob * K + k) * REG_THREADS + tid;
-        const int oc = min(o[k], n_off - 1);                     // a thread past the last offset walks the last one and drops it
-        const int dyi = oc / w1, dxi = oc - dyi * w1;
-        sh[k] = dxi & 3;
-        row_b[k] = dyi * bs + (dxi >> 2);
         cnt[k] = sa[k] = sb[k] = saa[k] = sbb[k] = sab[k] = 0u;
     }
     for (int r = 0; r < tile_rows; ++r) {
@@ -321,12 +193,16 @@ __global__ __launch_bounds__(REG_THREADS) void register_zncc_kernel(
                 const unsigned int bv = __builtin_amdgcn_alignbyte(hi.x, lo[k].x, sh[k]);
                 const unsigned int bm = __builtin_amdgcn_alignbyte(hi.y, lo[k].y, sh[k]);
                 const unsigned int am = av.x & bm, bmv = bv & av.y;              // a cell that either frame does not see adds 0 to every sum
-                sa[k] = __builtin_amdgcn_sad_u8(am, 0u, sa[k]);
-                sb[k] = __builtin_amdgcn_sad_u8(bmv, 0u, sb[k]);
-                saa[k] = __builtin_amdgcn_udot4(am, am, saa[k], false);
-                sbb[k] = __builtin_amdgcn_udot4(bmv, bmv, sbb[k], false);
-                sab[k] = __builtin_amdgcn_udot4(am, bmv, sab[k], false);
-                cnt[k] += __popc(av.y & bm);
+                if constexpr (ZNCC) {
+                    sa[k] = __builtin_amdgcn_sad_u8(am, 0u, sa[k]);
+                    sb[k] = __builtin_amdgcn_sad_u8(bmv, 0u, sb[k]);
+                    saa[k] = __builtin_amdgcn_udot4(am, am, saa[k], false);
+                    sbb[k] = __builtin_amdgcn_udot4(bmv, bmv, sbb[k], false);
+                    sab[k] = __builtin_amdgcn_udot4(am, bmv, sab[k], false);
+                } else {
+                    sad[k] = (int)__builtin_amdgcn_sad_u8(am, bmv, (unsigned int)sad[k]);
+                }
+                cnt[k] += __popc(av.y & bm);                     // 8 bits per counted cell
                 lo[k] = hi;
             }
         }
@@ -335,76 +211,143 @@ __global__ __launch_bounds__(REG_THREADS) void register_zncc_kernel(
     }
 #pragma unroll
     for (int k = 0; k < K; ++k)
-        if (o[k] < n_off && cnt[k]) {                            // a counted cell has a, b >= 1: all six partials are positive
-            unsigned long long* out = moments + ((size_t)p * n_off + o[k]) * REG_MOMENTS;
-            atomicAdd(out, (unsigned long long)(cnt[k] >> 3));
-            atomicAdd(out + 1, (unsigned long long)sa[k]);
-            atomicAdd(out + 2, (unsigned long long)sb[k]);
-            atomicAdd(out + 3, (unsigned long long)saa[k]);
-            atomicAdd(out + 4, (unsigned long long)sbb[k]);
-            atomicAdd(out + 5, (unsigned long long)sab[k]);
+        if (o[k] < n_off && cnt[k]) {                            // a counted cell has a, b >= 1: the correlation's six partials are positive
+            auto* out = table + ((size_t)p * n_off + o[k]) * reg_table<ZNCC>::entries;
+            if constexpr (ZNCC) {
+                atomicAdd(out, (unsigned long long)(cnt[k] >> 3));
+                atomicAdd(out + 1, (unsigned long long)sa[k]);
+                atomicAdd(out + 2, (unsigned long long)sb[k]);
+                atomicAdd(out + 3, (unsigned long long)saa[k]);
+                atomicAdd(out + 4, (unsigned long long)sbb[k]);
+                atomicAdd(out + 5, (unsigned long long)sab[k]);
+            } else {
+                if (sad[k]) atomicAdd(out, sad[k]);
+                atomicAdd(out + 1, (int)cnt[k] >> 3);
+            }
         }
 }
 
-struct zncc_cand { double q; int n, dy, dx; };                   // n < 0: no candidate
-
-// the header's order: p beats q
-__device__ __forceinline__ bool zncc_beats(const zncc_cand& p, const zncc_cand& q) {
-    if (p.n < 0) return false;
-    if (q.n < 0) return true;
-    if (p.q != q.q) return p.q > q.q;
-    return reg_key_less(p.dy, p.dx, q.dy, q.dx);
+// the tie key of both searches: the smaller (dy^2 + dx^2, dy, dx)
+__device__ __forceinline__ bool reg_key_less(int pdy, int pdx, int qdy, int qdx) {
+    const int dp = pdy * pdy + pdx * pdx, dq = qdy * qdy + qdx * qdx;
+    if (dp != dq) return dp < dq;
+    if (pdy != qdy) return pdy < qdy;
+    return pdx < qdx;
 }
 
-__global__ __launch_bounds__(REG_THREADS) void register_zncc_best_kernel(const long long* __restrict__ moments, int search, int min_cells,
-                                                                          int* __restrict__ best, double* __restrict__ peak) {
+template <class S> struct reg_cand { S score; int n, dy, dx; };   // an offset and its score; n < 0: no candidate
+
+// What reg_pick asks of a metric: the table's element and entries per offset, the score's type and its value in the empty
+// candidate, the header's order (p beats q), offer (the candidate of offset o = (dy, dx), if it has one that `skip` does
+// not exclude, replaces `mine` where it beats it) and write (best[2] of the pass, and the correlation's peak).
+struct reg_pick_sad {
+    using elem = int;
+    static constexpr int entries = reg_table<false>::entries;
+    using cand = reg_cand<int>;                              // score: the sad
+    static constexpr int no_score = -1;
+    static __device__ __forceinline__ bool beats(const cand& p, const cand& q) {
+        if (p.n < 0) return false;
+        if (q.n < 0) return true;
+        const long long l = (long long)p.score * q.n, r = (long long)q.score * p.n;
+        if (l != r) return l < r;
+        return reg_key_less(p.dy, p.dx, q.dy, q.dx);
+    }
+    template <class Skip>
+    static __device__ __forceinline__ void offer(const int* __restrict__ sc, int o, int dy, int dx, int min_cells, Skip skip, cand& mine) {
+        const cand c = {sc[o * 2], sc[o * 2 + 1], dy, dx};
+        if (c.n < min_cells) return;
+        if (skip(dy, dx)) return;
+        if (beats(c, mine)) mine = c;
+    }
+    static __device__ __forceinline__ void write(const cand& top, bool has, int* __restrict__ out, double*) { out[2] = has ? top.score : -1; }
+};
+
+struct reg_pick_zncc {
+    using elem = long long;
+    static constexpr int entries = reg_table<true>::entries;
+    using cand = reg_cand<double>;                           // score: q
+    static constexpr double no_score = 0.0;
+    static __device__ __forceinline__ bool beats(const cand& p, const cand& q) {
+        if (p.n < 0) return false;
+        if (q.n < 0) return true;
+        if (p.score != q.score) return p.score > q.score;
+        return reg_key_less(p.dy, p.dx, q.dy, q.dx);
+    }
+    // the score q of an offset: three IEEE double operations on exact integers, no contraction, no sqrt
+    template <class Skip>
+    static __device__ __forceinline__ void offer(const long long* __restrict__ mo, int o, int dy, int dx, int min_cells, Skip skip, cand& mine) {
 #pragma clang fp contract(off)
-    __shared__ zncc_cand s_wave[REG_THREADS / 64];
-    __shared__ zncc_cand s_first;
+        const long long* m = mo + (size_t)o * REG_MOMENTS;
+        const long long n = m[0];
+        if (n < min_cells) return;
+        if (skip(dy, dx)) return;
+        const long long sa = m[1], sb = m[2];
+        const long long va = n * m[3] - sa * sa, vb = n * m[4] - sb * sb;      // exact: every product is below 2^53
+        if (va <= 0 || vb <= 0) return;                                         // a flat plane has no correlation
+        const double c = (double)(n * m[5] - sa * sb);
+        const cand cd = {(c * fabs(c)) / ((double)va * (double)vb), (int)n, dy, dx};
+        if (beats(cd, mine)) mine = cd;
+    }
+    static __device__ __forceinline__ void write(const cand& top, bool has, int* __restrict__ out, double* __restrict__ peak) {
+        out[2] = has ? 1 : 0;
+        *peak = has ? top.score : __builtin_nan("");
+    }
+};
+
+// Both picks: the scan, the 3 x 3 exclusion on the second pass, the wave butterfly, the s_wave combine, the eight ints.
+template <class P>
+__device__ __forceinline__ void reg_pick(const typename P::elem* __restrict__ table, int search, int min_cells, int* __restrict__ best,
+                                         double* __restrict__ peak, typename P::cand* s_wave, typename P::cand& s_first) {
+    using cand = typename P::cand;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int p = blockIdx.x, w1 = 2 * search + 1, n_off = w1 * w1;
-    const long long* mo = moments + (size_t)p * n_off * REG_MOMENTS;
+    const typename P::elem* tab = table + (size_t)p * n_off * P::entries;
     for (int pass = 0; pass < 2; ++pass) {
-        zncc_cand first = {0.0, -1, 0, 0};
+        cand first = {P::no_score, -1, 0, 0};
         if (pass) first = s_first;
-        zncc_cand mine = {0.0, -1, 0, 0};
+        cand mine = {P::no_score, -1, 0, 0};
+        const auto in_first_3x3 = [&](int dy, int dx) { return pass && max(abs(dy - first.dy), abs(dx - first.dx)) < 2; };
         if (!pass || first.n >= 0)
-            for (int o = tid; o < n_off; o += REG_THREADS) {
-                const long long* m = mo + (size_t)o * REG_MOMENTS;
-                const long long n = m[0];
-                if (n < min_cells) continue;
-                const int dy = o / w1 - search, dx = o % w1 - search;
-                if (pass && max(abs(dy - first.dy), abs(dx - first.dx)) < 2) continue;
-                const long long sa = m[1], sb = m[2];
-                const long long va = n * m[3] - sa * sa, vb = n * m[4] - sb * sb;      // exact: every product is below 2^53
-                if (va <= 0 || vb <= 0) continue;                                       // a flat plane has no correlation
-                const double c = (double)(n * m[5] - sa * sb);
-                const zncc_cand cand = {(c * fabs(c)) / ((double)va * (double)vb), (int)n, dy, dx};
-                if (zncc_beats(cand, mine)) mine = cand;
-            }
+            for (int o = tid; o < n_off; o += REG_THREADS)
+                P::offer(tab, o, o / w1 - search, o % w1 - search, min_cells, in_first_3x3, mine);
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) {
-            const zncc_cand other = {__shfl_xor(mine.q, d), __shfl_xor(mine.n, d), __shfl_xor(mine.dy, d), __shfl_xor(mine.dx, d)};
-            if (zncc_beats(other, mine)) mine = other;
+            const cand other = {__shfl_xor(mine.score, d), __shfl_xor(mine.n, d), __shfl_xor(mine.dy, d), __shfl_xor(mine.dx, d)};
+            if (P::beats(other, mine)) mine = other;
         }
         if (lane == 0) s_wave[wave] = mine;
         __syncthreads();
         if (tid == 0) {
-            zncc_cand top = s_wave[0];
+            cand top = s_wave[0];
 #pragma unroll
             for (int k = 1; k < REG_THREADS / 64; ++k)
-                if (zncc_beats(s_wave[k], top)) top = s_wave[k];
+                if (P::beats(s_wave[k], top)) top = s_wave[k];
             int* out = best + (size_t)p * 8 + pass * 4;
             const bool has = top.n >= 0;
             out[0] = has ? top.dy : 0;
             out[1] = has ? top.dx : 0;
-            out[2] = has ? 1 : 0;
             out[3] = has ? top.n : 0;
-            peak[(size_t)p * 2 + pass] = has ? top.q : __builtin_nan("");
+            P::write(top, has, out, peak + (size_t)p * 2 + pass);
             s_first = top;
         }
         __syncthreads();
     }
+}
+
+// The shared memory is declared in the kernels and not in reg_pick: as a static of a function template it is not internal
+// to the code object, and a store that nothing reads (s_first.score) is then kept (profiles/register_family/README.md).
+__global__ __launch_bounds__(REG_THREADS) void register_best_kernel(const int* __restrict__ score, int search, int min_cells,
+                                                                     int* __restrict__ best) {
+    __shared__ reg_pick_sad::cand s_wave[REG_THREADS / 64];
+    __shared__ reg_pick_sad::cand s_first;
+    reg_pick<reg_pick_sad>(score, search, min_cells, best, nullptr, s_wave, s_first);
+}
+
+__global__ __launch_bounds__(REG_THREADS) void register_zncc_best_kernel(const long long* __restrict__ moments, int search, int min_cells,
+                                                                          int* __restrict__ best, double* __restrict__ peak) {
+    __shared__ reg_pick_zncc::cand s_wave[REG_THREADS / 64];
+    __shared__ reg_pick_zncc::cand s_first;
+    reg_pick<reg_pick_zncc>(moments, search, min_cells, best, peak, s_wave, s_first);
 }
 
 }  // namespace wm

@@ -1444,6 +1444,30 @@ def adjust(n_frames, pairs, measured, weights, fixed=None) -> Dict[str, np.ndarr
 REGISTER_METRICS = ("sad", "zncc")
 
 
+def _decode_sad(best, peak, min_corr):
+    """best (P,8) -> has, has2, mean, runner_up, corr, confident: best's third of four is sad (-1: none), the fourth n."""
+    sad, n1, sad2, n2 = (best[:, k].astype(np.int64) for k in (2, 3, 6, 7))
+    has, has2 = sad >= 0, sad2 >= 0
+    mean = np.where(has, sad / np.maximum(n1, 1), np.nan)
+    runner = np.where(has2, sad2 / np.maximum(n2, 1), np.nan)
+    return has, has2, mean, runner, np.full(best.shape[0], np.nan), has
+
+
+def _decode_zncc(best, peak, min_corr):
+    """best (P,8), peak (P,2) -> the same six: best's third of four is ok (1 / 0), peak holds q (NaN: none)."""
+    has, has2 = best[:, 2] == 1, best[:, 6] == 1
+    r = np.sign(peak) * np.sqrt(np.abs(peak))
+    corr = np.where(has, r[:, 0], np.nan)
+    mean = np.where(has, 1.0 - r[:, 0], np.nan)
+    runner = np.where(has2, 1.0 - r[:, 1], np.nan)
+    return has, has2, mean, runner, corr, has & (corr > min_corr)
+
+
+# per metric: the entry point, its table's dtype and last dimension, whether it fills a peak buffer, best[2] of "none", the decoder
+_REGISTER_METRIC = {"sad": ("wm_register_search", torch.int32, 2, False, -1, _decode_sad),
+                    "zncc": ("wm_register_search_zncc", torch.int64, 6, True, 0, _decode_zncc)}
+
+
 def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512, min_cells: int = 4096, min_ratio: float = 1.25,
              pairs=None, fixed=None, pair_chunk: int = 256, metric: str = "sad", min_corr: float = 0.0) -> Dict[str, object]:
     """Correct the georeferences of a survey by matching the pixels of its overlapping frames (wm_register_render_u8,
@@ -1486,7 +1510,7 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
             raise TypeError
     except (TypeError, ValueError):
         raise ValueError(f"{what}: min_corr {min_corr!r} must be a finite number in [-1, 1)") from None
-    zncc = metric == "zncc"
+    entry, table_dtype, table_last, has_peak, none, decode = _REGISTER_METRIC[metric]
     search, side, min_cells = _check_register_shape(search, side, min_cells, what)
     pair_chunk = _check_whole(pair_chunk, what, "pair_chunk")
     if pair_chunk > REGISTER_MAX_PAIRS:
@@ -1511,8 +1535,7 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
     P = table.shape[0]
     best = np.zeros((P, 8), dtype=np.int32)
     peak = np.full((P, 2), np.nan, dtype=np.float64)                 # (q, q2) of the correlation search
-    if not zncc:
-        best[:, 2] = best[:, 6] = -1
+    best[:, 2] = best[:, 6] = none
     if P:
         dev = _survey_device(what)
         lib = N.lib()
@@ -1534,38 +1557,20 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
                                                       cell, search, side, N.ptr(plane_a), N.ptr(plane_b), N.ptr(status), N.stream_ptr(dev)))
                     del resident, desc, slot_d                    # the stream orders their reuse after the launch
                 best_d = torch.empty((n, 8), device=dev, dtype=torch.int32)
-                if zncc:
-                    score = torch.empty((n, 2 * search + 1, 2 * search + 1, 6), device=dev, dtype=torch.int64)
-                    peak_d = torch.empty((n, 2), device=dev, dtype=torch.float64)
-                    N.check(lib.wm_register_search_zncc(N.ptr(plane_a), N.ptr(plane_b), N.ptr(pairs_d), n, search, side, min_cells,
-                                                        N.ptr(score), N.ptr(best_d), N.ptr(peak_d), N.stream_ptr(dev)))
+                score = torch.empty((n, 2 * search + 1, 2 * search + 1, table_last), device=dev, dtype=table_dtype)
+                peak_d = torch.empty((n, 2), device=dev, dtype=torch.float64) if has_peak else None
+                N.check(getattr(lib, entry)(N.ptr(plane_a), N.ptr(plane_b), N.ptr(pairs_d), n, search, side, min_cells, N.ptr(score),
+                                            N.ptr(best_d), *([N.ptr(peak_d)] if has_peak else []), N.stream_ptr(dev)))
+                if has_peak:
                     peak[c0:c0 + n] = peak_d.cpu().numpy()
-                    del peak_d
-                else:
-                    score = torch.empty((n, 2 * search + 1, 2 * search + 1, 2), device=dev, dtype=torch.int32)
-                    N.check(lib.wm_register_search(N.ptr(plane_a), N.ptr(plane_b), N.ptr(pairs_d), n, search, side, min_cells, N.ptr(score),
-                                                   N.ptr(best_d), N.stream_ptr(dev)))
                 best[c0:c0 + n] = best_d.cpu().numpy()
-                del plane_a, plane_b, score, best_d, pairs_d
+                del plane_a, plane_b, score, best_d, peak_d, pairs_d
             bad = int(status.item())
         if bad:
             raise RuntimeError(f"{what}: wm_register_render_u8 skipped planes (status {bad}): a resident frame did not match its slot or size")
-    dy, dx, sad, n1 = (best[:, k].astype(np.int64) for k in range(4))
-    sad2, n2 = best[:, 6].astype(np.int64), best[:, 7].astype(np.int64)
+    dy, dx, n1 = (best[:, k].astype(np.int64) for k in (0, 1, 3))
     with np.errstate(all="ignore"):
-        if zncc:                                                     # best's third of four is ok (1 / 0), peak holds q (NaN: none)
-            has, has2 = sad == 1, sad2 == 1
-            r = np.sign(peak) * np.sqrt(np.abs(peak))
-            corr = np.where(has, r[:, 0], np.nan)
-            mean = np.where(has, 1.0 - r[:, 0], np.nan)
-            runner = np.where(has2, 1.0 - r[:, 1], np.nan)
-            confident = has & (corr > min_corr)
-        else:
-            confident = has = sad >= 0
-            has2 = sad2 >= 0
-            corr = np.full(P, np.nan)
-            mean = np.where(has, sad / np.maximum(n1, 1), np.nan)
-            runner = np.where(has2, sad2 / np.maximum(n2, 1), np.nan)
+        has, has2, mean, runner, corr, confident = decode(best, peak, min_corr)
         accepted = confident & (np.abs(dy) < search) & (np.abs(dx) < search) & (~has2 | (runner >= min_ratio * mean))
     offset = np.stack([dx, dy], axis=1).reshape(P, 2)
     adj = adjust(F, table, -offset.astype(np.float64) * cell, np.where(accepted, n1, 0).astype(np.float64), fixed)
