@@ -3,12 +3,41 @@ from __future__ import annotations
 
 import ctypes as C
 
+import pytest
 import torch
 
 from oracle import wm_oracle as O          # checker only
 from wildlifemapper_amd import _native as N
+from wildlifemapper_amd import synth
+from wildlifemapper_amd.segment_anything import sam_model_registry
+from wildlifemapper_amd.segment_anything.network import MedSAM
 
 PRECS = {"bf16": (N.PREC_BF16, torch.bfloat16), "fp16": (N.PREC_FP16, torch.float16)}
+
+
+def need_gpu():
+    """Fails (no skip) the GPU test modules where there is no device: called by their autouse fixtures."""
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a ROCm device (run with -m 'not gpu' on CPU)")
+
+
+_MODELS = {}
+
+
+def _model(mt, prec):
+    """One model per type, kept for the whole module (ViT-H weights take ~30 s to synthesise);
+    switching precision re-packs the weights into a fresh native handle."""
+    if mt not in _MODELS:
+        for k in list(_MODELS):                               # one model type resident at a time
+            _MODELS.pop(k)[0]._hub.close()
+        sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(mt).items()}
+        sam, crit, post = sam_model_registry[mt](None, None)
+        m = MedSAM(sam.image_encoder, sam.mask_decoder, sam.prompt_encoder).eval()
+        m.load_state_dict(sd, strict=True)
+        _MODELS[mt] = (m, post["bbox"])
+    m, post = _MODELS[mt]
+    m._hub.set_precision(prec)
+    return m, post
 
 
 def dev():

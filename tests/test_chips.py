@@ -13,17 +13,12 @@ import pytest
 import torch
 
 from oracle.pil_resize import resize_bilinear_u8
+from survey_util import _StubModel, _animals, _guarded, _lib, _random_boxes
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
+from wildlifemapper_amd._survey import _frame_descs
 
-NQ = 51
 F = np.float32
-
-
-def _lib():
-    import __graft_entry__ as g
-    g.build()
-    return N.lib()
 
 
 # ---- the rule and the oracle, restated -------------------------------------------------------------------------------
@@ -78,31 +73,13 @@ def _oracle_chips(frames, windows, box_frame, S):
 WORKED = [((10.2, 20.7, 30.9, 33.1), (10, 4, 32)), ((-5, -5, 3, 2), (-18, -17, 32)), ((0, 0, 5000, 10), (-507, 1988, 1024))]
 
 
-def _random_boxes(rng, n):
-    c = rng.normal(0, 3000, (n, 2))
-    wh = np.abs(rng.normal(0, 120, (n, 2)))
-    b = np.concatenate([c - wh / 2, c + wh / 2], axis=1).astype(F)
-    k = n // 20
-    b[0 * k:1 * k, 2:] = b[0 * k:1 * k, :2] - rng.random((k, 2)).astype(F) * 50               # negative width and height
-    b[1 * k:2 * k] *= F(1e6)                                                                   # huge, centre beyond +-2^30
-    b[2 * k:3 * k] = (rng.normal(0, 1, (k, 4)) * 1e38).astype(F)                                # sums and differences overflow
-    b[3 * k:4 * k, rng.integers(0, 4, k)] = np.nan
-    b[4 * k:5 * k, rng.integers(0, 4, k)] = np.inf
-    b[5 * k:6 * k, rng.integers(0, 4, k)] = -np.inf
-    b[6 * k:7 * k] = np.round(b[6 * k:7 * k])                                                    # integers: centres on .0 and .5
-    b[7 * k:8 * k] = b[7 * k:8 * k] * F(0.01)                                                    # tiny boxes: min_side
-    b[8 * k:9 * k, :2] += F(3e9)                                                                 # one corner beyond 2^30
-    b[9 * k:10 * k] += F(-2.5e9)
-    return b
-
-
 def test_chip_window_rule():
     _lib()
     for box, want in WORKED:
         assert tuple(_rule([box])[0]) == want, box
         assert tuple(tiling.chip_windows(np.array([box], F))[0]) == want, box
     rng = np.random.default_rng(5)
-    boxes = _random_boxes(rng, 10000)
+    boxes = _random_boxes(rng, 10000, 0.01, far=True)
     got = tiling.chip_windows(boxes)
     assert got.shape == (10000, 3) and got.dtype == np.int32
     want = _rule(boxes)
@@ -184,13 +161,6 @@ def test_oracle_reproduces_pillow_fixture(golden_dir):
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------
 
-def _guarded(arr: np.ndarray, offset: int, dev):
-    """A device copy of `arr` starting `offset` bytes into a larger uint8 allocation filled with 255."""
-    flat = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
-    buf = torch.full((flat.size + 256,), 255, dtype=torch.uint8, device=dev)
-    buf[offset:offset + flat.size] = torch.from_numpy(flat).to(dev)
-    return buf, buf[offset:offset + flat.size]
-
 
 def _crop(frames, boxes, box_frame, S, context, min_side, max_side, windows_out=True):
     """wm_crop_chips_u8 on numpy frames: every frame at an odd byte offset inside a 255-filled allocation, chips and
@@ -198,7 +168,7 @@ def _crop(frames, boxes, box_frame, S, context, min_side, max_side, windows_out=
     dev = torch.device("cuda:0")
     keep = [_guarded(f, 61 + 2 * j, dev) for j, f in enumerate(frames)]
     views = [v.view(f.shape) for (_, v), f in zip(keep, frames)]
-    desc = tiling._frame_descs(views, dev)
+    desc = _frame_descs(views, dev)
     b = torch.from_numpy(np.ascontiguousarray(boxes, dtype=F)).to(dev)
     n = b.shape[0]
     bf = None if box_frame is None else torch.from_numpy(np.asarray(box_frame, dtype=np.int32)).to(dev)
@@ -327,63 +297,7 @@ def test_chips_many_frames_and_degenerate_boxes():
                              torch.zeros((0, 4), device="cuda:0"))[0].shape == (0, 128, 128, 3)
 
 
-# ---- end to end with a stub model ------------------------------------------------------------------------------------
-
-class _StubModel:
-    """detect() hands out hand-built per-tile records in the order detect_frames asks for tiles: frame by frame, tile by
-    tile.  An animal is a box in frame pixels; every tile that sees at least 6 px of it reports the part it sees, in tile
-    pixels, as a candidate (the way _records of tests/test_survey.py builds records)."""
-
-    def __init__(self, tiled_sizes, animals, overlap=128):
-        rng = np.random.default_rng(3)
-        recs = []
-        for (h, w), boxes in zip(tiled_sizes, animals):
-            for oy, ox in tiling.tile_origins(h, w, 1024, overlap):
-                b = np.zeros((NQ, 4), F)
-                score = (rng.random(NQ) * 0.5).astype(F)
-                cand = np.zeros(NQ, bool)
-                q = 0
-                for (x0, y0, x1, y1) in boxes:
-                    vx0, vy0 = max(x0, ox), max(y0, oy)
-                    vx1, vy1 = min(x1, ox + 1024, w), min(y1, oy + 1024, h)
-                    if vx1 - vx0 >= 6 and vy1 - vy0 >= 6:
-                        b[q] = (vx0 - ox, vy0 - oy, vx1 - ox, vy1 - oy)
-                        score[q] = F(0.5 + 0.5 * rng.random())
-                        cand[q] = True
-                        q += 3
-                recs.append((b, score, cand))
-        n = len(recs)
-        rec = torch.zeros((n, NQ, 8), dtype=torch.float32)
-        rec[..., 0:4] = torch.from_numpy(np.stack([r[0] for r in recs]))
-        rec[..., 4] = torch.from_numpy(np.stack([r[1] for r in recs]))
-        ints = rec.view(torch.int32)
-        ints[..., 5] = torch.from_numpy(rng.integers(0, 7, (n, NQ)).astype(np.int32))
-        cand = np.stack([r[2] for r in recs])
-        ints[..., 6] = torch.from_numpy(np.where(cand, N.FLAG_CONF | N.FLAG_SCORE | N.FLAG_NMS, N.FLAG_CONF).astype(np.int32))
-        ints[..., 7] = torch.from_numpy(rng.integers(-1, 51, (n, NQ)).astype(np.int32))
-        self.records = rec.to("cuda:0")
-        self.pos = 0
-
-    def detect(self, x, target_sizes=None):
-        n = x.shape[0]
-        assert self.pos + n <= self.records.shape[0]
-        out = self.records[self.pos:self.pos + n]
-        self.pos += n
-        return {"records": out}
-
-
-def _animals(h, w, rng, seams):
-    """Boxes in frame pixels: on each frame border, in each corner, across the tile seams, and a few inside."""
-    a = [(0, 40, 30, 75), (w - 25, 60, w, 100), (200, 0, 260, 22), (300, h - 18, 345, h), (0, 0, 28, 24), (w - 31, h - 27, w, h)]
-    for sx in seams[1]:
-        a.append((sx - 35, 300, sx + 45, 352))                                 # cut by a vertical seam
-    for sy in seams[0]:
-        a.append((420, sy - 30, 470, sy + 50))                                 # cut by a horizontal seam
-    for _ in range(4):
-        cx, cy = rng.integers(60, w - 60), rng.integers(120, h - 60)
-        a.append((cx - 20, cy - 14, cx + 23, cy + 19))
-    return [tuple(float(v) for v in b) for b in a]
-
+# ---- end to end with a stub model (survey_util._StubModel) -----------------------------------------------------------
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["plain", "fuse", "scale"])

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from survey_util import _axis, _kernel_constants, _some_frames, _yawed, _yawed_90
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
 
@@ -105,13 +106,6 @@ def coverage_oracle_by_frame(g2p, size, x0, y0, cell, gx, gy):
     return {"coverage": cov, "stats": stats}
 
 
-def _kernel_constants():
-    src = open(os.path.join(ROOT, "wildlifemapper_amd", "csrc", "coverage_kernels.h")).read()
-    get = lambda name: int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1))
-    threads, rows = get("COV_THREADS"), get("COV_ROWS")
-    return {"chunk": get("COV_CHUNK"), "block_x": get("COV_BLOCK_X"), "block_y": threads // 64 * rows}
-
-
 def _case(frames, x0, y0, cell, gx, gy, points=None, labels=None):
     """frames: a list of (g2p as 6 numbers or (2,3), height, width)."""
     g2p = np.array([np.asarray(f[0], dtype=F64).reshape(6) for f in frames], dtype=F64).reshape(-1, 6)
@@ -132,11 +126,6 @@ FRAME_A = ([2, 0, 0, 0, -2, 4], 4, 8)
 FRAME_B = ([2, 0, -4, 0, -2, 4], 4, 8)
 NAN = float("nan")
 INF = float("inf")
-
-
-def _yawed_90():
-    a = tiling.nadir_affine(4, 8, (10.0, 20.0), 0.5, 90.0)       # up is east: 2 m east-west (9..11), 4 m north-south (18..22)
-    return (tiling.ground_to_pixel(a), 4, 8)
 
 
 # name -> (case, expected coverage rows from j = 0 (south) upwards, expected stats[0:3])
@@ -405,23 +394,6 @@ def _run_and_check(case, want=None):
     assert got["stats"].sum() == case["gx"] * case["gy"]
     _assert_same(_device_abi(case), got)                                           # determinism
     return got, want
-
-
-def _axis(xw, xe, ys, yn, px):
-    """An axis-aligned frame with footprint [xw, xe) x (ys, yn] m at px pixels per metre (exact for the binary fractions used)."""
-    return ([px, 0, -px * xw, 0, -px, px * yn], int(round((yn - ys) * px)), int(round((xe - xw) * px)))
-
-
-def _yawed(centre, gsd, yaw, H, W):
-    return (tiling.ground_to_pixel(tiling.nadir_affine(H, W, centre, gsd, yaw)), H, W)
-
-
-def _some_frames(gx, gy, cell, seed, n=5):
-    """n yawed frames spread over the grid [0, gx * cell) x [0, gy * cell), each about a third of it."""
-    rng = np.random.default_rng(seed)
-    ex, ey = gx * cell, gy * cell
-    side = max(ex, ey) / 3 + cell
-    return [_yawed((rng.uniform(0, ex), rng.uniform(0, ey)), side / 400, rng.uniform(0, 360), 300, 400) for _ in range(n)]
 
 
 @functools.lru_cache(maxsize=None)

@@ -3,7 +3,6 @@ recorded from the reference's own matcher + scipy and SetCriterion (tools/gen_cr
 between SetCriterion and the stub, the no-CPU-fallback rule, the C-ABI's argument checks and reduce_dict over 2 gloo ranks."""
 import ctypes as C
 import os
-import socket
 from types import SimpleNamespace
 
 import numpy as np
@@ -13,6 +12,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 import criterion_ref as R
+from survey_util import _free_port
 from wildlifemapper_amd import _native as N
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -128,10 +128,6 @@ def test_criterion_argument_errors_without_gpu():
 # ---------------------------------------------------------------------------
 # reduce_dict over 2 gloo ranks (utils/misc.py:154-178)
 # ---------------------------------------------------------------------------
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _reduce_worker(rank, world, port, q):

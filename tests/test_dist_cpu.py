@@ -1,12 +1,12 @@
 """world_size-2 (and 3) gloo tests of the tile shard + fixed-size record all-gather (dist.py)."""
 import os
-import socket
 
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from survey_util import _free_port
 from wildlifemapper_amd import dist as wdist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,12 +21,6 @@ def test_shard_range_partitions():
                 assert e - s <= wdist.max_shard(n, world)
                 seen += list(range(s, e))
             assert seen == list(range(n))
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _worker(rank, world, port, n_tiles, q):

@@ -26,8 +26,7 @@ EPS = 2.0 ** -24
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
+    G.need_gpu()
 
 
 @pytest.fixture(scope="module")
@@ -269,7 +268,7 @@ def test_evaluate_returns_the_reference_loss_stats():
     from wildlifemapper_amd.segment_anything import sam_model_registry
     from wildlifemapper_amd.segment_anything.build_sam import InferenceCriterion
     from wildlifemapper_amd.segment_anything.utils.misc import nested_tensor_from_tensor_list
-    from test_gpu_e2e import _model                          # the suite's one resident ViT-B (synthetic weights)
+    from gpu_util import _model                              # the suite's one resident ViT-B (synthetic weights)
     args = SimpleNamespace(set_cost_class=1.0, set_cost_bbox=5.0, set_cost_giou=2.0, bbox_loss_coef=5.0, giou_loss_coef=2.0, eos_coef=0.1,
                            batch_size=1)
     _, crit, _ = sam_model_registry["vit_b"](None, args)

@@ -54,8 +54,7 @@ MAX_BATCH = 4
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
+    G.need_gpu()
     yield
     for dec, _ in _DECODERS.values():
         if dec._hub is not None:

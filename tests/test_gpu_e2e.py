@@ -22,10 +22,9 @@ pytestmark = pytest.mark.gpu
 from oracle import wm_oracle as O          # checker only
 from wildlifemapper_amd import synth
 from wildlifemapper_amd.engine import split_records
-from wildlifemapper_amd.segment_anything import sam_model_registry
-from wildlifemapper_amd.segment_anything.network import MedSAM
 from wildlifemapper_amd.segment_anything.utils.misc import NestedTensor, nested_tensor_from_tensor_list
 import gpu_util as G
+from gpu_util import _model
 
 LOGIT_TOL = {"fp16": 1e-3, "bf16": 1e-3}
 # what the tests ASSERT, per model below north_star's 1e-3 so that the margin itself is checked and a regression of it
@@ -37,33 +36,13 @@ EMB_TOL = {"fp16": 2e-3, "bf16": 5e-3}
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
+    G.need_gpu()
 
 
 def _sample(t, n):
     f = t.detach().reshape(-1)
     step = max(1, f.numel() // n)
     return f[::step][:n].float().cpu().numpy()
-
-
-_MODELS = {}
-
-
-def _model(mt, prec):
-    """One model per type, kept for the whole module (ViT-H weights take ~30 s to synthesise);
-    switching precision re-packs the weights into a fresh native handle."""
-    if mt not in _MODELS:
-        for k in list(_MODELS):                               # one model type resident at a time
-            _MODELS.pop(k)[0]._hub.close()
-        sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(mt).items()}
-        sam, crit, post = sam_model_registry[mt](None, None)
-        m = MedSAM(sam.image_encoder, sam.mask_decoder, sam.prompt_encoder).eval()
-        m.load_state_dict(sd, strict=True)
-        _MODELS[mt] = (m, post["bbox"])
-    m, post = _MODELS[mt]
-    m._hub.set_precision(prec)
-    return m, post
 
 
 # ---------------------------------------------------------------------------

@@ -35,8 +35,7 @@ _TAPS = {}                                   # the taps of the latest (model, mo
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
+    G.need_gpu()
     yield
     _TAPS.clear()
     for k in list(_MODELS):

@@ -21,8 +21,7 @@ OUT16_TOL = {"bf16": 5e-3, "fp16": 7e-4}
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device (run with -m 'not gpu' on CPU)")
+    G.need_gpu()
     torch.manual_seed(0)
 
 

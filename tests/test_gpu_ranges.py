@@ -32,8 +32,7 @@ QA = 16.0                                  # q's common component; k's is chosen
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device (run with -m 'not gpu' on CPU)")
+    G.need_gpu()
 
 
 def _randn(seed, *shape):

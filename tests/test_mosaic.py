@@ -12,8 +12,10 @@ import numpy as np
 import pytest
 import torch
 
+from survey_util import DEV, _axis, _kernel_constants, _Lazy, _some_frames, _up, _yawed, _yawed_90
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
+from wildlifemapper_amd._survey import _frame_descs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F64 = np.float64
@@ -154,13 +156,6 @@ def mosaic_oracle_by_frame(g2p, size, x0, y0, cell, gx, gy, frames=None, fill=SE
     return out
 
 
-def _kernel_constants():
-    src = open(os.path.join(ROOT, "wildlifemapper_amd", "csrc", "coverage_kernels.h")).read()
-    get = lambda name: int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1))
-    threads, rows = get("COV_THREADS"), get("COV_ROWS")
-    return {"chunk": get("COV_CHUNK"), "block_x": get("COV_BLOCK_X"), "block_y": threads // 64 * rows}
-
-
 def _content(h, w, seed):
     return np.random.default_rng(seed).integers(0, 256, (h, w, 3), dtype=np.uint8)
 
@@ -187,11 +182,6 @@ RAMP = np.array([[(16 * y + x, 100 + x, 200 - y) for x in range(8)] for y in ran
 # 2 x 1 px holding 10 and 13 in every channel, 1 m pixels: u = X, v = 1 - Y
 FRAME_PAIR = ([1, 0, 0, 0, -1, 1], 1, 2)
 PAIR = np.array([[(10, 10, 10), (13, 13, 13)]], dtype=np.uint8)
-
-
-def _yawed_90():
-    a = tiling.nadir_affine(4, 8, (10.0, 20.0), 0.5, 90.0)       # up is east: 2 m east-west (9..11), 4 m north-south (18..22)
-    return (tiling.ground_to_pixel(a), 4, 8)
 
 
 def _singular():
@@ -309,20 +299,6 @@ def test_resampled_georef():
             tiling.resampled_georef(g, bad, (4, 8))
         with pytest.raises(ValueError, match="new_size"):
             tiling.resampled_georef(g, (8, 16), bad)
-
-
-class _Lazy:
-    """A sequence that is only indexed, and records what was asked of it."""
-
-    def __init__(self, items):
-        self.items, self.asked = items, []
-
-    def __len__(self):
-        return len(self.items)
-
-    def __getitem__(self, i):
-        self.asked.append(i)
-        return self.items[i]
 
 
 def test_mosaic_python_argument_errors_before_device_work():
@@ -474,12 +450,6 @@ def test_mosaic_symbols_and_abi_13():
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------
 
-DEV = "cuda:0"
-
-
-def _up(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
 
 def _plan(case):
     """wm_mosaic_plan through the C-ABI, every output pre-filled with a poison value."""
@@ -500,7 +470,7 @@ def _fill(case, plan, mode, picture, status, resident, flags=0, descs=None, slot
     F, gx, gy = case["g2p"].shape[0], case["gx"], case["gy"]
     tensors = [_up(case["images"][f]) for f in resident]
     if descs is None:
-        descs = tiling._frame_descs(tensors, torch.device(DEV)) if tensors else None
+        descs = _frame_descs(tensors, torch.device(DEV)) if tensors else None
     if slot is None:
         slot = np.full(F, -1, dtype=np.int32)
         slot[list(resident)] = np.arange(len(resident), dtype=np.int32)
@@ -544,24 +514,6 @@ def _run_and_check(case, want=None):
     return got, want, plan
 
 
-def _axis(xw, xe, ys, yn, px):
-    """An axis-aligned frame with footprint [xw, xe) x (ys, yn] m at px pixels per metre (exact for the binary fractions used)."""
-    return ([px, 0, -px * xw, 0, -px, px * yn], int(round((yn - ys) * px)), int(round((xe - xw) * px)))
-
-
-def _yawed(centre, gsd, yaw, H, W):
-    return (tiling.ground_to_pixel(tiling.nadir_affine(H, W, centre, gsd, yaw)), H, W)
-
-
-def _some_frames(gx, gy, cell, seed, n=5):
-    """n yawed frames of different sizes spread over the grid [0, gx * cell) x [0, gy * cell), each about a third of it."""
-    rng = np.random.default_rng(seed)
-    ex, ey = gx * cell, gy * cell
-    side = max(ex, ey) / 3 + cell
-    shapes = [(30, 40), (17, 23), (40, 30), (9, 64), (33, 33)]
-    return [_yawed((rng.uniform(0, ex), rng.uniform(0, ey)), side / max(shapes[k % 5]), rng.uniform(0, 360), *shapes[k % 5]) for k in range(n)]
-
-
 @functools.lru_cache(maxsize=None)
 def _gpu_case(name):
     """name -> (case, oracle result), computed once."""
@@ -569,7 +521,7 @@ def _gpu_case(name):
     bx, by = k["block_x"], k["block_y"]
     if name.startswith("grid_"):                                                # grid_<gx>x<gy>: none a multiple of the block
         gx, gy = (int(v) for v in name[5:].split("x"))
-        case = _case(_some_frames(gx, gy, 0.7, gx) + [_axis(-1.0, gx * 0.7 / 2, -1.0, gy, 0.5)], 0.0, 0.0, 0.7, gx, gy, seed=1)
+        case = _case(_some_frames(gx, gy, 0.7, gx, shapes=((30, 40), (17, 23), (40, 30), (9, 64), (33, 33))) + [_axis(-1.0, gx * 0.7 / 2, -1.0, gy, 0.5)], 0.0, 0.0, 0.7, gx, gy, seed=1)
     elif name == "no_frames":
         case = _case([], 0.0, 0.0, 0.7, 70, 19)
     elif name == "one_1x1_px_frame":                                            # one pixel of 4 m over cells of 0.7 m

@@ -15,18 +15,13 @@ import pytest
 import torch
 
 from oracle.pil_resize import resize_bilinear_u8
-from test_chips import _StubModel, _animals
+from survey_util import _StubModel, _animals, _guarded, _lib, _random_boxes
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling, visualize
+from wildlifemapper_amd._survey import _frame_descs
 
 F = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _lib():
-    import __graft_entry__ as g
-    g.build()
-    return N.lib()
 
 
 # ---- the rule, restated ----------------------------------------------------------------------------------------------
@@ -128,24 +123,6 @@ def test_outline_rule_stays_inside_small_boxes():
     assert n > 500
 
 
-def _random_boxes(rng, n):
-    c = rng.normal(0, 3000, (n, 2))
-    wh = np.abs(rng.normal(0, 120, (n, 2)))
-    b = np.concatenate([c - wh / 2, c + wh / 2], axis=1).astype(F)
-    k = n // 20
-    b[0 * k:1 * k, 2:] = b[0 * k:1 * k, :2] - rng.random((k, 2)).astype(F) * 50               # negative width and height
-    b[1 * k:2 * k] *= F(1e6)                                                                   # beyond +-2^30
-    with np.errstate(over="ignore"):
-        b[2 * k:3 * k] = (rng.normal(0, 1, (k, 4)) * 1e38).astype(F)                           # some overflow to inf
-    b[3 * k:4 * k, rng.integers(0, 4, k)] = np.nan
-    b[4 * k:5 * k, rng.integers(0, 4, k)] = np.inf
-    b[5 * k:6 * k, rng.integers(0, 4, k)] = -np.inf
-    b[6 * k:7 * k] = np.round(b[6 * k:7 * k])                                                    # integers
-    b[7 * k:8 * k] = b[7 * k:8 * k] * F(0.0003)                                                  # around zero: truncation of both signs
-    b[8 * k:9 * k, 2:] = b[8 * k:9 * k, :2] + rng.random((k, 2)).astype(F)                       # less than a pixel
-    return b
-
-
 WORKED = [((10.9, 20.2, 30.99, 33.0), (10, 20, 30, 33), True), ((-0.9, -1.5, 0.5, 2.7), (0, -1, 0, 2), True),
           ((5, 5, 4.5, 9), (0, 0, 0, 0), False), ((-3e9, -5, 3e9, 1e20), (-2 ** 30, -5, 2 ** 30, 2 ** 30), True),
           ((1, 2, float("nan"), 4), (0, 0, 0, 0), False), ((1, 2, float("inf"), 4), (0, 0, 0, 0), False), ((7.2, 7.9, 7.8, 7.1), (7, 7, 7, 7), True)]
@@ -159,7 +136,7 @@ def test_box_outline_rect_rule():
         r, d = tiling.outline_rects(np.array([box], F))
         assert tuple(r[0]) == want and bool(d[0]) == drawn, box
     rng = np.random.default_rng(6)
-    boxes = _random_boxes(rng, 10000)
+    boxes = _random_boxes(rng, 10000, 0.0003)
     got, drawn = tiling.outline_rects(boxes)
     assert got.shape == (10000, 4) and got.dtype == np.int32 and drawn.dtype == bool
     want, wdrawn = _rects(boxes)
@@ -267,13 +244,6 @@ def test_plot_reference_on_hand_worked_values(tmp_path):
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------
 
-def _guarded(arr, offset, dev):
-    """A device copy of `arr` starting `offset` bytes into a larger uint8 allocation filled with 255."""
-    flat = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
-    buf = torch.full((flat.size + 256,), 255, dtype=torch.uint8, device=dev)
-    buf[offset:offset + flat.size] = torch.from_numpy(flat).to(dev)
-    return buf, buf[offset:offset + flat.size]
-
 
 def _draw(frames, boxes, labels, box_frame, palette, width):
     """wm_draw_boxes_u8 on numpy frames, each at an odd byte offset inside a 255-filled allocation whose guard bytes are
@@ -282,7 +252,7 @@ def _draw(frames, boxes, labels, box_frame, palette, width):
     offs = [61 + 2 * j for j in range(len(frames))]
     keep = [_guarded(f, o, dev) for f, o in zip(frames, offs)]
     views = [v.view(f.shape) for (_, v), f in zip(keep, frames)]
-    desc = tiling._frame_descs(views, dev)
+    desc = _frame_descs(views, dev)
     b = torch.from_numpy(np.ascontiguousarray(boxes, dtype=F).reshape(-1, 4)).to(dev)
     lab = torch.from_numpy(np.asarray(labels, dtype=np.int32)).to(dev)
     bf = None if box_frame is None else torch.from_numpy(np.asarray(box_frame, dtype=np.int32)).to(dev)

@@ -1,6 +1,6 @@
 """Survey registration (include/wm_hip.h "Survey registration", tiling.register): every overlapping pair of frames rendered
 onto a common ground patch as two luma planes, and the integer shift at which they agree.  The rule has no reference
-behaviour; register_oracle below restates it sequentially -- render, search and pick, one pair and one offset at a time,
+behaviour; register_oracle (tests/register_cases.py) restates it sequentially -- render, search and pick, one pair and one offset at a time,
 numpy float64 for the cell centres and int64 for everything after them, the header's operation order -- and the device
 result must equal it exactly: every device comparison is assert_array_equal and there is no tolerance on the GPU side.
 The only bound in this file is adjust()'s 1e-9 m on consistent measurements (double rounding of such a system sits near
@@ -13,122 +13,13 @@ import numpy as np
 import pytest
 import torch
 
+from register_cases import (ANIMALS, DISPLACED, F64, HAND_A, HAND_B, INF, NAN, POISON_A, POISON_B, ROOT,
+                            SCENE_H, SCENE_W, SHAPES, _axis_frame, _case, _content, _cover, _detections,
+                            _north_up, _oracle, _pairs, _planes, _render, _search, _shape_case, beats,
+                            luma, per_k_planes, pick_oracle, render_plane, search_oracle)
+from survey_util import DEV, _Lazy, _up
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F64 = np.float64
-NAN = float("nan")
-INF = float("inf")
-POISON_A, POISON_B = 0xA5, 0x5A
-
-
-def luma(px):
-    """max(1, (77 R + 150 G + 29 B + 128) >> 8) of (..., 3) uint8 pixels, in int64."""
-    p = np.asarray(px).astype(np.int64)
-    return np.maximum(1, (77 * p[..., 0] + 150 * p[..., 1] + 29 * p[..., 2] + 128) >> 8)
-
-
-def render_plane(b6, hw, img, x0, y0, cell, nx, ny, s, ext):
-    """One plane of the rule, ext x ext uint8: cell (j, i) has centre x0 + ((i - s) + 0.5) * cell; cells with i >= nx + 2 s
-    or j >= ny + 2 s are 0; a cell its frame does not see is 0; else the luma of the nearest pixel."""
-    h, w = int(hw[0]), int(hw[1])
-    b = np.asarray(b6, dtype=F64).reshape(6)
-    x0, y0, cell = F64(x0), F64(y0), F64(cell)
-    idx = np.arange(ext, dtype=np.int64)
-    with np.errstate(all="ignore"):
-        Xc = (x0 + ((idx - s).astype(F64) + F64(0.5)) * cell)[None, :]
-        Yc = (y0 + ((idx - s).astype(F64) + F64(0.5)) * cell)[:, None]
-        u = (b[0] * Xc + b[1] * Yc) + b[2]
-        v = (b[3] * Xc + b[4] * Yc) + b[5]
-        sees = (h >= 1) & (w >= 1) & (0 <= u) & (u < w) & (0 <= v) & (v < h)
-    sees = sees & (idx[None, :] < nx + 2 * s) & (idx[:, None] < ny + 2 * s)
-    out = np.zeros((ext, ext), dtype=np.uint8)
-    if sees.any():
-        out[sees] = luma(img[np.floor(v[sees]).astype(np.int64), np.floor(u[sees]).astype(np.int64)]).astype(np.uint8)
-    return out
-
-
-def search_oracle(A, B, gx, gy, S):
-    """score (2S+1, 2S+1, 2) int64 = (sad, n), one offset at a time."""
-    a = A[:gy, :gx].astype(np.int64)
-    score = np.zeros((2 * S + 1, 2 * S + 1, 2), dtype=np.int64)
-    for dy in range(-S, S + 1):
-        for dx in range(-S, S + 1):
-            bb = B[S + dy:S + dy + gy, S + dx:S + dx + gx].astype(np.int64)
-            both = (a != 0) & (bb != 0)
-            score[dy + S, dx + S] = (np.abs(a - bb)[both].sum(), both.sum())
-    return score
-
-
-def beats(p, q):
-    """Offset p = (sad, n, dy, dx) beats q: the cross products in Python integers, then (dy^2 + dx^2, dy, dx)."""
-    l, r = p[0] * q[1], q[0] * p[1]
-    if l != r:
-        return l < r
-    return (p[2] * p[2] + p[3] * p[3], p[2], p[3]) < (q[2] * q[2] + q[3] * q[3], q[2], q[3])
-
-
-def pick_two(S, candidate, beats):
-    """The pick of both searches, sequentially: the best offset, then the best outside its 3 x 3 (None where there is none).
-    candidate(dy, dx) is the offset's (score, n, dy, dx) or None; beats(p, q) the metric's order."""
-    def top(excluded):
-        best = None
-        for dy in range(-S, S + 1):
-            for dx in range(-S, S + 1):
-                if excluded is not None and max(abs(dy - excluded[2]), abs(dx - excluded[3])) < 2:
-                    continue
-                cand = candidate(dy, dx)
-                if cand is not None and (best is None or beats(cand, best)):
-                    best = cand
-        return best
-    first = top(None)
-    return first, (top(first) if first is not None else None)
-
-
-def pick_oracle(score, S, min_cells):
-    """best (8,) int64 from a score table, sequentially."""
-    def candidate(dy, dx):
-        sad, n = (int(v) for v in score[dy + S, dx + S])
-        return (sad, n, dy, dx) if n >= min_cells else None
-    first, second = pick_two(S, candidate, beats)
-    four = lambda c: [0, 0, -1, 0] if c is None else [c[2], c[3], c[0], c[1]]
-    return np.array(four(first) + four(second), dtype=np.int64)
-
-
-def register_oracle(g2p, size, images, pairs, cell, search, side, min_cells):
-    """The whole rule for a pair table: A (P,side,side), B (P,E,E) uint8, score (P,2S+1,2S+1,2) and best (P,8) int64.  A
-    pair outside the rule (a frame index out of range, gx or gy outside [1, side]) has no planes here (None)."""
-    E = side + 2 * search
-    out = {"a": [], "b": [], "score": [], "best": []}
-    nf = len(size)
-    for pr in pairs:
-        fa, fb, gx, gy = (int(pr[k]) for k in ("frame_a", "frame_b", "gx", "gy"))
-        if not (0 <= fa < nf and 0 <= fb < nf and 1 <= gx <= side and 1 <= gy <= side):
-            for k in out:
-                out[k].append(None)
-            continue
-        A = render_plane(g2p[fa], size[fa], images[fa], pr["x0"], pr["y0"], cell, gx, gy, 0, side)
-        B = render_plane(g2p[fb], size[fb], images[fb], pr["x0"], pr["y0"], cell, gx, gy, search, E)
-        score = search_oracle(A, B, gx, gy, search)
-        out["a"].append(A)
-        out["b"].append(B)
-        out["score"].append(score)
-        out["best"].append(pick_oracle(score, search, min_cells))
-    return out
-
-
-def _pairs(rows):
-    return np.array([tuple(r) for r in rows], dtype=tiling.REGISTER_PAIR).reshape(-1)
-
-
-def _axis_frame(img, x_west, y_north, gsd):
-    """A north-up frame: pixel (0, 0)'s corner at (x_west, y_north), gsd metres per pixel.  Returns (img, georef)."""
-    return img, np.array([[gsd, 0.0, x_west], [0.0, -gsd, y_north]], dtype=F64)
-
-
-def _content(h, w, seed, lo=0):
-    return np.random.default_rng(seed).integers(lo, 256, size=(h, w, 3), dtype=np.uint8)
 
 
 # ---- CPU: the oracle's hand cases ------------------------------------------------------------------------------------
@@ -155,8 +46,6 @@ def test_oracle_one_by_one_patch_at_search_0():
     assert want["best"][0].tolist() == [0, 0, 30, 1, 0, 0, -1, 0]
 
 
-HAND_A = np.array([[1, 2], [3, 4]], dtype=np.uint8)
-HAND_B = np.array([[0, 0, 0, 0], [0, 1, 2, 0], [0, 3, 4, 0], [0, 0, 0, 0]], dtype=np.uint8)
 # B[j + 1 + dy][i + 1 + dx] against A[j][i], only where both are not 0.  (0, 0): all four agree.  (0, 1): 2|1 and 4|3;
 # (0, -1): 1|2 and 3|4; (1, 0): 3|1 and 4|2; (-1, 0): 1|3 and 2|4; the corners meet in one cell: (1, 1) 4|1, (-1, -1) 1|4,
 # (1, -1) 3|2, (-1, 1) 2|3.
@@ -208,9 +97,6 @@ def test_oracle_black_pixel_is_seen_and_outside_is_not():
 
 
 # ---- CPU: register_pairs and adjust ----------------------------------------------------------------------------------
-
-def _north_up(x_west, y_south, w, h, gsd=1.0):
-    return np.array([[gsd, 0.0, x_west], [0.0, -gsd, y_south + h * gsd]], dtype=F64)
 
 
 def test_register_pairs_snapping_crop_and_drop():
@@ -302,20 +188,6 @@ def test_adjust_inconsistent_measurements_give_the_weighted_mean():
     out = tiling.adjust(3, [(0, 1), (1, 2), (0, 2)], [[1.0, 0.0], [1.0, 0.0], [5.0, 0.0]], [1.0, 1.0, 1.0])
     assert np.abs(out["residual"][:, 0] - np.array([1.0, 1.0, -1.0])).max() < 1e-9
     assert np.abs(out["shift"].sum(axis=0)).max() < 1e-9
-
-
-class _Lazy:
-    """A sequence that is only indexed, and records what was asked of it."""
-
-    def __init__(self, items):
-        self.items, self.asked = items, []
-
-    def __len__(self):
-        return len(self.items)
-
-    def __getitem__(self, i):
-        self.asked.append(i)
-        return self.items[i]
 
 
 def test_register_python_argument_errors_before_device_work():
@@ -457,42 +329,6 @@ def test_register_symbols_and_abi_13():
 
 # ---- cases -----------------------------------------------------------------------------------------------------------
 
-def _case(frames, pairs, cell, search, side, min_cells):
-    """frames: a list of (img (H,W,3) uint8, georef (2,3)); pairs: rows of (frame_a, frame_b, gx, gy, x0, y0)."""
-    georef = np.stack([f[1] for f in frames])
-    return {"images": [f[0] for f in frames], "g2p": tiling.ground_to_pixel(georef).reshape(-1, 6),
-            "size": np.array([f[0].shape[:2] for f in frames], dtype=np.int32), "pairs": _pairs(pairs), "cell": cell, "search": search,
-            "side": side, "min_cells": min_cells}
-
-
-def _oracle(case):
-    return register_oracle(case["g2p"], case["size"], case["images"], case["pairs"], case["cell"], case["search"], case["side"],
-                           case["min_cells"])
-
-
-def _cover(gx, gy, search, x0, y0, cell, seed, gsd_cells=1.5, yaw=0.0, margin=2):
-    """A frame of random pixels that sees the whole patch and its search margin: gsd = gsd_cells * cell."""
-    gsd = gsd_cells * cell
-    span = max(gx, gy) + 2 * search + 2 * margin
-    n = int(np.ceil(span / gsd_cells * (1.5 if yaw else 1.0))) + 2
-    centre = (x0 + 0.5 * gx * cell, y0 + 0.5 * gy * cell)
-    return _content(n, n + 1, seed), tiling.nadir_affine(n, n + 1, centre, gsd, yaw)
-
-
-def _shape_case(gx, gy, search, side, seed=0, min_cells=1):
-    x0, y0, cell = 500000.0 + 0.25 * seed, 6000000.0 - 0.5 * seed, 0.25
-    fa = _cover(gx, gy, search, x0, y0, cell, 2 * seed)
-    fb = _cover(gx, gy, search, x0, y0, cell, 2 * seed + 1, gsd_cells=1.25)
-    return _case([fa, fb], [(0, 1, gx, gy, x0, y0)], cell, search, side, min_cells)
-
-
-SHAPES = {  # gx, gy, search, side
-    "1x1_s0": (1, 1, 0, 1), "1x1_s1_side4": (1, 1, 1, 4), "3x5_s1": (3, 5, 1, 8), "4x4_s5": (4, 4, 5, 4), "5x3_s5": (5, 3, 5, 16),
-    "63x65_s5": (63, 65, 5, 65), "64x64_s1": (64, 64, 1, 64), "65x63_s5": (65, 63, 5, 80), "1x65_s5": (1, 65, 5, 65),
-    "64x1_s0": (64, 1, 0, 64), "70x19_s5": (70, 19, 5, 70), "257x65_s5": (257, 65, 5, 300), "96x80_s64": (96, 80, 64, 96),
-    "512x512_s4": (512, 512, 4, 512), "65x33_s16": (65, 33, 16, 67), "40x40_s33": (40, 40, 33, 41),
-    "33x37_s62": (33, 37, 62, 40), "33x37_s63": (33, 37, 63, 40)}             # the last search with 32-row tiles, the first with 16
-
 
 def _several_pairs():
     """Pairs of different sizes in one launch, sharing frames, patches at different places, one yawed 45 degrees."""
@@ -506,56 +342,6 @@ def _several_pairs():
 
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------
-
-DEV = "cuda:0"
-
-
-def _up(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _planes(case):
-    n, side, E = len(case["pairs"]), case["side"], case["side"] + 2 * case["search"]
-    return (torch.full((n, side, side), POISON_A, device=DEV, dtype=torch.uint8), torch.full((n, E, E), POISON_B, device=DEV, dtype=torch.uint8))
-
-
-def _render(case, a, b, status, resident, slot=None, images=None):
-    """One wm_register_render_u8 call with the frames `resident` (survey indices) on the device, in that order."""
-    F = case["g2p"].shape[0]
-    images = case["images"] if images is None else images
-    tensors = [_up(images[f]) for f in resident]
-    descs = tiling._frame_descs(tensors, torch.device(DEV)) if tensors else None
-    if slot is None:
-        slot = np.full(F, -1, dtype=np.int32)
-        slot[list(resident)] = np.arange(len(resident), dtype=np.int32)
-    pairs = _up(case["pairs"].view(np.uint8).reshape(len(case["pairs"]), 32))
-    slot_d, g_d, s_d = _up(slot), _up(case["g2p"]), _up(case["size"])                # held until the launch has run
-    N.check(N.lib().wm_register_render_u8(N.ptr(descs), len(resident), N.ptr(slot_d), N.ptr(g_d), N.ptr(s_d), F,
-                                          N.ptr(pairs), len(case["pairs"]), case["cell"], case["search"], case["side"], N.ptr(a), N.ptr(b),
-                                          N.ptr(status), N.stream_ptr(torch.device(DEV))))
-    torch.cuda.synchronize()
-
-
-def device_search(metric, a, b, table, S, side, min_cells):
-    """wm_register_search ("sad") or wm_register_search_zncc ("zncc") on device planes a (P, side, side), b (P, E, E) and a
-    pair table, every output pre-filled with a poison value.  Returns the offsets' table (P, 2S+1, 2S+1, 2 or 6) and best
-    (P, 8) as int64, and peak (P, 2) float64 (None for "sad")."""
-    zncc = metric == "zncc"
-    n, w1 = len(table), 2 * S + 1
-    pairs = _up(table.view(np.uint8).reshape(n, 32))
-    score = torch.full((n, w1, w1, 6 if zncc else 2), -77, device=DEV, dtype=torch.int64 if zncc else torch.int32)
-    best = torch.full((n, 8), -77, device=DEV, dtype=torch.int32)
-    peak = torch.full((n, 2), 123.0, device=DEV, dtype=torch.float64) if zncc else None
-    entry = N.lib().wm_register_search_zncc if zncc else N.lib().wm_register_search
-    N.check(entry(N.ptr(a), N.ptr(b), N.ptr(pairs), n, S, side, min_cells, N.ptr(score), N.ptr(best), *([N.ptr(peak)] if zncc else []),
-                  N.stream_ptr(torch.device(DEV))))
-    torch.cuda.synchronize()
-    return score.cpu().numpy().astype(np.int64), best.cpu().numpy().astype(np.int64), peak.cpu().numpy() if zncc else None
-
-
-def _search(case, a, b, min_cells=None):
-    """The SAD search of a case on device planes.  Returns (score, best) int64."""
-    return device_search("sad", a, b, case["pairs"], case["search"], case["side"], case["min_cells"] if min_cells is None else min_cells)[:2]
 
 
 def _run_and_check(case, want=None):
@@ -696,14 +482,6 @@ def test_gpu_extremes_white_against_black_and_sprinkled_zeros():
         np.testing.assert_array_equal(best[p], pick_oracle(want, 5, 300))
 
 
-def per_k_planes():
-    """The planes of the offsets-per-thread tests of both searches: 72 x 72 against 82 x 82 (search 5), 20 % / 30 % not seen."""
-    rng = np.random.default_rng(17)
-    A = np.where(rng.random((72, 72)) < 0.2, 0, rng.integers(1, 256, size=(72, 72))).astype(np.uint8)
-    B = np.where(rng.random((82, 82)) < 0.3, 0, rng.integers(1, 256, size=(82, 82))).astype(np.uint8)
-    return A, B
-
-
 _PER_K_WANT = []
 
 
@@ -815,10 +593,6 @@ def test_gpu_bad_residency_is_reported_and_skipped():
 
 # ---- end to end ------------------------------------------------------------------------------------------------------
 
-SCENE_H, SCENE_W = 400, 500
-DISPLACED = np.array([(3, -2), (-4, 1), (2, 3), (-1, -2)], dtype=F64)                  # whole cells (east, north), zero mean
-ANIMALS = np.array([(x, y) for y in (150.0, 180.0, 210.0) for x in (190.0, 215.0, 240.0, 265.0)])   # 12, >= 25 m apart
-
 
 def _scene(seed=3):
     """A multi-scale texture: independent uniform fields at 1, 4 and 16 px, mixed per channel."""
@@ -846,20 +620,6 @@ def _survey():
     displaced[:, 0, 2] += DISPLACED[:, 0]
     displaced[:, 1, 2] += DISPLACED[:, 1]
     return frames, true, displaced
-
-
-def _detections(true):
-    """Every animal boxed in each frame that sees it through the TRUE georeference."""
-    g2p = tiling.ground_to_pixel(true)
-    out = []
-    for f in range(len(true)):
-        u = g2p[f, 0, 0] * ANIMALS[:, 0] + g2p[f, 0, 1] * ANIMALS[:, 1] + g2p[f, 0, 2]
-        v = g2p[f, 1, 0] * ANIMALS[:, 0] + g2p[f, 1, 1] * ANIMALS[:, 1] + g2p[f, 1, 2]
-        ok = (u >= 4) & (u < 196) & (v >= 4) & (v < 156)
-        boxes = np.stack([u - 3, v - 3, u + 3, v + 3], axis=1)[ok].astype(np.float32)
-        out.append({"boxes": _up(boxes), "scores": _up(np.linspace(0.9, 0.5, ok.sum()).astype(np.float32)),
-                    "labels": torch.ones(int(ok.sum()), device=DEV, dtype=torch.int64)})
-    return out
 
 
 @pytest.mark.gpu

@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 import torch
 
-import test_register as T
+import register_cases as T
+from survey_util import _Lazy
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
 
@@ -248,7 +249,7 @@ def test_zncc_symbol_and_abi_13():
 def test_register_metric_and_min_corr_errors_before_device_work():
     g = np.stack([T._north_up(0, 0, 100, 80), T._north_up(10, 10, 100, 80)])
     sizes = [(80, 100), (80, 100)]
-    lazy = T._Lazy([np.zeros((80, 100, 3), dtype=np.uint8)] * 2)
+    lazy = _Lazy([np.zeros((80, 100, 3), dtype=np.uint8)] * 2)
     for bad in ("ncc", "SAD", "", None, 1, b"zncc", ("zncc",)):
         with pytest.raises(ValueError, match="metric"):
             tiling.register(lazy, g, 1.0, sizes=sizes, metric=bad)

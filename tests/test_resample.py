@@ -9,14 +9,9 @@ import numpy as np
 import pytest
 import torch
 
+from survey_util import _lib
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import preprocess, tiling
-
-
-def _lib():
-    import __graft_entry__ as g
-    g.build()
-    return N.lib()
 
 
 def test_resample_abi_rejects_bad_arguments():

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from survey_util import _records, model  # noqa: F401 (model: a fixture)
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
 
@@ -297,18 +298,6 @@ def test_fuse_entry_rejects_bad_arguments():
 
 # ---- GPU --------------------------------------------------------------------------------------------------------------
 
-def _records(boxes, scores, cand, rng):
-    n = boxes.shape[0]
-    rec = torch.zeros((n, NQ, 8), dtype=torch.float32)
-    rec[..., 0:4] = torch.from_numpy(boxes)
-    rec[..., 4] = torch.from_numpy(scores)
-    ints = rec.view(torch.int32)
-    ints[..., 5] = torch.from_numpy(rng.integers(0, 7, (n, NQ)).astype(np.int32))
-    ints[..., 6] = torch.from_numpy(np.where(cand, N.FLAG_CONF | N.FLAG_SCORE | N.FLAG_NMS | (rng.integers(0, 2, cand.shape) * 16),
-                                             N.FLAG_CONF | N.FLAG_MERGED).astype(np.int32))
-    ints[..., 7] = torch.from_numpy(rng.integers(-1, 51, (n, NQ)).astype(np.int32))
-    return rec
-
 
 def _fuse(frames, thr=0.5):
     """frames: list of (org, boxes, scores, cand, records) -> one merge_frames(fuse_thr=thr) call, results on the CPU."""
@@ -358,10 +347,10 @@ def test_fuse_seam_frames_bit_exact():
     frames = []
     for lo, hi in [(20, 60), (80, 250)]:
         org, boxes, scores, cand, _ = seam_simulation(rng, 4000, 6000, 60, lo, hi)
-        frames.append((org, boxes, scores, cand, _records(boxes, scores, cand, rng)))
+        frames.append((org, boxes, scores, cand, _records(boxes, scores, cand, rng, N.FLAG_CONF | N.FLAG_MERGED, stray_bit=True)))
     for H, W, pc in [(4000, 6000, 0.3), (3648, 5472, 0.15), (1024, 1024, 0.5)]:
         org, boxes, scores, cand = synth_seams(rng, H, W, pc)
-        frames.append((org, boxes, scores, cand, _records(boxes, scores, cand, rng)))
+        frames.append((org, boxes, scores, cand, _records(boxes, scores, cand, rng, N.FLAG_CONF | N.FLAG_MERGED, stray_bit=True)))
     out, offs = _fuse(frames)
     absorbed = 0
     for f, fr in enumerate(frames):
@@ -377,7 +366,7 @@ def test_fuse_above_4096_candidates_global_keys():
     rng = np.random.default_rng(42)
     org, boxes, scores, cand = synth_seams(rng, 14000, 18000, 0.25)
     assert int(cand.sum()) > 4096
-    fr = (org, boxes, scores, cand, _records(boxes, scores, cand, rng))
+    fr = (org, boxes, scores, cand, _records(boxes, scores, cand, rng, N.FLAG_CONF | N.FLAG_MERGED, stray_bit=True))
     out, offs = _fuse([fr])
     keep, mem = _check_frame(out, offs, 0, fr)
     assert (mem > 1).sum() > 50
@@ -391,7 +380,7 @@ def test_fuse_many_frames_one_call():
     frames = []
     for H, W in sizes:
         org, boxes, scores, cand = synth_seams(rng, H, W, 0.1)
-        frames.append((org, boxes, scores, cand, _records(boxes, scores, cand, rng)))
+        frames.append((org, boxes, scores, cand, _records(boxes, scores, cand, rng, N.FLAG_CONF | N.FLAG_MERGED, stray_bit=True)))
     for thr in (0.5, 0.0):
         out, offs = _fuse(frames, thr)
         for f, fr in enumerate(frames):
@@ -419,7 +408,7 @@ def test_fuse_adversarial():
     wh = rng.random((len(org), NQ, 2)) * 300 + 5
     boxes = np.concatenate([c - wh / 2, c + wh / 2], axis=-1).astype(np.float32)
     frames.append((org, boxes, rng.random((len(org), NQ)).astype(np.float32), np.ones((len(org), NQ), bool)))
-    recs = [(o, b, s, c, _records(b, s, c, rng)) for o, b, s, c in frames]
+    recs = [(o, b, s, c, _records(b, s, c, rng, N.FLAG_CONF | N.FLAG_MERGED, stray_bit=True)) for o, b, s, c in frames]
     out, offs = _fuse(recs)
     for f, fr in enumerate(recs):
         keep, mem = _check_frame(out, offs, f, fr)
@@ -435,7 +424,7 @@ def test_nms_entry_unchanged():
     frames = []
     for H, W in [(4000, 6000), (14000, 18000)]:
         org, boxes, scores, cand = synth_seams(rng, H, W, 0.2)
-        frames.append((org, boxes, scores, cand, _records(boxes, scores, cand, rng)))
+        frames.append((org, boxes, scores, cand, _records(boxes, scores, cand, rng, N.FLAG_CONF | N.FLAG_MERGED, stray_bit=True)))
     dev = torch.device("cuda:0")
     rec = torch.cat([f[4] for f in frames]).to(dev)
     org = torch.tensor([o for f in frames for o in f[0]], dtype=torch.int32)
@@ -460,19 +449,6 @@ def test_nms_entry_unchanged():
 
 
 # ---- GPU end to end ---------------------------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def model():
-    from wildlifemapper_amd import synth
-    from wildlifemapper_amd.segment_anything import sam_model_registry
-    from wildlifemapper_amd.segment_anything.network import MedSAM
-    sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict("vit_b").items()}
-    sam, _, _ = sam_model_registry["vit_b"](None, None)
-    m = MedSAM(sam.image_encoder, sam.mask_decoder, sam.prompt_encoder).eval()
-    m.load_state_dict(sd, strict=True)
-    m._hub.set_precision("fp16")
-    yield m
-    m._hub.close()
 
 
 def _per_tile_fuse(model, frame_dev, thr, ext=None):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from survey_util import _records
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
 
@@ -92,17 +93,6 @@ def test_merge_frames_rejects_bad_arguments():
 
 
 # ---- GPU --------------------------------------------------------------------------------------------------------------
-
-def _records(boxes, scores, cand, rng):
-    n = boxes.shape[0]
-    rec = torch.zeros((n, NQ, 8), dtype=torch.float32)
-    rec[..., 0:4] = torch.from_numpy(boxes)
-    rec[..., 4] = torch.from_numpy(scores)
-    ints = rec.view(torch.int32)
-    ints[..., 5] = torch.from_numpy(rng.integers(0, 7, (n, NQ)).astype(np.int32))
-    ints[..., 6] = torch.from_numpy(np.where(cand, N.FLAG_CONF | N.FLAG_SCORE | N.FLAG_NMS, N.FLAG_CONF).astype(np.int32))
-    ints[..., 7] = torch.from_numpy(rng.integers(-1, 51, (n, NQ)).astype(np.int32))
-    return rec
 
 
 def _synth_frame(H, W, rng, p_cand=0.15, dup=4, wide=False):

@@ -6,24 +6,11 @@ import numpy as np
 import pytest
 import torch
 
+from survey_util import model  # noqa: F401 (a fixture)
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import preprocess, tiling
 
 NQ = 51
-
-
-@pytest.fixture(scope="module")
-def model():
-    from wildlifemapper_amd import synth
-    from wildlifemapper_amd.segment_anything import sam_model_registry
-    from wildlifemapper_amd.segment_anything.network import MedSAM
-    sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict("vit_b").items()}
-    sam, _, _ = sam_model_registry["vit_b"](None, None)
-    m = MedSAM(sam.image_encoder, sam.mask_decoder, sam.prompt_encoder).eval()
-    m.load_state_dict(sd, strict=True)
-    m._hub.set_precision("fp16")
-    yield m
-    m._hub.close()
 
 
 def _bits(t):

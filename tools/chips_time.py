@@ -19,6 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from wildlifemapper_amd import _native as N, preprocess, tiling  # noqa: E402
+from wildlifemapper_amd._survey import _frame_descs  # noqa: E402
 
 
 def main():
@@ -40,7 +41,7 @@ def main():
     win = tiling.chip_windows(boxes_h)
     assert (win[:, :2] >= 0).all() and (win[:, 0] + win[:, 2] <= H).all() and (win[:, 1] + win[:, 2] <= W).all()
     boxes = torch.from_numpy(boxes_h).to(dev)
-    desc = tiling._frame_descs([frame], dev)
+    desc = _frame_descs([frame], dev)
     chips = torch.empty((a.n, S, S, 3), dtype=torch.uint8, device=dev)
     windows = torch.empty((a.n, 3), dtype=torch.int32, device=dev)
     L, s = N.lib(), N.stream_ptr(dev)

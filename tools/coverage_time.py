@@ -26,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from wildlifemapper_amd import _native as N  # noqa: E402
-from wildlifemapper_amd import tiling  # noqa: E402
+from survey_bench_util import timed, yawed_survey  # noqa: E402
 
 H, W = 400, 600
 OVERLAP = 3.5                 # mean frames per cell, were the frames spread evenly
@@ -35,32 +35,13 @@ OVERLAP = 3.5                 # mean frames per cell, were the frames spread eve
 def make(F, g, n_points, seed):
     """F yawed frames over a g x g grid whose side is chosen for OVERLAP; n_points ground points in and around it."""
     rng = np.random.default_rng(seed)
-    x0, y0 = 500000.1, 6000000.7
-    gsd = 0.05
-    side = (F * H * W * gsd * gsd / OVERLAP) ** 0.5
-    cell = side / g
-    georef = np.stack([tiling.nadir_affine(H, W, (x0 + rng.uniform(0, side), y0 + rng.uniform(0, side)), gsd, rng.uniform(0, 360))
-                       for _ in range(F)])
-    case = {"g2p": tiling.ground_to_pixel(georef).reshape(-1, 6), "size": np.tile(np.array([[H, W]], dtype=np.int32), (F, 1)),
-            "x0": x0, "y0": y0, "cell": cell, "gx": g, "gy": g, "points": None, "labels": None}
+    case, side = yawed_survey(rng, F, g, H, W, OVERLAP)
+    x0, y0 = case["x0"], case["y0"]
+    case.update(points=None, labels=None)
     if n_points:
         case["points"] = np.stack([x0 + rng.uniform(-0.02 * side, 1.02 * side, n_points), y0 + rng.uniform(-0.02 * side, 1.02 * side, n_points)], axis=1)
         case["labels"] = rng.integers(0, 7, n_points).astype(np.int32)
     return case
-
-
-def timed(call, reps):
-    call()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return round(float(np.min(ms)), 4), round(float(np.median(ms)), 4)
 
 
 def run(case, reps, skip_oracle):

@@ -8,6 +8,7 @@ step as it was before the criterion existed, measured in the same run.
   python tools/criterion_time.py [--model vit_h] [--batch 16] [--targets 51 300] [--out profiles/criterion]
 """
 import argparse
+import functools
 import os
 import sys
 import time
@@ -17,6 +18,7 @@ sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
 import numpy as np
 import torch
 import criterion_ref as CR
+import survey_bench_util
 from wildlifemapper_amd import synth
 from wildlifemapper_amd.segment_anything import sam_model_registry
 from wildlifemapper_amd.segment_anything.build_sam import SetCriterion
@@ -40,19 +42,7 @@ def say(s):
     print(s, flush=True)
     lines.append(s)
 
-
-def timed(fn, n):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
-
+timed = functools.partial(survey_bench_util.timed, warmup=5, together=True)       # the mean of n calls timed together
 
 sam, _, post = sam_model_registry[a.model](None, None)
 m = MedSAM(sam.image_encoder, sam.mask_decoder, sam.prompt_encoder).eval()

@@ -28,7 +28,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from wildlifemapper_amd import _native as N  # noqa: E402
-from wildlifemapper_amd import tiling  # noqa: E402
+from survey_bench_util import timed, yawed_survey  # noqa: E402
+from wildlifemapper_amd._survey import _frame_descs  # noqa: E402
 
 H, W = 400, 600
 OVERLAP = 3.5                 # mean frames per cell, were the frames spread evenly
@@ -37,28 +38,7 @@ HBM_PEAK = 8.0e12             # bytes per second
 
 def make(F, g, seed):
     """F yawed frames over a g x g grid whose side is chosen for OVERLAP."""
-    rng = np.random.default_rng(seed)
-    x0, y0 = 500000.1, 6000000.7
-    gsd = 0.05
-    side = (F * H * W * gsd * gsd / OVERLAP) ** 0.5
-    georef = np.stack([tiling.nadir_affine(H, W, (x0 + rng.uniform(0, side), y0 + rng.uniform(0, side)), gsd, rng.uniform(0, 360))
-                       for _ in range(F)])
-    return {"g2p": tiling.ground_to_pixel(georef).reshape(-1, 6), "size": np.tile(np.array([[H, W]], dtype=np.int32), (F, 1)),
-            "x0": x0, "y0": y0, "cell": side / g, "gx": g, "gy": g, "seed": seed}
-
-
-def timed(call, reps):
-    call()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return round(float(np.min(ms)), 4), round(float(np.median(ms)), 4)
+    return dict(yawed_survey(np.random.default_rng(seed), F, g, H, W, OVERLAP)[0], seed=seed)
 
 
 def run(case, reps, skip_oracle):
@@ -70,7 +50,7 @@ def run(case, reps, skip_oracle):
     gen = torch.Generator(device=dev).manual_seed(case["seed"])
     pixels = torch.randint(0, 256, (F, H, W, 3), device=dev, dtype=torch.uint8, generator=gen)
     frames = [pixels[f] for f in range(F)]
-    desc = tiling._frame_descs(frames, dev)
+    desc = _frame_descs(frames, dev)
     slot = torch.arange(F, device=dev, dtype=torch.int32)
     source = torch.empty((gy, gx), device=dev, dtype=torch.int32)
     won = torch.empty(F, device=dev, dtype=torch.int32)

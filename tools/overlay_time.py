@@ -15,6 +15,7 @@
       `rocprofv3 --kernel-trace --stats` for the kernel list.  Prints the detections.
 """
 import argparse
+import functools
 import json
 import os
 import sys
@@ -24,6 +25,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import survey_bench_util  # noqa: E402
 from wildlifemapper_amd import preprocess, synth, tiling  # noqa: E402
 
 H, W = 4000, 6000
@@ -35,16 +37,7 @@ def boxes_for(n, rng):
     return np.concatenate([c - wh / 2, c + wh / 2], axis=1).astype(np.float32), rng.integers(0, 7, n)
 
 
-def timed(fn, reps):
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return round(float(np.min(ms)), 4), round(float(np.median(ms)), 4)
+timed = functools.partial(survey_bench_util.timed, warmup=0)          # every call site below warms up itself
 
 
 def kernels(args):

@@ -21,7 +21,7 @@ wm_register_search_zncc, the correlation) on the same planes, against the host r
       Each search is also timed with each of the offsets-per-thread variants K = 1, 2, 4 (WM_REGISTER_K; the result does
       not depend on K), alternating, twice, next to the default choice.
       For the first --oracle-pairs pairs of the chunk the wall clock of the numpy restatement of the SAD rule on the same
-      input (tests/test_register.py: register_oracle), whose planes, score table and best the device's must equal; it
+      input (tests/register_cases.py: register_oracle), whose planes, score table and best the device's must equal; it
       costs seconds per pair at the survey setting, so it runs on a sample and its time for the survey is the sample's
       mean per byte difference times the survey's byte differences.  For the first --zncc-oracle-pairs pairs the device's
       moments, best and peak must equal the restatement of the correlation rule (tests/test_register_zncc.py:
@@ -42,7 +42,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from wildlifemapper_amd import _native as N  # noqa: E402
+from survey_bench_util import once, timed  # noqa: E402
 from wildlifemapper_amd import tiling  # noqa: E402
+from wildlifemapper_amd._survey import _frame_descs  # noqa: E402
 
 H, W, GSD = 400, 600, 0.05
 MIN_CELLS = 4096
@@ -57,22 +59,6 @@ def make(lines, per_line, seed):
     georef = np.stack([tiling.nadir_affine(H, W, (x0 + l * dx + rng.uniform(-0.5, 0.5), y0 + k * dy + rng.uniform(-0.5, 0.5)), GSD,
                                            rng.uniform(-3.0, 3.0)) for l in range(lines) for k in range(per_line)])
     return georef, np.tile(np.array([[H, W]], dtype=np.int32), (lines * per_line, 1))
-
-
-def once(call):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    call()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def timed(call, reps):
-    call()
-    torch.cuda.synchronize()
-    ms = [once(call) for _ in range(reps)]
-    return round(float(np.min(ms)), 4), round(float(np.median(ms)), 4)
 
 
 def by_offsets_per_thread(call, reps):
@@ -101,7 +87,7 @@ def run(lines, per_line, side, search, pair_chunk, seed, reps, oracle_pairs, znc
     gen = torch.Generator(device=dev).manual_seed(seed)
     pixels = torch.randint(0, 256, (len(needed), H, W, 3), device=dev, dtype=torch.uint8, generator=gen)
     frames = [pixels[k] for k in range(len(needed))]
-    desc = tiling._frame_descs(frames, dev)
+    desc = _frame_descs(frames, dev)
     slot = np.full(F, -1, dtype=np.int32)
     slot[needed] = np.arange(len(needed), dtype=np.int32)
     g2p = tiling.ground_to_pixel(georef).reshape(-1, 6)
@@ -152,7 +138,7 @@ def run(lines, per_line, side, search, pair_chunk, seed, reps, oracle_pairs, znc
     torch.cuda.synchronize()
     equal = []
     if oracle_pairs > 0:
-        from test_register import register_oracle
+        from register_cases import register_oracle
         m = min(oracle_pairs, n)
         host = pixels.cpu().numpy()
         images = {f: host[k] for k, f in enumerate(needed)}

@@ -1,0 +1,310 @@
+"""Survey registration: the georeferences of overlapping frames corrected by matching their pixels.
+  * register_pairs: the overlapping pairs of a survey and their ground patches, on the host;
+  * register: every pair's two frames rendered onto its patch (wm_register_render_u8) and the offset between them searched
+    (wm_register_search: sums of absolute differences; wm_register_search_zncc: zero-mean normalised correlation, which
+    survives exposure changes), a chunk of pairs and a few resident frames at a time (rule: include/wm_hip.h "Survey
+    registration");
+  * adjust: one translation per frame from the accepted pairs' offsets, a weighted least-squares bundle adjustment in
+    numpy double."""
+from __future__ import annotations
+
+import math
+from typing import Dict
+
+import numpy as np
+
+import torch
+
+from . import _native as N
+from ._survey import _check_whole, _finite_number, _pinned_upload
+from .ground import (COVERAGE_MAX_FRAMES, _check_cell, _check_georef, _check_sizes, _footprint_extent, _frame_sequence, _frame_tables,
+                     _resident_chunk, _survey_device)
+
+REGISTER_MAX_SIDE = N.REGISTER_MAX_SIDE       # include/wm_hip.h WM_REGISTER_MAX_SIDE
+REGISTER_MAX_SEARCH = N.REGISTER_MAX_SEARCH   # WM_REGISTER_MAX_SEARCH
+REGISTER_MAX_PAIRS = N.REGISTER_MAX_PAIRS     # WM_REGISTER_MAX_PAIRS, per launch: register() chunks by pair_chunk
+# wm_register_pair, 32 bytes: the patch of a pair is gx x gy cells with south-west corner (x0, y0)
+REGISTER_PAIR = np.dtype([("frame_a", "<i4"), ("frame_b", "<i4"), ("gx", "<i4"), ("gy", "<i4"), ("x0", "<f8"), ("y0", "<f8")])
+_REGISTER_FRAMES_RESIDENT = 8                 # frames on the device per render call of register()
+
+
+def _check_register_shape(search, side, min_cells, what: str):
+    search = _check_whole(search, what, "search", 0)
+    side = _check_whole(side, what, "side")
+    min_cells = _check_whole(min_cells, what, "min_cells")
+    if search > REGISTER_MAX_SEARCH:
+        raise ValueError(f"{what}: search {search} exceeds {REGISTER_MAX_SEARCH}")
+    if side > REGISTER_MAX_SIDE:
+        raise ValueError(f"{what}: side {side} exceeds {REGISTER_MAX_SIDE}")
+    if min_cells >= 2 ** 31:
+        raise ValueError(f"{what}: min_cells {min_cells} does not fit int32")
+    return search, side, min_cells
+
+
+def _check_pair_table(pairs, n_frames: int, side: int, what: str) -> np.ndarray:
+    """A (P,) array of REGISTER_PAIR as register_pairs returns it, every entry inside the limits of include/wm_hip.h."""
+    if not isinstance(pairs, np.ndarray) or pairs.dtype != REGISTER_PAIR or pairs.ndim != 1:
+        raise ValueError(f"{what}: pairs must be a (P,) array of tiling.REGISTER_PAIR, as register_pairs returns it")
+    t = np.ascontiguousarray(pairs)
+    if t.size:
+        a, b = t["frame_a"], t["frame_b"]
+        if a.min() < 0 or b.min() < 0 or a.max() >= n_frames or b.max() >= n_frames or np.any(a == b):
+            raise ValueError(f"{what}: pairs: frame_a and frame_b must be two different frames in 0..{n_frames - 1}")
+        if t["gx"].min() < 1 or t["gy"].min() < 1 or t["gx"].max() > side or t["gy"].max() > side:
+            raise ValueError(f"{what}: pairs: gx and gy must lie in 1..side ({side})")
+        if not (np.isfinite(t["x0"]).all() and np.isfinite(t["y0"]).all()):
+            raise ValueError(f"{what}: pairs: x0 and y0 must be finite")
+    return t
+
+
+def register_pairs(georef, sizes, cell, search: int = 16, side: int = 512, min_cells: int = 4096) -> np.ndarray:
+    """The overlapping pairs of a survey and their ground patches, for register().  Host only, in double.  georef (F,2,3)
+    float64 as for census(), sizes (F,2) (height, width), cell metres.  A pair (i < j) is proposed when the axis-aligned
+    ground bounding boxes of the two footprints (the extent of the corners (0, 0), (W, 0), (0, H), (W, H)) intersect with
+    a positive area.  Its patch is that intersection snapped outward to multiples of cell -- i0 = floor(lo / cell), i1 =
+    ceil(hi / cell), gx = i1 - i0, x0 = i0 * cell, the same north -- so the patches of all pairs lie on one lattice; a
+    patch wider than `side` cells is centre-cropped (i0 += (gx - side) // 2, gx = side); a patch of fewer than min_cells
+    cells is dropped.  A frame whose georeference is not finite or whose size is below 1 x 1 is in no pair.  search is
+    only validated here (the patch does not depend on it).  Returns a (P,) array of REGISTER_PAIR (frame_a, frame_b, gx,
+    gy, x0, y0), ordered by (frame_a, frame_b)."""
+    what = "register_pairs"
+    cell = _check_cell(cell, what)
+    g = _check_georef(georef, what)
+    s = _check_sizes(sizes, g.shape[0], what)
+    search, side, min_cells = _check_register_shape(search, side, min_cells, what)
+    F = g.shape[0]
+    ok, X, Y = _footprint_extent(g, s)
+    with np.errstate(all="ignore"):
+        xl, xh, yl, yh = X.min(axis=1), X.max(axis=1), Y.min(axis=1), Y.max(axis=1)
+    out = []
+    for i in range(F):
+        if not ok[i]:
+            continue
+        js = np.arange(i + 1, F)
+        lo_x, hi_x = np.maximum(xl[i], xl[js]), np.minimum(xh[i], xh[js])
+        lo_y, hi_y = np.maximum(yl[i], yl[js]), np.minimum(yh[i], yh[js])
+        for k in np.nonzero(ok[js] & (lo_x < hi_x) & (lo_y < hi_y))[0]:
+            i0, i1 = math.floor(lo_x[k] / cell), math.ceil(hi_x[k] / cell)
+            j0, j1 = math.floor(lo_y[k] / cell), math.ceil(hi_y[k] / cell)
+            gx, gy = i1 - i0, j1 - j0
+            if gx > side:
+                i0, gx = i0 + (gx - side) // 2, side
+            if gy > side:
+                j0, gy = j0 + (gy - side) // 2, side
+            if gx < 1 or gy < 1 or gx * gy < min_cells:
+                continue
+            out.append((i, int(js[k]), gx, gy, i0 * cell, j0 * cell))
+    return np.array(out, dtype=REGISTER_PAIR).reshape(-1)
+
+
+def adjust(n_frames, pairs, measured, weights, fixed=None) -> Dict[str, np.ndarray]:
+    """One translation per frame from pairwise measurements: weighted least squares of t_b - t_a = m_p.  Host only, numpy
+    double.  pairs: a REGISTER_PAIR table or a (P,2) array of (frame_a, frame_b); measured (P,2) metres (east, north);
+    weights (P,) >= 0 -- register() passes the cells n of an accepted pair and 0 for a rejected one; a pair of weight 0 is
+    not part of the system or of the graph.  The system is stacked with rows sqrt(w_p) * (t_b - t_a) = sqrt(w_p) * m_p and
+    solved by numpy.linalg.lstsq, whose minimum-norm solution fixes what the measurements leave free: in a connected
+    component of the graph without a fixed frame the mean shift of its frames is zero.  fixed: frames that stay at 0 (their
+    columns are left out), which pins every component that holds one.  A frame with no pair of positive weight keeps 0.
+    Returns 'shift' (n_frames,2) metres, to be added to (a2, a5); 'residual' (P,2) = (t_b - t_a) - m_p for every pair,
+    whatever its weight; 'component' (n_frames,) int64, the lowest frame index of the frame's component, -1 for a frame
+    with no pair of positive weight."""
+    what = "adjust"
+    F = _check_whole(n_frames, what, "n_frames", 0)
+    if isinstance(pairs, np.ndarray) and pairs.dtype == REGISTER_PAIR:
+        pairs = np.stack([pairs["frame_a"], pairs["frame_b"]], axis=1) if pairs.size else np.zeros((0, 2), dtype=np.int64)
+    try:
+        ab = np.asarray(pairs)
+        if ab.size == 0:
+            ab = ab.reshape(0, 2)
+        if ab.dtype.kind not in "iu" or ab.ndim != 2 or ab.shape[1] != 2:
+            raise TypeError
+        ab = ab.astype(np.int64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: pairs must be a REGISTER_PAIR table or a (P,2) array of whole numbers") from None
+    P = ab.shape[0]
+    if P and (ab.min() < 0 or ab.max() >= F or np.any(ab[:, 0] == ab[:, 1])):
+        raise ValueError(f"{what}: pairs: frame_a and frame_b must be two different frames in 0..{F - 1}")
+    try:
+        m = np.asarray(measured, dtype=np.float64).reshape(-1, 2) if np.size(measured) else np.zeros((0, 2))
+        w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: measured must be (P,2) numbers and weights (P,) numbers") from None
+    if m.shape != (P, 2) or w.shape != (P,):
+        raise ValueError(f"{what}: {P} pairs, measured of shape {m.shape} and weights of shape {w.shape}: expected ({P}, 2) and ({P},)")
+    if not (np.isfinite(w).all() and (w >= 0).all()):
+        raise ValueError(f"{what}: weights must be finite and >= 0")
+    used = w > 0
+    if not np.isfinite(m[used]).all():
+        raise ValueError(f"{what}: measured must be finite where the weight is positive")
+    fixed_a = np.zeros(F, dtype=bool)
+    if fixed is not None:
+        try:
+            fx = np.asarray(list(fixed))
+            if fx.size and (fx.dtype.kind not in "iu" or fx.ndim != 1 or fx.min() < 0 or fx.max() >= F):
+                raise TypeError
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: fixed {fixed!r} must be frame indices in 0..{F - 1}") from None
+        fixed_a[fx.astype(np.int64)] = True
+    # components of the graph of used pairs: union-find, labelled by their lowest frame
+    root = np.arange(F)
+
+    def find(x):
+        while root[x] != x:
+            root[x] = root[root[x]]
+            x = root[x]
+        return x
+
+    for a, b in ab[used]:
+        ra, rb = find(a), find(b)
+        if ra != rb:
+            root[max(ra, rb)] = min(ra, rb)
+    in_graph = np.zeros(F, dtype=bool)
+    in_graph[ab[used].reshape(-1)] = True
+    component = np.array([find(f) if in_graph[f] else -1 for f in range(F)], dtype=np.int64).reshape(F)
+    shift = np.zeros((F, 2), dtype=np.float64)
+    cols = np.nonzero(in_graph & ~fixed_a)[0]
+    if cols.size and used.any():
+        col_of = np.full(F, -1, dtype=np.int64)
+        col_of[cols] = np.arange(cols.size)
+        rows = np.nonzero(used)[0]
+        sw = np.sqrt(w[rows])
+        A = np.zeros((rows.size, cols.size), dtype=np.float64)
+        ca, cb = col_of[ab[rows, 0]], col_of[ab[rows, 1]]
+        r = np.arange(rows.size)
+        A[r[ca >= 0], ca[ca >= 0]] = -sw[ca >= 0]
+        A[r[cb >= 0], cb[cb >= 0]] = sw[cb >= 0]
+        t = np.linalg.lstsq(A, m[rows] * sw[:, None], rcond=None)[0]
+        shift[cols] = t
+    with np.errstate(all="ignore"):
+        residual = (shift[ab[:, 1]] - shift[ab[:, 0]]) - m
+    return {"shift": shift, "residual": residual, "component": component}
+
+
+REGISTER_METRICS = ("sad", "zncc")
+
+
+def _decode_sad(best, peak, min_corr):
+    """best (P,8) -> has, has2, mean, runner_up, corr, confident: best's third of four is sad (-1: none), the fourth n."""
+    sad, n1, sad2, n2 = (best[:, k].astype(np.int64) for k in (2, 3, 6, 7))
+    has, has2 = sad >= 0, sad2 >= 0
+    mean = np.where(has, sad / np.maximum(n1, 1), np.nan)
+    runner = np.where(has2, sad2 / np.maximum(n2, 1), np.nan)
+    return has, has2, mean, runner, np.full(best.shape[0], np.nan), has
+
+
+def _decode_zncc(best, peak, min_corr):
+    """best (P,8), peak (P,2) -> the same six: best's third of four is ok (1 / 0), peak holds q (NaN: none)."""
+    has, has2 = best[:, 2] == 1, best[:, 6] == 1
+    r = np.sign(peak) * np.sqrt(np.abs(peak))
+    corr = np.where(has, r[:, 0], np.nan)
+    mean = np.where(has, 1.0 - r[:, 0], np.nan)
+    runner = np.where(has2, 1.0 - r[:, 1], np.nan)
+    return has, has2, mean, runner, corr, has & (corr > min_corr)
+
+
+# per metric: the entry point, its table's dtype and last dimension, whether it fills a peak buffer, best[2] of "none", the decoder
+_REGISTER_METRIC = {"sad": ("wm_register_search", torch.int32, 2, False, -1, _decode_sad),
+                    "zncc": ("wm_register_search_zncc", torch.int64, 6, True, 0, _decode_zncc)}
+
+
+def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512, min_cells: int = 4096, min_ratio: float = 1.25,
+             pairs=None, fixed=None, pair_chunk: int = 256, metric: str = "sad", min_corr: float = 0.0) -> Dict[str, object]:
+    """Correct the georeferences of a survey by matching the pixels of its overlapping frames (wm_register_render_u8,
+    wm_register_search or wm_register_search_zncc; rule: include/wm_hip.h "Survey registration" and "Survey registration,
+    correlation search").  frames as mosaic() takes them: a sequence that is
+    only indexed -- tensors, arrays, or a lazy sequence that loads frame i when asked; georef (F,2,3) float64 as for
+    census(); cell metres; sizes (F,2) may be None only for a list of tensors or arrays.  pairs: the table to use, None for
+    register_pairs(georef, sizes, cell, search, side, min_cells).  Everything is validated before any device work.
+    The pairs are rendered and searched pair_chunk at a time, so the planes stay bounded (pair_chunk * (side^2 + (side +
+    2 * search)^2) bytes); within a chunk its frames go up a few at a time and are released after their render call, so a
+    frame is read only while a pair of the current chunk needs it (a frame shared by two chunks is read once per chunk).
+    A pair is ACCEPTED iff a best offset exists (some offset has n >= min_cells), |dy| < search and |dx| < search (a peak
+    on the window's edge is not a peak), and the runner-up outside the peak's 3 x 3 has a mean absolute difference of at
+    least min_ratio times the peak's (sad2 / n2 >= min_ratio * (sad / n), in double); a runner-up that does not exist also
+    accepts.  The accepted pairs, each measuring t_b - t_a = -(dx, dy) * cell with weight n, go to adjust(fixed=fixed).
+    metric: "sad" (the default) is the rule above, masked sums of absolute differences; it assumes the same exposure in
+    both frames of a pair (no gain or offset is fitted).  Where exposure changes between frames -- auto-exposure, cloud
+    shadow -- use metric="zncc": the offsets are scored by the zero-mean normalised correlation, which a gain and an offset
+    between the two frames do not change.  With r = sign(q) * sqrt(|q|) of the device's signed squared correlation q, a
+    pair is then accepted iff a best offset exists (n >= min_cells and neither plane flat), |dy| < search and |dx| <
+    search, r > min_corr (finite, in [-1, 1)), and the runner-up does not exist or 1 - r2 >= min_ratio * (1 - r): 1 - r
+    takes the part of the mean absolute difference, so min_ratio keeps its meaning.  Both defaults are policy, not
+    measurements on real imagery.  A cell coarser than the ground
+    sampling distance point-samples, so shrink the frames first (preprocess.resample_u8, resampled_georef); only a
+    translation is corrected, not yaw or scale; the resolution is one cell -- a second register() at a finer cell on the
+    corrected georef refines it.  Runs on the current device's current stream.  No CPU fallback.  Returns host arrays:
+      'georef' (F,2,3) float64 corrected (shift added to a2, a5), 'shift' (F,2) metres, 'pairs' the table,
+      'offset' (P,2) int64 cells (dx, dy), 'cells' (P,) int64 n at the best offset (0: none), 'mean' (P,) float64 sad / n
+      (NaN: none), 'runner_up' (P,) float64 sad2 / n2 (NaN: none), 'accepted' (P,) bool, 'residual' (P,2) metres after
+      the adjustment, 'component' (F,) int64 as adjust() gives it, 'corr' (P,) float64 NaN.  Under metric="zncc" 'mean'
+      is 1 - r and 'runner_up' 1 - r2 (NaN: none), and 'corr' is r (NaN: none)."""
+    what = "register"
+    if not isinstance(metric, str) or metric not in REGISTER_METRICS:
+        raise ValueError(f"{what}: metric {metric!r} must be one of {REGISTER_METRICS}")
+    must = "must be a finite number in [-1, 1)"
+    min_corr = _finite_number(min_corr, what, "min_corr", lambda r: -1.0 <= r < 1.0, must, must, refuse=bool, echo_float=True)
+    entry, table_dtype, table_last, has_peak, none, decode = _REGISTER_METRIC[metric]
+    search, side, min_cells = _check_register_shape(search, side, min_cells, what)
+    pair_chunk = _check_whole(pair_chunk, what, "pair_chunk")
+    if pair_chunk > REGISTER_MAX_PAIRS:
+        raise ValueError(f"{what}: pair_chunk {pair_chunk} exceeds {REGISTER_MAX_PAIRS}")
+    must = "must be a finite number >= 0"
+    min_ratio = _finite_number(min_ratio, what, "min_ratio", lambda r: r >= 0.0, must, must, echo_float=True)
+    n_given, sizes = _frame_sequence(frames, sizes, what, "the frames of the current chunk of pairs")
+    cell = _check_cell(cell, what)
+    g = _check_georef(georef, what)
+    s = _check_sizes(sizes, g.shape[0], what)
+    F = g.shape[0]
+    if F > COVERAGE_MAX_FRAMES:
+        raise ValueError(f"{what}: {F} frames exceed {COVERAGE_MAX_FRAMES}")
+    if n_given != F:
+        raise ValueError(f"{what}: {n_given} frames for {F} georeferences")
+    table = register_pairs(g, s, cell, search, side, min_cells) if pairs is None else _check_pair_table(pairs, F, side, what)
+    adjust(F, np.zeros((0, 2), dtype=np.int64), np.zeros((0, 2)), np.zeros(0), fixed)         # fixed= validated before device work
+    P = table.shape[0]
+    best = np.zeros((P, 8), dtype=np.int32)
+    peak = np.full((P, 2), np.nan, dtype=np.float64)                 # (q, q2) of the correlation search
+    best[:, 2] = best[:, 6] = none
+    if P:
+        dev = _survey_device(what)
+        lib = N.lib()
+        E = side + 2 * search
+        with torch.cuda.device(dev):
+            g_d, s_d = _frame_tables(g, s, dev)
+            status = torch.zeros(1, device=dev, dtype=torch.int32)
+            for c0 in range(0, P, pair_chunk):
+                chunk = table[c0:c0 + pair_chunk]
+                n = chunk.shape[0]
+                pairs_d = _pinned_upload(chunk.view(np.uint8).reshape(n, REGISTER_PAIR.itemsize), dev)
+                plane_a = torch.empty((n, side, side), device=dev, dtype=torch.uint8)
+                plane_b = torch.empty((n, E, E), device=dev, dtype=torch.uint8)
+                needed = sorted(set(chunk["frame_a"].tolist()) | set(chunk["frame_b"].tolist()))
+                for f0 in range(0, len(needed), _REGISTER_FRAMES_RESIDENT):
+                    ids = needed[f0:f0 + _REGISTER_FRAMES_RESIDENT]
+                    desc, slot_d, resident = _resident_chunk(frames, ids, s, dev, what)
+                    N.check(lib.wm_register_render_u8(N.ptr(desc), len(ids), N.ptr(slot_d), N.ptr(g_d), N.ptr(s_d), F, N.ptr(pairs_d), n,
+                                                      cell, search, side, N.ptr(plane_a), N.ptr(plane_b), N.ptr(status), N.stream_ptr(dev)))
+                    del resident, desc, slot_d                    # the stream orders their reuse after the launch
+                best_d = torch.empty((n, 8), device=dev, dtype=torch.int32)
+                score = torch.empty((n, 2 * search + 1, 2 * search + 1, table_last), device=dev, dtype=table_dtype)
+                peak_d = torch.empty((n, 2), device=dev, dtype=torch.float64) if has_peak else None
+                N.check(getattr(lib, entry)(N.ptr(plane_a), N.ptr(plane_b), N.ptr(pairs_d), n, search, side, min_cells, N.ptr(score),
+                                            N.ptr(best_d), *([N.ptr(peak_d)] if has_peak else []), N.stream_ptr(dev)))
+                if has_peak:
+                    peak[c0:c0 + n] = peak_d.cpu().numpy()
+                best[c0:c0 + n] = best_d.cpu().numpy()
+                del plane_a, plane_b, score, best_d, peak_d, pairs_d
+            bad = int(status.item())
+        if bad:
+            raise RuntimeError(f"{what}: wm_register_render_u8 skipped planes (status {bad}): a resident frame did not match its slot or size")
+    dy, dx, n1 = (best[:, k].astype(np.int64) for k in (0, 1, 3))
+    with np.errstate(all="ignore"):
+        has, has2, mean, runner, corr, confident = decode(best, peak, min_corr)
+        accepted = confident & (np.abs(dy) < search) & (np.abs(dx) < search) & (~has2 | (runner >= min_ratio * mean))
+    offset = np.stack([dx, dy], axis=1).reshape(P, 2)
+    adj = adjust(F, table, -offset.astype(np.float64) * cell, np.where(accepted, n1, 0).astype(np.float64), fixed)
+    out_g = g.copy()
+    out_g[:, 0, 2] += adj["shift"][:, 0]
+    out_g[:, 1, 2] += adj["shift"][:, 1]
+    return {"georef": out_g, "shift": adj["shift"], "pairs": table, "offset": offset, "cells": np.where(has, n1, 0), "mean": mean,
+            "runner_up": runner, "accepted": accepted, "residual": adj["residual"], "component": adj["component"], "corr": corr}

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from . import tiling
+from . import review, tiling
 
 PLOT_SCRATCH_BYTES = 1024          # include/wm_hip.h WM_PLOT_SCRATCH_BYTES, per image
 
@@ -61,8 +61,8 @@ def plot_points(image: torch.Tensor, labels, boxes, width: int = 2, palette=None
     the order given, later over earlier, `width` pixels inward (tiling.draw_boxes).  palette: (P,3) uint8, row `label`
     written as it is -- the reference's table is given in that order; None: tiling.DEFAULT_PALETTE with each row reversed,
     so a label has the colour in the saved file that it has on a survey overlay."""
-    width = tiling._check_draw_width(width, "plot_points")
-    pal = tiling._check_palette(palette, "plot_points") if palette is not None else np.ascontiguousarray(tiling.DEFAULT_PALETTE[:, ::-1])
+    width = review._check_draw_width(width, "plot_points")
+    pal = review._check_palette(palette, "plot_points") if palette is not None else np.ascontiguousarray(tiling.DEFAULT_PALETTE[:, ::-1])
     pic = plot_image(image)
     single = image.dim() == 3
     B = 1 if single else image.shape[0]
@@ -103,9 +103,9 @@ def visualize_predictions(model, postprocessors, data_loader, out_dir: str, thre
     the canvas (H, W) of the batch instead, so they lie on the pixels shown."""
     if sizes not in ("orig", "canvas"):
         raise ValueError(f"visualize_predictions: sizes {sizes!r} must be 'orig' or 'canvas'")
-    width = tiling._check_draw_width(width, "visualize_predictions")
+    width = review._check_draw_width(width, "visualize_predictions")
     if palette is not None:
-        palette = tiling._check_palette(palette, "visualize_predictions")
+        palette = review._check_palette(palette, "visualize_predictions")
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     os.makedirs(out_dir, exist_ok=True)
