@@ -43,6 +43,8 @@ extern "C" {
  *    registration: frame georeferences corrected by image matching); the number stays 13 for the same reason.
  *    13, additive: wm_register_search_zncc (survey registration, correlation search: a score that a gain and an offset
  *    between the two frames of a pair do not change); the number stays 13 for the same reason.
+ *    13, additive: wm_register_refine, WM_REGISTER_REFINE_SUMS (survey registration, refinement: the integer normal
+ *    equations of a sub-cell shift, yaw, scale, gain and offset per pair); the number stays 13 for the same reason.
  * 12: wm_box_outline_rect, wm_draw_boxes_u8, wm_plot_image_u8, WM_DRAW_MAX_WIDTH, WM_DRAW_MAX_PALETTE, WM_PLOT_SCRATCH_BYTES
  *    (survey overlays: detections outlined on frames and tiles, on the GPU); nothing else changed.
  * 11: wm_chip_window, wm_crop_chips_u8, WM_CHIP_MAX_SIDE (survey review chips: one PIL-exact crop per detection, cut on
@@ -526,6 +528,38 @@ int wm_register_search(const uint8_t* a_dev, const uint8_t* b_dev, const wm_regi
 int wm_register_search_zncc(const uint8_t* a_dev, const uint8_t* b_dev, const wm_register_pair* pairs_dev, int n_pairs, int search,
                             int side, int min_cells, int64_t* moments_dev /* [n_pairs][2S+1][2S+1][6] */,
                             int32_t* best_dev /* [n_pairs][8] */, double* peak_dev /* [n_pairs][2] */, void* stream);
+
+/* Survey registration, refinement (tiling.refine, tiling.register(refine=k)): the searches above resolve one cell and one
+ * translation per frame.  Around the integer peak, one Gauss-Newton step of the brightness-constancy equation gives the
+ * sub-cell shift, the rotation and the scale of a pair, and the gain and offset between its two exposures; it reads every
+ * cell once.  This entry computes the integer normal equations of that step; the 4 x 4 or 6 x 6 solve is the host's
+ * (tiling.refine_solve).  Planes, pairs and limits are those of "Survey registration", word for word, and the planes are
+ * wm_register_render_u8's -- except 1 <= search <= WM_REGISTER_MAX_SEARCH: B must carry a ring of at least one cell.  Only
+ * the centre offset is used.
+ * Sums (wm_register_refine): for pair p and cell (j, i), j < gy, i < gx, let J = j + search, I = i + search and
+ *     a = A[j][i]    b = B[J][I]    e = B[J][I + 1]    w = B[J][I - 1]    nn = B[J + 1][I]    ss = B[J - 1][I]
+ * A cell COUNTS iff all six are non-zero.  For a counted cell, all in integers (rows grow north, columns east),
+ *     r  = a - b                gxv = e - w               gyv = nn - ss
+ *     x  = 2 * i + 1 - gx       y   = 2 * j + 1 - gy      (twice the cell centre's offset from the patch centre, in cells)
+ *     c0 = gxv    c1 = gyv    c2 = x * gyv - y * gxv    c3 = x * gxv + y * gyv    c4 = b    c5 = 1
+ * sums_dev[p][WM_REGISTER_REFINE_SUMS] int64 holds, over the counted cells: the 21 products sum c_k * c_l, k <= l, row-major
+ * -- (0,0), (0,1), ... (0,5), (1,1), ... (5,5); entry 20 is the number of counted cells -- then the 6 values sum c_k * r,
+ * then sum r * r.  Nothing overflows: |c2|, |c3| <= 2 * 511 * 254 = 259 588, a square is below 6.8e10, and 512^2 of them are
+ * below 1.8e16 < 2^63.  Only gx and gy of a pair are read here; a pair with gx or gy outside [1, side] keeps all-zero sums.
+ * Meaning of the sums, which fixes the signs: the model is A(X) ~ (1 + gamma) * B(X + d(X)) + o with the field, in cells,
+ *     d = (tx - theta * y' + sigma * x', ty + theta * x' + sigma * y'),   (x', y') = (x, y) / 2
+ * With N the symmetric 6 x 6 matrix of the products and R the six sums c_k * r, the solution q of N q = R gives
+ *     tx = 2 q0    ty = 2 q1    theta = 4 q2 (radians, counter-clockwise)    sigma = 4 q3    gamma = q4    o = q5
+ * (the central differences gxv, gyv are twice the gradient, and x, y twice the offset); without the exposure terms it is the
+ * leading 4 x 4.  As in "Survey registration", B's content appears d displaced relative to A's, so the corrections u_f of
+ * the two frames satisfy u_b(X) - u_a(X) = -d(X) * cell.
+ * Asynchronous on `stream`, nothing allocated; sums_dev is zeroed on `stream` and accumulated into with 64-bit integer
+ * vector atomics (integers: the order is irrelevant); plain vector loads and stores.  sums_dev and pairs_dev 8-byte aligned.
+ * Bad arguments fail before any HIP call with a message that names the argument; n_pairs == 0 returns 0 before looking at
+ * anything. */
+#define WM_REGISTER_REFINE_SUMS 28
+int wm_register_refine(const uint8_t* a_dev, const uint8_t* b_dev, const wm_register_pair* pairs_dev, int n_pairs, int search,
+                       int side, int64_t* sums_dev /* [n_pairs][WM_REGISTER_REFINE_SUMS] */, void* stream);
 
 /* Survey resampling (tiling.detect_frames(scale=..., resize=...)): a frame brought to the scale the checkpoint was trained
  * at (the val transform's long side of 768, dataloader_coco.py:288) before it is tiled.

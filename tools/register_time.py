@@ -1,13 +1,16 @@
 """Times of the survey registration: the render (wm_register_render_u8) and both searches (wm_register_search, SAD, and
 wm_register_search_zncc, the correlation) on the same planes, against the host route a caller had before.
 
-  python tools/register_time.py [--reps 20] [--oracle-pairs 4] [--zncc-oracle-pairs 2] [--only NAME]
+  python tools/register_time.py [--reps 20] [--oracle-pairs 4] [--zncc-oracle-pairs 2] [--refine-oracle-pairs 2] [--only NAME]
       HIP-event min and median over --reps repetitions of one wm_register_render_u8 call with every frame of the chunk
       resident (one launch) and of one search call (one memset, the search launch, the pick launch) on ONE CHUNK of
       pairs, as tiling.register issues them (pair_chunk pairs at a time; buffers and frames are allocated once, outside
       the timed region).  The SAD search is timed in a run of its own (search_ms_*), and then, in the same process,
       --reps rounds of one SAD call and one correlation call, alternating, each between two HIP events (sad_ms_*,
-      zncc_ms_*, and the ratio zncc / sad of the minima and of the medians).
+      zncc_ms_*, and the ratio zncc / sad of the minima and of the medians).  The refinement's sums (wm_register_refine: one
+      memset and one launch, one pass over the same planes, of which it uses the centre offset alone) are timed the same
+      way, alternating with the SAD search (refine_ms_*, sad_beside_refine_ms_min and the ratio sad / refine of the minima);
+      for the first --refine-oracle-pairs pairs they must equal tests/test_register_refine.py's refine_sums_oracle.
       Two settings, nadir frames of 400 x 600 px (20 x 30 m at 0.05 m) of random content at UTM-sized coordinates on
       flight lines with 55 % forward overlap and 30 % sidelap, a little jitter in position and heading, cell = 0.05 m:
         f40      F = 40 (4 lines of 10), side 256, search 16, pair_chunk 64;
@@ -72,7 +75,7 @@ def by_offsets_per_thread(call, reps):
     return by_k
 
 
-def run(lines, per_line, side, search, pair_chunk, seed, reps, oracle_pairs, zncc_oracle_pairs):
+def run(lines, per_line, side, search, pair_chunk, seed, reps, oracle_pairs, zncc_oracle_pairs, refine_oracle_pairs=2):
     dev = torch.device("cuda:0")
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     georef, size = make(lines, per_line, seed)
@@ -132,6 +135,19 @@ def run(lines, per_line, side, search, pair_chunk, seed, reps, oracle_pairs, znc
                 "zncc_over_sad_min": round(z_min / a_min, 3), "zncc_over_sad_median": round(z_med / a_med, 3),
                 "zncc_cell_pairs_per_s": float(f"{rate:.4g}"), "valu_bound_cell_pairs_per_s": float(f"{bound:.4g}"),
                 "zncc_fraction_of_valu_bound": round(rate / bound, 4)})
+    sums = torch.empty((n, N.REGISTER_REFINE_SUMS), device=dev, dtype=torch.int64)
+    refine = lambda: N.check(lib.wm_register_refine(N.ptr(a), N.ptr(b), N.ptr(pairs_d), n, search, side, N.ptr(sums), st))
+    sad(), refine()
+    torch.cuda.synchronize()
+    ms = {"sad": [], "refine": []}
+    for _ in range(reps):                                     # alternating, in one process, on the same planes
+        ms["sad"].append(once(sad))
+        ms["refine"].append(once(refine))
+    f_min, f_med, b_min = float(np.min(ms["refine"])), float(np.median(ms["refine"])), float(np.min(ms["sad"]))
+    cells = diffs // (w1 * w1)
+    out.update({"refine_ms_min": round(f_min, 4), "refine_ms_median": round(f_med, 4), "sad_beside_refine_ms_min": round(b_min, 4),
+                "sad_over_refine_min": round(b_min / f_min, 1), "refine_cells": cells, "refine_cells_per_s": float(f"{cells / (f_min * 1e-3):.4g}"),
+                "refine_plane_bytes_per_s": float(f"{n * (side * side + E * E) / (f_min * 1e-3):.4g}")})
     out["search_ms_min_by_offsets_per_thread"] = by_offsets_per_thread(sad, reps)
     out["zncc_ms_min_by_offsets_per_thread"] = by_offsets_per_thread(zncc, reps)
     sad(), zncc()
@@ -167,6 +183,15 @@ def run(lines, per_line, side, search, pair_chunk, seed, reps, oracle_pairs, znc
         equal.append(ok)
         out["zncc_oracle_pairs"], out["zncc_oracle_host_s"], out["zncc_equals_oracle"] = m, round(time.perf_counter() - t, 2), bool(ok)
         out["sampled_peaks_r"] = [round(float(np.sign(q) * np.sqrt(abs(q))), 4) for q in got_p[:, 0]]
+    if refine_oracle_pairs > 0:
+        from test_register_refine import refine_sums_oracle
+        m = min(refine_oracle_pairs, n)
+        refine()
+        torch.cuda.synchronize()
+        A, B, got = a[:m].cpu().numpy(), b[:m].cpu().numpy(), sums[:m].cpu().numpy()
+        ok = all(got[p].tolist() == refine_sums_oracle(A[p], B[p], int(chunk["gx"][p]), int(chunk["gy"][p]), search) for p in range(m))
+        equal.append(ok)
+        out["refine_oracle_pairs"], out["refine_equals_oracle"] = m, bool(ok)
     if equal:
         out["equals_oracle"] = bool(all(equal))
         assert all(equal), "the device result differs from the oracle: sad %s, zncc %s" % (out.get("sad_equals_oracle"), out.get("zncc_equals_oracle"))
@@ -178,13 +203,14 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--oracle-pairs", type=int, default=4)
     ap.add_argument("--zncc-oracle-pairs", type=int, default=2)
+    ap.add_argument("--refine-oracle-pairs", type=int, default=2)
     ap.add_argument("--only", default=None)
     a = ap.parse_args()
     settings = {"f40": (4, 10, 256, 16, 64), "f1000": (25, 40, 512, 32, 256)}
     out = {"reps": a.reps}
     for i, (name, (lines, per_line, side, search, chunk)) in enumerate(settings.items()):
         if a.only in (None, name):
-            out[name] = run(lines, per_line, side, search, chunk, i, a.reps, a.oracle_pairs, a.zncc_oracle_pairs)
+            out[name] = run(lines, per_line, side, search, chunk, i, a.reps, a.oracle_pairs, a.zncc_oracle_pairs, a.refine_oracle_pairs)
     print(json.dumps(out))
 
 

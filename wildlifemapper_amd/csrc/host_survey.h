@@ -6,6 +6,7 @@
 #include "coverage_kernels.h"
 #include "mosaic_kernels.h"
 #include "register_kernels.h"
+#include "register_refine_kernels.h"
 #include "chip_kernels.h"
 #include "overlay_kernels.h"
 #include "host_core.h"
@@ -308,6 +309,26 @@ int launch_register_search_zncc(const uint8_t* a_dev, const uint8_t* b_dev, cons
                                 int side, int min_cells, int64_t* moments_dev, int32_t* best_dev, double* peak_dev, hipStream_t s) {
     return launch_register_search_as<true>("wm_register_search_zncc", a_dev, b_dev, pairs_dev, n_pairs, search, side, min_cells, moments_dev,
                                            best_dev, peak_dev, s);
+}
+
+// The refinement's sums: one memset and one launch.  B must carry a ring of one cell, so search 0 is refused here.
+int launch_register_refine(const uint8_t* a_dev, const uint8_t* b_dev, const wm_register_pair* pairs_dev, int n_pairs, int search, int side,
+                           int64_t* sums_dev, hipStream_t s) {
+    const char* name = "wm_register_refine";
+    if (n_pairs < 0 || n_pairs > WM_REGISTER_MAX_PAIRS) return fail("%s: n_pairs %d outside 0..%d", name, n_pairs, WM_REGISTER_MAX_PAIRS);
+    if (n_pairs == 0) return 0;
+    if (search < 1 || search > WM_REGISTER_MAX_SEARCH) return fail("%s: search %d outside 1..%d", name, search, WM_REGISTER_MAX_SEARCH);
+    WM_TRY(check_register_shape(name, pairs_dev, search, side));
+    if (!a_dev) return fail("%s: null a_dev", name);
+    if (!b_dev) return fail("%s: null b_dev", name);
+    if (!sums_dev) return fail("%s: null sums_dev", name);
+    if ((uintptr_t)sums_dev % 8) return fail("%s: sums_dev not 8-byte aligned", name);
+    HIP_TRY(hipMemsetAsync(sums_dev, 0, (size_t)n_pairs * REFINE_SUMS * sizeof(*sums_dev), s));
+    const int tiles_x = (side + REFINE_TILE_X - 1) / REFINE_TILE_X, tiles_y = (side + REFINE_TILE_Y - 1) / REFINE_TILE_Y;
+    hipLaunchKernelGGL(register_refine_kernel, dim3(tiles_x * tiles_y, n_pairs), dim3(REG_THREADS), 0, s, a_dev, b_dev, pairs_dev, search, side,
+                       tiles_x, (unsigned long long*)sums_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // ---- survey review chips: one PIL-exact crop per detection, windows and coefficients derived on the device ----

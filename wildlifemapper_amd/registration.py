@@ -5,7 +5,11 @@
     survives exposure changes), a chunk of pairs and a few resident frames at a time (rule: include/wm_hip.h "Survey
     registration");
   * adjust: one translation per frame from the accepted pairs' offsets, a weighted least-squares bundle adjustment in
-    numpy double."""
+    numpy double;
+  * refine: below one cell -- the sub-cell shift, yaw and scale of every frame (and the gain and offset between exposures)
+    from the integer normal equations of one Gauss-Newton step per pair (wm_register_refine; rule: include/wm_hip.h "Survey
+    registration, refinement"), iterated; its host parts are refine_solve (the 4 x 4 or 6 x 6 solve per pair),
+    adjust_similarity (one similarity per frame, two calls of adjust) and refine_step (both, and the corrected georef)."""
 from __future__ import annotations
 
 import math
@@ -207,8 +211,25 @@ _REGISTER_METRIC = {"sad": ("wm_register_search", torch.int32, 2, False, -1, _de
                     "zncc": ("wm_register_search_zncc", torch.int64, 6, True, 0, _decode_zncc)}
 
 
+def _render_chunk(lib, frames, chunk, s, g_d, s_d, cell, search, side, status, dev, what):
+    """The planes of one chunk of pairs, as register() and refine() render them: the chunk's frames go up a few at a time,
+    one wm_register_render_u8 call each, and are released after it.  Returns (pairs_d, plane_a, plane_b) on dev."""
+    n, F, E = chunk.shape[0], s.shape[0], side + 2 * search
+    pairs_d = _pinned_upload(chunk.view(np.uint8).reshape(n, REGISTER_PAIR.itemsize), dev)
+    plane_a = torch.empty((n, side, side), device=dev, dtype=torch.uint8)
+    plane_b = torch.empty((n, E, E), device=dev, dtype=torch.uint8)
+    needed = sorted(set(chunk["frame_a"].tolist()) | set(chunk["frame_b"].tolist()))
+    for f0 in range(0, len(needed), _REGISTER_FRAMES_RESIDENT):
+        ids = needed[f0:f0 + _REGISTER_FRAMES_RESIDENT]
+        desc, slot_d, resident = _resident_chunk(frames, ids, s, dev, what)
+        N.check(lib.wm_register_render_u8(N.ptr(desc), len(ids), N.ptr(slot_d), N.ptr(g_d), N.ptr(s_d), F, N.ptr(pairs_d), n,
+                                          cell, search, side, N.ptr(plane_a), N.ptr(plane_b), N.ptr(status), N.stream_ptr(dev)))
+        del resident, desc, slot_d                    # the stream orders their reuse after the launch
+    return pairs_d, plane_a, plane_b
+
+
 def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512, min_cells: int = 4096, min_ratio: float = 1.25,
-             pairs=None, fixed=None, pair_chunk: int = 256, metric: str = "sad", min_corr: float = 0.0) -> Dict[str, object]:
+             pairs=None, fixed=None, pair_chunk: int = 256, metric: str = "sad", min_corr: float = 0.0, refine: int = 0) -> Dict[str, object]:
     """Correct the georeferences of a survey by matching the pixels of its overlapping frames (wm_register_render_u8,
     wm_register_search or wm_register_search_zncc; rule: include/wm_hip.h "Survey registration" and "Survey registration,
     correlation search").  frames as mosaic() takes them: a sequence that is
@@ -230,9 +251,12 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
     search, r > min_corr (finite, in [-1, 1)), and the runner-up does not exist or 1 - r2 >= min_ratio * (1 - r): 1 - r
     takes the part of the mean absolute difference, so min_ratio keeps its meaning.  Both defaults are policy, not
     measurements on real imagery.  A cell coarser than the ground
-    sampling distance point-samples, so shrink the frames first (preprocess.resample_u8, resampled_georef); only a
-    translation is corrected, not yaw or scale; the resolution is one cell -- a second register() at a finer cell on the
-    corrected georef refines it.  Runs on the current device's current stream.  No CPU fallback.  Returns host arrays:
+    sampling distance point-samples, so shrink the frames first (preprocess.resample_u8, resampled_georef).  The search
+    itself corrects only a translation per frame, at a resolution of one cell; refine=k > 0 follows it with k iterations of
+    refine() on the corrected georef and the same pair table -- the sub-cell shift, the yaw and the scale of every frame,
+    with exposure=(metric == "zncc") -- and adds one key, 'refine', its result ('refine'['georef'] is the refined
+    georeference).  With refine=0 nothing changes, neither the keys nor the launches.
+    Runs on the current device's current stream.  No CPU fallback.  Returns host arrays:
       'georef' (F,2,3) float64 corrected (shift added to a2, a5), 'shift' (F,2) metres, 'pairs' the table,
       'offset' (P,2) int64 cells (dx, dy), 'cells' (P,) int64 n at the best offset (0: none), 'mean' (P,) float64 sad / n
       (NaN: none), 'runner_up' (P,) float64 sad2 / n2 (NaN: none), 'accepted' (P,) bool, 'residual' (P,2) metres after
@@ -248,6 +272,7 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
     pair_chunk = _check_whole(pair_chunk, what, "pair_chunk")
     if pair_chunk > REGISTER_MAX_PAIRS:
         raise ValueError(f"{what}: pair_chunk {pair_chunk} exceeds {REGISTER_MAX_PAIRS}")
+    refine = _check_whole(refine, what, "refine", 0)
     must = "must be a finite number >= 0"
     min_ratio = _finite_number(min_ratio, what, "min_ratio", lambda r: r >= 0.0, must, must, echo_float=True)
     n_given, sizes = _frame_sequence(frames, sizes, what, "the frames of the current chunk of pairs")
@@ -268,23 +293,13 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
     if P:
         dev = _survey_device(what)
         lib = N.lib()
-        E = side + 2 * search
         with torch.cuda.device(dev):
             g_d, s_d = _frame_tables(g, s, dev)
             status = torch.zeros(1, device=dev, dtype=torch.int32)
             for c0 in range(0, P, pair_chunk):
                 chunk = table[c0:c0 + pair_chunk]
                 n = chunk.shape[0]
-                pairs_d = _pinned_upload(chunk.view(np.uint8).reshape(n, REGISTER_PAIR.itemsize), dev)
-                plane_a = torch.empty((n, side, side), device=dev, dtype=torch.uint8)
-                plane_b = torch.empty((n, E, E), device=dev, dtype=torch.uint8)
-                needed = sorted(set(chunk["frame_a"].tolist()) | set(chunk["frame_b"].tolist()))
-                for f0 in range(0, len(needed), _REGISTER_FRAMES_RESIDENT):
-                    ids = needed[f0:f0 + _REGISTER_FRAMES_RESIDENT]
-                    desc, slot_d, resident = _resident_chunk(frames, ids, s, dev, what)
-                    N.check(lib.wm_register_render_u8(N.ptr(desc), len(ids), N.ptr(slot_d), N.ptr(g_d), N.ptr(s_d), F, N.ptr(pairs_d), n,
-                                                      cell, search, side, N.ptr(plane_a), N.ptr(plane_b), N.ptr(status), N.stream_ptr(dev)))
-                    del resident, desc, slot_d                    # the stream orders their reuse after the launch
+                pairs_d, plane_a, plane_b = _render_chunk(lib, frames, chunk, s, g_d, s_d, cell, search, side, status, dev, what)
                 best_d = torch.empty((n, 8), device=dev, dtype=torch.int32)
                 score = torch.empty((n, 2 * search + 1, 2 * search + 1, table_last), device=dev, dtype=table_dtype)
                 peak_d = torch.empty((n, 2), device=dev, dtype=torch.float64) if has_peak else None
@@ -306,5 +321,258 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
     out_g = g.copy()
     out_g[:, 0, 2] += adj["shift"][:, 0]
     out_g[:, 1, 2] += adj["shift"][:, 1]
-    return {"georef": out_g, "shift": adj["shift"], "pairs": table, "offset": offset, "cells": np.where(has, n1, 0), "mean": mean,
-            "runner_up": runner, "accepted": accepted, "residual": adj["residual"], "component": adj["component"], "corr": corr}
+    out = {"georef": out_g, "shift": adj["shift"], "pairs": table, "offset": offset, "cells": np.where(has, n1, 0), "mean": mean,
+           "runner_up": runner, "accepted": accepted, "residual": adj["residual"], "component": adj["component"], "corr": corr}
+    if refine:
+        out["refine"] = _refine(frames, out_g, cell, sizes=s, pairs=table, side=side, min_cells=min_cells, iters=refine,
+                                exposure=metric == "zncc", fixed=fixed, pair_chunk=pair_chunk)
+    return out
+
+
+REGISTER_REFINE_SUMS = N.REGISTER_REFINE_SUMS     # include/wm_hip.h WM_REGISTER_REFINE_SUMS
+_TRI = [(k, l) for k in range(6) for l in range(k, 6)]           # the order of the 21 products in a pair's sums
+
+
+def _check_refine_policy(min_cells, max_step, exposure, what: str):
+    min_cells = _check_whole(min_cells, what, "min_cells")
+    must = "must be a finite number > 0"
+    max_step = _finite_number(max_step, what, "max_step", lambda r: r > 0.0, must, must, refuse=bool, echo_float=True)
+    if not isinstance(exposure, (bool, np.bool_)):
+        raise ValueError(f"{what}: exposure {exposure!r} must be True or False")
+    return min_cells, max_step, bool(exposure)
+
+
+def _check_sums(sums, what: str) -> np.ndarray:
+    a = np.asarray(sums)
+    if a.size == 0:
+        a = a.reshape(0, REGISTER_REFINE_SUMS).astype(np.int64)
+    if a.dtype.kind not in "iu" or a.ndim != 2 or a.shape[1] != REGISTER_REFINE_SUMS:
+        raise ValueError(f"{what}: sums must be a (P, {REGISTER_REFINE_SUMS}) array of whole numbers, as wm_register_refine writes it")
+    return a.astype(np.int64)
+
+
+def refine_solve(sums, pairs, exposure: bool = False, min_cells: int = 4096, max_step: float = 2.0) -> Dict[str, np.ndarray]:
+    """The parameters of every pair from its sums (wm_register_refine; rule and signs: include/wm_hip.h "Survey
+    registration, refinement").  Host only, numpy double.  sums (P,28) int64; pairs the (P,) REGISTER_PAIR table (gx and gy
+    are read).  With N the symmetric matrix of the 21 products and R the six sums c_k * r, N q = R is solved per pair --
+    the leading 4 x 4, or all 6 x 6 with exposure=True, which also fits the gain and the offset between the two frames --
+    after the symmetric diagonal scaling N_kl / sqrt(N_kk N_ll), which brings the columns (grey-level differences next to
+    their products with cell offsets of hundreds) to one magnitude.  A pair is ACCEPTED iff its counted cells n >=
+    min_cells, the system solves (a diagonal entry that is not positive, numpy.linalg.LinAlgError or a result that is not
+    finite rejects; nothing is raised), and the displacement |d| of the solution at the four corners of the patch is at
+    most max_step cells.  max_step = 2.0 is policy -- the basin of one linearisation of planes sampled a cell apart -- not a
+    measurement.  Returns 'param' (P,6) float64 (tx, ty in cells, theta radians counter-clockwise, sigma, gamma, o; gamma
+    and o are 0 when exposure is false; NaN where nothing was solved), 'cells' (P,) int64 n, 'rms' (P,) float64 sqrt(sum r^2
+    / n) of the planes as they are (NaN: n = 0), 'accepted' (P,) bool."""
+    what = "refine_solve"
+    min_cells, max_step, exposure = _check_refine_policy(min_cells, max_step, exposure, what)
+    sm = _check_sums(sums, what)
+    P = sm.shape[0]
+    if not isinstance(pairs, np.ndarray) or pairs.dtype != REGISTER_PAIR or pairs.shape != (P,):
+        raise ValueError(f"{what}: pairs must be the ({P},) array of tiling.REGISTER_PAIR that the sums were computed for")
+    m = 6 if exposure else 4
+    param = np.full((P, 6), np.nan)
+    n = sm[:, 20].copy()
+    accepted = np.zeros(P, dtype=bool)
+    with np.errstate(all="ignore"):
+        rms = np.where(n > 0, np.sqrt(sm[:, 27] / np.maximum(n, 1)), np.nan)
+    for p in range(P):
+        if n[p] < 1:
+            continue
+        Nm = np.zeros((6, 6))
+        for v, (k, l) in zip(sm[p, :21].astype(np.float64), _TRI):
+            Nm[k, l] = Nm[l, k] = v
+        diag = np.diag(Nm)[:m]
+        if not (diag > 0).all():
+            continue
+        d = 1.0 / np.sqrt(diag)
+        try:
+            with np.errstate(all="ignore"):
+                q = d * np.linalg.solve(Nm[:m, :m] * d[:, None] * d[None, :], d * sm[p, 21:21 + m].astype(np.float64))
+        except np.linalg.LinAlgError:
+            continue
+        if not np.isfinite(q).all():
+            continue
+        q = np.concatenate([q, np.zeros(6 - m)])
+        param[p] = (2.0 * q[0], 2.0 * q[1], 4.0 * q[2], 4.0 * q[3], q[4], q[5])
+        tx, ty, th, sg = param[p, :4]
+        hx, hy = 0.5 * float(pairs["gx"][p]), 0.5 * float(pairs["gy"][p])
+        step = max(math.hypot(tx - th * y + sg * x, ty + th * x + sg * y) for x in (-hx, hx) for y in (-hy, hy))
+        accepted[p] = bool(n[p] >= min_cells and step <= max_step)
+    return {"param": param, "cells": n, "rms": rms, "accepted": accepted}
+
+
+def adjust_similarity(n_frames, pairs, patch_centres, frame_centres, measured, weights, fixed=None) -> Dict[str, np.ndarray]:
+    """One similarity per frame from pairwise measurements, u_f(X) = t_f + (theta_f J + sigma_f I)(X - c_f) with J = [[0, -1],
+    [1, 0]]: the correction of frame f at the ground position X.  Host only, numpy double, in two calls of adjust().
+    pairs as adjust() takes them; patch_centres (P,2) the c_p, frame_centres (n_frames,2) the c_f, metres; measured (P,4) =
+    (dx, dy, theta, sigma) of the field d(X) = (dx, dy) + (theta J + sigma I)(X - c_p) by which B's content appears
+    displaced relative to A's, dx and dy in metres; weights (P,) >= 0.  With u_b(X) - u_a(X) = -d(X):
+      first (theta, sigma) from theta_b - theta_a = -theta_m, sigma_b - sigma_a = -sigma_m;
+      then t from t_b - t_a = -(dx, dy) - (theta_b J + sigma_b I)(c_p - c_b) + (theta_a J + sigma_a I)(c_p - c_a).
+    The gauge is adjust()'s, in both calls: in a component without a fixed frame the mean yaw, the mean scale and the mean
+    shift of its frames are zero; fixed frames do not move; a frame with no pair of positive weight keeps the identity.
+    Returns 'shift' (n_frames,2) the t_f, 'yaw' (n_frames,) the theta_f, 'scale' (n_frames,) the sigma_f, 'residual' (P,4)
+    (the translation's two, then yaw's and scale's) and 'component' as adjust() gives it."""
+    what = "adjust_similarity"
+    F = _check_whole(n_frames, what, "n_frames", 0)
+    try:
+        m = np.asarray(measured, dtype=np.float64).reshape(-1, 4) if np.size(measured) else np.zeros((0, 4))
+        cp = np.asarray(patch_centres, dtype=np.float64).reshape(-1, 2) if np.size(patch_centres) else np.zeros((0, 2))
+        cf = np.asarray(frame_centres, dtype=np.float64).reshape(-1, 2) if np.size(frame_centres) else np.zeros((0, 2))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: measured must be (P,4), patch_centres (P,2) and frame_centres (n_frames,2) numbers") from None
+    P = m.shape[0]
+    if cp.shape != (P, 2) or cf.shape != (F, 2):
+        raise ValueError(f"{what}: measured of shape {m.shape}, patch_centres of shape {cp.shape}, frame_centres of shape {cf.shape}: "
+                         f"expected ({P}, 4), ({P}, 2) and ({F}, 2)")
+    first = adjust(F, pairs, -m[:, 2:4], weights, fixed)                       # validates pairs, weights and fixed
+    yaw, scale = first["shift"][:, 0], first["shift"][:, 1]
+    if isinstance(pairs, np.ndarray) and pairs.dtype == REGISTER_PAIR:
+        ab = np.stack([pairs["frame_a"], pairs["frame_b"]], axis=1).astype(np.int64).reshape(-1, 2)
+    else:
+        ab = np.asarray(pairs).astype(np.int64).reshape(-1, 2)
+    a, b = ab[:, 0], ab[:, 1]
+
+    def linear(f, v):                                                          # (theta_f J + sigma_f I) v
+        return np.stack([scale[f] * v[:, 0] - yaw[f] * v[:, 1], yaw[f] * v[:, 0] + scale[f] * v[:, 1]], axis=1)
+
+    with np.errstate(all="ignore"):
+        want_t = -m[:, :2] - linear(b, cp - cf[b]) + linear(a, cp - cf[a])
+    used = np.asarray(weights, dtype=np.float64).reshape(-1) > 0
+    if not np.isfinite(want_t[used]).all():
+        raise ValueError(f"{what}: measured, patch_centres and frame_centres must be finite where the weight is positive")
+    second = adjust(F, ab, want_t, weights, fixed)
+    return {"shift": second["shift"], "yaw": yaw.copy(), "scale": scale.copy(),
+            "residual": np.concatenate([second["residual"], first["residual"]], axis=1).reshape(P, 4), "component": second["component"]}
+
+
+def _frame_centres(g: np.ndarray, s: np.ndarray) -> np.ndarray:
+    """The ground position of every frame's centre pixel (width / 2, height / 2) under g, (F,2)."""
+    u, v = 0.5 * s[:, 1].astype(np.float64), 0.5 * s[:, 0].astype(np.float64)
+    with np.errstate(all="ignore"):
+        return np.stack([g[:, 0, 0] * u + g[:, 0, 1] * v + g[:, 0, 2], g[:, 1, 0] * u + g[:, 1, 1] * v + g[:, 1, 2]], axis=1)
+
+
+def refine_step(georef, sizes, pairs, sums, cell, exposure: bool = False, min_cells: int = 4096, max_step: float = 2.0,
+                fixed=None) -> Dict[str, object]:
+    """One iteration of refine() on the host, numpy double: refine_solve(sums), then adjust_similarity with the weight n for
+    an accepted pair and 0 otherwise, c_f the ground position of frame f's centre pixel under georef and c_p the centre of
+    the pair's patch, then the corrected georeference.  With M_f = (1 + sigma_f) * Rot(theta_f), counter-clockwise, the 2 x 2
+    part of frame f becomes M_f @ g[:, :2] and its offset M_f @ g[:, 2] + t_f + c_f - M_f @ c_f: the ground moves by u_f about
+    the frame's centre.  A frame whose centre is not finite stays as it is.  Returns 'georef' (F,2,3), 'shift' (F,2) metres,
+    'yaw' (F,) radians, 'scale' (F,), refine_solve's 'param', 'cells', 'rms', 'accepted', adjust_similarity's 'residual' and
+    'component', 'weighted_rms' (the accepted pairs' sqrt(sum of sum r^2 / sum of n), NaN without one) and 'max_corner'
+    (metres: the largest displacement this step applies to a corner of a frame)."""
+    what = "refine_step"
+    cell = _check_cell(cell, what)
+    g = _check_georef(georef, what)
+    s = _check_sizes(sizes, g.shape[0], what)
+    F = g.shape[0]
+    sm = _check_sums(sums, what)
+    table = _check_pair_table(pairs, F, REGISTER_MAX_SIDE, what)
+    sol = refine_solve(sm, table, exposure, min_cells, max_step)
+    acc, par = sol["accepted"], sol["param"]
+    w = np.where(acc, sol["cells"], 0).astype(np.float64)
+    cf = _frame_centres(g, s)
+    cp = np.stack([table["x0"] + 0.5 * table["gx"] * cell, table["y0"] + 0.5 * table["gy"] * cell], axis=1).reshape(-1, 2)
+    measured = np.where(acc[:, None], np.concatenate([par[:, :2] * cell, par[:, 2:4]], axis=1), 0.0).reshape(-1, 4)
+    adj = adjust_similarity(F, table, cp, np.where(np.isfinite(cf), cf, 0.0), measured, w, fixed)
+    out_g = g.copy()
+    _, X0, Y0 = _footprint_extent(g, s)
+    for f in np.nonzero(np.isfinite(cf).all(axis=1))[0]:
+        th, k = adj["yaw"][f], 1.0 + adj["scale"][f]
+        M = k * np.array([[math.cos(th), -math.sin(th)], [math.sin(th), math.cos(th)]])
+        out_g[f, :, :2] = M @ g[f, :, :2]
+        out_g[f, :, 2] = g[f, :, 2] + adj["shift"][f] + (M - np.eye(2)) @ (g[f, :, 2] - cf[f])    # = M g2 + t + c - M c; exact for the identity
+    _, X1, Y1 = _footprint_extent(out_g, s)
+    with np.errstate(all="ignore"):
+        moved = np.hypot(X1 - X0, Y1 - Y0)
+        moved = moved[np.isfinite(moved)]
+        n_acc = float(sol["cells"][acc].sum())
+        wrms = math.sqrt(float(sm[acc, 27].sum()) / n_acc) if n_acc > 0 else float("nan")
+    return {"georef": out_g, "shift": adj["shift"], "yaw": adj["yaw"], "scale": adj["scale"], "param": par, "cells": sol["cells"],
+            "rms": sol["rms"], "accepted": acc, "residual": adj["residual"], "component": adj["component"], "weighted_rms": wrms,
+            "max_corner": float(moved.max()) if moved.size else 0.0}
+
+
+def refine(frames, georef, cell, sizes=None, pairs=None, side: int = 512, min_cells: int = 4096, iters: int = 3, exposure: bool = False,
+           fixed=None, max_step: float = 2.0, pair_chunk: int = 256) -> Dict[str, object]:
+    """Refine the georeferences of a survey below one cell: the sub-cell shift, the yaw and the scale of every frame, from the
+    planes register() searches (wm_register_render_u8 at search 1, wm_register_refine; rule: include/wm_hip.h "Survey
+    registration, refinement").  Arguments as for register(); georef is usually register()'s 'georef' -- the step is one
+    linearisation and converges from within about max_step cells at the patch corners; farther off, run register() first, or
+    refine at a coarser cell.  pairs: the table to use, None for register_pairs(georef, sizes, cell, 1, side, min_cells);
+    it is made once, from the input georef.  Everything is validated before any device work.  Per iteration, for every
+    chunk of pair_chunk pairs: the planes are rendered at the current georef (frames go up as in register(): a frame is read
+    only while a pair of the current chunk needs it), one wm_register_refine call gives the chunk's (n,28) sums, and they
+    go to the host; then refine_step() solves every pair (refine_solve), solves one similarity per frame
+    (adjust_similarity, fixed=fixed) and corrects the georef.  exposure=True also fits a gain and an offset per pair, for
+    frames whose exposure differs.  A survey whose planes coincide cell for cell -- cell = gsd = the scene's pixel and frames
+    aligned with the axes, so nearest sampling snaps every plane onto one lattice -- shows the step nothing: the planes are
+    identical while the georef is still up to half a cell off.  Runs on the current device's current stream.  No CPU
+    fallback.  Returns host values: 'georef' (F,2,3) refined; 'yaw' (F,) radians counter-clockwise, 'scale' (F,) and 'shift'
+    (F,2) metres, the whole correction of each frame -- with M = out 2 x 2 @ inverse(in 2 x 2): atan2(M10, M00), sqrt(det M)
+    - 1, and the displacement of the frame centre's ground position; 'pairs' the table; the last iteration's 'param',
+    'cells', 'rms' and 'accepted' as refine_solve returns them; 'history', per iteration a dict of 'rms' (refine_step's
+    'weighted_rms' before the step) and 'max_corner' (metres, the largest corner displacement the step applied)."""
+    what = "refine"
+    side = _check_register_shape(1, side, 1, what)[1]
+    min_cells, max_step, exposure = _check_refine_policy(min_cells, max_step, exposure, what)
+    if min_cells >= 2 ** 31:
+        raise ValueError(f"{what}: min_cells {min_cells} does not fit int32")
+    iters = _check_whole(iters, what, "iters")
+    pair_chunk = _check_whole(pair_chunk, what, "pair_chunk")
+    if pair_chunk > REGISTER_MAX_PAIRS:
+        raise ValueError(f"{what}: pair_chunk {pair_chunk} exceeds {REGISTER_MAX_PAIRS}")
+    n_given, sizes = _frame_sequence(frames, sizes, what, "the frames of the current chunk of pairs")
+    cell = _check_cell(cell, what)
+    g = _check_georef(georef, what)
+    s = _check_sizes(sizes, g.shape[0], what)
+    F = g.shape[0]
+    if F > COVERAGE_MAX_FRAMES:
+        raise ValueError(f"{what}: {F} frames exceed {COVERAGE_MAX_FRAMES}")
+    if n_given != F:
+        raise ValueError(f"{what}: {n_given} frames for {F} georeferences")
+    table = register_pairs(g, s, cell, 1, side, min_cells) if pairs is None else _check_pair_table(pairs, F, side, what)
+    adjust(F, np.zeros((0, 2), dtype=np.int64), np.zeros((0, 2)), np.zeros(0), fixed)         # fixed= validated before device work
+    P = table.shape[0]
+    cur = g.copy()
+    step = refine_step(cur, s, table, np.zeros((0, REGISTER_REFINE_SUMS), dtype=np.int64), cell, exposure, min_cells, max_step, fixed) if not P else None
+    history = []
+    if P:
+        dev = _survey_device(what)
+        lib = N.lib()
+        with torch.cuda.device(dev):
+            status = torch.zeros(1, device=dev, dtype=torch.int32)
+            for _ in range(iters):
+                g_d, s_d = _frame_tables(cur, s, dev)
+                sums = np.zeros((P, REGISTER_REFINE_SUMS), dtype=np.int64)
+                for c0 in range(0, P, pair_chunk):
+                    chunk = table[c0:c0 + pair_chunk]
+                    n = chunk.shape[0]
+                    pairs_d, plane_a, plane_b = _render_chunk(lib, frames, chunk, s, g_d, s_d, cell, 1, side, status, dev, what)
+                    sums_d = torch.empty((n, REGISTER_REFINE_SUMS), device=dev, dtype=torch.int64)
+                    N.check(lib.wm_register_refine(N.ptr(plane_a), N.ptr(plane_b), N.ptr(pairs_d), n, 1, side, N.ptr(sums_d), N.stream_ptr(dev)))
+                    sums[c0:c0 + n] = sums_d.cpu().numpy()
+                    del plane_a, plane_b, sums_d, pairs_d
+                bad = int(status.item())
+                if bad:
+                    raise RuntimeError(f"{what}: wm_register_render_u8 skipped planes (status {bad}): a resident frame did not match its slot or size")
+                step = refine_step(cur, s, table, sums, cell, exposure, min_cells, max_step, fixed)
+                history.append({"rms": step["weighted_rms"], "max_corner": step["max_corner"]})
+                cur = step["georef"]
+    with np.errstate(all="ignore"):
+        yaw, scale = np.zeros(F), np.zeros(F)
+        for f in range(F):
+            if (cur[f] == g[f]).all():
+                continue                                  # a frame that did not move: exactly 0
+            if np.isfinite(g[f]).all() and np.isfinite(cur[f]).all() and abs(np.linalg.det(g[f, :, :2])) > 0:
+                M = cur[f, :, :2] @ np.linalg.inv(g[f, :, :2])
+                yaw[f], scale[f] = math.atan2(M[1, 0], M[0, 0]), math.sqrt(abs(np.linalg.det(M))) - 1.0
+        shift = np.where(np.isfinite(_frame_centres(g, s)), _frame_centres(cur, s) - _frame_centres(g, s), 0.0)
+    return {"georef": cur, "yaw": yaw, "scale": scale, "shift": shift, "pairs": table, "param": step["param"], "cells": step["cells"],
+            "rms": step["rms"], "accepted": step["accepted"], "history": history}
+
+
+_refine = refine                                  # register() has a parameter of this name
