@@ -45,6 +45,8 @@ extern "C" {
  *    between the two frames of a pair do not change); the number stays 13 for the same reason.
  *    13, additive: wm_register_refine, WM_REGISTER_REFINE_SUMS (survey registration, refinement: the integer normal
  *    equations of a sub-cell shift, yaw, scale, gain and offset per pair); the number stays 13 for the same reason.
+ *    13, also additive: wm_mosaic_blend_plan, wm_mosaic_blend_accum_u8, wm_mosaic_blend_finish_u8 (survey mosaic, blended:
+ *    every cell an integer-weighted mean of the exposure-corrected frames that see it); the number stays 13 for the same reason.
  * 12: wm_box_outline_rect, wm_draw_boxes_u8, wm_plot_image_u8, WM_DRAW_MAX_WIDTH, WM_DRAW_MAX_PALETTE, WM_PLOT_SCRATCH_BYTES
  *    (survey overlays: detections outlined on frames and tiles, on the GPU); nothing else changed.
  * 11: wm_chip_window, wm_crop_chips_u8, WM_CHIP_MAX_SIDE (survey review chips: one PIL-exact crop per detection, cut on
@@ -435,6 +437,66 @@ int wm_mosaic_fill_u8(const wm_frame_desc* frames_dev, int n_resident, const int
                       const double* g2p_dev, const int32_t* size_dev, int n_frames, double x0, double y0, double cell, int gx,
                       int gy, const int32_t* source_dev /* [gy][gx] */, int mode, int flags,
                       uint8_t* mosaic_dev /* [gy][gx][3] */, int32_t* status_dev /* [1] */, void* stream);
+
+/* Survey mosaic, blended (tiling.mosaic(blend=), tiling.mosaic_blend_plan): the hard mosaic above gives every cell to one
+ * frame, so residual misregistration tears and an exposure difference steps at the Voronoi lines.  Here every cell is an
+ * integer-weighted mean of the exposure-corrected pixels of ALL the frames that see it, each frame's weight falling to
+ * zero at its own border and away from the seam, over a band the caller chooses.  No reference behaviour exists; this rule
+ * is the contract, and tests/test_mosaic_blend.py restates it sequentially (blend_oracle).  The grid, the cell centres,
+ * g2p, size, sees and the (u, v) expression are those of "Survey coverage", word for word; all double arithmetic is IEEE,
+ * one rounding per operation, no contraction, in the order written; there is no sqrt, and one division, k, on the host.
+ * For a cell with centre (Xc, Yc) and every frame f with sees(f, Xc, Yc):
+ *     m_f    = min(min(u, (double)width - u), min(v, (double)height - v))      distance to the frame's nearest border, px
+ *     m*     = the largest m_f over the frames that see the cell
+ *     k      = 256.0 / band          band: double, finite, > 0, in source pixels; k computed once on the host, and finite
+ *     edge_f = min(m_f * k, 256.0)
+ *     seam_f = 256.0                                           if m_f >= m*
+ *              min(max(((m_f - m*) + band) * k, 0.0), 255.0)   otherwise
+ *     q_f    = (int)floor(min(seam_f, edge_f));   a frame with m_f >= m* gets max(q_f, 1)
+ * Every frame fades to nothing at its own border; a frame contributes only where its border distance is within band
+ * pixels of the best one's; the best frame, or frames at a tie, always contributes, so the weight sum is at least 1 wherever
+ * a frame sees the cell.  Far inside one frame's territory (m* - m_f >= band for all others) the cell is that frame's pixel
+ * alone.  Frames of different ground sampling distance compare in their OWN pixels: of two frames that reach equally far
+ * over the ground, the finer one has the larger m and is favoured.
+ * Pixel: p_c of frame f is the uint8 sample wm_mosaic_fill_u8 would fetch, WM_MOSAIC_NEAREST or WM_MOSAIC_BILINEAR as above.
+ * Exposure: exposure_dev[n_frames][2] int32 (A, B), Q12 fixed point, NULL for none:
+ *     p'_c = min(max(floor(((int64)A * p_c + B + 2048) / 4096), 0), 255)
+ * in int64, so that no int32 table overflows; the same (A, B) for the three channels (the luma weights 77 + 150 + 29 = 256
+ * make a gain and an offset on luma a gain and an offset per channel).  (4096, 0) is the identity, p' = p exactly: a NULL
+ * table and an all-identity table give the same bytes.
+ * Accumulators: acc[j][i] = (sum q_f * p'_r, sum q_f * p'_g, sum q_f * p'_b, sum q_f), four uint32.  With q <= 256, p' <= 255
+ * and at most 65535 frames a channel sum is at most 4 278 124 800 < 2^32; integer sums do not depend on the order.
+ * Picture: a cell with wsum > 0 gets (acc_c + (wsum >> 1)) / wsum per channel -- in uint32 at most 4 286 513 280, which still
+ * fits; a cell with wsum == 0 is left as it was (the caller's fill colour).
+ * wm_mosaic_blend_plan, geometry only, in the shape of wm_mosaic_plan: best_dev[gy][gx] double, m*, or -1.0 where no frame
+ * sees the cell; cells_dev[n_frames] int32, the cells where frame f has q_f > 0 (exactly the frames a caller has to load);
+ * stats_dev[3] int64: [0] cells seen, [1] cells not seen, [2] cells with two or more frames of q > 0.  Every element is
+ * written; cells and stats are zeroed on `stream` first.  n_frames == 0 (g2p_dev, size_dev, cells_dev may be NULL) gives
+ * all -1.0.
+ * wm_mosaic_blend_accum_u8: frames_dev[n_resident] describes the frames on the device in this call and index_dev[n_resident]
+ * int32 the survey index of each; only these are walked, never all n_frames.  The caller zeroes acc_dev[gy][gx][4] before
+ * its first call; the entry never clears it.  A frame adds into the cells where its q_f > 0; m_f is recomputed with the
+ * plan's expression, so m_f >= best compares the plan's bits.  A cell's accumulators are read and written only when a
+ * resident frame contributes to it.  The frames of a survey may be split over any number of calls in any order, each
+ * frame once (a frame given twice counts twice: the caller's contract).  A frame is SKIPPED, and a bit ORed into
+ * status_dev[0] (int32, zeroed by the caller, never cleared here), when its index is outside [0, n_frames) or its data is
+ * NULL (WM_MOSAIC_BAD_SLOT), or its descriptor's (height, width) differ from size_dev[f] (WM_MOSAIC_BAD_SIZE).
+ * n_resident == 0 returns 0 after the checks.
+ * wm_mosaic_blend_finish_u8 performs the division into mosaic_dev[gy][gx][3]; flags may hold WM_MOSAIC_NORTH_UP, which flips
+ * the picture only: acc and best keep row 0 south.
+ * All three: asynchronous on `stream`, nothing allocated; no atomics touch best, acc or the picture.  Argument limits are
+ * the coverage's, plus band finite and > 0 (and 256 / band finite); doubles, int64 and descriptors 8-byte, int32 and uint32
+ * 4-byte aligned.  Bad arguments fail before any HIP call with a message that names the argument. */
+int wm_mosaic_blend_plan(const double* g2p_dev /* [n_frames][6] */, const int32_t* size_dev /* [n_frames][2] */, int n_frames,
+                         double x0, double y0, double cell, int gx, int gy, double band, double* best_dev /* [gy][gx] */,
+                         int32_t* cells_dev /* [n_frames] */, int64_t* stats_dev /* [3] */, void* stream);
+int wm_mosaic_blend_accum_u8(const wm_frame_desc* frames_dev, const int32_t* index_dev /* [n_resident] */, int n_resident,
+                             const double* g2p_dev, const int32_t* size_dev, int n_frames,
+                             const int32_t* exposure_dev /* [n_frames][2], may be NULL */, double x0, double y0, double cell, int gx,
+                             int gy, double band, const double* best_dev /* [gy][gx] */, int mode,
+                             uint32_t* acc_dev /* [gy][gx][4] */, int32_t* status_dev /* [1] */, void* stream);
+int wm_mosaic_blend_finish_u8(const uint32_t* acc_dev /* [gy][gx][4] */, int gx, int gy, int flags,
+                              uint8_t* mosaic_dev /* [gy][gx][3] */, void* stream);
 
 /* Survey registration (tiling.register): census, coverage and mosaic take each frame's georeference on trust, and one built
  * from GPS and heading is wrong by metres from frame to frame.  Frames overlap, so every pair of neighbours shows the same

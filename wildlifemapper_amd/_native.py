@@ -76,6 +76,9 @@ SYMBOLS = {
     "wm_coverage_points": (_I, [_P, _P, _I, _P, _P, _I, C.c_double, C.c_double, C.c_double, _I, _I, _P, _P, _P, _P, _P]),
     "wm_mosaic_plan": (_I, [_P, _P, _I, C.c_double, C.c_double, C.c_double, _I, _I, _P, _P, _P, _P]),
     "wm_mosaic_fill_u8": (_I, [_P, _I, _P, _P, _P, _I, C.c_double, C.c_double, C.c_double, _I, _I, _P, _I, _I, _P, _P, _P]),
+    "wm_mosaic_blend_plan": (_I, [_P, _P, _I, C.c_double, C.c_double, C.c_double, _I, _I, C.c_double, _P, _P, _P, _P]),
+    "wm_mosaic_blend_accum_u8": (_I, [_P, _P, _I, _P, _P, _I, _P, C.c_double, C.c_double, C.c_double, _I, _I, C.c_double, _P, _I, _P, _P, _P]),
+    "wm_mosaic_blend_finish_u8": (_I, [_P, _I, _I, _I, _P, _P]),
     "wm_register_render_u8": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, C.c_double, _I, _I, _P, _P, _P, _P]),
     "wm_register_search": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "wm_register_search_zncc": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),

@@ -5,6 +5,7 @@
 #include "census_kernels.h"
 #include "coverage_kernels.h"
 #include "mosaic_kernels.h"
+#include "mosaic_blend_kernels.h"
 #include "register_kernels.h"
 #include "register_refine_kernels.h"
 #include "chip_kernels.h"
@@ -188,6 +189,77 @@ int launch_mosaic_fill(const wm_frame_desc* frames_dev, int n_resident, const in
                            (const int*)size_dev, n_frames, x0, y0, cell, gx, gy, (const int*)source_dev, north_up, mosaic_dev, (int*)status_dev);
     };
     mode == WM_MOSAIC_NEAREST ? launch(mosaic_fill_kernel<WM_MOSAIC_NEAREST>) : launch(mosaic_fill_kernel<WM_MOSAIC_BILINEAR>);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Survey mosaic, blended: the mosaic's checks plus band, every argument checked on the host before the first HIP call.
+// k = 256 / band, the rule's one division, is computed here; a band so small that k overflows is refused with the band.
+static int check_blend_band(const char* name, double band, double& k) {
+    k = 256.0 / band;
+    if (!(std::isfinite(band) && band > 0.0 && std::isfinite(k))) return fail("%s: band %g: need a finite band > 0 with a finite 256 / band", name, band);
+    return 0;
+}
+
+int launch_mosaic_blend_plan(const double* g2p_dev, const int32_t* size_dev, int n_frames, double x0, double y0, double cell, int gx, int gy,
+                             double band, double* best_dev, int32_t* cells_dev, int64_t* stats_dev, hipStream_t s) {
+    const char* name = "wm_mosaic_blend_plan";
+    double k;
+    WM_TRY(check_coverage_frames(name, g2p_dev, size_dev, n_frames));
+    WM_TRY(check_coverage_grid(name, x0, y0, cell, gx, gy));
+    WM_TRY(check_blend_band(name, band, k));
+    if (!best_dev) return fail("%s: null best_dev", name);
+    if (!stats_dev) return fail("%s: null stats_dev", name);
+    if (n_frames > 0 && !cells_dev) return fail("%s: null cells_dev with n_frames %d", name, n_frames);
+    if ((uintptr_t)best_dev % 8 || (uintptr_t)stats_dev % 8 || (uintptr_t)cells_dev % 4)
+        return fail("%s: best_dev / stats_dev not 8-byte aligned, or cells_dev not 4-byte aligned", name);
+    HIP_TRY(hipMemsetAsync(stats_dev, 0, 3 * sizeof(int64_t), s));
+    if (n_frames > 0) HIP_TRY(hipMemsetAsync(cells_dev, 0, (size_t)n_frames * sizeof(int32_t), s));
+    hipLaunchKernelGGL(mosaic_blend_plan_kernel, coverage_block_grid(gx, gy), dim3(COV_THREADS), 0, s, g2p_dev, (const int*)size_dev, n_frames,
+                       x0, y0, cell, gx, gy, band, k, best_dev, (int*)cells_dev, (unsigned long long*)stats_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_mosaic_blend_accum(const wm_frame_desc* frames_dev, const int32_t* index_dev, int n_resident, const double* g2p_dev,
+                              const int32_t* size_dev, int n_frames, const int32_t* exposure_dev, double x0, double y0, double cell, int gx,
+                              int gy, double band, const double* best_dev, int mode, uint32_t* acc_dev, int32_t* status_dev, hipStream_t s) {
+    const char* name = "wm_mosaic_blend_accum_u8";
+    double k;
+    WM_TRY(check_coverage_frames(name, g2p_dev, size_dev, n_frames));
+    WM_TRY(check_n_resident(name, n_resident));
+    WM_TRY(check_coverage_grid(name, x0, y0, cell, gx, gy));
+    WM_TRY(check_blend_band(name, band, k));
+    if (mode != WM_MOSAIC_NEAREST && mode != WM_MOSAIC_BILINEAR) return fail("%s: mode %d is neither WM_MOSAIC_NEAREST nor WM_MOSAIC_BILINEAR", name, mode);
+    if (!best_dev) return fail("%s: null best_dev", name);
+    if (!acc_dev) return fail("%s: null acc_dev", name);
+    if (!status_dev) return fail("%s: null status_dev", name);
+    if (n_resident > 0 && !frames_dev) return fail("%s: null frames_dev with n_resident %d", name, n_resident);
+    if (n_resident > 0 && !index_dev) return fail("%s: null index_dev with n_resident %d", name, n_resident);
+    if ((uintptr_t)frames_dev % 8 || (uintptr_t)best_dev % 8 || (uintptr_t)index_dev % 4 || (uintptr_t)exposure_dev % 4 ||
+        (uintptr_t)acc_dev % 4 || (uintptr_t)status_dev % 4)
+        return fail("%s: frames_dev / best_dev not 8-byte aligned, or index_dev / exposure_dev / acc_dev / status_dev not 4-byte aligned", name);
+    if (n_resident == 0) return 0;                                    // no frame to walk: nothing is read or written
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, coverage_block_grid(gx, gy), dim3(COV_THREADS), 0, s, (const frame_desc*)frames_dev, (const int*)index_dev,
+                           n_resident, g2p_dev, (const int*)size_dev, n_frames, (const int*)exposure_dev, x0, y0, cell, gx, gy, band, k, best_dev,
+                           (unsigned int*)acc_dev, (int*)status_dev);
+    };
+    mode == WM_MOSAIC_NEAREST ? launch(mosaic_blend_accum_kernel<WM_MOSAIC_NEAREST>) : launch(mosaic_blend_accum_kernel<WM_MOSAIC_BILINEAR>);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_mosaic_blend_finish(const uint32_t* acc_dev, int gx, int gy, int flags, uint8_t* mosaic_dev, hipStream_t s) {
+    const char* name = "wm_mosaic_blend_finish_u8";
+    WM_TRY(check_coverage_grid(name, 0.0, 0.0, 1.0, gx, gy));
+    if (flags & ~WM_MOSAIC_NORTH_UP) return fail("%s: flags 0x%x", name, (unsigned)flags);
+    if (!acc_dev) return fail("%s: null acc_dev", name);
+    if (!mosaic_dev) return fail("%s: null mosaic_dev", name);
+    if ((uintptr_t)acc_dev % 4) return fail("%s: acc_dev not 4-byte aligned", name);
+    const dim3 grid((gx + COV_BLOCK_X - 1) / COV_BLOCK_X, (gy + MOS_FILL_BLOCK_Y - 1) / MOS_FILL_BLOCK_Y);
+    hipLaunchKernelGGL(mosaic_blend_finish_kernel, grid, dim3(COV_THREADS), 0, s, (const unsigned int*)acc_dev, gx, gy, flags & WM_MOSAIC_NORTH_UP,
+                       mosaic_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -25,6 +25,8 @@
 // n_resident, a non-null data pointer, the descriptor's (height, width) equal to size[f], and 0 <= u < width, 0 <= v <
 // height re-checked here (a source raster that did not come from the plan of these frames cannot index outside a frame);
 // a cell that fails one of them is skipped and a status bit is set.
+// The sampling (mos_sample) and the store of a wave's row (mos_store_row) are functions of their own: the blended mosaic
+// (mosaic_blend_kernels.h) samples and stores through them too.
 #pragma once
 
 #include "coverage_kernels.h"
@@ -135,6 +137,31 @@ __device__ __forceinline__ unsigned char mos_lerp(double p00, double p10, double
     return (unsigned char)fmin(floor(val + 0.5), 255.0);
 }
 
+// The header's sampling rule: the three bytes of frame fd (h x w, checked by the caller) at the pixel position (u, v), 0 <= u
+// < w, 0 <= v < h.  The fill and the blend's accumulate (mosaic_blend_kernels.h) both sample through it.
+template <int MODE>
+__device__ __forceinline__ void mos_sample(const frame_desc& fd, int h, int w, double u, double v, unsigned char (&px)[3]) {
+#pragma clang fp contract(off)
+    if (MODE == WM_MOSAIC_NEAREST) {
+        const unsigned char* p = cov_nearest_pixel(fd, w, u, v);
+        px[0] = p[0];
+        px[1] = p[1];
+        px[2] = p[2];
+    } else {
+        const double fu = u - 0.5, fv = v - 0.5;
+        const double xf = floor(fu), yf = floor(fv);
+        const double tx = fu - xf, ty = fv - yf;
+        const int xa = min(max((int)xf, 0), w - 1), xb = min(max((int)xf + 1, 0), w - 1);
+        const int ya = min(max((int)yf, 0), h - 1), yb = min(max((int)yf + 1, 0), h - 1);
+        const unsigned char* p00 = fd.data + ((size_t)ya * w + xa) * 3;
+        const unsigned char* p10 = fd.data + ((size_t)ya * w + xb) * 3;
+        const unsigned char* p01 = fd.data + ((size_t)yb * w + xa) * 3;
+        const unsigned char* p11 = fd.data + ((size_t)yb * w + xb) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) px[c] = mos_lerp((double)p00[c], (double)p10[c], (double)p01[c], (double)p11[c], tx, ty);
+    }
+}
+
 // One cell of the fill: false when it is not written (no source, a source that is not resident, or a failed check, which
 // sets a bit of `bad`); else its three bytes in px.
 template <int MODE>
@@ -155,31 +182,35 @@ __device__ __forceinline__ bool mos_cell(const frame_desc* __restrict__ frames, 
     double u, v;
     cov_uv(b[0] * Xc, b[3] * Xc, b[1], b[2], b[4], b[5], Y, u, v);
     if (!cov_inside(u, v, (double)w, (double)h)) { bad |= WM_MOSAIC_BAD_SOURCE; return false; }   // not the plan's source
-    if (MODE == WM_MOSAIC_NEAREST) {
-        const unsigned char* p = cov_nearest_pixel(fd, w, u, v);
-        px[0] = p[0];
-        px[1] = p[1];
-        px[2] = p[2];
-    } else {
-        const double fu = u - 0.5, fv = v - 0.5;
-        const double xf = floor(fu), yf = floor(fv);
-        const double tx = fu - xf, ty = fv - yf;
-        const int xa = min(max((int)xf, 0), w - 1), xb = min(max((int)xf + 1, 0), w - 1);
-        const int ya = min(max((int)yf, 0), h - 1), yb = min(max((int)yf + 1, 0), h - 1);
-        const unsigned char* p00 = fd.data + ((size_t)ya * w + xa) * 3;
-        const unsigned char* p10 = fd.data + ((size_t)ya * w + xb) * 3;
-        const unsigned char* p01 = fd.data + ((size_t)yb * w + xa) * 3;
-        const unsigned char* p11 = fd.data + ((size_t)yb * w + xb) * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) px[c] = mos_lerp((double)p00[c], (double)p10[c], (double)p01[c], (double)p11[c], tx, ty);
-    }
+    mos_sample<MODE>(fd, h, w, u, v, px);
     return true;
 }
 
 // A row of a wave whose 64 cells are all written, and whose 192 bytes start on a dword, goes through LDS and leaves as 48
 // dword stores; every other row as three byte stores per cell (a dword that holds a byte of a cell that is not written
 // must not be stored: that byte is left as it was).  Measured against byte stores everywhere at F = 1 000 on 8192 x 8192
-// cells: -3 % (nearest) and -5 % (bilinear), profiles/mosaic/.
+// cells: -3 % (nearest) and -5 % (bilinear), profiles/mosaic/.  s_wave_row is the wave's own 48 dwords of LDS, row the
+// picture's first byte of the wave's 64 cells; wr: this lane's cell is written; packed, wave-uniform: __ballot(wr) == ~0ull &&
+// ((uintptr_t)row & 3) == 0, which the CALLER writes out (evaluated in here or in a helper, the fill's code comes out with the
+// operands of four scalar ORs swapped: the same work, other bytes).
+__device__ __forceinline__ void mos_store_row(unsigned int (&s_wave_row)[48], unsigned char* row, int lane, bool packed, bool wr,
+                                              const unsigned char (&px)[3]) {
+    if (packed) {
+        unsigned char* sb = (unsigned char*)s_wave_row;
+        sb[lane * 3] = px[0];
+        sb[lane * 3 + 1] = px[1];
+        sb[lane * 3 + 2] = px[2];
+        __builtin_amdgcn_wave_barrier();                     // the wave's LDS writes are issued before its reads
+        if (lane < 48) ((unsigned int*)row)[lane] = s_wave_row[lane];
+        __builtin_amdgcn_wave_barrier();                     // and the reads before the next row's writes
+    } else if (wr) {
+        unsigned char* out = row + lane * 3;
+        out[0] = px[0];
+        out[1] = px[1];
+        out[2] = px[2];
+    }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(COV_THREADS) void mosaic_fill_kernel(
         const frame_desc* __restrict__ frames, int n_resident, const int* __restrict__ slot, const double* __restrict__ g2p,
@@ -200,20 +231,7 @@ __global__ __launch_bounds__(COV_THREADS) void mosaic_fill_kernel(
         const bool wr = i < gx && mos_cell<MODE>(frames, n_resident, slot, g2p, size, n_frames, source[(size_t)j * gx + i], Xc,
                                                  cov_centre(y0, j, cell), bad, px);
         unsigned char* row = mosaic + ((size_t)(north_up ? gy - 1 - j : j) * gx + i_first) * 3;
-        if (__ballot(wr) == ~0ull && ((uintptr_t)row & 3) == 0) {
-            unsigned char* sb = (unsigned char*)s_row[wave];
-            sb[lane * 3] = px[0];
-            sb[lane * 3 + 1] = px[1];
-            sb[lane * 3 + 2] = px[2];
-            __builtin_amdgcn_wave_barrier();                 // the wave's LDS writes are issued before its reads
-            if (lane < 48) ((unsigned int*)row)[lane] = s_row[wave][lane];
-            __builtin_amdgcn_wave_barrier();                 // and the reads before the next row's writes
-        } else if (wr) {
-            unsigned char* out = row + lane * 3;
-            out[0] = px[0];
-            out[1] = px[1];
-            out[2] = px[2];
-        }
+        mos_store_row(s_row[wave], row, lane, __ballot(wr) == ~0ull && ((uintptr_t)row & 3) == 0, wr, px);
     }
     if (bad) atomicOr(status, bad);
 }

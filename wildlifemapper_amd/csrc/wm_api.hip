@@ -253,6 +253,23 @@ extern "C" int wm_mosaic_fill_u8(const wm_frame_desc* frames_dev, int n_resident
                               mosaic_dev, status_dev, (hipStream_t)stream);
 }
 
+extern "C" int wm_mosaic_blend_plan(const double* g2p_dev, const int32_t* size_dev, int n_frames, double x0, double y0, double cell, int gx,
+                                    int gy, double band, double* best_dev, int32_t* cells_dev, int64_t* stats_dev, void* stream) {
+    return launch_mosaic_blend_plan(g2p_dev, size_dev, n_frames, x0, y0, cell, gx, gy, band, best_dev, cells_dev, stats_dev, (hipStream_t)stream);
+}
+
+extern "C" int wm_mosaic_blend_accum_u8(const wm_frame_desc* frames_dev, const int32_t* index_dev, int n_resident, const double* g2p_dev,
+                                        const int32_t* size_dev, int n_frames, const int32_t* exposure_dev, double x0, double y0, double cell,
+                                        int gx, int gy, double band, const double* best_dev, int mode, uint32_t* acc_dev, int32_t* status_dev,
+                                        void* stream) {
+    return launch_mosaic_blend_accum(frames_dev, index_dev, n_resident, g2p_dev, size_dev, n_frames, exposure_dev, x0, y0, cell, gx, gy, band,
+                                     best_dev, mode, acc_dev, status_dev, (hipStream_t)stream);
+}
+
+extern "C" int wm_mosaic_blend_finish_u8(const uint32_t* acc_dev, int gx, int gy, int flags, uint8_t* mosaic_dev, void* stream) {
+    return launch_mosaic_blend_finish(acc_dev, gx, gy, flags, mosaic_dev, (hipStream_t)stream);
+}
+
 extern "C" int wm_register_render_u8(const wm_frame_desc* frames_dev, int n_resident, const int32_t* slot_dev, const double* g2p_dev,
                                      const int32_t* size_dev, int n_frames, const wm_register_pair* pairs_dev, int n_pairs, double cell,
                                      int search, int side, uint8_t* a_dev, uint8_t* b_dev, int32_t* status_dev, void* stream) {

@@ -9,7 +9,10 @@
   * mosaic, mosaic_plan, resampled_georef: the map -- the frames laid onto the coverage's ground grid; every cell takes its
     pixel from the one frame that saw it most vertically (seam rule and sampling: include/wm_hip.h), chosen for all cells
     by one wm_mosaic_plan launch and fetched by wm_mosaic_fill_u8, a chunk of resident frames per launch, so only the
-    frames that won a cell are ever loaded; the census' individuals can be outlined on it.
+    frames that won a cell are ever loaded; the census' individuals can be outlined on it.  mosaic(blend=band),
+    mosaic_blend_plan: instead of one frame per cell, the integer-weighted mean of the exposure-corrected frames that see
+    it, every weight falling to zero at the frame's border and away from the seam (include/wm_hip.h "Survey mosaic,
+    blended"; wm_mosaic_blend_plan, wm_mosaic_blend_accum_u8 per chunk, wm_mosaic_blend_finish_u8).
 The validators of georeferences, sizes, cells and grids, the footprints' extent, the census-dict reader and the resident
 chunk of frames are shared with registration.py."""
 from __future__ import annotations
@@ -460,6 +463,54 @@ def mosaic_plan(georef, sizes, cell, bounds=None) -> Dict[str, object]:
     return _mosaic_plan(g, s, cell, x0, y0, gx, gy, _survey_device(what))[0]
 
 
+def _check_band(band, what: str, name: str = "band") -> float:
+    """Validate band= (mosaic's blend=) before any device work: a finite number > 0 (no bool) whose 256 / band is finite too."""
+    must = "must be a finite number > 0"
+    return _finite_number(band, what, name, lambda b: b > 0.0 and math.isfinite(256.0 / b), must, must, refuse=(bool, np.bool_, str, bytes))
+
+
+def _check_exposure(exposure, n_frames: int, what: str) -> np.ndarray:
+    """exposure= of mosaic(): the (F,2) int32 table exposure_table() returns, as an array or a tensor."""
+    a = exposure.detach().cpu().numpy() if isinstance(exposure, torch.Tensor) else exposure
+    if not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.shape != (n_frames, 2):
+        raise ValueError(f"{what}: exposure must be the ({n_frames}, 2) int32 table tiling.exposure_table() returns")
+    return np.ascontiguousarray(a)
+
+
+def _mosaic_blend_plan(g_d, s_d, F, cell, x0, y0, gx, gy, band, dev):
+    """wm_mosaic_blend_plan on validated arguments and the device copies of g2p and sizes.  Returns the plan's dict."""
+    with torch.cuda.device(dev):
+        cells = torch.empty(F, device=dev, dtype=torch.int32) if F else None
+        best = torch.empty((gy, gx), device=dev, dtype=torch.float64)
+        stats = torch.empty(3, device=dev, dtype=torch.int64)
+        N.check(N.lib().wm_mosaic_blend_plan(N.ptr(g_d), N.ptr(s_d), F, x0, y0, cell, gx, gy, band, N.ptr(best), N.ptr(cells), N.ptr(stats),
+                                             N.stream_ptr(dev)))
+        seen, gap, blended = (int(v) for v in stats.cpu().tolist())
+    cells = cells.to(torch.int64) if F else torch.zeros(0, device=dev, dtype=torch.int64)
+    return {"best": best, "cells": cells, "origin": (x0, y0), "cell": cell, "shape": (gy, gx), "band": band, "seen_cells": seen,
+            "gap_cells": gap, "blended_cells": blended}
+
+
+def mosaic_blend_plan(georef, sizes, cell, band, bounds=None) -> Dict[str, object]:
+    """Which frames blend into each ground cell (wm_mosaic_blend_plan; rule: include/wm_hip.h "Survey mosaic, blended").
+    Geometry only, no pixels; the arguments and the validation of mosaic_plan(), plus band: the width in SOURCE PIXELS, a
+    finite number > 0, over which a frame's weight falls to zero at its own border and away from the seam.  One launch on
+    the current device's current stream and one small copy of the statistics, which waits for it.  No CPU fallback.  Returns
+      'best' (gy,gx) float64 on the device: the largest distance, in its own pixels, of a frame that sees the cell to that
+          frame's nearest border, -1.0 where no frame sees it; row 0 is the SOUTHERNMOST;
+      'cells' (F,) int64 on the device: the cells into which each frame blends with a positive weight -- the frames
+          mosaic(blend=band) loads are exactly those with cells > 0;
+      'origin' (x0, y0), 'cell', 'shape' (gy, gx), 'band'; 'seen_cells', 'gap_cells' and 'blended_cells' int: the cells a
+          frame sees, those none sees, and those that mix two or more frames."""
+    what = "mosaic_blend_plan"
+    band = _check_band(band, what)
+    g, s, cell, x0, y0, gx, gy = _survey_grid(georef, sizes, cell, bounds, what)
+    dev = _survey_device(what)
+    with torch.cuda.device(dev):
+        g_d, s_d = _frame_tables(g, s, dev)
+    return _mosaic_blend_plan(g_d, s_d, g.shape[0], cell, x0, y0, gx, gy, band, dev)
+
+
 def resampled_georef(georef, size, new_size) -> np.ndarray:
     """The georeference of a frame after resampling: georef (2,3) or (F,2,3) float64 (pixel -> ground) of frames of `size`
     (height, width) gives that of the same frames resampled to `new_size` (H', W') -- a pixel of the new frame spans W / W'
@@ -496,7 +547,7 @@ def resampled_georef(georef, size, new_size) -> np.ndarray:
 
 
 def mosaic(frames, georef, cell, sizes=None, bounds=None, sample: str = "bilinear", fill=(0, 0, 0), north_up: bool = True,
-           chunk: int = 8, census=None, marker=None, width: int = 2, palette=None) -> Dict[str, object]:
+           chunk: int = 8, census=None, marker=None, width: int = 2, palette=None, blend=None, exposure=None) -> Dict[str, object]:
     """The map of a survey: its frames laid onto the ground grid (wm_mosaic_plan, wm_mosaic_fill_u8; rule: include/wm_hip.h
     "Survey mosaic").  frames: a sequence that is only indexed (frames[i], len) -- a list of (H,W,3) uint8 ROCm tensors,
     CPU tensors or numpy arrays as detect_frames accepts them, or a lazy sequence that loads frame i from disk when it is
@@ -517,11 +568,27 @@ def mosaic(frames, georef, cell, sizes=None, bounds=None, sample: str = "bilinea
     individual whose keeper point is finite and inside the grid is outlined in its class colour by one draw_boxes launch
     on the finished mosaic (width, palette as for draw_boxes); the square is centred on ((X - x0) / cell, (Y - y0) / cell),
     the y mirrored (gy - y) when north_up.
+    blend= (None: the hard seams above, untouched) a band in SOURCE PIXELS, a finite number > 0: every cell becomes the
+    integer-weighted mean of all the frames that see it, each frame's weight falling to zero at its own border and, over
+    the band, away from the seam (wm_mosaic_blend_plan, wm_mosaic_blend_accum_u8, wm_mosaic_blend_finish_u8; rule:
+    include/wm_hip.h "Survey mosaic, blended").  The hard plan still runs, so 'source', 'won' and 'gap_cells' keep their
+    meaning; then the blend plan; exactly the frames that blend into a cell (mosaic_blend_plan's cells > 0) are indexed,
+    each once, ascending, `chunk` at a time; one accumulate launch per chunk and one finish into the fill-coloured
+    picture.  The result does not depend on chunk.  Memory: 16 bytes per cell of accumulators plus 8 of 'best' while it
+    runs, 1.5 GiB at 8192 x 8192 cells.  Within band pixels of the OUTER rim of the covered ground a step can remain, where
+    two frames reach their borders at one point and neither has weight left to fade with.
+    exposure= (needs blend=) the (F,2) int32 table exposure_table() makes of adjust_exposure()'s gains and offsets: every
+    frame's pixels pass through its gain and offset before they are summed.
     Runs on the current device's current stream (with census=, on its tensors' device).  No CPU fallback.  Returns the
     plan's dict ('source', 'won', 'origin', 'cell', 'shape', 'gap_cells') plus 'mosaic' (gy,gx,3) uint8 on the device and
-    'north_up'; with markers also 'marker_boxes' (k',4) fp32 xyxy in picture pixels and 'marker_index' (k',) int64, the
-    individuals they belong to."""
+    'north_up'; with blend= also 'blend_cells' (F,) int64 on the device (the cells each frame blends into) and
+    'blended_cells' int (the cells that mix two or more frames); with markers also 'marker_boxes' (k',4) fp32 xyxy in
+    picture pixels and 'marker_index' (k',) int64, the individuals they belong to."""
     what = "mosaic"
+    if blend is not None:
+        blend = _check_band(blend, what, "blend")
+    elif exposure is not None:
+        raise ValueError(f"{what}: exposure needs blend=: the hard-seam mosaic copies pixels as they are")
     if not isinstance(sample, str) or sample not in MOSAIC_SAMPLES:
         raise ValueError(f"{what}: sample {sample!r} must be 'bilinear' or 'nearest'")
     try:
@@ -545,6 +612,8 @@ def mosaic(frames, georef, cell, sizes=None, bounds=None, sample: str = "bilinea
     F = g.shape[0]
     if n_given != F:
         raise ValueError(f"{what}: {n_given} frames for {F} georeferences")
+    if exposure is not None:
+        exposure = _check_exposure(exposure, F, what)
     dev = _survey_device(what, pts)
     out, g_d, s_d = _mosaic_plan(g, s, cell, x0, y0, gx, gy, dev)
     lib = N.lib()
@@ -552,16 +621,36 @@ def mosaic(frames, georef, cell, sizes=None, bounds=None, sample: str = "bilinea
     with torch.cuda.device(dev):
         picture = torch.from_numpy(fill_a).to(dev).expand(gy, gx, 3).contiguous()
         status = torch.zeros(1, device=dev, dtype=torch.int32)
-        winners = torch.nonzero(out["won"] > 0).flatten().cpu().tolist()
-        for c0 in range(0, len(winners), chunk):
-            ids = winners[c0:c0 + chunk]
-            desc, slot_d, resident = _resident_chunk(frames, ids, s, dev, what)
-            N.check(lib.wm_mosaic_fill_u8(N.ptr(desc), len(ids), N.ptr(slot_d), N.ptr(g_d), N.ptr(s_d), F, x0, y0, cell, gx, gy,
-                                          N.ptr(out["source"]), mode, flags, N.ptr(picture), N.ptr(status), N.stream_ptr(dev)))
-            del resident, desc, slot_d                        # the stream orders their reuse after the launch
-        bad = int(status.item()) if winners else 0
-        if bad:
-            raise RuntimeError(f"{what}: wm_mosaic_fill_u8 skipped cells (status {bad}): a resident frame did not match its slot or size")
+        if blend is None:
+            winners = torch.nonzero(out["won"] > 0).flatten().cpu().tolist()
+            for c0 in range(0, len(winners), chunk):
+                ids = winners[c0:c0 + chunk]
+                desc, slot_d, resident = _resident_chunk(frames, ids, s, dev, what)
+                N.check(lib.wm_mosaic_fill_u8(N.ptr(desc), len(ids), N.ptr(slot_d), N.ptr(g_d), N.ptr(s_d), F, x0, y0, cell, gx, gy,
+                                              N.ptr(out["source"]), mode, flags, N.ptr(picture), N.ptr(status), N.stream_ptr(dev)))
+                del resident, desc, slot_d                    # the stream orders their reuse after the launch
+            bad = int(status.item()) if winners else 0
+            if bad:
+                raise RuntimeError(f"{what}: wm_mosaic_fill_u8 skipped cells (status {bad}): a resident frame did not match its slot or size")
+        else:
+            plan = _mosaic_blend_plan(g_d, s_d, F, cell, x0, y0, gx, gy, blend, dev)
+            acc = torch.zeros((gy, gx, 4), device=dev, dtype=torch.int32)       # the entry's uint32, as torch can hold them
+            e_d = _pinned_upload(exposure, dev) if exposure is not None and F else None
+            users = torch.nonzero(plan["cells"] > 0).flatten().cpu().tolist()
+            for c0 in range(0, len(users), chunk):
+                ids = users[c0:c0 + chunk]
+                desc, _, resident = _resident_chunk(frames, ids, s, dev, what)
+                index_d = _pinned_upload(np.asarray(ids, dtype=np.int32), dev)
+                N.check(lib.wm_mosaic_blend_accum_u8(N.ptr(desc), N.ptr(index_d), len(ids), N.ptr(g_d), N.ptr(s_d), F, N.ptr(e_d), x0, y0,
+                                                     cell, gx, gy, blend, N.ptr(plan["best"]), mode, N.ptr(acc), N.ptr(status),
+                                                     N.stream_ptr(dev)))
+                del resident, desc, index_d                   # the stream orders their reuse after the launch
+            bad = int(status.item()) if users else 0
+            if bad:
+                raise RuntimeError(f"{what}: wm_mosaic_blend_accum_u8 skipped frames (status {bad}): a resident frame did not match its index or size")
+            N.check(lib.wm_mosaic_blend_finish_u8(N.ptr(acc), gx, gy, flags, N.ptr(picture), N.stream_ptr(dev)))
+            del acc
+            out.update({"blend_cells": plan["cells"], "blended_cells": plan["blended_cells"]})
         out.update({"mosaic": picture, "north_up": bool(north_up)})
         if pts is not None:
             p = pts.detach().cpu().numpy()

@@ -9,7 +9,9 @@
   * refine: below one cell -- the sub-cell shift, yaw and scale of every frame (and the gain and offset between exposures)
     from the integer normal equations of one Gauss-Newton step per pair (wm_register_refine; rule: include/wm_hip.h "Survey
     registration, refinement"), iterated; its host parts are refine_solve (the 4 x 4 or 6 x 6 solve per pair),
-    adjust_similarity (one similarity per frame, two calls of adjust) and refine_step (both, and the corrected georef)."""
+    adjust_similarity (one similarity per frame, two calls of adjust) and refine_step (both, and the corrected georef);
+  * adjust_exposure, exposure_table: one gain and one offset per frame from the pairs' exposure fits, two calls of adjust,
+    and the Q12 table of them that mosaic(blend=, exposure=) applies."""
 from __future__ import annotations
 
 import math
@@ -445,6 +447,75 @@ def adjust_similarity(n_frames, pairs, patch_centres, frame_centres, measured, w
     second = adjust(F, ab, want_t, weights, fixed)
     return {"shift": second["shift"], "yaw": yaw.copy(), "scale": scale.copy(),
             "residual": np.concatenate([second["residual"], first["residual"]], axis=1).reshape(P, 4), "component": second["component"]}
+
+
+def adjust_exposure(n_frames, pairs, param, weights, fixed=None) -> Dict[str, np.ndarray]:
+    """One gain and one offset per frame from the pairwise exposure fits: the exposure analogue of adjust().  Host only,
+    numpy double, in two calls of adjust().  pairs as adjust() takes them; param (P,6) as refine_solve(exposure=True) and
+    refine(..., exposure=True) return it, of which only gamma = param[:, 4] and o = param[:, 5] are read: the pair model is
+    A ~ (1 + gamma) * B + o on luma.  With L'_f = k_f * L_f + c_f the corrected luma of frame f, two frames agree where they
+    overlap when k_b = k_a * (1 + gamma) and c_b = c_a + k_a * o:
+      first ln k from ln k_b - ln k_a = ln(1 + gamma);
+      then c from c_b - c_a = k_a * o, with the solved k.
+    weights (P,) >= 0; a pair whose gamma or o is not finite, or whose 1 + gamma <= 0, gets weight 0.  From refine(...,
+    exposure=True): weights = np.where(out['accepted'], out['cells'], 0).  The gauge is adjust()'s, in both calls: in a
+    component without a fixed frame the mean ln k and the mean c of its frames are zero; fixed frames keep (1, 0); a frame
+    without a used pair keeps (1, 0).  Returns 'gain' (n_frames,) the k_f, 'offset' (n_frames,) the c_f in grey levels,
+    'residual' (P,2) (ln k's, then c's; NaN for a pair that could not be used) and 'component' as adjust() gives it.
+    exposure_table() turns 'gain' and 'offset' into the table mosaic(blend=, exposure=) takes."""
+    what = "adjust_exposure"
+    F = _check_whole(n_frames, what, "n_frames", 0)
+    try:
+        par = np.asarray(param, dtype=np.float64)
+        if par.size == 0:
+            par = par.reshape(0, 6)
+        if par.ndim != 2 or par.shape[1] != 6:
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: param must be (P,6) numbers, as refine_solve returns it") from None
+    P = par.shape[0]
+    gamma, o = par[:, 4], par[:, 5]
+    with np.errstate(all="ignore"):
+        usable = np.isfinite(gamma) & np.isfinite(o) & (1.0 + gamma > 0.0)
+        ln_g = np.where(usable, np.log(np.where(usable, 1.0 + gamma, 1.0)), np.nan)
+    try:
+        w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: weights must be (P,) numbers") from None
+    if w.shape != (P,):
+        raise ValueError(f"{what}: {P} pairs and weights of shape {w.shape}: expected ({P},)")
+    w = np.where(usable, w, np.where(np.isfinite(w) & (w >= 0), 0.0, w))          # a bad weight still reaches adjust()'s check
+    first = adjust(F, pairs, np.stack([ln_g, np.zeros(P)], axis=1), w, fixed)     # validates pairs, weights and fixed
+    gain = np.exp(first["shift"][:, 0])
+    if isinstance(pairs, np.ndarray) and pairs.dtype == REGISTER_PAIR:
+        ab = np.stack([pairs["frame_a"], pairs["frame_b"]], axis=1).astype(np.int64).reshape(-1, 2)
+    else:
+        ab = np.asarray(pairs).astype(np.int64).reshape(-1, 2)
+    with np.errstate(all="ignore"):
+        want_c = np.where(usable, gain[ab[:, 0]] * o, np.nan)
+    second = adjust(F, ab, np.stack([want_c, np.zeros(P)], axis=1), w, fixed)
+    return {"gain": gain, "offset": second["shift"][:, 0].copy(),
+            "residual": np.stack([first["residual"][:, 0], second["residual"][:, 0]], axis=1).reshape(P, 2), "component": second["component"]}
+
+
+def exposure_table(gain, offset) -> np.ndarray:
+    """adjust_exposure()'s gains and offsets as the Q12 table of wm_mosaic_blend_accum_u8 (include/wm_hip.h "Survey mosaic,
+    blended"): (F,2) int32 (floor(gain * 4096 + 0.5), floor(offset * 4096 + 0.5)).  gain (F,) finite in [1/16, 16), offset
+    (F,) grey levels with |offset| <= 255, else ValueError: beyond them the fit is not an exposure change.  (1, 0) gives
+    (4096, 0), the identity."""
+    what = "exposure_table"
+    try:
+        k = np.asarray(gain, dtype=np.float64).reshape(-1) if np.size(gain) else np.zeros(0)
+        c = np.asarray(offset, dtype=np.float64).reshape(-1) if np.size(offset) else np.zeros(0)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: gain and offset must be (F,) numbers") from None
+    if np.ndim(gain) > 1 or np.ndim(offset) > 1 or k.shape != c.shape:
+        raise ValueError(f"{what}: gain of shape {np.shape(gain)} and offset of shape {np.shape(offset)}: expected (F,) and (F,)")
+    if not (np.isfinite(k).all() and (k >= 1.0 / 16.0).all() and (k < 16.0).all()):
+        raise ValueError(f"{what}: every gain must be finite in [1/16, 16)")
+    if not (np.isfinite(c).all() and (np.abs(c) <= 255.0).all()):
+        raise ValueError(f"{what}: every offset must be finite with |offset| <= 255")
+    return np.stack([np.floor(k * 4096.0 + 0.5), np.floor(c * 4096.0 + 0.5)], axis=1).astype(np.int32).reshape(-1, 2)
 
 
 def _frame_centres(g: np.ndarray, s: np.ndarray) -> np.ndarray:
