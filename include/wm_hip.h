@@ -294,7 +294,7 @@ int wm_merge_frames_fuse(const wm_box_record* records_dev, const int32_t* origin
 
 /* Survey census (tiling.census): survey frames overlap (60-80 % along a flight line, and sideways between lines), so an
  * animal is detected in two to four frames; the census groups the detections of a whole survey into individuals.  No
- * reference behaviour exists; this rule is the contract, and tests/test_census.py restates it sequentially.
+ * reference behaviour exists; this rule is the contract, and tests/ground_oracle.py restates it sequentially.
  * Inputs: n detections, each a box (x0, y0, x1, y1) fp32 in the pixels of its frame, a score fp32, a label int32 and a
  * frame index f int32; georef_dev[n_frames][6] doubles (a0..a5) per frame, frame pixels -> ground metres, X east, Y north.
  * Ground point, in double, every operation correctly rounded on its own (no contraction):
@@ -335,7 +335,7 @@ int wm_census(const float* boxes_dev, const float* scores_dev, const int32_t* la
  * frames overlap, so that ground is the union of the frame footprints, not their sum.  A ground grid is laid over the
  * survey; every cell gets the number of frames that saw its centre, and the census' individuals are counted into the same
  * grid per class, each with the number of frames that could have seen it.  No reference behaviour exists; this rule is the
- * contract, and tests/test_coverage.py restates it sequentially (coverage_oracle).  All arithmetic is IEEE double, every
+ * contract, and tests/ground_oracle.py restates it sequentially (coverage_oracle).  All arithmetic is IEEE double, every
  * operation correctly rounded on its own (no contraction), in the order written.
  * Frames: g2p_dev[n_frames][6] doubles (b0..b5), the GROUND -> PIXEL affine of each frame (the inverse of the census'
  * georeference: tiling.ground_to_pixel); size_dev[n_frames][2] int32, (height, width) of the source frame in the pixels
@@ -383,7 +383,7 @@ int wm_coverage_points(const double* g2p_dev, const int32_t* size_dev, int n_fra
 
 /* Survey mosaic (tiling.mosaic, tiling.mosaic_plan): the map itself -- the frames laid onto the ground grid, one picture of
  * the whole survey.  For every ground cell ONE frame is chosen and its pixel fetched.  No reference behaviour exists (the
- * reference has no georeferencing); this rule is the contract, and tests/test_mosaic.py restates it sequentially
+ * reference has no georeferencing); this rule is the contract, and tests/ground_oracle.py restates it sequentially
  * (mosaic_oracle).  The grid, the cell centres, the frames and sees are those of "Survey coverage", word for word:
  * g2p_dev[n_frames][6] doubles (b0..b5, ground -> pixel) and size_dev[n_frames][2] int32 (height, width); the centre of cell
  * (j, i) is Xc = x0 + ((double)i + 0.5) * cell, Yc = y0 + ((double)j + 0.5) * cell, row j = 0 the SOUTHERNMOST;
@@ -442,7 +442,7 @@ int wm_mosaic_fill_u8(const wm_frame_desc* frames_dev, int n_resident, const int
  * frame, so residual misregistration tears and an exposure difference steps at the Voronoi lines.  Here every cell is an
  * integer-weighted mean of the exposure-corrected pixels of ALL the frames that see it, each frame's weight falling to
  * zero at its own border and away from the seam, over a band the caller chooses.  No reference behaviour exists; this rule
- * is the contract, and tests/test_mosaic_blend.py restates it sequentially (blend_oracle).  The grid, the cell centres,
+ * is the contract, and tests/ground_oracle.py restates it sequentially (blend_oracle).  The grid, the cell centres,
  * g2p, size, sees and the (u, v) expression are those of "Survey coverage", word for word; all double arithmetic is IEEE,
  * one rounding per operation, no contraction, in the order written; there is no sqrt, and one division, k, on the host.
  * For a cell with centre (Xc, Yc) and every frame f with sees(f, Xc, Yc):
@@ -502,7 +502,7 @@ int wm_mosaic_blend_finish_u8(const uint32_t* acc_dev /* [gy][gx][4] */, int gx,
  * from GPS and heading is wrong by metres from frame to frame.  Frames overlap, so every pair of neighbours shows the same
  * ground twice: each pair is rendered onto a common ground patch and the shift at which the two agree is found by an
  * exhaustive integer search; one translation per frame is then solved on the host (tiling.adjust).  No reference behaviour
- * exists; this rule is the contract, and tests/test_register.py restates it sequentially (register_oracle).  The frames
+ * exists; this rule is the contract, and tests/register_cases.py restates it sequentially (register_oracle).  The frames
  * (g2p_dev[n_frames][6] doubles b0..b5, ground -> pixel; size_dev[n_frames][2] int32, (height, width)), the predicate sees
  * and the cell-centre expression are those of "Survey coverage", word for word; all double arithmetic is IEEE, every
  * operation correctly rounded on its own (no contraction), in the order written.  Everything after the render is integer.

@@ -1,17 +1,17 @@
-"""What tests/test_register.py and tests/test_register_zncc.py share: the sequential oracle of the registration rule (render,
-search, pick -- include/wm_hip.h "Survey registration"), the cases both files build, the thin calls of the C-ABI entry points
-and the end-to-end scene's constants.  Nothing here asserts."""
-import os
-
+"""What the registration tests (tests/test_register.py, test_register_zncc.py, test_register_refine.py) and tools/register_time.py
+share: the sequential oracles of the registration rules (render, search and pick; the correlation search; the refinement's
+sums -- include/wm_hip.h "Survey registration" and the two sections after it), the cases the files build, the thin calls of
+the C-ABI entry points and the end-to-end scene.  The ground rule of render_plane is ground_oracle.py's.  Nothing here asserts
+about a device."""
 import numpy as np
 import torch
 
+from ground_oracle import inside, uv
 from survey_util import DEV, _up
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
 from wildlifemapper_amd._survey import _frame_descs
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F64 = np.float64
 NAN = float("nan")
 INF = float("inf")
@@ -34,9 +34,8 @@ def render_plane(b6, hw, img, x0, y0, cell, nx, ny, s, ext):
     with np.errstate(all="ignore"):
         Xc = (x0 + ((idx - s).astype(F64) + F64(0.5)) * cell)[None, :]
         Yc = (y0 + ((idx - s).astype(F64) + F64(0.5)) * cell)[:, None]
-        u = (b[0] * Xc + b[1] * Yc) + b[2]
-        v = (b[3] * Xc + b[4] * Yc) + b[5]
-        sees = (h >= 1) & (w >= 1) & (0 <= u) & (u < w) & (0 <= v) & (v < h)
+        u, v = uv(b, Xc, Yc)
+        sees = inside(u, v, h, w)
     sees = sees & (idx[None, :] < nx + 2 * s) & (idx[:, None] < ny + 2 * s)
     out = np.zeros((ext, ext), dtype=np.uint8)
     if sees.any():
@@ -90,6 +89,90 @@ def pick_oracle(score, S, min_cells):
     four = lambda c: [0, 0, -1, 0] if c is None else [c[2], c[3], c[0], c[1]]
     return np.array(four(first) + four(second), dtype=np.int64)
 
+
+# ---- the correlation search: six moments per offset, the score in three float64 operations ----------------------------------
+
+def zncc_search_oracle(A, B, gx, gy, S):
+    """moments (2S+1, 2S+1, 6) int64 = (n, Sa, Sb, Saa, Sbb, Sab) over the cells both planes see, one offset at a time."""
+    a = A[:gy, :gx].astype(np.int64)
+    out = np.zeros((2 * S + 1, 2 * S + 1, 6), dtype=np.int64)
+    for dy in range(-S, S + 1):
+        for dx in range(-S, S + 1):
+            bb = B[S + dy:S + dy + gy, S + dx:S + dx + gx].astype(np.int64)
+            both = (a != 0) & (bb != 0)
+            x, y = a[both], bb[both]
+            out[dy + S, dx + S] = (both.sum(), x.sum(), y.sum(), (x * x).sum(), (y * y).sum(), (x * y).sum())
+    return out
+
+
+def zncc_q(m):
+    """The score of one offset from its six moments, or None where a plane is flat: c, va, vb in Python integers, then
+    q = (c * |c|) / (va * vb) in three float64 operations."""
+    n, sa, sb, saa, sbb, sab = (int(v) for v in m)
+    c, va, vb = n * sab - sa * sb, n * saa - sa * sa, n * sbb - sb * sb
+    if va <= 0 or vb <= 0:
+        return None
+    assert max(abs(c), va, vb, n * sab, sa * sb, n * saa, n * sbb) < 2 ** 53           # the conversions are exact
+    cf = F64(c)
+    return (cf * np.abs(cf)) / (F64(va) * F64(vb))
+
+
+def zncc_beats(p, q):
+    """Offset p = (q, n, dy, dx) beats q: the larger score, then the smaller (dy^2 + dx^2, dy, dx)."""
+    if p[0] != q[0]:
+        return p[0] > q[0]
+    return (p[2] * p[2] + p[3] * p[3], p[2], p[3]) < (q[2] * q[2] + q[3] * q[3], q[2], q[3])
+
+
+def zncc_pick_oracle(moments, S, min_cells):
+    """(best (8,) int64, peak (2,) float64) from a moments table, sequentially."""
+    def candidate(dy, dx):
+        m = moments[dy + S, dx + S]
+        q = zncc_q(m) if int(m[0]) >= min_cells else None
+        return None if q is None else (q, int(m[0]), dy, dx)
+    first, second = pick_two(S, candidate, zncc_beats)
+    four = lambda c: [0, 0, 0, 0] if c is None else [c[2], c[3], 1, c[1]]
+    peak = np.array([NAN if c is None else c[0] for c in (first, second)], dtype=F64)
+    return np.array(four(first) + four(second), dtype=np.int64), peak
+
+
+def same_bytes(got, want):
+    return np.ascontiguousarray(got, dtype=F64).tobytes() == np.ascontiguousarray(want, dtype=F64).tobytes()
+
+
+# ---- refinement: the 28 integer sums of one Gauss-Newton step per pair ---------------------------------------------------
+
+SUMS = 28
+TRI = [(k, l) for k in range(6) for l in range(k, 6)]
+
+
+def refine_sums_oracle(A, B, gx, gy, search):
+    """The 28 sums of one pair as a list of Python integers.  A (side, side), B (side + 2 search, side + 2 search) uint8."""
+    S = search
+    a = A[:gy, :gx].astype(np.int64)
+    sl = lambda dj, di: B[S + dj:S + dj + gy, S + di:S + di + gx].astype(np.int64)
+    b, e, w, nn, ss = sl(0, 0), sl(0, 1), sl(0, -1), sl(1, 0), sl(-1, 0)
+    counts = (a != 0) & (b != 0) & (e != 0) & (w != 0) & (nn != 0) & (ss != 0)
+    r, gxv, gyv = a - b, e - w, nn - ss
+    x = (2 * np.arange(gx, dtype=np.int64) + 1 - gx)[None, :] + np.zeros((gy, 1), dtype=np.int64)
+    y = (2 * np.arange(gy, dtype=np.int64) + 1 - gy)[:, None] + np.zeros((1, gx), dtype=np.int64)
+    c = [gxv, gyv, x * gyv - y * gxv, x * gxv + y * gyv, b, np.ones_like(b)]
+    total = lambda v: int(v[counts].astype(object).sum()) if counts.any() else 0       # Python integers
+    return [total(c[k] * c[l]) for k, l in TRI] + [total(c[k] * r) for k in range(6)] + [total(r * r)]
+
+
+def _oracle_sums(frames, georef, sizes, table, cell, side, search=1):
+    g2p = tiling.ground_to_pixel(georef).reshape(-1, 6)
+    out = []
+    for pr in table:
+        fa, fb, gx, gy = (int(pr[k]) for k in ("frame_a", "frame_b", "gx", "gy"))
+        A = render_plane(g2p[fa], sizes[fa], frames[fa], pr["x0"], pr["y0"], cell, gx, gy, 0, side)
+        B = render_plane(g2p[fb], sizes[fb], frames[fb], pr["x0"], pr["y0"], cell, gx, gy, search, side + 2 * search)
+        out.append(refine_sums_oracle(A, B, gx, gy, search))
+    return np.array(out, dtype=np.int64).reshape(len(table), SUMS)
+
+
+# ---- the whole rule for a pair table -------------------------------------------------------------------------------------
 
 def register_oracle(g2p, size, images, pairs, cell, search, side, min_cells):
     """The whole rule for a pair table: A (P,side,side), B (P,E,E) uint8, score (P,2S+1,2S+1,2) and best (P,8) int64.  A
@@ -171,6 +254,17 @@ SHAPES = {  # gx, gy, search, side
     "33x37_s62": (33, 37, 62, 40), "33x37_s63": (33, 37, 63, 40)}             # the last search with 32-row tiles, the first with 16
 
 
+def _several_pairs():
+    """Pairs of different sizes in one launch, sharing frames, patches at different places, one yawed 45 degrees."""
+    x0, y0, cell = 1000.0, 2000.0, 0.5
+    diamond = _content(90, 90, 13), tiling.nadir_affine(90, 90, (x0 + 17.5, y0 + 17.5), 0.5, 45.0)       # 45 m a side, yawed
+    frames = [_cover(70, 70, 6, x0, y0, cell, 11), _cover(70, 70, 6, x0, y0, cell, 12, gsd_cells=1.25), diamond,
+              _cover(30, 30, 6, x0 + 10.0, y0 + 10.0, cell, 14, gsd_cells=0.75)]
+    pairs = [(0, 1, 70, 19, x0, y0), (1, 2, 5, 66, x0 + 3.0, y0 + 1.5), (0, 3, 33, 30, x0 + 9.5, y0 + 8.0), (2, 3, 72, 72, x0 - 4.0, y0 - 4.0),
+             (0, 2, 1, 1, x0 + 7.0, y0 + 7.0)]
+    return _case(frames, pairs, cell, 6, 72, 40)
+
+
 def _planes(case):
     n, side, E = len(case["pairs"]), case["side"], case["side"] + 2 * case["search"]
     return (torch.full((n, side, side), POISON_A, device=DEV, dtype=torch.uint8), torch.full((n, E, E), POISON_B, device=DEV, dtype=torch.uint8))
@@ -240,3 +334,31 @@ def _detections(true):
         out.append({"boxes": _up(boxes), "scores": _up(np.linspace(0.9, 0.5, ok.sum()).astype(np.float32)),
                     "labels": torch.ones(int(ok.sum()), device=DEV, dtype=torch.int64)})
     return out
+
+
+def _scene(seed=3):
+    """A multi-scale texture: independent uniform fields at 1, 4 and 16 px, mixed per channel."""
+    rng = np.random.default_rng(seed)
+    out = np.zeros((SCENE_H, SCENE_W, 3), dtype=F64)
+    for k, wt in ((1, 0.3), (4, 0.3), (16, 0.4)):
+        field = rng.random((SCENE_H // k + 1, SCENE_W // k + 1, 3))
+        out += wt * np.kron(field, np.ones((k, k, 1)))[:SCENE_H, :SCENE_W]
+    return np.clip(out * 255.0, 0, 255).astype(np.uint8)
+
+
+def _survey():
+    """Four 160 x 200 frames cut from the scene (1 m per pixel; scene pixel (r, c) is the ground [c, c + 1) x [399 - r, 400 - r))
+    through their TRUE georeferences, at yaw 0 / 0 / 180 / 90.  Returns frames, true georef, displaced georef."""
+    scene = _scene()
+    true = np.stack([tiling.nadir_affine(160, 200, c, 1.0, yaw) for c, yaw in
+                     (((200.0, 200.0), 0.0), ((280.0, 220.0), 0.0), ((240.0, 170.0), 180.0), ((250.0, 210.0), 90.0))])
+    yy, xx = np.meshgrid(np.arange(160) + 0.5, np.arange(200) + 0.5, indexing="ij")
+    frames = []
+    for g in true:
+        X = g[0, 0] * xx + g[0, 1] * yy + g[0, 2]
+        Y = g[1, 0] * xx + g[1, 1] * yy + g[1, 2]
+        frames.append(scene[SCENE_H - 1 - np.floor(Y).astype(np.int64), np.floor(X).astype(np.int64)].copy())
+    displaced = true.copy()
+    displaced[:, 0, 2] += DISPLACED[:, 0]
+    displaced[:, 1, 2] += DISPLACED[:, 1]
+    return frames, true, displaced

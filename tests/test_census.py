@@ -1,7 +1,7 @@
 """Survey census (include/wm_hip.h "Survey census", tiling.census): the detections of overlapping frames grouped into
-individuals on the ground.  The rule has no reference behaviour; census_oracle below restates it sequentially -- numpy
-float64, the header's operation order, one detection at a time -- and the device result must equal it exactly: integers
-as integers, ground points bit for bit."""
+individuals on the ground.  The rule has no reference behaviour; census_oracle (tests/ground_oracle.py) restates it
+sequentially -- numpy float64, the header's operation order, one detection at a time -- and the device result must equal it
+exactly: integers as integers, ground points bit for bit."""
 import ctypes as C
 import math
 import os
@@ -11,63 +11,13 @@ import numpy as np
 import pytest
 import torch
 
+from ground_cases import entry_is_whole, macro
+from ground_oracle import census_oracle
+from survey_util import ROOT
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDENT = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]
-
-
-def census_oracle(boxes, scores, labels, frame, georef, radius, same_class=False):
-    """The census rule, sequentially.  Returns points (n,2) float64, individual (n,) int64, keeper (k,) int64,
-    members (k,) int64 and count."""
-    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
-    scores = np.asarray(scores, dtype=np.float32).reshape(-1)
-    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
-    frame = np.asarray(frame, dtype=np.int64).reshape(-1)
-    g = np.asarray(georef, dtype=np.float64).reshape(-1, 6)
-    n, F = boxes.shape[0], g.shape[0]
-    pts = np.full((n, 2), np.nan, dtype=np.float64)
-    valid = []
-    with np.errstate(all="ignore"):
-        for i in range(n):
-            if not (np.isfinite(boxes[i]).all() and np.isfinite(scores[i]) and 0 <= frame[i] < F):
-                continue
-            a = g[frame[i]]
-            x0, y0, x1, y1 = (np.float64(v) for v in boxes[i])
-            cx = (x0 + x1) * np.float64(0.5)
-            cy = (y0 + y1) * np.float64(0.5)
-            X = (a[0] * cx + a[1] * cy) + a[2]
-            Y = (a[3] * cx + a[4] * cy) + a[5]
-            if np.isfinite(X) and np.isfinite(Y):
-                pts[i] = (X, Y)
-                valid.append(i)
-        order = sorted(valid, key=lambda i: (-float(scores[i]), i))        # -0.0 == 0.0: the index breaks the tie
-        r2 = np.float64(radius) * np.float64(radius)
-        individual = np.full(n, -1, dtype=np.int64)
-        kx, ky = np.empty(len(order)), np.empty(len(order))
-        klabel = np.empty(len(order), dtype=np.int64)
-        kframes = np.zeros((len(order), max(F, 1)), dtype=bool)           # kframes[q, f]: individual q has a member of frame f
-        keeper, members = [], []
-        for p in order:
-            k = len(keeper)
-            dx, dy = pts[p, 0] - kx[:k], pts[p, 1] - ky[:k]
-            d2 = dx * dx + dy * dy
-            ok = (d2 <= r2) & ~kframes[:k, frame[p]]
-            if same_class:
-                ok &= klabel[:k] == labels[p]
-            if ok.any():
-                q = int(np.argmin(np.where(ok, d2, np.inf)))                # first minimum: the individual founded earlier
-                members[q] += 1
-            else:
-                q = k
-                kx[q], ky[q], klabel[q] = pts[p, 0], pts[p, 1], labels[p]
-                keeper.append(p)
-                members.append(1)
-            kframes[q, frame[p]] = True
-            individual[p] = q
-    return {"points": pts, "individual": individual, "keeper": np.array(keeper, dtype=np.int64),
-            "members": np.array(members, dtype=np.int64), "count": len(keeper)}
 
 
 def _pt_boxes(xy):
@@ -224,14 +174,11 @@ def test_census_abi_argument_errors_without_gpu():
 
 
 def test_census_abi_13_and_symbols():
-    hdr = open(os.path.join(ROOT, "include", "wm_hip.h")).read()
-    assert int(re.search(r"#define WM_ABI_VERSION (\d+)", hdr).group(1)) == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
-    for name in ("wm_census", "wm_census_scratch_bytes"):
-        assert name in N.SYMBOLS and re.search(r"\b%s\(" % name, hdr)
-        assert getattr(N.lib(), name) is not None
-    for macro, val in (("WM_CENSUS_MAX_DETS", N.CENSUS_MAX_DETS), ("WM_CENSUS_SAME_CLASS", N.CENSUS_SAME_CLASS),
-                       ("WM_CENSUS_UNSOLVED", N.CENSUS_UNSOLVED)):
-        assert int(re.search(r"#define %s (\d+)" % macro, hdr).group(1)) == val
+    assert macro("WM_ABI_VERSION") == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
+    assert entry_is_whole("wm_census") and entry_is_whole("wm_census_scratch_bytes", returns="int64_t")
+    for name, val in (("WM_CENSUS_MAX_DETS", N.CENSUS_MAX_DETS), ("WM_CENSUS_SAME_CLASS", N.CENSUS_SAME_CLASS),
+                      ("WM_CENSUS_UNSOLVED", N.CENSUS_UNSOLVED)):
+        assert macro(name) == val, name
     assert tiling.CENSUS_MAX_DETS == 262144
 
 

@@ -1,131 +1,24 @@
 """Survey coverage (include/wm_hip.h "Survey coverage", tiling.coverage): the ground a survey saw, its gaps, and the
-census' individuals per cell.  The rule has no reference behaviour; coverage_oracle below restates it sequentially -- one
-cell and one point at a time, numpy float64, the header's operation order -- and the device result must equal it exactly:
-everything is an integer, so every comparison is assert_array_equal and there is no tolerance anywhere."""
-import ctypes as C
+census' individuals per cell.  The rule has no reference behaviour; coverage_oracle (tests/ground_oracle.py) restates it
+sequentially -- one cell and one point at a time, numpy float64, the header's operation order -- and the device result must
+equal it exactly: everything is an integer, so every comparison is assert_array_equal and there is no tolerance anywhere."""
 import functools
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+from ground_cases import (FRAME_A, FRAME_B, FRAME_SWEEP, GRID_SWEEP, INF, NAN, ORIGIN_CELL_SWEEP, _case, _geometries, _p, entry_is_whole, header,
+                          last_error, macro)
+from ground_oracle import coverage_oracle, coverage_oracle_by_frame
 from survey_util import _axis, _kernel_constants, _some_frames, _yawed, _yawed_90
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F64 = np.float64
-
-
-def _sees(b, h, w, X, Y):
-    """sees(f, X, Y) for every frame at once: b (F,6) float64, h and w (F,) and the scalars X, Y.  Elementwise numpy
-    arithmetic is one correctly rounded IEEE operation per element and operator, in the order written."""
-    u = (b[:, 0] * X + b[:, 1] * Y) + b[:, 2]
-    v = (b[:, 3] * X + b[:, 4] * Y) + b[:, 5]
-    return (h >= 1) & (w >= 1) & (0 <= u) & (u < w) & (0 <= v) & (v < h)
-
-
-def coverage_oracle(g2p, size, x0, y0, cell, gx, gy, points=None, labels=None):
-    """The coverage rule, one cell and one point at a time.  Returns coverage (gy,gx) int64 and stats (16,) int64, and
-    with points also seen_by (P,), cell (P,2), counts (7,gy,gx) and pstats (2,), all int64."""
-    b = np.asarray(g2p, dtype=F64).reshape(-1, 6)
-    size = np.asarray(size, dtype=np.int64).reshape(-1, 2)
-    h, w = size[:, 0], size[:, 1]
-    x0, y0, cell = F64(x0), F64(y0), F64(cell)
-    cov = np.zeros((gy, gx), dtype=np.int64)
-    stats = np.zeros(16, dtype=np.int64)
-    with np.errstate(all="ignore"):
-        for j in range(gy):
-            Yc = y0 + (F64(j) + F64(0.5)) * cell
-            for i in range(gx):
-                Xc = x0 + (F64(i) + F64(0.5)) * cell
-                m = int(_sees(b, h, w, Xc, Yc).sum())
-                cov[j, i] = m
-                stats[min(m, 15)] += 1
-        out = {"coverage": cov, "stats": stats}
-        if points is None:
-            return out
-        pts = np.asarray(points, dtype=F64).reshape(-1, 2)
-        labels = np.asarray(labels, dtype=np.int64).reshape(-1)
-        P = pts.shape[0]
-        seen = np.zeros(P, dtype=np.int64)
-        cidx = np.full((P, 2), -1, dtype=np.int64)
-        counts = np.zeros((7, gy, gx), dtype=np.int64)
-        pstats = np.zeros(2, dtype=np.int64)
-        for p in range(P):
-            X, Y = pts[p]
-            finite = bool(np.isfinite(X) and np.isfinite(Y))
-            if finite:
-                seen[p] = int(_sees(b, h, w, X, Y).sum())
-            fi = np.floor((X - x0) / cell)
-            fj = np.floor((Y - y0) / cell)
-            if finite and 0 <= fi < gx and 0 <= fj < gy and 0 <= labels[p] < 7:
-                cidx[p] = (int(fj), int(fi))
-                counts[labels[p], int(fj), int(fi)] += 1
-                pstats[0] += 1
-            else:
-                pstats[1] += 1
-    out.update({"seen_by": seen, "cell": cidx, "counts": counts, "pstats": pstats})
-    return out
-
-
-def coverage_oracle_by_frame(g2p, size, x0, y0, cell, gx, gy):
-    """The raster part of the rule, one FRAME at a time over the window of cells around its footprint (the corners of the
-    pixel rectangle mapped back through the numerically inverted affine, two cells of margin; the whole grid for a frame
-    that cannot be inverted): the same operations per cell as coverage_oracle, fast enough for the grids tools/coverage_time.py
-    times.  Checked equal to coverage_oracle below."""
-    b = np.asarray(g2p, dtype=F64).reshape(-1, 6)
-    size = np.asarray(size, dtype=np.int64).reshape(-1, 2)
-    x0, y0, cell = F64(x0), F64(y0), F64(cell)
-    Xc = x0 + (np.arange(gx, dtype=F64) + F64(0.5)) * cell
-    Yc = y0 + (np.arange(gy, dtype=F64) + F64(0.5)) * cell
-    cov = np.zeros((gy, gx), dtype=np.int64)
-    with np.errstate(all="ignore"):
-        for f in range(b.shape[0]):
-            h, w = size[f]
-            if h < 1 or w < 1 or not np.isfinite(b[f]).all():
-                continue
-            i0, i1, j0, j1 = 0, gx, 0, gy
-            A = np.array([[b[f, 0], b[f, 1]], [b[f, 3], b[f, 4]]])
-            if abs(np.linalg.det(A)) > 0:
-                corners = np.array([[0, 0], [w, 0], [0, h], [w, h]], dtype=F64) - b[f, [2, 5]]
-                ground = np.linalg.solve(A, corners.T).T
-                if np.isfinite(ground).all():
-                    i0 = int(np.clip(np.floor((ground[:, 0].min() - x0) / cell) - 2, 0, gx))
-                    i1 = int(np.clip(np.ceil((ground[:, 0].max() - x0) / cell) + 2, 0, gx))
-                    j0 = int(np.clip(np.floor((ground[:, 1].min() - y0) / cell) - 2, 0, gy))
-                    j1 = int(np.clip(np.ceil((ground[:, 1].max() - y0) / cell) + 2, 0, gy))
-            X, Y = Xc[None, i0:i1], Yc[j0:j1, None]
-            u = (b[f, 0] * X + b[f, 1] * Y) + b[f, 2]
-            v = (b[f, 3] * X + b[f, 4] * Y) + b[f, 5]
-            cov[j0:j1, i0:i1] += (0 <= u) & (u < w) & (0 <= v) & (v < h)
-    stats = np.bincount(np.minimum(cov, 15).ravel(), minlength=16).astype(np.int64)
-    return {"coverage": cov, "stats": stats}
-
-
-def _case(frames, x0, y0, cell, gx, gy, points=None, labels=None):
-    """frames: a list of (g2p as 6 numbers or (2,3), height, width)."""
-    g2p = np.array([np.asarray(f[0], dtype=F64).reshape(6) for f in frames], dtype=F64).reshape(-1, 6)
-    size = np.array([[f[1], f[2]] for f in frames], dtype=np.int32).reshape(-1, 2)
-    c = {"g2p": g2p, "size": size, "x0": float(x0), "y0": float(y0), "cell": float(cell), "gx": gx, "gy": gy, "points": None, "labels": None}
-    if points is not None:
-        c["points"] = np.asarray(points, dtype=F64).reshape(-1, 2)
-        c["labels"] = np.asarray(labels, dtype=np.int32).reshape(-1)
-    return c
-
 
 def _oracle(case):
     return coverage_oracle(case["g2p"], case["size"], case["x0"], case["y0"], case["cell"], case["gx"], case["gy"], case["points"], case["labels"])
-
-
-# Frame A: 8 x 4 px (W x H), 0.5 m pixels, footprint [0, 4) x (0, 2] m; frame B: the same, 2 m further east.
-FRAME_A = ([2, 0, 0, 0, -2, 4], 4, 8)
-FRAME_B = ([2, 0, -4, 0, -2, 4], 4, 8)
-NAN = float("nan")
-INF = float("inf")
 
 
 # name -> (case, expected coverage rows from j = 0 (south) upwards, expected stats[0:3])
@@ -287,37 +180,20 @@ def test_coverage_python_argument_errors_before_device_work():
 
 def _abi_raster(n_frames=2, x0=0.0, y0=0.0, cell=1.0, gx=5, gy=3, g2p=0x2000, size=0x3000, cov=0x4000, stats=0x5000):
     """wm_coverage_raster with fake, never dereferenced device pointers: only paths that return before any HIP call."""
-    p = lambda v: C.c_void_p(v) if v else None
-    return N.lib().wm_coverage_raster(p(g2p), p(size), n_frames, x0, y0, cell, gx, gy, p(cov), p(stats), None)
+    return N.lib().wm_coverage_raster(_p(g2p), _p(size), n_frames, x0, y0, cell, gx, gy, _p(cov), _p(stats), None)
 
 
 def _abi_points(n_points=4, n_frames=2, x0=0.0, y0=0.0, cell=1.0, gx=5, gy=3, g2p=0x2000, size=0x3000, pts=0x4000, labels=0x5000,
                 seen=0x6000, cidx=0x7000, counts=0x8000, pstats=0x9000):
-    p = lambda v: C.c_void_p(v) if v else None
-    return N.lib().wm_coverage_points(p(g2p), p(size), n_frames, p(pts), p(labels), n_points, x0, y0, cell, gx, gy, p(seen), p(cidx),
-                                      p(counts), p(pstats), None)
+    return N.lib().wm_coverage_points(_p(g2p), _p(size), n_frames, _p(pts), _p(labels), n_points, x0, y0, cell, gx, gy, _p(seen), _p(cidx),
+                                      _p(counts), _p(pstats), None)
 
 
 def test_coverage_abi_argument_errors_without_gpu():
-    err = lambda: N.lib().wm_last_error().decode()
+    err = last_error
     for call in (_abi_raster, _abi_points):
-        assert call(gx=0) < 0 and "gx" in err()
-        assert call(gx=N.COVERAGE_MAX_SIDE + 1) < 0 and "gx" in err()
-        assert call(gy=0) < 0 and "gy" in err()
-        assert call(gy=-4) < 0 and "gy" in err()
-        assert call(gy=N.COVERAGE_MAX_SIDE + 1) < 0 and "gy" in err()
-        assert call(gx=16384, gy=8192) < 0 and "gx * gy" in err()
-        assert call(gx=8192, gy=8192 + 1) < 0 and "gx * gy" in err()
-        assert call(n_frames=-1) < 0 and "n_frames" in err()
-        assert call(n_frames=N.COVERAGE_MAX_FRAMES + 1) < 0 and "n_frames" in err()
-        for bad in (NAN, INF, -INF):
-            assert call(x0=bad) < 0 and "x0" in err()
-            assert call(y0=bad) < 0 and "y0" in err()
-        for bad in (0.0, -1.0, NAN, INF):
-            assert call(cell=bad) < 0 and "cell" in err()
-        assert call(g2p=0) < 0 and "g2p_dev" in err()
-        assert call(size=0) < 0 and "size_dev" in err()
-        assert call(g2p=0x2004) < 0 and "aligned" in err()
+        for kwargs, word in GRID_SWEEP + FRAME_SWEEP + ORIGIN_CELL_SWEEP:
+            assert call(**kwargs) < 0 and word in err(), (call.__name__, kwargs, word, err())
     assert _abi_raster(cov=0) < 0 and "coverage_dev" in err()
     assert _abi_raster(stats=0) < 0 and "stats_dev" in err()
     assert _abi_raster(cov=0x4001) < 0 and "aligned" in err()
@@ -333,16 +209,14 @@ def test_coverage_abi_argument_errors_without_gpu():
 
 
 def test_coverage_symbols_and_abi_13():
-    hdr = open(os.path.join(ROOT, "include", "wm_hip.h")).read()
-    assert int(re.search(r"#define WM_ABI_VERSION (\d+)", hdr).group(1)) == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
-    assert "Survey coverage" in hdr and "13, additive" in hdr
+    assert macro("WM_ABI_VERSION") == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
+    assert "Survey coverage" in header() and "13, additive" in header()
     for name in ("wm_coverage_raster", "wm_coverage_points"):
-        assert name in N.SYMBOLS and re.search(r"\b%s\(" % name, hdr)
-        assert getattr(N.lib(), name) is not None
-    for macro, val in (("WM_COVERAGE_MAX_SIDE", N.COVERAGE_MAX_SIDE), ("WM_COVERAGE_MAX_CELLS", N.COVERAGE_MAX_CELLS),
-                       ("WM_COVERAGE_MAX_FRAMES", N.COVERAGE_MAX_FRAMES), ("WM_COVERAGE_CLASSES", N.COVERAGE_CLASSES),
-                       ("WM_COVERAGE_STATS", N.COVERAGE_STATS)):
-        assert int(re.search(r"#define %s (\d+)" % macro, hdr).group(1)) == val
+        assert entry_is_whole(name), name
+    for name, val in (("WM_COVERAGE_MAX_SIDE", N.COVERAGE_MAX_SIDE), ("WM_COVERAGE_MAX_CELLS", N.COVERAGE_MAX_CELLS),
+                      ("WM_COVERAGE_MAX_FRAMES", N.COVERAGE_MAX_FRAMES), ("WM_COVERAGE_CLASSES", N.COVERAGE_CLASSES),
+                      ("WM_COVERAGE_STATS", N.COVERAGE_STATS)):
+        assert macro(name) == val, name
     assert (N.COVERAGE_MAX_SIDE, N.COVERAGE_MAX_CELLS, N.COVERAGE_MAX_FRAMES) == (16384, 2 ** 26, 65535)
     assert tiling.COVERAGE_MAX_CELLS == 2 ** 26 and tiling.CENSUS_CLASSES == N.COVERAGE_CLASSES
     k = _kernel_constants()
@@ -400,12 +274,12 @@ def _run_and_check(case, want=None):
 def _gpu_case(name):
     """name -> (case, oracle result), computed once."""
     k = _kernel_constants()
-    bx, by = k["block_x"], k["block_y"]
-    if name.startswith("grid_"):                                                # grid_<gx>x<gy>: none a multiple of the block
+    if name in _geometries():
+        frames, grid = _geometries()[name]
+        case = _case(frames, *grid)
+    elif name.startswith("grid_"):                                                # grid_<gx>x<gy>: none a multiple of the block
         gx, gy = (int(v) for v in name[5:].split("x"))
         case = _case(_some_frames(gx, gy, 0.7, gx) + [_axis(-1.0, gx * 0.7 / 2, -1.0, gy, 4.0)], 0.0, 0.0, 0.7, gx, gy)
-    elif name == "no_frames":
-        case = _case([], 0.0, 0.0, 0.7, 70, 19)
     elif name == "one_frame":
         case = _case(_some_frames(70, 19, 0.7, 1, n=1), 0.0, 0.0, 0.7, 70, 19)
     elif name == "past_one_chunk":
@@ -415,25 +289,8 @@ def _gpu_case(name):
         far[100] = _axis(0.0, 49.0, 0.0, 13.0, 4.0)[:1] + (0, 196)
         near = [_yawed((20.0, 6.0), 0.05, 30.0, 300, 400), _axis(10.0, 30.0, 2.0, 9.0, 4.0), _yawed((40.0, 10.0), 0.04, 115.0, 300, 400)]
         case = _case(far + near, 0.0, 0.0, 0.7, 70, 19)
-    elif name == "cull_tiny_frame":                                             # 0.5 m of footprint around one centre, inside one block
-        case = _case([_axis(100.25, 100.75, 40.25, 40.75, 8.0)], 0.0, 0.0, 1.0, 257, 65)
-    elif name == "cull_thin_between_rows":                                      # (40.625, 40.875]: between the rows of centres 40.5 and 41.5
-        case = _case([_axis(0.0, 257.0, 40.625, 40.875, 8.0)], 0.0, 0.0, 1.0, 257, 65)
-    elif name == "cull_thin_on_one_row":                                        # (40.375, 40.625] holds the row of centres 40.5
-        case = _case([_axis(0.0, 257.0, 40.375, 40.625, 8.0)], 0.0, 0.0, 1.0, 257, 65)
-    elif name == "cull_yaw_45":                                                 # a 1.5 m x 150 m strip across the grid's blocks
-        case = _case([_yawed((128.0, 32.0), 0.05, 45.0, 30, 3000), _yawed((60.3, 30.1), 0.05, 135.0, 3000, 20)], 0.0, 0.0, 1.0, 257, 65)
     elif name == "cover_all":
         case = _case([_axis(-10.0, 300.0, -10.0, 100.0, 2.0), _yawed((128.0, 32.0), 0.5, 45.0, 1200, 1200)], 0.0, 0.0, 1.0, 257, 65)
-    elif name == "block_edges":
-        # centres at multiples of 0.5 m; footprints whose edges are the centres of the first cells of blocks: the west
-        # edge is inside, the east edge outside; the north edge inside, the south edge outside
-        c = 0.5
-        frames = [_axis(bx * c, 2 * bx * c, (by - 1) * c, (2 * by - 1) * c, 2.0),            # columns bx..2bx-1, rows by..2by-1
-                  _axis(0.0, bx * c, -c, (by - 1) * c, 2.0),                                   # block (0, 0) exactly
-                  _axis(2 * bx * c, 4 * bx * c, (by - 1) * c, (2 * by - 1) * c, 2.0),          # east of the first, to the grid's edge region
-                  _axis((bx - 1) * c, (bx + 1) * c, (by - 2) * c, by * c, 2.0)]                # 2 x 2 cells across a block corner
-        case = _case(frames, -0.25, -0.25, c, 257, 65)
     elif name == "random_survey":
         rng = np.random.default_rng(11)
         x0, y0, cell, gx, gy = 500000.1, 6000000.7, 0.3, 300, 200

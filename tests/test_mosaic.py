@@ -1,10 +1,8 @@
 """Survey mosaic (include/wm_hip.h "Survey mosaic", tiling.mosaic): the frames of a survey laid onto the ground grid.  The rule
-has no reference behaviour; mosaic_oracle below restates it sequentially -- one cell at a time, numpy float64, vectorised
-over the frames only, the header's operation order -- and the device result must equal it exactly: sources are integers and
-pixels are uint8 behind arithmetic that is rounded once per operation, so every comparison is assert_array_equal and there
-is no tolerance anywhere."""
-import ctypes as C
-import functools
+has no reference behaviour; mosaic_oracle (tests/ground_oracle.py) restates it sequentially -- one cell at a time, numpy
+float64, vectorised over the frames only, the header's operation order -- and the device result must equal it exactly: sources
+are integers and pixels are uint8 behind arithmetic that is rounded once per operation, so every comparison is
+assert_array_equal and there is no tolerance anywhere."""
 import os
 import re
 
@@ -12,172 +10,15 @@ import numpy as np
 import pytest
 import torch
 
-from survey_util import DEV, _axis, _kernel_constants, _Lazy, _some_frames, _up, _yawed, _yawed_90
+from ground_cases import (FRAME_A, FRAME_B, FRAME_SWEEP, GRID_SWEEP, INF, NAN, ORIGIN_CELL_SWEEP, RESIDENT_SWEEP, _case, _mosaic_gpu_case,
+                          _mosaic_oracle, _mosaic_python_case, _p, entry_is_whole, header, last_error, macro)
+from ground_oracle import MODES, SENTINEL, mosaic_oracle, mosaic_oracle_by_frame, uv
+from survey_util import DEV, ROOT, _kernel_constants, _Lazy, _up, _yawed_90
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
 from wildlifemapper_amd._survey import _frame_descs
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F64 = np.float64
-NAN = float("nan")
-INF = float("inf")
-MODES = {"nearest": N.MOSAIC_NEAREST, "bilinear": N.MOSAIC_BILINEAR}
-SENTINEL = (7, 201, 77)
-
-
-def _sample(img, u, v, mode):
-    """One cell from its source frame img (H,W,3) uint8 at the pixel position (u, v), by the header's sampling rule."""
-    h, w = img.shape[:2]
-    if mode == "nearest":
-        return img[int(np.floor(v)), int(np.floor(u))]
-    fu, fv = u - F64(0.5), v - F64(0.5)
-    xf, yf = np.floor(fu), np.floor(fv)
-    tx, ty = fu - xf, fv - yf
-    xa, xb = min(max(int(xf), 0), w - 1), min(max(int(xf) + 1, 0), w - 1)
-    ya, yb = min(max(int(yf), 0), h - 1), min(max(int(yf) + 1, 0), h - 1)
-    p00, p10, p01, p11 = (img[y, x].astype(F64) for y, x in ((ya, xa), (ya, xb), (yb, xa), (yb, xb)))
-    a = (F64(1.0) - tx) * p00 + tx * p10
-    b = (F64(1.0) - tx) * p01 + tx * p11
-    val = (F64(1.0) - ty) * a + ty * b
-    return np.minimum(np.floor(val + F64(0.5)), F64(255.0)).astype(np.uint8)
-
-
-def mosaic_oracle(g2p, size, x0, y0, cell, gx, gy, frames=None, fill=SENTINEL):
-    """The mosaic rule, one cell at a time.  Returns source (gy,gx), won (F,), stats (2,), all int64, and with frames (a
-    list of (H,W,3) uint8 arrays, None for a frame without pixels) the pictures 'nearest' and 'bilinear' (gy,gx,3) uint8,
-    row 0 south, cells without a source holding `fill`.  Elementwise numpy arithmetic is one correctly rounded IEEE
-    operation per element and operator, in the order written; argmin returns the first, that is the lowest, index."""
-    b = np.asarray(g2p, dtype=F64).reshape(-1, 6)
-    size = np.asarray(size, dtype=np.int64).reshape(-1, 2)
-    h, w = size[:, 0], size[:, 1]
-    cu, cv = F64(0.5) * w.astype(F64), F64(0.5) * h.astype(F64)
-    x0, y0, cell = F64(x0), F64(y0), F64(cell)
-    nf = b.shape[0]
-    source = np.full((gy, gx), -1, dtype=np.int64)
-    pics = {m: np.empty((gy, gx, 3), dtype=np.uint8) for m in MODES} if frames is not None else {}
-    for p in pics.values():
-        p[:] = np.asarray(fill, dtype=np.uint8)
-    with np.errstate(all="ignore"):
-        for j in range(gy):
-            Yc = y0 + (F64(j) + F64(0.5)) * cell
-            for i in range(gx):
-                if not nf:
-                    continue
-                Xc = x0 + (F64(i) + F64(0.5)) * cell
-                u = (b[:, 0] * Xc + b[:, 1] * Yc) + b[:, 2]
-                v = (b[:, 3] * Xc + b[:, 4] * Yc) + b[:, 5]
-                sees = (h >= 1) & (w >= 1) & (0 <= u) & (u < w) & (0 <= v) & (v < h)
-                if not sees.any():
-                    continue
-                du, dv = u - cu, v - cv
-                e = du * du + dv * dv
-                f = int(np.argmin(np.where(sees, e, np.inf)))
-                source[j, i] = f
-                for m, p in pics.items():
-                    p[j, i] = _sample(frames[f], u[f], v[f], m)
-    seen = source >= 0
-    out = {"source": source, "won": np.bincount(source[seen], minlength=nf).astype(np.int64),
-           "stats": np.array([seen.sum(), (~seen).sum()], dtype=np.int64)}
-    out.update(pics)
-    return out
-
-
-def _sample_many(img, u, v, mode):
-    """_sample for arrays of positions: the same operations, elementwise."""
-    h, w = img.shape[:2]
-    if mode == "nearest":
-        return img[np.floor(v).astype(np.int64), np.floor(u).astype(np.int64)]
-    fu, fv = u - F64(0.5), v - F64(0.5)
-    xf, yf = np.floor(fu), np.floor(fv)
-    tx, ty = (fu - xf)[:, None], (fv - yf)[:, None]
-    xa, xb = np.clip(xf.astype(np.int64), 0, w - 1), np.clip(xf.astype(np.int64) + 1, 0, w - 1)
-    ya, yb = np.clip(yf.astype(np.int64), 0, h - 1), np.clip(yf.astype(np.int64) + 1, 0, h - 1)
-    p00, p10, p01, p11 = img[ya, xa].astype(F64), img[ya, xb].astype(F64), img[yb, xa].astype(F64), img[yb, xb].astype(F64)
-    a = (F64(1.0) - tx) * p00 + tx * p10
-    b = (F64(1.0) - tx) * p01 + tx * p11
-    val = (F64(1.0) - ty) * a + ty * b
-    return np.minimum(np.floor(val + F64(0.5)), F64(255.0)).astype(np.uint8)
-
-
-def mosaic_oracle_by_frame(g2p, size, x0, y0, cell, gx, gy, frames=None, fill=SENTINEL, modes=tuple(MODES)):
-    """The same rule one FRAME at a time over the window of cells around its footprint (the window of
-    test_coverage.coverage_oracle_by_frame), with a running best e per cell: frames in ascending order and a strict <, so
-    the lowest index keeps a tie.  The same operations per cell as mosaic_oracle, fast enough for the grids
-    tools/mosaic_time.py times.  Checked equal to mosaic_oracle below."""
-    b = np.asarray(g2p, dtype=F64).reshape(-1, 6)
-    size = np.asarray(size, dtype=np.int64).reshape(-1, 2)
-    x0, y0, cell = F64(x0), F64(y0), F64(cell)
-    Xc = x0 + (np.arange(gx, dtype=F64) + F64(0.5)) * cell
-    Yc = y0 + (np.arange(gy, dtype=F64) + F64(0.5)) * cell
-    best = np.full((gy, gx), np.inf, dtype=F64)
-    source = np.full((gy, gx), -1, dtype=np.int64)
-    windows = {}
-    with np.errstate(all="ignore"):
-        for f in range(b.shape[0]):
-            h, w = size[f]
-            if h < 1 or w < 1 or not np.isfinite(b[f]).all():
-                continue
-            i0, i1, j0, j1 = 0, gx, 0, gy
-            A = np.array([[b[f, 0], b[f, 1]], [b[f, 3], b[f, 4]]])
-            if abs(np.linalg.det(A)) > 0:
-                corners = np.array([[0, 0], [w, 0], [0, h], [w, h]], dtype=F64) - b[f, [2, 5]]
-                ground = np.linalg.solve(A, corners.T).T
-                if np.isfinite(ground).all():
-                    i0 = int(np.clip(np.floor((ground[:, 0].min() - x0) / cell) - 2, 0, gx))
-                    i1 = int(np.clip(np.ceil((ground[:, 0].max() - x0) / cell) + 2, 0, gx))
-                    j0 = int(np.clip(np.floor((ground[:, 1].min() - y0) / cell) - 2, 0, gy))
-                    j1 = int(np.clip(np.ceil((ground[:, 1].max() - y0) / cell) + 2, 0, gy))
-            windows[f] = (i0, i1, j0, j1)
-            X, Y = Xc[None, i0:i1], Yc[j0:j1, None]
-            u = (b[f, 0] * X + b[f, 1] * Y) + b[f, 2]
-            v = (b[f, 3] * X + b[f, 4] * Y) + b[f, 5]
-            du, dv = u - F64(0.5) * F64(w), v - F64(0.5) * F64(h)
-            e = du * du + dv * dv
-            better = (0 <= u) & (u < w) & (0 <= v) & (v < h) & (e < best[j0:j1, i0:i1])
-            best[j0:j1, i0:i1][better] = e[better]
-            source[j0:j1, i0:i1][better] = f
-        seen = source >= 0
-        out = {"source": source, "won": np.bincount(source[seen], minlength=b.shape[0]).astype(np.int64),
-               "stats": np.array([seen.sum(), (~seen).sum()], dtype=np.int64)}
-        if frames is None:
-            return out
-        for m in modes:
-            out[m] = np.empty((gy, gx, 3), dtype=np.uint8)
-            out[m][:] = np.asarray(fill, dtype=np.uint8)
-        for f, (i0, i1, j0, j1) in windows.items():
-            jj, ii = np.nonzero(source[j0:j1, i0:i1] == f)
-            if not len(jj):
-                continue
-            X, Y = Xc[i0 + ii], Yc[j0 + jj]
-            u = (b[f, 0] * X + b[f, 1] * Y) + b[f, 2]
-            v = (b[f, 3] * X + b[f, 4] * Y) + b[f, 5]
-            for m in modes:
-                out[m][j0 + jj, i0 + ii] = _sample_many(frames[f], u, v, m)
-    return out
-
-
-def _content(h, w, seed):
-    return np.random.default_rng(seed).integers(0, 256, (h, w, 3), dtype=np.uint8)
-
-
-def _case(frames, x0, y0, cell, gx, gy, images=None, seed=0):
-    """frames: a list of (g2p as 6 numbers or (2,3), height, width).  images: one (H,W,3) uint8 array per frame; by default
-    random content for every frame of at least 1 x 1 px and None for the others."""
-    g2p = np.array([np.asarray(f[0], dtype=F64).reshape(6) for f in frames], dtype=F64).reshape(-1, 6)
-    size = np.array([[f[1], f[2]] for f in frames], dtype=np.int32).reshape(-1, 2)
-    if images is None:
-        images = [_content(h, w, seed * 100003 + k) if h >= 1 and w >= 1 else None for k, (h, w) in enumerate(size.tolist())]
-    return {"g2p": g2p, "size": size, "x0": float(x0), "y0": float(y0), "cell": float(cell), "gx": gx, "gy": gy, "images": images}
-
-
-def _oracle(case):
-    return mosaic_oracle(case["g2p"], case["size"], case["x0"], case["y0"], case["cell"], case["gx"], case["gy"], case["images"])
-
-
-# Frame A: 8 x 4 px (W x H), 0.5 m pixels, footprint [0, 4) x (0, 2] m, u = 2 X, v = 4 - 2 Y; frame B: the same, 2 m further
-# east.  Pixel (y, x) of either holds (16 y + x, 100 + x, 200 - y).
-FRAME_A = ([2, 0, 0, 0, -2, 4], 4, 8)
-FRAME_B = ([2, 0, -4, 0, -2, 4], 4, 8)
+# Pixel (y, x) of frame A and of frame B (ground_cases.py: u = 2 X, v = 4 - 2 Y; B 2 m further east) holds (16 y + x, 100 + x, 200 - y).
 RAMP = np.array([[(16 * y + x, 100 + x, 200 - y) for x in range(8)] for y in range(4)], dtype=np.uint8)
 # 2 x 1 px holding 10 and 13 in every channel, 1 m pixels: u = X, v = 1 - Y
 FRAME_PAIR = ([1, 0, 0, 0, -1, 1], 1, 2)
@@ -193,19 +34,19 @@ def _seam_cases():
     cases = {}
     none5 = [-1] * 5
     one = [[0, 0, 0, 0, -1], [0, 0, 0, 0, -1], none5]
-    cases["one_frame"] = (_case([FRAME_A], 0, 0, 1, 5, 3, [RAMP]), one)
+    cases["one_frame"] = (_case([FRAME_A], 0, 0, 1, 5, 3, images=[RAMP]), one)
     # centres at X = 1..6: A sees 1, 2, 3; B sees 2..5.  At X = 3 both are 2 px from their centre column (u = 6 and u = 2,
     # centre 4) on the same row: the two e are the same number, and the lower index wins
-    cases["two_frames_2m_apart"] = (_case([FRAME_A, FRAME_B], 0.5, 0, 1, 6, 3, [RAMP, RAMP]),
+    cases["two_frames_2m_apart"] = (_case([FRAME_A, FRAME_B], 0.5, 0, 1, 6, 3, images=[RAMP, RAMP]),
                                     [[0, 0, 0, 1, 1, -1], [0, 0, 0, 1, 1, -1], [-1] * 6])
-    cases["two_frames_2m_apart_swapped"] = (_case([FRAME_B, FRAME_A], 0.5, 0, 1, 6, 3, [RAMP, RAMP]),
+    cases["two_frames_2m_apart_swapped"] = (_case([FRAME_B, FRAME_A], 0.5, 0, 1, 6, 3, images=[RAMP, RAMP]),
                                             [[1, 1, 0, 0, 0, -1], [1, 1, 0, 0, 0, -1], [-1] * 6])
-    cases["identical_georeferences"] = (_case([FRAME_A, FRAME_A], 0, 0, 1, 5, 3, [RAMP, RAMP[::-1].copy()]), one)
+    cases["identical_georeferences"] = (_case([FRAME_A, FRAME_A], 0, 0, 1, 5, 3, images=[RAMP, RAMP[::-1].copy()]), one)
     side = [-1, 0, 0, -1]
-    cases["yawed_90"] = (_case([_yawed_90()], 8, 17, 1, 4, 6, [RAMP]), [[-1] * 4, side, side, side, side, [-1] * 4])
+    cases["yawed_90"] = (_case([_yawed_90()], 8, 17, 1, 4, 6, images=[RAMP]), [[-1] * 4, side, side, side, side, [-1] * 4])
     five = [[5, 5, 5, 5, -1], [5, 5, 5, 5, -1], none5]
     never = [([2, NAN, 0, 0, -2, 4], 4, 8), ([2, 0, 0, 0, -2, INF], 4, 8), _singular(), ([2, 0, 0, 0, -2, 4], 0, 8), ([2, 0, 0, 0, -2, 4], 4, -3)]
-    cases["never_a_source"] = (_case(never + [FRAME_A], 0, 0, 1, 5, 3, [RAMP, RAMP, RAMP, None, None, RAMP]), five)
+    cases["never_a_source"] = (_case(never + [FRAME_A], 0, 0, 1, 5, 3, images=[RAMP, RAMP, RAMP, None, None, RAMP]), five)
     return cases
 
 
@@ -216,17 +57,17 @@ SEAM = _seam_cases()
 def _pixel_cases():
     cases = {}
     # centres at X = 0.25 + 0.5 i, Y = 0.25 + 0.5 j: u = i + 0.5, v = 3.5 - j, every centre on a pixel centre
-    cases["on_pixel_centres"] = (_case([FRAME_A], 0, 0, 0.5, 8, 4, [RAMP]), None, RAMP[::-1, :, 0].tolist())
+    cases["on_pixel_centres"] = (_case([FRAME_A], 0, 0, 0.5, 8, 4, images=[RAMP]), None, RAMP[::-1, :, 0].tolist())
     # u = 1 exactly (column 1, not 0), v = 3 exactly (row 3): cell (0, 0) of the 1 m grid
-    cases["nearest_at_integer_u"] = (_case([FRAME_A], 0, 0, 1, 5, 3, [RAMP]), "nearest",
+    cases["nearest_at_integer_u"] = (_case([FRAME_A], 0, 0, 1, 5, 3, images=[RAMP]), "nearest",
                                      [[49, 51, 53, 55, SENTINEL[0]], [17, 19, 21, 23, SENTINEL[0]], [SENTINEL[0]] * 5])
     # the same cells, bilinear: half way between columns and rows, (32 + 33 + 48 + 49) / 4 = 40.5 -> 41
-    cases["bilinear_between_four"] = (_case([FRAME_A], 0, 0, 1, 5, 3, [RAMP]), "bilinear",
+    cases["bilinear_between_four"] = (_case([FRAME_A], 0, 0, 1, 5, 3, images=[RAMP]), "bilinear",
                                       [[41, 43, 45, 47, SENTINEL[0]], [9, 11, 13, 15, SENTINEL[0]], [SENTINEL[0]] * 5])
     # u = 1.0: half way between 10 and 13, 11.5 rounds up
-    cases["bilinear_half_way"] = (_case([FRAME_PAIR], 0.5, 0, 1, 1, 1, [PAIR]), "bilinear", [[12]])
+    cases["bilinear_half_way"] = (_case([FRAME_PAIR], 0.5, 0, 1, 1, 1, images=[PAIR]), "bilinear", [[12]])
     # u = 0.25, 0.75, 1.25, 1.75: the first and the last lie within half a pixel of the edge and replicate it
-    cases["bilinear_edge_replicate"] = (_case([FRAME_PAIR], 0, 0.25, 0.5, 4, 1, [PAIR]), "bilinear", [[10, 11, 12, 13]])
+    cases["bilinear_edge_replicate"] = (_case([FRAME_PAIR], 0, 0.25, 0.5, 4, 1, images=[PAIR]), "bilinear", [[10, 11, 12, 13]])
     return cases
 
 
@@ -236,7 +77,7 @@ PIXEL = _pixel_cases()
 @pytest.mark.parametrize("name", sorted(SEAM))
 def test_oracle_seam_hand_cases(name):
     case, rows = SEAM[name]
-    got = _oracle(case)
+    got = _mosaic_oracle(case)
     assert got["source"].tolist() == rows
     flat = [f for r in rows for f in r]
     assert got["won"].tolist() == [flat.count(f) for f in range(case["g2p"].shape[0])]
@@ -245,9 +86,8 @@ def test_oracle_seam_hand_cases(name):
 
 def test_oracle_two_frames_tie_is_exact():
     case, _ = SEAM["two_frames_2m_apart"]
-    b, Xc, Yc = case["g2p"], F64(3.0), F64(0.5)
-    u = (b[:, 0] * Xc + b[:, 1] * Yc) + b[:, 2]
-    v = (b[:, 3] * Xc + b[:, 4] * Yc) + b[:, 5]
+    b, Xc, Yc = case["g2p"], np.float64(3.0), np.float64(0.5)
+    u, v = uv(b, Xc, Yc)
     e = (u - 4.0) * (u - 4.0) + (v - 2.0) * (v - 2.0)
     assert u.tolist() == [6.0, 2.0] and e[0] == e[1] == 5.0
 
@@ -255,7 +95,7 @@ def test_oracle_two_frames_tie_is_exact():
 @pytest.mark.parametrize("name", sorted(PIXEL))
 def test_oracle_pixel_hand_cases(name):
     case, mode, rows = PIXEL[name]
-    got = _oracle(case)
+    got = _mosaic_oracle(case)
     for m in ([mode] if mode else sorted(MODES)):
         assert got[m][:, :, 0].tolist() == rows, m
     if name == "on_pixel_centres":
@@ -269,9 +109,9 @@ def test_oracle_pixel_hand_cases(name):
 def test_oracle_by_frame_equals_oracle(name):
     if name in SEAM or name in PIXEL:
         case = (SEAM.get(name) or PIXEL.get(name))[0]
-        want = _oracle(case)
+        want = _mosaic_oracle(case)
     else:
-        case, want = _gpu_case(name)
+        case, want = _mosaic_gpu_case(name)
     got = mosaic_oracle_by_frame(case["g2p"], case["size"], case["x0"], case["y0"], case["cell"], case["gx"], case["gy"], case["images"])
     assert set(got) == set(want)
     for key in want:
@@ -371,46 +211,28 @@ def test_mosaic_python_argument_errors_before_device_work():
 
 def _abi_plan(n_frames=2, x0=0.0, y0=0.0, cell=1.0, gx=5, gy=3, g2p=0x2000, size=0x3000, source=0x4000, won=0x5000, stats=0x6000):
     """wm_mosaic_plan with fake, never dereferenced device pointers: only paths that return before any HIP call."""
-    p = lambda v: C.c_void_p(v) if v else None
-    return N.lib().wm_mosaic_plan(p(g2p), p(size), n_frames, x0, y0, cell, gx, gy, p(source), p(won), p(stats), None)
+    return N.lib().wm_mosaic_plan(_p(g2p), _p(size), n_frames, x0, y0, cell, gx, gy, _p(source), _p(won), _p(stats), None)
 
 
 def _abi_fill(n_frames=2, n_resident=2, x0=0.0, y0=0.0, cell=1.0, gx=5, gy=3, mode=N.MOSAIC_BILINEAR, flags=0, frames=0x1000, slot=0x7000,
               g2p=0x2000, size=0x3000, source=0x4000, mosaic=0x8000, status=0x9000):
-    p = lambda v: C.c_void_p(v) if v else None
-    return N.lib().wm_mosaic_fill_u8(p(frames), n_resident, p(slot), p(g2p), p(size), n_frames, x0, y0, cell, gx, gy, p(source), mode, flags,
-                                     p(mosaic), p(status), None)
+    return N.lib().wm_mosaic_fill_u8(_p(frames), n_resident, _p(slot), _p(g2p), _p(size), n_frames, x0, y0, cell, gx, gy, _p(source), mode, flags,
+                                     _p(mosaic), _p(status), None)
 
 
 def test_mosaic_abi_argument_errors_without_gpu():
-    err = lambda: N.lib().wm_last_error().decode()
+    err = last_error
     for call in (_abi_plan, _abi_fill):
-        assert call(gx=0) < 0 and "gx" in err()
-        assert call(gx=N.COVERAGE_MAX_SIDE + 1) < 0 and "gx" in err()
-        assert call(gy=0) < 0 and "gy" in err()
-        assert call(gy=-4) < 0 and "gy" in err()
-        assert call(gy=N.COVERAGE_MAX_SIDE + 1) < 0 and "gy" in err()
-        assert call(gx=16384, gy=8192) < 0 and "gx * gy" in err()
-        assert call(gx=8192, gy=8192 + 1) < 0 and "gx * gy" in err()
-        assert call(n_frames=-1) < 0 and "n_frames" in err()
-        assert call(n_frames=N.COVERAGE_MAX_FRAMES + 1) < 0 and "n_frames" in err()
-        for bad in (NAN, INF, -INF):
-            assert call(x0=bad) < 0 and "x0" in err()
-            assert call(y0=bad) < 0 and "y0" in err()
-        for bad in (0.0, -1.0, NAN, INF):
-            assert call(cell=bad) < 0 and "cell" in err()
-        assert call(g2p=0) < 0 and "g2p_dev" in err()
-        assert call(size=0) < 0 and "size_dev" in err()
-        assert call(g2p=0x2004) < 0 and "aligned" in err()
-        assert call(size=0x3002) < 0 and "aligned" in err()
+        for kwargs, word in GRID_SWEEP + FRAME_SWEEP + ORIGIN_CELL_SWEEP:
+            assert call(**kwargs) < 0 and word in err(), (call.__name__, kwargs, word, err())
         assert call(source=0) < 0 and "source_dev" in err()
         assert call(source=0x4002) < 0 and "aligned" in err()
     assert _abi_plan(won=0) < 0 and "won_dev" in err()
     assert _abi_plan(stats=0) < 0 and "stats_dev" in err()
     assert _abi_plan(won=0x5002) < 0 and "aligned" in err()
     assert _abi_plan(stats=0x6004) < 0 and "aligned" in err()
-    assert _abi_fill(n_resident=-1) < 0 and "n_resident" in err()
-    assert _abi_fill(n_resident=N.COVERAGE_MAX_FRAMES + 1) < 0 and "n_resident" in err()
+    for kwargs, word in RESIDENT_SWEEP:
+        assert _abi_fill(**kwargs) < 0 and word in err(), ("_abi_fill", kwargs, word, err())
     for bad in (-1, 2, 7):
         assert _abi_fill(mode=bad) < 0 and "mode" in err()
     for bad in (2, 4, 3, -2):
@@ -429,15 +251,14 @@ def test_mosaic_abi_argument_errors_without_gpu():
 
 
 def test_mosaic_symbols_and_abi_13():
-    hdr = open(os.path.join(ROOT, "include", "wm_hip.h")).read()
-    assert int(re.search(r"#define WM_ABI_VERSION (\d+)", hdr).group(1)) == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
-    assert "Survey mosaic" in hdr and len(re.findall("13, additive", hdr)) >= 2
+    assert macro("WM_ABI_VERSION") == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
+    assert "Survey mosaic" in header() and len(re.findall("13, additive", header())) >= 2
     for name in ("wm_mosaic_plan", "wm_mosaic_fill_u8"):
-        assert name in N.SYMBOLS and re.search(r"\bint %s\(" % name, hdr)
-        assert getattr(N.lib(), name) is not None
-    for macro, val in (("WM_MOSAIC_NEAREST", N.MOSAIC_NEAREST), ("WM_MOSAIC_BILINEAR", N.MOSAIC_BILINEAR), ("WM_MOSAIC_NORTH_UP", N.MOSAIC_NORTH_UP),
-                       ("WM_MOSAIC_BAD_SLOT", N.MOSAIC_BAD_SLOT), ("WM_MOSAIC_BAD_SIZE", N.MOSAIC_BAD_SIZE), ("WM_MOSAIC_BAD_SOURCE", N.MOSAIC_BAD_SOURCE)):
-        assert int(re.search(r"#define %s (\d+)" % macro, hdr).group(1)) == val
+        assert entry_is_whole(name), name
+    for name, val in (("WM_MOSAIC_NEAREST", N.MOSAIC_NEAREST), ("WM_MOSAIC_BILINEAR", N.MOSAIC_BILINEAR), ("WM_MOSAIC_NORTH_UP", N.MOSAIC_NORTH_UP),
+                      ("WM_MOSAIC_BAD_SLOT", N.MOSAIC_BAD_SLOT), ("WM_MOSAIC_BAD_SIZE", N.MOSAIC_BAD_SIZE), ("WM_MOSAIC_BAD_SOURCE", N.MOSAIC_BAD_SOURCE)):
+        assert macro(name) == val, name
+    assert MODES == {"nearest": N.MOSAIC_NEAREST, "bilinear": N.MOSAIC_BILINEAR}              # ground_oracle.py holds the two integers
     assert N.MOSAIC_NEAREST != N.MOSAIC_BILINEAR and tiling.MOSAIC_SAMPLES == MODES
     kern = open(os.path.join(ROOT, "wildlifemapper_amd", "csrc", "mosaic_kernels.h")).read()
     shared = ("cov_stage(", "cov_load_frame(", ".may_touch(", "cov_uv(", "cov_inside(")        # the cull is behind CovBlock::may_touch
@@ -507,68 +328,11 @@ def _assert_same(got, want):
 
 
 def _run_and_check(case, want=None):
-    want = _oracle(case) if want is None else want
+    want = _mosaic_oracle(case) if want is None else want
     got, plan = _device(case)
     _assert_same(got, want)
     assert got["stats"].sum() == case["gx"] * case["gy"] and got["won"].sum() == got["stats"][0]
     return got, want, plan
-
-
-@functools.lru_cache(maxsize=None)
-def _gpu_case(name):
-    """name -> (case, oracle result), computed once."""
-    k = _kernel_constants()
-    bx, by = k["block_x"], k["block_y"]
-    if name.startswith("grid_"):                                                # grid_<gx>x<gy>: none a multiple of the block
-        gx, gy = (int(v) for v in name[5:].split("x"))
-        case = _case(_some_frames(gx, gy, 0.7, gx, shapes=((30, 40), (17, 23), (40, 30), (9, 64), (33, 33))) + [_axis(-1.0, gx * 0.7 / 2, -1.0, gy, 0.5)], 0.0, 0.0, 0.7, gx, gy, seed=1)
-    elif name == "no_frames":
-        case = _case([], 0.0, 0.0, 0.7, 70, 19)
-    elif name == "one_1x1_px_frame":                                            # one pixel of 4 m over cells of 0.7 m
-        case = _case([_axis(10.0, 14.0, 4.0, 8.0, 0.25)], 0.0, 0.0, 0.7, 70, 19, seed=2)
-    elif name == "past_one_chunk":
-        # the first COV_CHUNK frames are far away, not finite or without pixels, but for frame 10; of the frames after them,
-        # the first has frame 10's georeference (an exact tie across the chunk boundary: 10 wins), the second overlaps frame
-        # 10 and is nearer for some cells, the third lies alone
-        ch = k["chunk"]
-        ten = tiling.nadir_affine(30, 40, (16.0, 6.5), 0.5, 0.0)
-        far = [_yawed((5000.0 + 40 * f, -3000.0), 0.1, 7.0 * f, 3, 4) for f in range(ch)]
-        far[3] = ([2, NAN, 0, 0, -2, 4], 4, 8)
-        far[100] = _axis(0.0, 49.0, 0.0, 13.0, 4.0)[:1] + (0, 196)
-        far[10] = (tiling.ground_to_pixel(ten), 30, 40)
-        near = [(tiling.ground_to_pixel(ten), 30, 40), _yawed((24.0, 6.5), 0.5, 0.0, 30, 40), _yawed((42.0, 8.0), 0.25, 115.0, 30, 40)]
-        case = _case(far + near, 0.0, 0.0, 0.7, 70, 19, seed=3)
-    elif name == "mixed_sizes_in_one_chunk":
-        frames = [_axis(0.0, 32.0, 0.0, 12.0, 2.0), _axis(8.0, 40.0, 2.0, 10.0, 0.5), _axis(20.0, 49.0, 0.0, 13.0, 1.0),
-                  _axis(30.0, 34.0, 4.0, 8.0, 0.25), _yawed((25.0, 6.0), 0.3, 30.0, 7, 90)]
-        case = _case(frames, 0.0, 0.0, 0.7, 70, 19, seed=4)
-    elif name == "cull_tiny_frame":                                             # 0.5 m of footprint around one centre, inside one block
-        case = _case([_axis(100.25, 100.75, 40.25, 40.75, 8.0)], 0.0, 0.0, 1.0, 257, 65, seed=5)
-    elif name == "cull_thin_between_rows":                                      # (40.625, 40.875]: between the rows of centres 40.5 and 41.5
-        case = _case([_axis(0.0, 257.0, 40.625, 40.875, 8.0)], 0.0, 0.0, 1.0, 257, 65, seed=6)
-    elif name == "cull_thin_on_one_row":                                        # (40.375, 40.625] holds the row of centres 40.5
-        case = _case([_axis(0.0, 257.0, 40.375, 40.625, 8.0)], 0.0, 0.0, 1.0, 257, 65, seed=7)
-    elif name == "cull_yaw_45":                                                 # 1.5 m and 1 m strips across the grid's blocks
-        case = _case([_yawed((128.0, 32.0), 0.05, 45.0, 30, 3000), _yawed((60.3, 30.1), 0.05, 135.0, 3000, 20)], 0.0, 0.0, 1.0, 257, 65, seed=8)
-    elif name == "cover_all":
-        case = _case([_axis(-10.0, 300.0, -10.0, 100.0, 0.5), _yawed((128.0, 32.0), 2.0, 45.0, 300, 300)], 0.0, 0.0, 1.0, 257, 65, seed=9)
-    elif name == "block_edges":
-        # centres at multiples of 0.5 m; footprints whose edges are the centres of the first cells of blocks: the west
-        # edge is inside, the east edge outside; the north edge inside, the south edge outside
-        c = 0.5
-        frames = [_axis(bx * c, 2 * bx * c, (by - 1) * c, (2 * by - 1) * c, 2.0),            # columns bx..2bx-1, rows by..2by-1
-                  _axis(0.0, bx * c, -c, (by - 1) * c, 2.0),                                   # block (0, 0) exactly
-                  _axis(2 * bx * c, 4 * bx * c, (by - 1) * c, (2 * by - 1) * c, 2.0),          # east of the first, to the grid's edge region
-                  _axis((bx - 1) * c, (bx + 1) * c, (by - 2) * c, by * c, 2.0)]                # 2 x 2 cells across a block corner
-        case = _case(frames, -0.25, -0.25, c, 257, 65, seed=10)
-    elif name == "random_survey":
-        rng = np.random.default_rng(11)
-        x0, y0, cell, gx, gy = 500000.1, 4000000.7, 0.11, 128, 96                # 14.1 m x 10.6 m; a frame is 3.2 m x 2.4 m
-        frames = [_yawed((x0 + rng.uniform(0, 14), y0 + rng.uniform(0, 10.5)), 0.05, rng.uniform(0, 360), 48, 64) for _ in range(40)]
-        case = _case(frames, x0, y0, cell, gx, gy, seed=11)
-    else:
-        raise KeyError(name)
-    return case, _oracle(case)
 
 
 @pytest.mark.gpu
@@ -592,7 +356,7 @@ def test_gpu_pixel_hand_cases(name):
 @pytest.mark.parametrize("name", ["grid_1x1", "grid_70x19", "grid_257x65", "no_frames", "one_1x1_px_frame", "past_one_chunk",
                                   "mixed_sizes_in_one_chunk"])
 def test_gpu_smallest_shapes(name):
-    case, want = _gpu_case(name)
+    case, want = _mosaic_gpu_case(name)
     got, _, _ = _run_and_check(case, want)
     src = got["source"]
     if name == "no_frames":
@@ -618,7 +382,7 @@ def test_gpu_smallest_shapes(name):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["cull_tiny_frame", "cull_thin_between_rows", "cull_thin_on_one_row", "cull_yaw_45", "cover_all", "block_edges"])
 def test_gpu_aimed_at_the_cull(name):
-    case, want = _gpu_case(name)
+    case, want = _mosaic_gpu_case(name)
     got, _, _ = _run_and_check(case, want)
     src = got["source"]
     k = _kernel_constants()
@@ -648,7 +412,7 @@ def test_gpu_aimed_at_the_cull(name):
 
 @pytest.mark.gpu
 def test_gpu_random_survey_invariants():
-    case, want = _gpu_case("random_survey")
+    case, want = _mosaic_gpu_case("random_survey")
     got, _, plan = _run_and_check(case, want)
     src = got["source"]
     F, gx, gy = 40, case["gx"], case["gy"]
@@ -666,7 +430,7 @@ def test_gpu_random_survey_invariants():
 
 @pytest.mark.gpu
 def test_gpu_fill_is_order_free():
-    case, want = _gpu_case("random_survey")
+    case, want = _mosaic_gpu_case("random_survey")
     plan = _plan(case)
     src = plan["source"]
     sentinel = np.asarray(SENTINEL, dtype=np.uint8)
@@ -685,7 +449,7 @@ def test_gpu_fill_is_order_free():
 
 @pytest.mark.gpu
 def test_gpu_bad_residency_is_reported_and_skipped():
-    case, want = _gpu_case("mixed_sizes_in_one_chunk")
+    case, want = _mosaic_gpu_case("mixed_sizes_in_one_chunk")
     plan = _plan(case)
     src = plan["source"]
     sentinel = np.asarray(SENTINEL, dtype=np.uint8)
@@ -737,7 +501,7 @@ def test_gpu_bad_residency_is_reported_and_skipped():
 
 @pytest.mark.gpu
 def test_gpu_north_up_flips_the_picture_only():
-    case, want = _gpu_case("grid_70x19")
+    case, want = _mosaic_gpu_case("grid_70x19")
     plan = _plan(case)
     before = plan["source_dev"].clone()
     resident = [f for f, im in enumerate(case["images"]) if im is not None]
@@ -751,23 +515,12 @@ def test_gpu_north_up_flips_the_picture_only():
     np.testing.assert_array_equal(before.cpu().numpy(), want["source"])
 
 
-def _python_case():
-    """Three overlapping yawed frames and a fourth off to the east, pixel -> ground georeferences."""
-    E0, N0 = 500000.0, 4000000.0
-    specs = [((E0 + 4.0, N0 + 3.0), 0.1, 10.0, 48, 64), ((E0 + 7.0, N0 + 3.5), 0.1, 40.0, 40, 56), ((E0 + 5.5, N0 + 5.0), 0.125, 200.0, 48, 64),
-             ((E0 + 16.0, N0 + 3.0), 0.1, 0.0, 24, 32)]
-    georef = np.stack([tiling.nadir_affine(H, W, c, gsd, yaw) for c, gsd, yaw, H, W in specs])
-    sizes = np.array([(H, W) for *_, H, W in specs], dtype=np.int32)
-    images = [_content(H, W, 50 + k) for k, (H, W) in enumerate(sizes.tolist())]
-    return georef, sizes, images
-
-
 PLAN_KEYS = {"source", "won", "origin", "cell", "shape", "gap_cells"}
 
 
 @pytest.mark.gpu
 def test_gpu_python_mosaic_end_to_end():
-    georef, sizes, images = _python_case()
+    georef, sizes, images = _mosaic_python_case()
     cell, fill = 0.08, (9, 8, 250)
     x0, y0, gx, gy = tiling.footprint_bounds(georef, sizes, cell)
     g2p = tiling.ground_to_pixel(georef)
@@ -817,7 +570,7 @@ def test_gpu_python_mosaic_end_to_end():
 
 @pytest.mark.gpu
 def test_gpu_python_mosaic_markers():
-    georef, sizes, images = _python_case()
+    georef, sizes, images = _mosaic_python_case()
     cell = 0.08
     x0, y0, gx, gy = tiling.footprint_bounds(georef, sizes, cell)
     pts = np.array([[x0 + 5.0, y0 + 3.0], [x0 + 0.04, y0 + 0.04], [NAN, y0 + 1.0], [x0 - 0.5, y0 + 1.0], [x0 + 2.0, y0 + gy * cell + 0.01],

@@ -1,10 +1,10 @@
 """Survey mosaic, blended (include/wm_hip.h "Survey mosaic, blended", tiling.mosaic(blend=), tiling.mosaic_blend_plan): every
 ground cell an integer-weighted mean of the exposure-corrected pixels of the frames that see it.  The rule has no reference
-behaviour; blend_oracle below restates it sequentially -- one cell at a time, numpy float64, vectorised over the frames only,
-the header's operation order -- and the device result must equal it exactly: the weights are integers behind arithmetic that
-is rounded once per operation and the sums are integers, so every device comparison is assert_array_equal and there is no
-tolerance anywhere.  blend_oracle_by_frame is the same rule one frame at a time, held equal to it, for tools/mosaic_blend_time.py."""
-import ctypes as C
+behaviour; blend_oracle (tests/ground_oracle.py) restates it sequentially -- one cell at a time, numpy float64, vectorised over
+the frames only, the header's operation order -- and the device result must equal it exactly: the weights are integers behind
+arithmetic that is rounded once per operation and the sums are integers, so every device comparison is assert_array_equal and
+there is no tolerance anywhere.  blend_oracle_by_frame is the same rule one frame at a time, held equal to it here, for
+tools/mosaic_blend_time.py."""
 import functools
 import os
 import re
@@ -13,172 +13,14 @@ import numpy as np
 import pytest
 import torch
 
-from survey_util import DEV, _axis, _kernel_constants, _Lazy, _up
-from test_mosaic import MODES, SENTINEL, _case, _content, _gpu_case, _python_case, _sample, _sample_many, mosaic_oracle
+from ground_cases import (FRAME_SWEEP, GRID_SWEEP, INF, NAN, ORIGIN_CELL_SWEEP, RESIDENT_SWEEP, _case, _mosaic_gpu_case, _mosaic_python_case, _p,
+                          entry_is_whole, header, last_error, macro)
+from ground_oracle import F64, MODES, SENTINEL, _expose, blend_oracle, blend_oracle_by_frame, mosaic_oracle
+from register_cases import _oracle_sums
+from survey_util import DEV, ROOT, _axis, _kernel_constants, _Lazy, _up
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
 from wildlifemapper_amd._survey import _frame_descs
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F64 = np.float64
-NAN = float("nan")
-INF = float("inf")
-
-
-def _weight(m, best, band):
-    """q of the header, elementwise, for frames that see the cell: m their border distance, best the cell's m*."""
-    band = F64(band)
-    k = F64(256.0) / band
-    top = m >= best
-    edge = np.minimum(m * k, F64(256.0))
-    seam = np.where(top, F64(256.0), np.minimum(np.maximum(((m - best) + band) * k, F64(0.0)), F64(255.0)))
-    q = np.floor(np.minimum(seam, edge)).astype(np.int64)
-    return np.where(top, np.maximum(q, 1), q)
-
-
-def _expose(p, ab):
-    """p' of the header: uint8 pixels p through the Q12 (A, B), in int64; // is floor."""
-    if ab is None:
-        return p.astype(np.int64)
-    return np.clip((np.int64(ab[0]) * p.astype(np.int64) + np.int64(ab[1]) + 2048) // 4096, 0, 255)
-
-
-def _finish(acc, fill):
-    """The picture of the header from acc (gy,gx,4) uint64: (acc_c + (wsum >> 1)) // wsum where wsum > 0, else fill."""
-    pic = np.empty(acc.shape[:2] + (3,), dtype=np.uint8)
-    pic[:] = np.asarray(fill, dtype=np.uint8)
-    has = acc[..., 3] > 0
-    ws = acc[..., 3][has]
-    pic[has] = ((acc[..., :3][has] + (ws >> np.uint64(1))[:, None]) // ws[:, None]).astype(np.uint8)
-    return pic
-
-
-def blend_oracle(g2p, size, x0, y0, cell, gx, gy, band, frames=None, exposure=None, fill=SENTINEL, resident=None):
-    """The blend rule, one cell at a time.  Returns best (gy,gx) float64, cells (F,) and stats (3,) int64, and with frames (a
-    list of (H,W,3) uint8 arrays, None for a frame without pixels) 'acc_nearest' / 'acc_bilinear' (gy,gx,4) uint32 and the
-    pictures 'nearest' / 'bilinear' (gy,gx,3) uint8, row 0 south, cells without a weight holding `fill`.  exposure: (F,2)
-    int32 or None.  resident: the frames that are accumulated (None: all with pixels); best, cells and stats are the whole
-    survey's whatever it says.  Elementwise numpy arithmetic is one correctly rounded IEEE operation per element and
-    operator, in the order written."""
-    b = np.asarray(g2p, dtype=F64).reshape(-1, 6)
-    size = np.asarray(size, dtype=np.int64).reshape(-1, 2)
-    h, w = size[:, 0], size[:, 1]
-    fw, fh = w.astype(F64), h.astype(F64)
-    x0, y0, cell = F64(x0), F64(y0), F64(cell)
-    nf = b.shape[0]
-    best = np.full((gy, gx), -1.0, dtype=F64)
-    cells = np.zeros(nf, dtype=np.int64)
-    nq = np.zeros((gy, gx), dtype=np.int64)
-    acc = {m: np.zeros((gy, gx, 4), dtype=np.uint64) for m in MODES} if frames is not None else {}
-    take = set(range(nf)) if resident is None else set(resident)
-    with np.errstate(all="ignore"):
-        for j in range(gy):
-            Yc = y0 + (F64(j) + F64(0.5)) * cell
-            for i in range(gx):
-                if not nf:
-                    continue
-                Xc = x0 + (F64(i) + F64(0.5)) * cell
-                u = (b[:, 0] * Xc + b[:, 1] * Yc) + b[:, 2]
-                v = (b[:, 3] * Xc + b[:, 4] * Yc) + b[:, 5]
-                sees = (h >= 1) & (w >= 1) & (0 <= u) & (u < w) & (0 <= v) & (v < h)
-                if not sees.any():
-                    continue
-                fs = np.nonzero(sees)[0]
-                us, vs = u[fs], v[fs]
-                m = np.minimum(np.minimum(us, fw[fs] - us), np.minimum(vs, fh[fs] - vs))
-                best[j, i] = m.max()
-                q = _weight(m, best[j, i], band)
-                cells[fs[q > 0]] += 1
-                nq[j, i] = (q > 0).sum()
-                for f, qf, uf, vf in zip(fs.tolist(), q.tolist(), us, vs):
-                    if qf > 0 and f in take and frames is not None and frames[f] is not None:
-                        for mode, a in acc.items():
-                            p = _expose(_sample(frames[f], uf, vf, mode), None if exposure is None else exposure[f])
-                            a[j, i, :3] += (qf * p).astype(np.uint64)
-                            a[j, i, 3] += np.uint64(qf)
-    seen = best >= 0
-    out = {"best": best, "cells": cells, "stats": np.array([seen.sum(), (~seen).sum(), (nq >= 2).sum()], dtype=np.int64)}
-    for mode, a in acc.items():
-        assert a.max(initial=0) < 2 ** 32
-        out["acc_" + mode] = a.astype(np.uint32)
-        out[mode] = _finish(a, fill)
-    return out
-
-
-def _window(bf, h, w, x0, y0, cell, gx, gy):
-    """The cells (i0, i1, j0, j1) around frame bf's footprint, two cells of margin; the whole grid when it cannot be told."""
-    i0, i1, j0, j1 = 0, gx, 0, gy
-    A = np.array([[bf[0], bf[1]], [bf[3], bf[4]]])
-    if abs(np.linalg.det(A)) > 0:
-        corners = np.array([[0, 0], [w, 0], [0, h], [w, h]], dtype=F64) - bf[[2, 5]]
-        ground = np.linalg.solve(A, corners.T).T
-        if np.isfinite(ground).all():
-            i0 = int(np.clip(np.floor((ground[:, 0].min() - x0) / cell) - 2, 0, gx))
-            i1 = int(np.clip(np.ceil((ground[:, 0].max() - x0) / cell) + 2, 0, gx))
-            j0 = int(np.clip(np.floor((ground[:, 1].min() - y0) / cell) - 2, 0, gy))
-            j1 = int(np.clip(np.ceil((ground[:, 1].max() - y0) / cell) + 2, 0, gy))
-    return i0, i1, j0, j1
-
-
-def blend_oracle_by_frame(g2p, size, x0, y0, cell, gx, gy, band, frames=None, exposure=None, fill=SENTINEL, modes=tuple(MODES)):
-    """The same rule one FRAME at a time over the window of cells around its footprint, in two walks as the plan kernel makes
-    them: first the running maximum m*, then every frame's weights against the finished m* and its sums.  The same operations
-    per cell as blend_oracle, fast enough for the grids tools/mosaic_blend_time.py times.  Checked equal to blend_oracle below."""
-    b = np.asarray(g2p, dtype=F64).reshape(-1, 6)
-    size = np.asarray(size, dtype=np.int64).reshape(-1, 2)
-    x0, y0, cell = F64(x0), F64(y0), F64(cell)
-    Xc = x0 + (np.arange(gx, dtype=F64) + F64(0.5)) * cell
-    Yc = y0 + (np.arange(gy, dtype=F64) + F64(0.5)) * cell
-    nf = b.shape[0]
-    best = np.full((gy, gx), -1.0, dtype=F64)
-    cells = np.zeros(nf, dtype=np.int64)
-    nq = np.zeros((gy, gx), dtype=np.int64)
-    acc = {m: np.zeros((gy, gx, 4), dtype=np.uint64) for m in modes} if frames is not None else {}
-    def geometry(f):
-        """Frame f's window (i0, j0) and, on it, u, v, inside and m; None for a frame that sees nothing."""
-        h, w = size[f]
-        if h < 1 or w < 1 or not np.isfinite(b[f]).all():
-            return None
-        i0, i1, j0, j1 = _window(b[f], h, w, x0, y0, cell, gx, gy)
-        X, Y = Xc[None, i0:i1], Yc[j0:j1, None]
-        u = (b[f, 0] * X + b[f, 1] * Y) + b[f, 2]
-        v = (b[f, 3] * X + b[f, 4] * Y) + b[f, 5]
-        inside = (0 <= u) & (u < w) & (0 <= v) & (v < h)
-        return i0, j0, u, v, inside, np.minimum(np.minimum(u, F64(w) - u), np.minimum(v, F64(h) - v))
-
-    with np.errstate(all="ignore"):
-        for f in range(nf):
-            geo = geometry(f)
-            if geo is not None:
-                i0, j0, u, v, inside, m = geo
-                sub = best[j0:j0 + m.shape[0], i0:i0 + m.shape[1]]
-                upd = inside & (m > sub)
-                sub[upd] = m[upd]
-        for f in range(nf):
-            geo = geometry(f)                                   # computed again, not kept: a survey of 1 000 frames stays small
-            if geo is None:
-                continue
-            i0, j0, u, v, inside, m = geo
-            jj, ii = np.nonzero(inside)
-            if not len(jj):
-                continue
-            q = _weight(m[jj, ii], best[j0 + jj, i0 + ii], band)
-            pos = q > 0
-            jj, ii, q = jj[pos], ii[pos], q[pos]
-            cells[f] = len(q)
-            nq[j0 + jj, i0 + ii] += 1
-            if frames is None or frames[f] is None:
-                continue
-            for mode, a in acc.items():
-                p = _expose(_sample_many(frames[f], u[jj, ii], v[jj, ii], mode), None if exposure is None else exposure[f])
-                a[j0 + jj, i0 + ii, :3] += (q[:, None] * p).astype(np.uint64)
-                a[j0 + jj, i0 + ii, 3] += q.astype(np.uint64)
-    seen = best >= 0
-    out = {"best": best, "cells": cells, "stats": np.array([seen.sum(), (~seen).sum(), (nq >= 2).sum()], dtype=np.int64)}
-    for mode, a in acc.items():
-        out["acc_" + mode] = a.astype(np.uint32)
-        out[mode] = _finish(a, fill)
-    return out
 
 
 def _oracle(case, band, **kw):
@@ -286,8 +128,8 @@ GPU_CASES = ["grid_70x19", "grid_257x65", "no_frames", "one_1x1_px_frame", "mixe
 
 @functools.lru_cache(maxsize=None)
 def _blend_case(name):
-    """name -> (case, band, oracle result): the cases of test_mosaic.py, computed once."""
-    case = _gpu_case(name)[0]
+    """name -> (case, band, oracle result): the mosaic's cases (ground_cases.py), computed once."""
+    case = _mosaic_gpu_case(name)[0]
     band = BANDS.get(name, 6.0)
     return case, band, _oracle(case, band)
 
@@ -358,7 +200,6 @@ def _e2e_scene(X, Y):
 
 
 def test_exposure_end_to_end_on_the_host():
-    from test_register_refine import _oracle_sums
     H, W, cell = 48, 64, 1.0
     spec = [((32.3, 24.7), 4.0), ((66.1, 27.2), -6.0), ((35.4, 55.9), 8.0), ((68.8, 57.3), -3.0)]
     georef = np.stack([tiling.nadir_affine(H, W, c, 1.0, yaw) for c, yaw in spec])
@@ -429,9 +270,6 @@ def test_blend_python_argument_errors_before_device_work():
     assert lazy.asked == []
 
 
-_p = lambda v: C.c_void_p(v) if v else None
-
-
 def _abi_plan(n_frames=2, x0=0.0, y0=0.0, cell=1.0, gx=5, gy=3, band=4.0, g2p=0x2000, size=0x3000, best=0x4000, cells=0x5000, stats=0x6000):
     """wm_mosaic_blend_plan with fake, never dereferenced device pointers: only paths that return before any HIP call."""
     return N.lib().wm_mosaic_blend_plan(_p(g2p), _p(size), n_frames, x0, y0, cell, gx, gy, band, _p(best), _p(cells), _p(stats), None)
@@ -448,37 +286,23 @@ def _abi_finish(gx=5, gy=3, flags=0, acc=0x8000, mosaic=0xB001):
 
 
 def test_blend_abi_argument_errors_without_gpu():
-    err = lambda: N.lib().wm_last_error().decode()
+    err = last_error
     for call in (_abi_plan, _abi_accum, _abi_finish):
-        assert call(gx=0) < 0 and "gx" in err()
-        assert call(gx=N.COVERAGE_MAX_SIDE + 1) < 0 and "gx" in err()
-        assert call(gy=0) < 0 and "gy" in err()
-        assert call(gy=-4) < 0 and "gy" in err()
-        assert call(gy=N.COVERAGE_MAX_SIDE + 1) < 0 and "gy" in err()
-        assert call(gx=16384, gy=8192) < 0 and "gx * gy" in err()
-        assert call(gx=8192, gy=8192 + 1) < 0 and "gx * gy" in err()
+        for kwargs, word in GRID_SWEEP:
+            assert call(**kwargs) < 0 and word in err(), (call.__name__, kwargs, word, err())
     for call in (_abi_plan, _abi_accum):
-        assert call(n_frames=-1) < 0 and "n_frames" in err()
-        assert call(n_frames=N.COVERAGE_MAX_FRAMES + 1) < 0 and "n_frames" in err()
-        for bad in (NAN, INF, -INF):
-            assert call(x0=bad) < 0 and "x0" in err()
-            assert call(y0=bad) < 0 and "y0" in err()
-        for bad in (0.0, -1.0, NAN, INF):
-            assert call(cell=bad) < 0 and "cell" in err()
+        for kwargs, word in FRAME_SWEEP + ORIGIN_CELL_SWEEP:
+            assert call(**kwargs) < 0 and word in err(), (call.__name__, kwargs, word, err())
         for bad in (0.0, -0.0, -8.0, NAN, INF, -INF, 1e-320):
             assert call(band=bad) < 0 and "band" in err()
-        assert call(g2p=0) < 0 and "g2p_dev" in err()
-        assert call(size=0) < 0 and "size_dev" in err()
-        assert call(g2p=0x2004) < 0 and "aligned" in err()
-        assert call(size=0x3002) < 0 and "aligned" in err()
         assert call(best=0) < 0 and "best_dev" in err()
         assert call(best=0x4004) < 0 and "aligned" in err()
     assert _abi_plan(cells=0) < 0 and "cells_dev" in err()
     assert _abi_plan(stats=0) < 0 and "stats_dev" in err()
     assert _abi_plan(cells=0x5002) < 0 and "aligned" in err()
     assert _abi_plan(stats=0x6004) < 0 and "aligned" in err()
-    assert _abi_accum(n_resident=-1) < 0 and "n_resident" in err()
-    assert _abi_accum(n_resident=N.COVERAGE_MAX_FRAMES + 1) < 0 and "n_resident" in err()
+    for kwargs, word in RESIDENT_SWEEP:
+        assert _abi_accum(**kwargs) < 0 and word in err(), ("_abi_accum", kwargs, word, err())
     for bad in (-1, 2, 7):
         assert _abi_accum(mode=bad) < 0 and "mode" in err()
     assert _abi_accum(frames=0) < 0 and "frames_dev" in err()
@@ -503,15 +327,14 @@ def test_blend_abi_argument_errors_without_gpu():
 
 
 def test_blend_symbols_header_and_kernel_file():
-    hdr = open(os.path.join(ROOT, "include", "wm_hip.h")).read()
-    assert int(re.search(r"#define WM_ABI_VERSION (\d+)", hdr).group(1)) == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
+    hdr = header()
+    assert macro("WM_ABI_VERSION") == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
     assert "Survey mosaic, blended" in hdr and hdr.index("Survey mosaic, blended (") > hdr.index("Survey mosaic (")
     # the history's line of this addition.  It is worded "13, also additive": tests/test_register_refine.py holds the header to
     # exactly five occurrences of "13, additive", so the count of that phrase cannot grow
     assert re.search(r"13, also additive: wm_mosaic_blend_plan, wm_mosaic_blend_accum_u8, wm_mosaic_blend_finish_u8", hdr)
     for name in ("wm_mosaic_blend_plan", "wm_mosaic_blend_accum_u8", "wm_mosaic_blend_finish_u8"):
-        assert name in N.SYMBOLS and re.search(r"\bint %s\(" % name, hdr)
-        assert getattr(N.lib(), name) is not None
+        assert entry_is_whole(name), name
     for name in ("mosaic_blend_plan", "adjust_exposure", "exposure_table"):
         assert callable(getattr(tiling, name))
     kern = open(os.path.join(ROOT, "wildlifemapper_amd", "csrc", "mosaic_blend_kernels.h")).read()
@@ -818,7 +641,7 @@ PLAN_KEYS = {"source", "won", "origin", "cell", "shape", "gap_cells"}
 
 @pytest.mark.gpu
 def test_gpu_python_mosaic_blend_end_to_end():
-    georef, sizes, images = _python_case()
+    georef, sizes, images = _mosaic_python_case()
     cell, fill, band = 0.08, (9, 8, 250), 12.0
     x0, y0, gx, gy = tiling.footprint_bounds(georef, sizes, cell)
     g2p = tiling.ground_to_pixel(georef)

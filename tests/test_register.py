@@ -5,7 +5,6 @@ numpy float64 for the cell centres and int64 for everything after them, the head
 result must equal it exactly: every device comparison is assert_array_equal and there is no tolerance on the GPU side.
 The only bound in this file is adjust()'s 1e-9 m on consistent measurements (double rounding of such a system sits near
 1e-15; the bound is slack, not measured)."""
-import ctypes as C
 import os
 import re
 
@@ -13,11 +12,11 @@ import numpy as np
 import pytest
 import torch
 
-from register_cases import (ANIMALS, DISPLACED, F64, HAND_A, HAND_B, INF, NAN, POISON_A, POISON_B, ROOT,
-                            SCENE_H, SCENE_W, SHAPES, _axis_frame, _case, _content, _cover, _detections,
-                            _north_up, _oracle, _pairs, _planes, _render, _search, _shape_case, beats,
-                            luma, per_k_planes, pick_oracle, render_plane, search_oracle)
-from survey_util import DEV, _Lazy, _up
+from ground_cases import FRAME_SWEEP, RESIDENT_SWEEP, _p, entry_is_whole, header, last_error, macro
+from register_cases import (ANIMALS, DISPLACED, HAND_A, HAND_B, INF, NAN, POISON_A, POISON_B, SHAPES, _axis_frame, _case, _content, _cover, _detections,
+                            _north_up, _oracle, _pairs, _planes, _render, _search, _several_pairs, _shape_case, _survey,
+                            beats, luma, per_k_planes, pick_oracle, render_plane, search_oracle)
+from survey_util import DEV, ROOT, _Lazy, _up
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
 
@@ -261,18 +260,16 @@ def test_register_python_argument_errors_before_device_work():
 def _abi_render(n_frames=2, n_resident=2, n_pairs=3, cell=1.0, search=4, side=64, frames=0x1000, slot=0x7000, g2p=0x2000, size=0x3000,
                 pairs=0x4000, a=0x5001, b=0x6001, status=0x9000):
     """wm_register_render_u8 with fake, never dereferenced device pointers: only paths that return before any HIP call."""
-    p = lambda v: C.c_void_p(v) if v else None
-    return N.lib().wm_register_render_u8(p(frames), n_resident, p(slot), p(g2p), p(size), n_frames, p(pairs), n_pairs, cell, search, side,
-                                         p(a), p(b), p(status), None)
+    return N.lib().wm_register_render_u8(_p(frames), n_resident, _p(slot), _p(g2p), _p(size), n_frames, _p(pairs), n_pairs, cell, search, side,
+                                         _p(a), _p(b), _p(status), None)
 
 
 def _abi_search(n_pairs=3, search=4, side=64, min_cells=1, a=0x5001, b=0x6001, pairs=0x4000, score=0x8000, best=0xa000):
-    p = lambda v: C.c_void_p(v) if v else None
-    return N.lib().wm_register_search(p(a), p(b), p(pairs), n_pairs, search, side, min_cells, p(score), p(best), None)
+    return N.lib().wm_register_search(_p(a), _p(b), _p(pairs), n_pairs, search, side, min_cells, _p(score), _p(best), None)
 
 
 def test_register_abi_argument_errors_without_gpu():
-    err = lambda: N.lib().wm_last_error().decode()
+    err = last_error
     for call in (_abi_render, _abi_search):
         assert call(n_pairs=-1) < 0 and "n_pairs" in err()
         assert call(n_pairs=N.REGISTER_MAX_PAIRS + 1) < 0 and "n_pairs" in err()
@@ -286,16 +283,10 @@ def test_register_abi_argument_errors_without_gpu():
         assert call(b=0) < 0 and "b_dev" in err()
         # n_pairs == 0 returns 0 before looking at any pointer or any other argument
         assert call(n_pairs=0, pairs=0, a=0, b=0, search=-5, side=0) == 0
-    assert _abi_render(n_frames=-1) < 0 and "n_frames" in err()
-    assert _abi_render(n_frames=N.COVERAGE_MAX_FRAMES + 1) < 0 and "n_frames" in err()
-    assert _abi_render(n_resident=-1) < 0 and "n_resident" in err()
-    assert _abi_render(n_resident=N.COVERAGE_MAX_FRAMES + 1) < 0 and "n_resident" in err()
+    for kwargs, word in FRAME_SWEEP + RESIDENT_SWEEP:                         # the frame tables and the resident list of the ground entries
+        assert _abi_render(**kwargs) < 0 and word in err(), ("_abi_render", kwargs, word, err())
     for bad in (0.0, -1.0, NAN, INF):
         assert _abi_render(cell=bad) < 0 and "cell" in err()
-    assert _abi_render(g2p=0) < 0 and "g2p_dev" in err()
-    assert _abi_render(size=0) < 0 and "size_dev" in err()
-    assert _abi_render(g2p=0x2004) < 0 and "aligned" in err()
-    assert _abi_render(size=0x3002) < 0 and "aligned" in err()
     assert _abi_render(frames=0) < 0 and "frames_dev" in err()
     assert _abi_render(slot=0) < 0 and "slot_dev" in err()
     assert _abi_render(status=0) < 0 and "status_dev" in err()
@@ -311,34 +302,18 @@ def test_register_abi_argument_errors_without_gpu():
 
 
 def test_register_symbols_and_abi_13():
-    hdr = open(os.path.join(ROOT, "include", "wm_hip.h")).read()
-    assert int(re.search(r"#define WM_ABI_VERSION (\d+)", hdr).group(1)) == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
-    assert "Survey registration" in hdr and len(re.findall("13, additive", hdr)) >= 3
+    assert macro("WM_ABI_VERSION") == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
+    assert "Survey registration" in header() and len(re.findall("13, additive", header())) >= 3
     for name in ("wm_register_render_u8", "wm_register_search"):
-        assert name in N.SYMBOLS and re.search(r"\bint %s\(" % name, hdr)
-        assert getattr(N.lib(), name) is not None
-    for macro, val in (("WM_REGISTER_MAX_SIDE", N.REGISTER_MAX_SIDE), ("WM_REGISTER_MAX_SEARCH", N.REGISTER_MAX_SEARCH),
+        assert entry_is_whole(name), name
+    for name, val in (("WM_REGISTER_MAX_SIDE", N.REGISTER_MAX_SIDE), ("WM_REGISTER_MAX_SEARCH", N.REGISTER_MAX_SEARCH),
                        ("WM_REGISTER_MAX_PAIRS", N.REGISTER_MAX_PAIRS), ("WM_REGISTER_BAD_SLOT", N.REGISTER_BAD_SLOT),
                        ("WM_REGISTER_BAD_SIZE", N.REGISTER_BAD_SIZE), ("WM_REGISTER_BAD_PAIR", N.REGISTER_BAD_PAIR)):
-        assert int(re.search(r"#define %s (\d+)" % macro, hdr).group(1)) == val
+        assert macro(name) == val, name
     assert (N.REGISTER_MAX_SIDE, N.REGISTER_MAX_SEARCH, N.REGISTER_MAX_PAIRS) == (512, 64, 65535)
     assert tiling.REGISTER_PAIR.itemsize == 32 and [tiling.REGISTER_PAIR.fields[k][1] for k in tiling.REGISTER_PAIR.names] == [0, 4, 8, 12, 16, 24]
     kern = open(os.path.join(ROOT, "wildlifemapper_amd", "csrc", "register_kernels.h")).read()
     assert "__builtin_amdgcn_sad_u8(" in kern and "asm" not in kern
-
-
-# ---- cases -----------------------------------------------------------------------------------------------------------
-
-
-def _several_pairs():
-    """Pairs of different sizes in one launch, sharing frames, patches at different places, one yawed 45 degrees."""
-    x0, y0, cell = 1000.0, 2000.0, 0.5
-    diamond = _content(90, 90, 13), tiling.nadir_affine(90, 90, (x0 + 17.5, y0 + 17.5), 0.5, 45.0)       # 45 m a side, yawed
-    frames = [_cover(70, 70, 6, x0, y0, cell, 11), _cover(70, 70, 6, x0, y0, cell, 12, gsd_cells=1.25), diamond,
-              _cover(30, 30, 6, x0 + 10.0, y0 + 10.0, cell, 14, gsd_cells=0.75)]
-    pairs = [(0, 1, 70, 19, x0, y0), (1, 2, 5, 66, x0 + 3.0, y0 + 1.5), (0, 3, 33, 30, x0 + 9.5, y0 + 8.0), (2, 3, 72, 72, x0 - 4.0, y0 - 4.0),
-             (0, 2, 1, 1, x0 + 7.0, y0 + 7.0)]
-    return _case(frames, pairs, cell, 6, 72, 40)
 
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------
@@ -592,34 +567,6 @@ def test_gpu_bad_residency_is_reported_and_skipped():
 
 
 # ---- end to end ------------------------------------------------------------------------------------------------------
-
-
-def _scene(seed=3):
-    """A multi-scale texture: independent uniform fields at 1, 4 and 16 px, mixed per channel."""
-    rng = np.random.default_rng(seed)
-    out = np.zeros((SCENE_H, SCENE_W, 3), dtype=F64)
-    for k, wt in ((1, 0.3), (4, 0.3), (16, 0.4)):
-        field = rng.random((SCENE_H // k + 1, SCENE_W // k + 1, 3))
-        out += wt * np.kron(field, np.ones((k, k, 1)))[:SCENE_H, :SCENE_W]
-    return np.clip(out * 255.0, 0, 255).astype(np.uint8)
-
-
-def _survey():
-    """Four 160 x 200 frames cut from the scene (1 m per pixel; scene pixel (r, c) is the ground [c, c + 1) x [399 - r, 400 - r))
-    through their TRUE georeferences, at yaw 0 / 0 / 180 / 90.  Returns frames, true georef, displaced georef."""
-    scene = _scene()
-    true = np.stack([tiling.nadir_affine(160, 200, c, 1.0, yaw) for c, yaw in
-                     (((200.0, 200.0), 0.0), ((280.0, 220.0), 0.0), ((240.0, 170.0), 180.0), ((250.0, 210.0), 90.0))])
-    yy, xx = np.meshgrid(np.arange(160) + 0.5, np.arange(200) + 0.5, indexing="ij")
-    frames = []
-    for g in true:
-        X = g[0, 0] * xx + g[0, 1] * yy + g[0, 2]
-        Y = g[1, 0] * xx + g[1, 1] * yy + g[1, 2]
-        frames.append(scene[SCENE_H - 1 - np.floor(Y).astype(np.int64), np.floor(X).astype(np.int64)].copy())
-    displaced = true.copy()
-    displaced[:, 0, 2] += DISPLACED[:, 0]
-    displaced[:, 1, 2] += DISPLACED[:, 1]
-    return frames, true, displaced
 
 
 @pytest.mark.gpu

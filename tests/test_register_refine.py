@@ -3,7 +3,6 @@ equations of one Gauss-Newton step per pair -- 28 sums -- and the host's solve, 
 reference behaviour; refine_sums_oracle restates it: the terms of every cell are formed one expression at a time in int64
 (each is below 2^37) and summed in Python integers, so nothing in it can overflow.  The device's sums must equal it exactly:
 every device comparison of sums is assert_array_equal.  The bounds of the host part are stated where they are used."""
-import ctypes as C
 import os
 import re
 
@@ -11,29 +10,12 @@ import numpy as np
 import pytest
 import torch
 
-from register_cases import (DISPLACED, F64, INF, NAN, ROOT, _case, _content, _cover, _pairs, _planes, _render, per_k_planes, render_plane)
-from survey_util import DEV, _Lazy, _up
-from test_register import _several_pairs, _survey
+from ground_cases import _p, entry_is_whole, header, last_error, macro
+from register_cases import (DISPLACED, F64, INF, NAN, SUMS, _case, _content, _cover, _oracle_sums, _pairs, _planes, _render, _several_pairs,
+                            _survey, per_k_planes, refine_sums_oracle)
+from survey_util import DEV, ROOT, _Lazy, _up
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
-
-SUMS = 28
-TRI = [(k, l) for k in range(6) for l in range(k, 6)]
-
-
-def refine_sums_oracle(A, B, gx, gy, search):
-    """The 28 sums of one pair as a list of Python integers.  A (side, side), B (side + 2 search, side + 2 search) uint8."""
-    S = search
-    a = A[:gy, :gx].astype(np.int64)
-    sl = lambda dj, di: B[S + dj:S + dj + gy, S + di:S + di + gx].astype(np.int64)
-    b, e, w, nn, ss = sl(0, 0), sl(0, 1), sl(0, -1), sl(1, 0), sl(-1, 0)
-    counts = (a != 0) & (b != 0) & (e != 0) & (w != 0) & (nn != 0) & (ss != 0)
-    r, gxv, gyv = a - b, e - w, nn - ss
-    x = (2 * np.arange(gx, dtype=np.int64) + 1 - gx)[None, :] + np.zeros((gy, 1), dtype=np.int64)
-    y = (2 * np.arange(gy, dtype=np.int64) + 1 - gy)[:, None] + np.zeros((1, gx), dtype=np.int64)
-    c = [gxv, gyv, x * gyv - y * gxv, x * gxv + y * gyv, b, np.ones_like(b)]
-    total = lambda v: int(v[counts].astype(object).sum()) if counts.any() else 0       # Python integers
-    return [total(c[k] * c[l]) for k, l in TRI] + [total(c[k] * r) for k in range(6)] + [total(r * r)]
 
 
 def _oracle_table(A, B, table, search):
@@ -298,17 +280,6 @@ def _corner_error(g, true):
     return float(np.linalg.norm(np.einsum("fij,cj->fci", g - true, corners), axis=2).max())
 
 
-def _oracle_sums(frames, georef, sizes, table, cell, side, search=1):
-    g2p = tiling.ground_to_pixel(georef).reshape(-1, 6)
-    out = []
-    for pr in table:
-        fa, fb, gx, gy = (int(pr[k]) for k in ("frame_a", "frame_b", "gx", "gy"))
-        A = render_plane(g2p[fa], sizes[fa], frames[fa], pr["x0"], pr["y0"], cell, gx, gy, 0, side)
-        B = render_plane(g2p[fb], sizes[fb], frames[fb], pr["x0"], pr["y0"], cell, gx, gy, search, side + 2 * search)
-        out.append(refine_sums_oracle(A, B, gx, gy, search))
-    return np.array(out, dtype=np.int64).reshape(len(table), SUMS)
-
-
 _LOOPS = {}
 
 
@@ -426,12 +397,11 @@ def test_refine_python_argument_errors_before_device_work():
 
 def _abi_refine(n_pairs=3, search=4, side=64, a=0x5001, b=0x6001, pairs=0x4000, sums=0x8000):
     """wm_register_refine with fake, never dereferenced device pointers: only paths that return before any HIP call."""
-    p = lambda v: C.c_void_p(v) if v else None
-    return N.lib().wm_register_refine(p(a), p(b), p(pairs), n_pairs, search, side, p(sums), None)
+    return N.lib().wm_register_refine(_p(a), _p(b), _p(pairs), n_pairs, search, side, _p(sums), None)
 
 
 def test_refine_abi_argument_errors_without_gpu():
-    err = lambda: N.lib().wm_last_error().decode()
+    err = last_error
     assert _abi_refine(n_pairs=-1) < 0 and "n_pairs" in err()
     assert _abi_refine(n_pairs=N.REGISTER_MAX_PAIRS + 1) < 0 and "n_pairs" in err()
     for bad in (0, -1, N.REGISTER_MAX_SEARCH + 1):
@@ -450,13 +420,13 @@ def test_refine_abi_argument_errors_without_gpu():
 
 
 def test_refine_symbol_constant_and_abi_13():
-    hdr = open(os.path.join(ROOT, "include", "wm_hip.h")).read()
-    assert int(re.search(r"#define WM_ABI_VERSION (\d+)", hdr).group(1)) == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
+    hdr = header()
+    assert macro("WM_ABI_VERSION") == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
     assert "Survey registration, refinement" in hdr and len(re.findall("13, additive", hdr)) == 5
     assert re.search(r"13, additive: wm_register_refine", hdr)
-    assert "wm_register_refine" in N.SYMBOLS and re.search(r"\bint wm_register_refine\(", hdr) and N.lib().wm_register_refine is not None
+    assert entry_is_whole("wm_register_refine")
     kern = open(os.path.join(ROOT, "wildlifemapper_amd", "csrc", "register_refine_kernels.h")).read()
-    assert int(re.search(r"#define WM_REGISTER_REFINE_SUMS (\d+)", hdr).group(1)) == N.REGISTER_REFINE_SUMS == tiling.REGISTER_REFINE_SUMS == SUMS
+    assert macro("WM_REGISTER_REFINE_SUMS") == N.REGISTER_REFINE_SUMS == tiling.REGISTER_REFINE_SUMS == SUMS
     assert int(re.search(r"constexpr int REFINE_SUMS = (\d+);", kern).group(1)) == SUMS and "asm" not in kern
     assert "static_assert(REFINE_SUMS == WM_REGISTER_REFINE_SUMS" in kern
 

@@ -1,11 +1,10 @@
 """Survey registration, correlation search (include/wm_hip.h "Survey registration, correlation search",
 tiling.register(metric="zncc")): the offset search of test_register.py with a score that a gain and an offset between the two
-frames of a pair do not change.  The rule has no reference behaviour; zncc_search_oracle and zncc_pick_oracle below restate
+frames of a pair do not change.  The rule has no reference behaviour; zncc_search_oracle and zncc_pick_oracle (tests/register_cases.py) restate
 it sequentially -- one offset at a time, Python integers for the six moments and their cross terms, three np.float64
 operations for the score, in the header's order -- and the device result must equal it exactly: moments and best by
 assert_array_equal, peak by its bytes (NaN included).  There is no tolerance in this file.  Planes, pairs and the SAD
-oracles are test_register.py's."""
-import ctypes as C
+oracles are the ones test_register.py uses."""
 import os
 import re
 
@@ -14,7 +13,8 @@ import pytest
 import torch
 
 import register_cases as T
-from survey_util import _Lazy
+from ground_cases import _p, entry_is_whole, header, last_error, macro
+from survey_util import ROOT, _Lazy
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
 
@@ -22,54 +22,6 @@ F64 = np.float64
 NAN = float("nan")
 INF = float("inf")
 DEV = T.DEV
-
-
-def zncc_search_oracle(A, B, gx, gy, S):
-    """moments (2S+1, 2S+1, 6) int64 = (n, Sa, Sb, Saa, Sbb, Sab) over the cells both planes see, one offset at a time."""
-    a = A[:gy, :gx].astype(np.int64)
-    out = np.zeros((2 * S + 1, 2 * S + 1, 6), dtype=np.int64)
-    for dy in range(-S, S + 1):
-        for dx in range(-S, S + 1):
-            bb = B[S + dy:S + dy + gy, S + dx:S + dx + gx].astype(np.int64)
-            both = (a != 0) & (bb != 0)
-            x, y = a[both], bb[both]
-            out[dy + S, dx + S] = (both.sum(), x.sum(), y.sum(), (x * x).sum(), (y * y).sum(), (x * y).sum())
-    return out
-
-
-def zncc_q(m):
-    """The score of one offset from its six moments, or None where a plane is flat: c, va, vb in Python integers, then
-    q = (c * |c|) / (va * vb) in three float64 operations."""
-    n, sa, sb, saa, sbb, sab = (int(v) for v in m)
-    c, va, vb = n * sab - sa * sb, n * saa - sa * sa, n * sbb - sb * sb
-    if va <= 0 or vb <= 0:
-        return None
-    assert max(abs(c), va, vb, n * sab, sa * sb, n * saa, n * sbb) < 2 ** 53           # the conversions are exact
-    cf = F64(c)
-    return (cf * np.abs(cf)) / (F64(va) * F64(vb))
-
-
-def zncc_beats(p, q):
-    """Offset p = (q, n, dy, dx) beats q: the larger score, then the smaller (dy^2 + dx^2, dy, dx)."""
-    if p[0] != q[0]:
-        return p[0] > q[0]
-    return (p[2] * p[2] + p[3] * p[3], p[2], p[3]) < (q[2] * q[2] + q[3] * q[3], q[2], q[3])
-
-
-def zncc_pick_oracle(moments, S, min_cells):
-    """(best (8,) int64, peak (2,) float64) from a moments table, sequentially."""
-    def candidate(dy, dx):
-        m = moments[dy + S, dx + S]
-        q = zncc_q(m) if int(m[0]) >= min_cells else None
-        return None if q is None else (q, int(m[0]), dy, dx)
-    first, second = T.pick_two(S, candidate, zncc_beats)
-    four = lambda c: [0, 0, 0, 0] if c is None else [c[2], c[3], 1, c[1]]
-    peak = np.array([NAN if c is None else c[0] for c in (first, second)], dtype=F64)
-    return np.array(four(first) + four(second), dtype=np.int64), peak
-
-
-def same_bytes(got, want):
-    return np.ascontiguousarray(got, dtype=F64).tobytes() == np.ascontiguousarray(want, dtype=F64).tobytes()
 
 
 def corr(q):
@@ -89,27 +41,27 @@ HAND_MOMENTS = [[(1, 4, 1, 16, 1, 4), (2, 7, 3, 25, 5, 11), (1, 3, 2, 9, 4, 6)],
 
 
 def test_oracle_2x2_moments_at_search_1():
-    mo = zncc_search_oracle(T.HAND_A, T.HAND_B, 2, 2, 1)
+    mo = T.zncc_search_oracle(T.HAND_A, T.HAND_B, 2, 2, 1)
     assert mo.tolist() == [[list(c) for c in row] for row in HAND_MOMENTS]
     # (0, 0): c = 4 * 30 - 100 = 20 = va = vb: q = 400 / 400.  (0, +-1): c = 2 * 14 - 24 = 4, va = 20 - 16 = 4, vb = 40 - 36 = 4: q = 1
     # too, as (+-1, 0): c = 22 - 21 = 1 = va = vb.  One cell has va = 0.  All five tie at q == 1: (0, 0) has the smallest key.
-    assert zncc_q(mo[1, 1]) == 1.0 and zncc_q(mo[1, 2]) == 1.0 and zncc_q(mo[0, 1]) == 1.0 and zncc_q(mo[0, 0]) is None
-    best, peak = zncc_pick_oracle(mo, 1, 1)
+    assert T.zncc_q(mo[1, 1]) == 1.0 and T.zncc_q(mo[1, 2]) == 1.0 and T.zncc_q(mo[0, 1]) == 1.0 and T.zncc_q(mo[0, 0]) is None
+    best, peak = T.zncc_pick_oracle(mo, 1, 1)
     assert best.tolist() == [0, 0, 1, 4, 0, 0, 0, 0] and peak[0] == 1.0 and np.isnan(peak[1])   # nothing outside the peak's 3 x 3
-    best, peak = zncc_pick_oracle(mo, 1, 3)
+    best, peak = T.zncc_pick_oracle(mo, 1, 3)
     assert best.tolist() == [0, 0, 1, 4, 0, 0, 0, 0] and peak[0] == 1.0
-    best, peak = zncc_pick_oracle(mo, 1, 5)                                           # no offset has 5 cells
+    best, peak = T.zncc_pick_oracle(mo, 1, 5)                                           # no offset has 5 cells
     assert best.tolist() == [0] * 8 and np.isnan(peak).all()
 
 
 def test_oracle_constant_plane_has_no_eligible_offset():
     rng = np.random.default_rng(1)
     A, B = np.full((4, 4), 9, dtype=np.uint8), rng.integers(1, 256, size=(8, 8), dtype=np.uint8)
-    mo = zncc_search_oracle(A, B, 4, 4, 2)
+    mo = T.zncc_search_oracle(A, B, 4, 4, 2)
     assert (mo[..., 0] == 16).all() and (mo[..., 1] == 144).all() and (mo[..., 3] == 1296).all()      # va = 16 * 1296 - 144^2 = 0
-    best, peak = zncc_pick_oracle(mo, 2, 1)
+    best, peak = T.zncc_pick_oracle(mo, 2, 1)
     assert best.tolist() == [0] * 8 and np.isnan(peak).all()
-    best, peak = zncc_pick_oracle(zncc_search_oracle(B[:4, :4], np.full((8, 8), 200, dtype=np.uint8), 4, 4, 2), 2, 1)   # vb = 0
+    best, peak = T.zncc_pick_oracle(T.zncc_search_oracle(B[:4, :4], np.full((8, 8), 200, dtype=np.uint8), 4, 4, 2), 2, 1)   # vb = 0
     assert best.tolist() == [0] * 8 and np.isnan(peak).all()
 
 
@@ -118,10 +70,10 @@ def test_oracle_gain_and_offset_score_exactly_one():
     A = rng.integers(1, 120, size=(6, 6), dtype=np.uint8)
     B = rng.integers(1, 256, size=(10, 10), dtype=np.uint8)
     B[2 + 1:2 + 1 + 6, 2 - 2:2 - 2 + 6] = 2 * A + 7                                   # B = 2 A + 7 at (dy, dx) = (1, -2)
-    mo = zncc_search_oracle(A, B, 6, 6, 2)
+    mo = T.zncc_search_oracle(A, B, 6, 6, 2)
     # c = 2 va and vb = 4 va there: q = (2 va)^2 / (va * 4 va), and both products are exact in double (va < 2^26)
-    assert zncc_q(mo[3, 0]) == 1.0
-    best, peak = zncc_pick_oracle(mo, 2, 1)
+    assert T.zncc_q(mo[3, 0]) == 1.0
+    best, peak = T.zncc_pick_oracle(mo, 2, 1)
     assert best[:4].tolist() == [1, -2, 1, 36] and peak[0] == 1.0 and best[6] == 1 and peak[1] < 1.0
 
 
@@ -130,30 +82,30 @@ def test_oracle_anticorrelation_is_negative_and_loses():
     A = rng.integers(1, 200, size=(5, 5), dtype=np.uint8)
     B = rng.integers(1, 256, size=(9, 9), dtype=np.uint8)
     B[2:7, 2:7] = 255 - A                                                            # (0, 0): the negative of A
-    mo = zncc_search_oracle(A, B, 5, 5, 2)
-    assert zncc_q(mo[2, 2]) == -1.0
+    mo = T.zncc_search_oracle(A, B, 5, 5, 2)
+    assert T.zncc_q(mo[2, 2]) == -1.0
     table = np.zeros((5, 5, 6), dtype=np.int64)
     table[2, 2] = mo[2, 2]                                                            # q = -1 at (0, 0), the smallest key
     table[4, 4] = (4, 10, 14, 30, 54, 39)                                             # (2, 2): c = 16, va = 20, vb = 20: q = 0.64
-    assert zncc_q(table[4, 4]) == F64(256.0) / F64(400.0)
-    best, peak = zncc_pick_oracle(table, 2, 1)
+    assert T.zncc_q(table[4, 4]) == F64(256.0) / F64(400.0)
+    best, peak = T.zncc_pick_oracle(table, 2, 1)
     assert best.tolist() == [2, 2, 1, 4, 0, 0, 1, 25] and peak.tolist() == [0.64, -1.0]   # any positive score beats it
-    assert not zncc_beats((F64(-1.0), 25, 0, 0), (F64(0.64), 4, 2, 2))
+    assert not T.zncc_beats((F64(-1.0), 25, 0, 0), (F64(0.64), 4, 2, 2))
 
 
 def test_oracle_equal_scores_fall_to_the_key():
     table = np.zeros((5, 5, 6), dtype=np.int64)
     m = (4, 10, 14, 30, 54, 39)                                                       # q = 0.64
     twice = (8, 20, 28, 60, 108, 78)                                                  # the same cells twice: c, va, vb * 4, q the same
-    assert zncc_q(m) == zncc_q(twice)
+    assert T.zncc_q(m) == T.zncc_q(twice)
     table[4, 2], table[0, 2] = m, twice                                               # (2, 0) and (-2, 0): dy = -2 < 2
-    best, peak = zncc_pick_oracle(table, 2, 1)
+    best, peak = T.zncc_pick_oracle(table, 2, 1)
     assert best.tolist() == [-2, 0, 1, 8, 2, 0, 1, 4] and peak[0] == peak[1]
     table[2, 3] = m                                                                   # (0, 1): d2 = 1 wins; (2, 0) then (-2, 0) are outside its 3 x 3
-    best, peak = zncc_pick_oracle(table, 2, 1)
+    best, peak = T.zncc_pick_oracle(table, 2, 1)
     assert best.tolist() == [0, 1, 1, 4, -2, 0, 1, 8]
     table[2, 3] = (4, 10, 14, 30, 54, 38)                                             # a lower score loses whatever its key
-    best, peak = zncc_pick_oracle(table, 2, 1)
+    best, peak = T.zncc_pick_oracle(table, 2, 1)
     assert best.tolist() == [-2, 0, 1, 8, 2, 0, 1, 4]
 
 
@@ -194,7 +146,7 @@ def test_exposure_change_breaks_sad_and_not_zncc():
     assert A.min() >= 1 and B.min() >= 1
     sad = T.pick_oracle(T.search_oracle(A, B, G, G, S), S, 1)
     assert tuple(sad[:2].tolist()) != EXPO_TRUE                                        # SAD's minimum has moved off the true shift
-    best, peak = zncc_pick_oracle(zncc_search_oracle(A, B, G, G, S), S, 1)
+    best, peak = T.zncc_pick_oracle(T.zncc_search_oracle(A, B, G, G, S), S, 1)
     assert tuple(best[:2].tolist()) == EXPO_TRUE and best[2] == 1 and peak[0] > 0.99 and peak[1] < peak[0]
     # without the gain and the offset SAD finds it too: the fixture isolates the exposure
     same = np.floor(2.0 * (B.astype(F64) - 20.0)).astype(np.uint8)
@@ -205,12 +157,11 @@ def test_exposure_change_breaks_sad_and_not_zncc():
 
 def _abi_zncc(n_pairs=3, search=4, side=64, min_cells=1, a=0x5001, b=0x6001, pairs=0x4000, moments=0x8000, best=0xa000, peak=0xb000):
     """wm_register_search_zncc with fake, never dereferenced device pointers: only paths that return before any HIP call."""
-    p = lambda v: C.c_void_p(v) if v else None
-    return N.lib().wm_register_search_zncc(p(a), p(b), p(pairs), n_pairs, search, side, min_cells, p(moments), p(best), p(peak), None)
+    return N.lib().wm_register_search_zncc(_p(a), _p(b), _p(pairs), n_pairs, search, side, min_cells, _p(moments), _p(best), _p(peak), None)
 
 
 def test_zncc_abi_argument_errors_without_gpu():
-    err = lambda: N.lib().wm_last_error().decode()
+    err = last_error
     assert _abi_zncc(n_pairs=-1) < 0 and "n_pairs" in err()
     assert _abi_zncc(n_pairs=N.REGISTER_MAX_PAIRS + 1) < 0 and "n_pairs" in err()
     assert _abi_zncc(search=-1) < 0 and "search" in err()
@@ -236,13 +187,11 @@ def test_zncc_abi_argument_errors_without_gpu():
 
 
 def test_zncc_symbol_and_abi_13():
-    hdr = open(os.path.join(T.ROOT, "include", "wm_hip.h")).read()
-    assert int(re.search(r"#define WM_ABI_VERSION (\d+)", hdr).group(1)) == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
-    assert "Survey registration, correlation search" in hdr and len(re.findall("13, additive", hdr)) >= 4
-    assert "wm_register_search_zncc" in N.SYMBOLS and re.search(r"\bint wm_register_search_zncc\(", hdr)
-    assert N.lib().wm_register_search_zncc is not None
+    assert macro("WM_ABI_VERSION") == 13 == N.ABI_VERSION == N.lib().wm_abi_version()
+    assert "Survey registration, correlation search" in header() and len(re.findall("13, additive", header())) >= 4
+    assert entry_is_whole("wm_register_search_zncc")
     assert len(N.SYMBOLS["wm_register_search_zncc"][1]) == 11
-    kern = open(os.path.join(T.ROOT, "wildlifemapper_amd", "csrc", "register_kernels.h")).read()
+    kern = open(os.path.join(ROOT, "wildlifemapper_amd", "csrc", "register_kernels.h")).read()
     assert "__builtin_amdgcn_udot4(" in kern and "asm" not in kern
 
 
@@ -287,11 +236,11 @@ def _check(A, B, sizes, S, min_cells, want=None):
     moments, best, peak = _zncc(A, B, sizes, S, min_cells)
     out = []
     for p, (gx, gy) in enumerate(sizes):
-        mo = zncc_search_oracle(A[p], B[p], gx, gy, S) if want is None else want[p]
-        wb, wp = zncc_pick_oracle(mo, S, min_cells)
+        mo = T.zncc_search_oracle(A[p], B[p], gx, gy, S) if want is None else want[p]
+        wb, wp = T.zncc_pick_oracle(mo, S, min_cells)
         np.testing.assert_array_equal(moments[p], mo, err_msg=f"moments of pair {p}")
         np.testing.assert_array_equal(best[p], wb, err_msg=f"best of pair {p}")
-        assert same_bytes(peak[p], wp), (p, peak[p], wp)
+        assert T.same_bytes(peak[p], wp), (p, peak[p], wp)
         out.append((mo, wb, wp))
     return out
 
@@ -383,7 +332,7 @@ def test_gpu_zncc_min_cells_boundary_on_a_hand_built_mask():
     A[:, 66:] = 200                                                                   # beyond gx: must not count
     A[67:, :] = 200
     B = rng.integers(1, 256, size=(70, 70), dtype=np.uint8)                           # search 0: E = side; B sees everything
-    want = zncc_search_oracle(A, B, 66, 67, 0)
+    want = T.zncc_search_oracle(A, B, 66, 67, 0)
     assert want[0, 0, 0] == 1234
     (_, best, peak), = _check([A], [B], [(66, 67)], 0, 1234, want=[want])
     assert best.tolist() == [0, 0, 1, 1234, 0, 0, 0, 0] and np.isfinite(peak[0])       # n == min_cells is eligible
@@ -482,7 +431,7 @@ def _e2e_oracles():
         fa, fb, gx, gy = (int(pr[k]) for k in ("frame_a", "frame_b", "gx", "gy"))
         A = T.render_plane(g2p[fa], sizes[fa], frames[fa], pr["x0"], pr["y0"], 1.0, gx, gy, 0, side)
         B = T.render_plane(g2p[fb], sizes[fb], frames[fb], pr["x0"], pr["y0"], 1.0, gx, gy, S, side + 2 * S)
-        out.append((T.pick_oracle(T.search_oracle(A, B, gx, gy, S), S, mc), zncc_pick_oracle(zncc_search_oracle(A, B, gx, gy, S), S, mc)))
+        out.append((T.pick_oracle(T.search_oracle(A, B, gx, gy, S), S, mc), T.zncc_pick_oracle(T.zncc_search_oracle(A, B, gx, gy, S), S, mc)))
     return pairs, out
 
 

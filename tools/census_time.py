@@ -3,7 +3,7 @@
   python tools/census_time.py [--reps 20] [--skip-oracle]
       HIP-event min and median over --reps repetitions of one wm_census call (its single launch; buffers and scratch are
       allocated once, outside the timed region), the rounds its resolution took, and -- once each -- the wall clock of
-      census_oracle (tests/test_census.py: the sequential numpy restatement, the host route) on the same inputs, whose
+      census_oracle (tests/ground_oracle.py: the sequential numpy restatement, the host route) on the same inputs, whose
       result the device's must equal.  Three settings, radius 1 m, every animal seen by 3 frames with 0.15 m of noise:
         survey_2000     n = 2 000, F = 40, 2 animals per 100 m^2;
         survey_50000    n = 50 000, F = 1 000, 2 animals per 100 m^2;
@@ -76,7 +76,7 @@ def run(case, reps, skip_oracle):
            "rounds": int(scratch[:4].view(torch.int32).item()),
            "ms_min": round(float(np.min(ms)), 4), "ms_median": round(float(np.median(ms)), 4)}
     if not skip_oracle:
-        from test_census import census_oracle
+        from ground_oracle import census_oracle
         t = time.perf_counter()
         want = census_oracle(case["boxes"], case["scores"], case["labels"], case["frame"], case["georef"], RADIUS)
         out["oracle_host_s"] = round(time.perf_counter() - t, 2)

@@ -3,7 +3,7 @@
   python tools/coverage_time.py [--reps 20] [--skip-oracle] [--only NAME]
       HIP-event min and median over --reps repetitions of one wm_coverage_raster call and, with points, of one
       wm_coverage_points call (their memsets and single launches; buffers are allocated once, outside the timed region),
-      and -- once each -- the wall clock of the numpy restatement of the rule on the same input (tests/test_coverage.py:
+      and -- once each -- the wall clock of the numpy restatement of the rule on the same input (tests/ground_oracle.py:
       coverage_oracle_by_frame for the raster, a frame at a time over the cells around its footprint; the points part
       of coverage_oracle on a 1 x 1 grid's worth of arithmetic per point), whose result the device's must equal.
       Three settings, yawed nadir frames of 400 x 600 px at UTM-sized coordinates, placed so that a cell is seen by
@@ -72,7 +72,7 @@ def run(case, reps, skip_oracle):
         call(counts)
         out["binned"] = int(pstats[0].item())
     if not skip_oracle:
-        from test_coverage import coverage_oracle, coverage_oracle_by_frame
+        from ground_oracle import coverage_oracle, coverage_oracle_by_frame
         t = time.perf_counter()
         want = coverage_oracle_by_frame(case["g2p"], case["size"], *grid)
         out["oracle_raster_host_s"] = round(time.perf_counter() - t, 2)

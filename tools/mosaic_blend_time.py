@@ -10,7 +10,7 @@ hard mosaic it replaces (wm_mosaic_plan, wm_mosaic_fill_u8) and the host route.
         the timed region), and the finish (one launch);
         wm_mosaic_plan and wm_mosaic_fill_u8 on the same survey: what the blend costs over the hard mosaic;
       and -- once per setting -- the wall clock of the numpy restatement of the rule on the same input
-      (tests/test_mosaic_blend.py: blend_oracle_by_frame), whose best, cells, statistics, accumulators and pictures the
+      (tests/ground_oracle.py: blend_oracle_by_frame), whose best, cells, statistics, accumulators and pictures the
       device's must equal.  The settings are those of tools/mosaic_time.py: yawed nadir frames of 400 x 600 px of random
       content at UTM-sized coordinates, three to four frames per cell on average,
         f40_512      F = 40 on a 512 x 512 grid;
@@ -109,7 +109,7 @@ def run(case, reps, band, skip_oracle):
         blend = out["blend_plan_ms_min"] + out[f"accum_{mode}_resident_ms_min"] + out["finish_ms_min"]
         out[f"blend_over_hard_{mode}"] = round(blend / hard, 2)
     if not skip_oracle:
-        from test_mosaic_blend import blend_oracle_by_frame
+        from ground_oracle import blend_oracle_by_frame
         host = pixels.cpu().numpy()
         t = time.perf_counter()
         want = blend_oracle_by_frame(case["g2p"], case["size"], *grid, band, frames=host, fill=(0, 0, 0))

@@ -4,7 +4,7 @@
       HIP-event min and median over --reps repetitions of one wm_mosaic_plan call (its two memsets and one launch) and of
       one wm_mosaic_fill_u8 call in each mode with every frame of the survey resident (one launch; buffers and frames are
       allocated once, outside the timed region), and -- once per setting -- the wall clock of the numpy restatement of the
-      rule on the same input (tests/test_mosaic.py: mosaic_oracle_by_frame, a frame at a time over the cells around its
+      rule on the same input (tests/ground_oracle.py: mosaic_oracle_by_frame, a frame at a time over the cells around its
       footprint), whose source raster, statistics and pictures the device's must equal.
       Two settings, yawed nadir frames of 400 x 600 px of random content at UTM-sized coordinates, placed so that a cell
       is seen by three to four frames on average:
@@ -78,7 +78,7 @@ def run(case, reps, skip_oracle):
         pictures[mode] = pic
     out["fill_status"] = int(status.item())
     if not skip_oracle:
-        from test_mosaic import mosaic_oracle_by_frame
+        from ground_oracle import mosaic_oracle_by_frame
         host = pixels.cpu().numpy()
         t = time.perf_counter()
         want = mosaic_oracle_by_frame(case["g2p"], case["size"], *grid, frames=host, fill=(0, 0, 0))

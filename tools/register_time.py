@@ -10,7 +10,7 @@ wm_register_search_zncc, the correlation) on the same planes, against the host r
       zncc_ms_*, and the ratio zncc / sad of the minima and of the medians).  The refinement's sums (wm_register_refine: one
       memset and one launch, one pass over the same planes, of which it uses the centre offset alone) are timed the same
       way, alternating with the SAD search (refine_ms_*, sad_beside_refine_ms_min and the ratio sad / refine of the minima);
-      for the first --refine-oracle-pairs pairs they must equal tests/test_register_refine.py's refine_sums_oracle.
+      for the first --refine-oracle-pairs pairs they must equal tests/register_cases.py's refine_sums_oracle.
       Two settings, nadir frames of 400 x 600 px (20 x 30 m at 0.05 m) of random content at UTM-sized coordinates on
       flight lines with 55 % forward overlap and 30 % sidelap, a little jitter in position and heading, cell = 0.05 m:
         f40      F = 40 (4 lines of 10), side 256, search 16, pair_chunk 64;
@@ -27,7 +27,7 @@ wm_register_search_zncc, the correlation) on the same planes, against the host r
       input (tests/register_cases.py: register_oracle), whose planes, score table and best the device's must equal; it
       costs seconds per pair at the survey setting, so it runs on a sample and its time for the survey is the sample's
       mean per byte difference times the survey's byte differences.  For the first --zncc-oracle-pairs pairs the device's
-      moments, best and peak must equal the restatement of the correlation rule (tests/test_register_zncc.py:
+      moments, best and peak must equal the restatement of the correlation rule (tests/register_cases.py:
       zncc_search_oracle, zncc_pick_oracle) on the device's planes, peak by its bytes.  The tool asserts both;
       equals_oracle is true where every comparison that ran held.
       Prints one JSON line.  No figure is a pass mark: the numbers are records.
@@ -170,7 +170,7 @@ def run(lines, per_line, side, search, pair_chunk, seed, reps, oracle_pairs, znc
                          np.array_equal(got_s[p], want["score"][p]) and np.array_equal(got_best[p], want["best"][p]) for p in range(m)))
         out["sad_equals_oracle"] = bool(equal[-1])
     if zncc_oracle_pairs > 0:
-        from test_register_zncc import same_bytes, zncc_pick_oracle, zncc_search_oracle
+        from register_cases import same_bytes, zncc_pick_oracle, zncc_search_oracle
         m = min(zncc_oracle_pairs, n)
         A, B = a[:m].cpu().numpy(), b[:m].cpu().numpy()
         got_m, got_b, got_p = moments[:m].cpu().numpy(), best[:m].cpu().numpy(), peak[:m].cpu().numpy()
@@ -184,7 +184,7 @@ def run(lines, per_line, side, search, pair_chunk, seed, reps, oracle_pairs, znc
         out["zncc_oracle_pairs"], out["zncc_oracle_host_s"], out["zncc_equals_oracle"] = m, round(time.perf_counter() - t, 2), bool(ok)
         out["sampled_peaks_r"] = [round(float(np.sign(q) * np.sqrt(abs(q))), 4) for q in got_p[:, 0]]
     if refine_oracle_pairs > 0:
-        from test_register_refine import refine_sums_oracle
+        from register_cases import refine_sums_oracle
         m = min(refine_oracle_pairs, n)
         refine()
         torch.cuda.synchronize()

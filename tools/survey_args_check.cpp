@@ -1,0 +1,273 @@
+// Stand-alone check of the host-side argument validation of every survey entry point -- wm_census, wm_coverage_raster,
+// wm_coverage_points, wm_mosaic_plan, wm_mosaic_fill_u8, wm_mosaic_blend_plan, wm_mosaic_blend_accum_u8,
+// wm_mosaic_blend_finish_u8, wm_register_render_u8, wm_register_search, wm_register_search_zncc and wm_register_refine -- for
+// a sanitizer build of the host code (no GPU needed: every call here returns before the first HIP call).  Build and run,
+// from the repository root, as a program of its own:
+//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Wno-unused-value -Xarch_host -fsanitize=address,undefined \
+//         -Xarch_host -fno-sanitize-recover=undefined -I include tools/survey_args_check.cpp wildlifemapper_amd/csrc/wm_api.hip \
+//         -o survey_args_check && ./survey_args_check
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <initializer_list>
+#include <limits>
+
+#include "wm_hip.h"
+
+static int failures = 0, checks = 0;
+
+static void expect(bool ok, const char* what) {
+    ++checks;
+    if (!ok) { std::printf("FAIL: %s (last error: %s)\n", what, wm_last_error()); ++failures; }
+}
+
+static bool says(const char* word) { return std::strstr(wm_last_error(), word) != nullptr; }
+
+// Fake device pointers, never dereferenced on these paths; every one as aligned as its entry asks, and no more where an
+// entry asks for nothing (a, b, mosaic).  buf stands for all eleven buffers of wm_census.
+struct Args {
+    uintptr_t frames = 0x1000, g2p = 0x2000, size = 0x3000, pairs = 0x4000, a = 0x5001, b = 0x6003, slot = 0x7000, score = 0x8000,
+              status = 0x9000, best = 0xa000, peak = 0xb000, moments = 0xc000, sums = 0xd000, cov = 0xe000, stats = 0xf000, pts = 0x10000,
+              labels = 0x11000, seen = 0x12000, cidx = 0x13000, counts = 0x14000, pstats = 0x15000, source = 0x16000, won = 0x17000,
+              mosaic = 0x18001, blend_best = 0x19000, cells = 0x1a000, index = 0x1b000, acc = 0x1c000, exposure = 0x1d000, scratch = 0x1e000,
+              buf = 0x20000;
+    int n_frames = 2, n_resident = 2, n_pairs = 3, n_points = 4, search = 4, side = 64, min_cells = 1, gx = 5, gy = 3,
+        mode = WM_MOSAIC_BILINEAR, flags = WM_MOSAIC_NORTH_UP, n = 10, census_frames = 1, census_flags = 0;
+    int64_t scratch_bytes = wm_census_scratch_bytes(10);
+    double x0 = 0.0, y0 = 0.0, cell = 0.5, band = 8.0, radius = 1.0;
+};
+
+static int census(const Args& a) {
+    void* p = (void*)a.buf;
+    return wm_census((const float*)p, (const float*)p, (const int32_t*)p, (const int32_t*)p, a.n, (const double*)p, a.census_frames, a.radius,
+                     a.census_flags, (void*)a.scratch, a.scratch_bytes, (double*)p, (int32_t*)p, (int32_t*)p, (int32_t*)p, (int32_t*)p, nullptr);
+}
+
+static int raster(const Args& a) {
+    return wm_coverage_raster((const double*)a.g2p, (const int32_t*)a.size, a.n_frames, a.x0, a.y0, a.cell, a.gx, a.gy, (uint16_t*)a.cov,
+                              (int64_t*)a.stats, nullptr);
+}
+
+static int points(const Args& a) {
+    return wm_coverage_points((const double*)a.g2p, (const int32_t*)a.size, a.n_frames, (const double*)a.pts, (const int32_t*)a.labels,
+                              a.n_points, a.x0, a.y0, a.cell, a.gx, a.gy, (int32_t*)a.seen, (int32_t*)a.cidx, (int32_t*)a.counts,
+                              (int64_t*)a.pstats, nullptr);
+}
+
+static int plan(const Args& a) {
+    return wm_mosaic_plan((const double*)a.g2p, (const int32_t*)a.size, a.n_frames, a.x0, a.y0, a.cell, a.gx, a.gy, (int32_t*)a.source,
+                          (int32_t*)a.won, (int64_t*)a.stats, nullptr);
+}
+
+static int fill(const Args& a) {
+    return wm_mosaic_fill_u8((const wm_frame_desc*)a.frames, a.n_resident, (const int32_t*)a.slot, (const double*)a.g2p, (const int32_t*)a.size,
+                             a.n_frames, a.x0, a.y0, a.cell, a.gx, a.gy, (const int32_t*)a.source, a.mode, a.flags, (uint8_t*)a.mosaic,
+                             (int32_t*)a.status, nullptr);
+}
+
+static int blend_plan(const Args& a) {
+    return wm_mosaic_blend_plan((const double*)a.g2p, (const int32_t*)a.size, a.n_frames, a.x0, a.y0, a.cell, a.gx, a.gy, a.band,
+                                (double*)a.blend_best, (int32_t*)a.cells, (int64_t*)a.stats, nullptr);
+}
+
+static int accum(const Args& a) {
+    return wm_mosaic_blend_accum_u8((const wm_frame_desc*)a.frames, (const int32_t*)a.index, a.n_resident, (const double*)a.g2p,
+                                    (const int32_t*)a.size, a.n_frames, (const int32_t*)a.exposure, a.x0, a.y0, a.cell, a.gx, a.gy, a.band,
+                                    (const double*)a.blend_best, a.mode, (uint32_t*)a.acc, (int32_t*)a.status, nullptr);
+}
+
+static int finish(const Args& a) { return wm_mosaic_blend_finish_u8((const uint32_t*)a.acc, a.gx, a.gy, a.flags, (uint8_t*)a.mosaic, nullptr); }
+
+static int render(const Args& a) {
+    return wm_register_render_u8((const wm_frame_desc*)a.frames, a.n_resident, (const int32_t*)a.slot, (const double*)a.g2p,
+                                 (const int32_t*)a.size, a.n_frames, (const wm_register_pair*)a.pairs, a.n_pairs, a.cell, a.search, a.side,
+                                 (uint8_t*)a.a, (uint8_t*)a.b, (int32_t*)a.status, nullptr);
+}
+
+static int search(const Args& a) {
+    return wm_register_search((const uint8_t*)a.a, (const uint8_t*)a.b, (const wm_register_pair*)a.pairs, a.n_pairs, a.search, a.side,
+                              a.min_cells, (int32_t*)a.score, (int32_t*)a.best, nullptr);
+}
+
+static int zncc(const Args& a) {
+    return wm_register_search_zncc((const uint8_t*)a.a, (const uint8_t*)a.b, (const wm_register_pair*)a.pairs, a.n_pairs, a.search, a.side,
+                                   a.min_cells, (int64_t*)a.moments, (int32_t*)a.best, (double*)a.peak, nullptr);
+}
+
+static int refine(const Args& a) {
+    return wm_register_refine((const uint8_t*)a.a, (const uint8_t*)a.b, (const wm_register_pair*)a.pairs, a.n_pairs, a.search, a.side,
+                              (int64_t*)a.sums, nullptr);
+}
+
+// an entry and the name its messages begin with
+struct Entry { int (*call)(const Args&); const char* name; };
+static const Entry CENSUS = {census, "wm_census: "}, RASTER = {raster, "wm_coverage_raster: "}, POINTS = {points, "wm_coverage_points: "},
+                   PLAN = {plan, "wm_mosaic_plan: "}, FILL = {fill, "wm_mosaic_fill_u8: "}, BPLAN = {blend_plan, "wm_mosaic_blend_plan: "},
+                   ACCUM = {accum, "wm_mosaic_blend_accum_u8: "}, FINISH = {finish, "wm_mosaic_blend_finish_u8: "},
+                   RENDER = {render, "wm_register_render_u8: "}, SEARCH = {search, "wm_register_search: "},
+                   ZNCC = {zncc, "wm_register_search_zncc: "}, REFINE = {refine, "wm_register_refine: "};
+
+// a bad argument: each of the entries refuses it under its own name with `word` in the message
+template <class F>
+static void bad(std::initializer_list<Entry> entries, F change, const char* word, const char* what) {
+    Args a;
+    change(a);
+    for (const Entry& e : entries) expect(e.call(a) < 0 && says(e.name) && says(word), what);
+}
+
+// arguments that are in order: the entry returns 0 before any HIP call
+template <class F>
+static void fine(const Entry& e, F change, const char* what) {
+    Args a;
+    change(a);
+    expect(e.call(a) == 0, what);
+}
+
+int main() {
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    const int imax = std::numeric_limits<int>::max(), imin = std::numeric_limits<int>::min();
+    expect(wm_abi_version() == WM_ABI_VERSION && WM_ABI_VERSION == 13, "ABI version 13");
+
+    // ---- what the ground entries share (host_survey.h: check_coverage_grid, check_coverage_frames, check_n_resident) ----
+    for (int g : {0, imin, WM_COVERAGE_MAX_SIDE + 1, imax})
+        bad({RASTER, POINTS, PLAN, FILL, BPLAN, ACCUM, FINISH}, [&](Args& a) { a.gx = g; }, "gx", "gx outside 1..the cap");
+    for (int g : {0, -1, -4, WM_COVERAGE_MAX_SIDE + 1, imax})
+        bad({RASTER, POINTS, PLAN, FILL, BPLAN, ACCUM, FINISH}, [&](Args& a) { a.gy = g; }, "gy", "gy outside 1..the cap");
+    bad({RASTER, POINTS, PLAN, FILL, BPLAN, ACCUM, FINISH}, [](Args& a) { a.gx = WM_COVERAGE_MAX_SIDE; a.gy = WM_COVERAGE_MAX_SIDE; }, "gx * gy", "2^28 cells");
+    bad({RASTER, POINTS, PLAN, FILL, BPLAN, ACCUM, FINISH}, [](Args& a) { a.gx = 16384; a.gy = 8192; }, "gx * gy", "2^27 cells");
+    bad({RASTER, POINTS, PLAN, FILL, BPLAN, ACCUM, FINISH}, [](Args& a) { a.gx = 8192; a.gy = 8193; }, "gx * gy", "one row past 2^26 cells");
+    for (int nf : {-1, imin, WM_COVERAGE_MAX_FRAMES + 1, imax})
+        bad({RASTER, POINTS, PLAN, FILL, BPLAN, ACCUM, RENDER}, [&](Args& a) { a.n_frames = nf; }, "n_frames", "n_frames outside 0..the cap");
+    bad({RASTER, POINTS, PLAN, FILL, BPLAN, ACCUM, RENDER}, [](Args& a) { a.g2p = 0; }, "g2p_dev", "null g2p");
+    bad({RASTER, POINTS, PLAN, FILL, BPLAN, ACCUM, RENDER}, [](Args& a) { a.size = 0; }, "size_dev", "null size");
+    bad({RASTER, POINTS, PLAN, FILL, BPLAN, ACCUM, RENDER}, [](Args& a) { a.g2p += 4; }, "aligned", "misaligned g2p");
+    bad({RASTER, POINTS, PLAN, FILL, BPLAN, ACCUM, RENDER}, [](Args& a) { a.size += 2; }, "aligned", "misaligned size");
+    for (double o : {nan, inf, -inf}) {
+        bad({RASTER, POINTS, PLAN, FILL, BPLAN, ACCUM}, [&](Args& a) { a.x0 = o; }, "x0", "x0 not finite");
+        bad({RASTER, POINTS, PLAN, FILL, BPLAN, ACCUM}, [&](Args& a) { a.y0 = o; }, "y0", "y0 not finite");
+    }
+    for (double cell : {0.0, -0.5, nan, inf, -inf})
+        bad({RASTER, POINTS, PLAN, FILL, BPLAN, ACCUM, RENDER}, [&](Args& a) { a.cell = cell; }, "cell", "cell not a finite number > 0");
+    for (int nr : {-1, imin, WM_COVERAGE_MAX_FRAMES + 1, imax})
+        bad({FILL, ACCUM, RENDER}, [&](Args& a) { a.n_resident = nr; }, "n_resident", "n_resident outside 0..the cap");
+    bad({FILL, ACCUM, RENDER}, [](Args& a) { a.frames = 0; }, "frames_dev", "null frames");
+    bad({FILL, ACCUM, RENDER}, [](Args& a) { a.frames += 4; }, "aligned", "misaligned frames");
+    bad({FILL, ACCUM, RENDER}, [](Args& a) { a.status = 0; }, "status_dev", "null status");
+    bad({FILL, ACCUM, RENDER}, [](Args& a) { a.status += 2; }, "aligned", "misaligned status");
+    bad({FILL, RENDER}, [](Args& a) { a.slot = 0; }, "slot_dev", "null slot");
+    bad({FILL, RENDER}, [](Args& a) { a.slot += 2; }, "aligned", "misaligned slot");
+    bad({RASTER, PLAN, BPLAN}, [](Args& a) { a.stats = 0; }, "stats_dev", "null stats");
+    bad({RASTER, PLAN, BPLAN}, [](Args& a) { a.stats += 4; }, "aligned", "misaligned stats");
+    for (int mode : {-1, 2, 7, imax, imin}) bad({FILL, ACCUM}, [&](Args& a) { a.mode = mode; }, "mode", "bad mode");
+    for (int flags : {2, 3, 4, -1, -2, imin, imax}) bad({FILL, FINISH}, [&](Args& a) { a.flags = flags; }, "flags", "unknown flags bits");
+    bad({FILL, FINISH}, [](Args& a) { a.mosaic = 0; }, "mosaic_dev", "null mosaic");
+
+    // ---- census ----
+    expect(wm_census_scratch_bytes(0) >= 0, "scratch bytes of 0");
+    expect(wm_census_scratch_bytes(WM_CENSUS_MAX_DETS) > 0, "scratch bytes at the cap");
+    expect(wm_census_scratch_bytes(WM_CENSUS_MAX_DETS + 1) < 0, "scratch bytes past the cap");
+    expect(wm_census_scratch_bytes(-1) < 0 && wm_census_scratch_bytes(imin) < 0, "scratch bytes of n < 0");
+    expect(wm_census_scratch_bytes(imax) < 0, "scratch bytes of INT_MAX");
+    expect(wm_census(nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nan, -1, nullptr, -1, nullptr, nullptr, nullptr, nullptr, nullptr,
+                     nullptr) == 0, "census: n == 0 returns 0 before any pointer");
+    bad({CENSUS}, [](Args& a) { a.n = -1; }, "outside", "census: n < 0");
+    bad({CENSUS}, [](Args& a) { a.n = WM_CENSUS_MAX_DETS + 1; a.scratch_bytes = INT64_MAX; }, "outside", "census: n past the cap");
+    bad({CENSUS}, [&](Args& a) { a.n = imax; a.scratch_bytes = INT64_MAX; }, "outside", "census: n = INT_MAX");
+    bad({CENSUS}, [](Args& a) { a.buf = 0; }, "null", "census: null buffers");
+    bad({CENSUS}, [](Args& a) { a.census_frames = 0; }, "n_frames", "census: n_frames 0");
+    for (double r : {-1.0, nan, inf}) bad({CENSUS}, [&](Args& a) { a.radius = r; }, "radius", "census: radius not a finite number >= 0");
+    bad({CENSUS}, [](Args& a) { a.radius = 1e200; }, "square", "census: radius^2 overflows");
+    bad({CENSUS}, [](Args& a) { a.census_flags = 2; }, "flags", "census: unknown flag");
+    bad({CENSUS}, [](Args& a) { a.census_flags = -1; }, "flags", "census: flags -1");
+    bad({CENSUS}, [](Args& a) { a.scratch_bytes -= 1; }, "scratch of", "census: scratch one byte short");
+    bad({CENSUS}, [](Args& a) { a.scratch_bytes = -5; }, "scratch of", "census: negative scratch size");
+    bad({CENSUS}, [](Args& a) { a.scratch += 8; }, "aligned", "census: misaligned scratch");
+    bad({CENSUS}, [](Args& a) { a.buf += 4; }, "aligned", "census: misaligned boxes / points");
+
+    // ---- coverage ----
+    bad({RASTER}, [](Args& a) { a.cov = 0; }, "coverage_dev", "null coverage");
+    bad({RASTER}, [](Args& a) { a.cov += 1; }, "aligned", "misaligned coverage");
+    bad({POINTS}, [](Args& a) { a.pts = 0; }, "null", "null points");
+    bad({POINTS}, [](Args& a) { a.labels = 0; }, "null", "null labels");
+    bad({POINTS}, [](Args& a) { a.seen = 0; }, "null", "null seen_by");
+    bad({POINTS}, [](Args& a) { a.cidx = 0; }, "null", "null cell");
+    bad({POINTS}, [](Args& a) { a.pstats = 0; }, "null", "null pstats");
+    bad({POINTS}, [](Args& a) { a.pts += 4; }, "aligned", "misaligned points");
+    bad({POINTS}, [](Args& a) { a.pstats += 4; }, "aligned", "misaligned pstats");
+    bad({POINTS}, [](Args& a) { a.counts += 2; }, "aligned", "misaligned counts");
+    for (int np : {-1, WM_CENSUS_MAX_DETS + 1, imax}) bad({POINTS}, [&](Args& a) { a.n_points = np; }, "n_points", "n_points outside 0..the cap");
+    expect(wm_coverage_points(nullptr, nullptr, -5, nullptr, nullptr, 0, nan, nan, -1.0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr) == 0,
+           "points: n_points == 0 returns 0 before any pointer");
+
+    // ---- mosaic ----
+    bad({PLAN, FILL}, [](Args& a) { a.source = 0; }, "source_dev", "null source");
+    bad({PLAN, FILL}, [](Args& a) { a.source += 2; }, "aligned", "misaligned source");
+    bad({PLAN}, [](Args& a) { a.won = 0; }, "won_dev", "null won");
+    bad({PLAN}, [](Args& a) { a.won += 2; }, "aligned", "misaligned won");
+    // nothing can be resident: 0 after the checks, before any HIP call
+    fine(FILL, [](Args& a) { a.n_resident = 0; a.frames = 0; a.slot = 0; }, "fill: n_resident == 0 returns 0");
+    fine(FILL, [](Args& a) { a.n_frames = 0; a.g2p = 0; a.size = 0; a.frames = 0; a.slot = 0; }, "fill: n_frames == 0 returns 0");
+    bad({FILL}, [](Args& a) { a.n_resident = 0; a.mode = 9; }, "mode", "fill: n_resident == 0 still checks mode");
+
+    // ---- mosaic, blended ----
+    for (double band : {0.0, -0.0, -8.0, nan, inf, -inf, std::numeric_limits<double>::denorm_min()})      // the last: 256 / band overflows
+        bad({BPLAN, ACCUM}, [&](Args& a) { a.band = band; }, "band", "band not a finite number > 0 with a finite 256 / band");
+    bad({BPLAN, ACCUM}, [](Args& a) { a.blend_best = 0; }, "best_dev", "null best");
+    bad({BPLAN, ACCUM}, [](Args& a) { a.blend_best += 4; }, "aligned", "misaligned best");
+    bad({BPLAN}, [](Args& a) { a.cells = 0; }, "cells_dev", "null cells");
+    bad({BPLAN}, [](Args& a) { a.cells += 2; }, "aligned", "misaligned cells");
+    bad({ACCUM}, [](Args& a) { a.index = 0; }, "index_dev", "null index");
+    bad({ACCUM}, [](Args& a) { a.index += 2; }, "aligned", "misaligned index");
+    bad({ACCUM}, [](Args& a) { a.exposure += 2; }, "aligned", "misaligned exposure");
+    bad({ACCUM, FINISH}, [](Args& a) { a.acc = 0; }, "acc_dev", "null acc");
+    bad({ACCUM, FINISH}, [](Args& a) { a.acc += 2; }, "aligned", "misaligned acc");
+    // no frame to walk: 0 after the checks, before any HIP call; the exposure table may be NULL
+    fine(ACCUM, [](Args& a) { a.n_resident = 0; a.frames = 0; a.index = 0; }, "accum: n_resident == 0 returns 0");
+    fine(ACCUM, [](Args& a) { a.n_resident = 0; a.frames = 0; a.index = 0; a.exposure = 0; }, "accum: n_resident == 0 and no table returns 0");
+    bad({ACCUM}, [](Args& a) { a.n_resident = 0; a.mode = 9; }, "mode", "accum: n_resident == 0 still checks mode");
+    bad({ACCUM}, [](Args& a) { a.n_resident = 0; a.band = 0.0; }, "band", "accum: n_resident == 0 still checks band");
+    bad({ACCUM}, [](Args& a) { a.n_resident = 0; a.acc = 0; }, "acc_dev", "accum: n_resident == 0 still checks acc");
+
+    // ---- registration ----
+    expect(sizeof(wm_register_pair) == 32, "wm_register_pair is 32 bytes");
+    for (int np : {-1, imin, WM_REGISTER_MAX_PAIRS + 1, imax})
+        bad({RENDER, SEARCH, ZNCC, REFINE}, [&](Args& a) { a.n_pairs = np; }, "n_pairs", "n_pairs outside 0..the cap");
+    for (int s : {-1, imin, WM_REGISTER_MAX_SEARCH + 1, imax})
+        bad({RENDER, SEARCH, ZNCC, REFINE}, [&](Args& a) { a.search = s; }, "search", "search outside 0..the cap");
+    for (int side : {0, -7, WM_REGISTER_MAX_SIDE + 1, imax, imin})
+        bad({RENDER, SEARCH, ZNCC, REFINE}, [&](Args& a) { a.side = side; }, "side", "side outside 1..the cap");
+    bad({RENDER, SEARCH, ZNCC, REFINE}, [](Args& a) { a.pairs = 0; }, "pairs_dev", "null pairs");
+    bad({RENDER, SEARCH, ZNCC, REFINE}, [](Args& a) { a.pairs += 4; }, "pairs_dev not 8-byte aligned", "misaligned pairs");
+    bad({RENDER, SEARCH, ZNCC, REFINE}, [](Args& a) { a.a = 0; }, "a_dev", "null a");
+    bad({RENDER, SEARCH, ZNCC, REFINE}, [](Args& a) { a.b = 0; }, "b_dev", "null b");
+    // n_pairs == 0: 0 before looking at any pointer or any other argument
+    for (const Entry& e : {RENDER, SEARCH, ZNCC, REFINE})
+        fine(e, [&](Args& a) { a.n_pairs = 0; a.pairs = a.a = a.b = a.score = a.moments = a.sums = a.best = a.peak = a.status = 0; a.search = -3; a.side = 0;
+                               a.min_cells = 0; a.cell = nan; a.n_frames = -1; }, "n_pairs == 0 returns 0");
+    for (int mc : {0, -1, imin}) bad({SEARCH, ZNCC}, [&](Args& a) { a.min_cells = mc; }, "min_cells", "min_cells below 1");
+    bad({SEARCH, ZNCC}, [](Args& a) { a.best = 0; }, "best_dev", "null best");
+    bad({SEARCH}, [](Args& a) { a.score = 0; }, "score_dev", "null score");
+    bad({SEARCH}, [](Args& a) { a.score += 2; }, "aligned", "misaligned score");
+    bad({SEARCH}, [](Args& a) { a.best += 1; }, "aligned", "misaligned best");
+    bad({ZNCC}, [](Args& a) { a.moments = 0; }, "moments_dev", "null moments");
+    bad({ZNCC}, [](Args& a) { a.peak = 0; }, "peak_dev", "null peak");
+    for (uintptr_t off : {1, 2, 4, 7}) {
+        bad({ZNCC}, [&](Args& a) { a.moments += off; }, "moments_dev not 8-byte aligned", "misaligned moments");
+        bad({ZNCC}, [&](Args& a) { a.peak += off; }, "peak_dev not 8-byte aligned", "misaligned peak");
+        bad({REFINE}, [&](Args& a) { a.sums += off; }, "sums_dev not 8-byte aligned", "misaligned sums");
+    }
+    for (uintptr_t off : {1, 2, 3}) bad({ZNCC}, [&](Args& a) { a.best += off; }, "best_dev not 4-byte aligned", "misaligned best");
+    expect(WM_REGISTER_REFINE_SUMS == 28, "WM_REGISTER_REFINE_SUMS is 28");
+    bad({REFINE}, [](Args& a) { a.search = 0; }, "search", "refine: search 0 (B carries no ring)");
+    bad({REFINE}, [](Args& a) { a.sums = 0; }, "sums_dev", "null sums");
+    // the largest legal shape passes every size computation before the pointer checks stop it
+    const auto largest = [&](Args& a) { a.n_pairs = WM_REGISTER_MAX_PAIRS; a.search = WM_REGISTER_MAX_SEARCH; a.side = WM_REGISTER_MAX_SIDE; a.min_cells = imax; };
+    bad({SEARCH}, [&](Args& a) { largest(a); a.best = 0; }, "best_dev", "largest shape, null best");
+    bad({RENDER}, [&](Args& a) { largest(a); a.status = 0; }, "status_dev", "largest shape, null status");
+    bad({ZNCC}, [&](Args& a) { largest(a); a.peak = 0; }, "peak_dev", "largest shape, null peak");
+    bad({REFINE}, [&](Args& a) { largest(a); a.sums = 0; }, "sums_dev", "largest shape, null sums");
+
+    std::printf("survey_args_check: %d checks, ", checks);
+    std::printf(failures ? "%d FAILED\n" : "all passed\n", failures);
+    return failures ? 1 : 0;
+}

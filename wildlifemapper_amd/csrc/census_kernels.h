@@ -1,7 +1,7 @@
 // Survey census (include/wm_hip.h, "Survey census"): the detections of a whole survey, projected to the ground through
 // their frames' georeferences and grouped into individuals, at most one detection of any frame per individual.  No
 // reference behaviour exists (the reference evaluates single down-scaled images); the rule is the header's, and the
-// checker is its sequential restatement census_oracle in tests/test_census.py.
+// checker is its sequential restatement census_oracle in tests/ground_oracle.py.
 //
 // census_kernel, one workgroup per survey, built from the survey merge's pieces (survey_kernels.h: mf_ord keys, the
 // any-n mf_bitonic in LDS or global scratch, mf_row / mf_lower_bound windows, a state word per candidate read with

@@ -1,7 +1,7 @@
 // Survey coverage (include/wm_hip.h, "Survey coverage"): a ground grid laid over a survey; every cell gets the number of
 // frames whose footprint holds its centre, and the census' individuals are counted into the same grid per class, each
 // with the number of frames that could have seen it.  No reference behaviour exists; the rule is the header's, and the
-// checker is its sequential restatement coverage_oracle in tests/test_coverage.py.  Everything is integer counting behind
+// checker is its sequential restatement coverage_oracle in tests/ground_oracle.py.  Everything is integer counting behind
 // an exact double predicate (one rounding per operation, no contraction), so the result equals the oracle bit for bit.
 //
 // coverage_raster_kernel, gather: one workgroup of COV_THREADS owns a block of COV_BLOCK_X x COV_BLOCK_Y cells; lane =

@@ -1,7 +1,7 @@
 // Survey mosaic, blended (include/wm_hip.h, "Survey mosaic, blended"): every ground cell is an integer-weighted mean of the
 // exposure-corrected pixels of the frames that see it.  A frame's weight falls to zero at its own border and, over `band`
 // source pixels, away from the frame whose border is farthest (the seam).  No reference behaviour exists; the rule is the
-// header's, and the checker is its sequential restatement blend_oracle in tests/test_mosaic_blend.py.  The weights are
+// header's, and the checker is its sequential restatement blend_oracle in tests/ground_oracle.py.  The weights are
 // integers behind double arithmetic with one rounding per operation (no contraction) and the sums are integers, so every
 // kernel equals the oracle bit for bit and the accumulators do not depend on how the frames are split over calls.  The
 // grid, the centres, the staging and the cull are the coverage's (coverage_kernels.h: CovBlock, cov_load_frame, cov_stage,

@@ -1,7 +1,7 @@
 // Survey mosaic (include/wm_hip.h, "Survey mosaic"): the frames of a survey laid onto the ground grid of the coverage.
 // Every cell chooses ONE frame among those that see its centre -- the one whose centre pixel is nearest, ties to the lowest
 // index -- and fetches that frame's pixel.  No reference behaviour exists; the rule is the header's, and the checker is its
-// sequential restatement mosaic_oracle in tests/test_mosaic.py.  All arithmetic is IEEE double with one rounding per
+// sequential restatement mosaic_oracle in tests/ground_oracle.py.  All arithmetic is IEEE double with one rounding per
 // operation (no contraction), so both kernels equal the oracle bit for bit.  The grid, the centres, the staging and the
 // cull are the coverage's (coverage_kernels.h: CovBlock, whose may_touch is the two cov_row_may_touch() calls, cov_load_frame,
 // cov_stage, cov_uv, cov_inside), included, not copied.

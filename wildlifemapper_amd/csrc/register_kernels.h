@@ -1,7 +1,7 @@
 // Survey registration (include/wm_hip.h, "Survey registration"): every overlapping pair of frames is rendered onto a common
 // ground patch as two uint8 luma planes, and the shift at which they agree is found by an exhaustive integer search.  No
 // reference behaviour exists; the rule is the header's, and the checker is its sequential restatement register_oracle in
-// tests/test_register.py.  The render's arithmetic is the coverage's (IEEE double, one rounding per operation, no
+// tests/register_cases.py.  The render's arithmetic is the coverage's (IEEE double, one rounding per operation, no
 // contraction); everything after it is integer, so all three kernels equal the oracle bit for bit.
 //
 // register_render_kernel: lane = column, a thread owns REG_RENDER_ROWS cells of one column, blockIdx.z = pair, blockIdx.y =
@@ -19,10 +19,10 @@
 // mask by (a != 0) & (b != 0), so a cell that either frame does not see adds 0) and one v_bcnt_u32_b32 (8 bits per counted
 // cell).  The decomposition, the pair check, the staging, the offset setup, the walk and the flush guard are the same text
 // for both metrics; the metric decides three spots under `if constexpr`:
-//   SAD (include/wm_hip.h, "Survey registration"; checker: search_oracle in tests/test_register.py): one v_sad_u8 per 4
+//   SAD (include/wm_hip.h, "Survey registration"; checker: search_oracle in tests/register_cases.py): one v_sad_u8 per 4
 //     cells and offset; tile partials go to score by int32 atomics, two per (tile, offset), against tile_rows * 16 steps.
 //   correlation (include/wm_hip.h, "Survey registration, correlation search"; checker: zncc_search_oracle in
-//     tests/test_register_zncc.py): two v_sad_u8 against 0 (the byte sums) and three v_dot4_u32_u8 (sum a^2, sum b^2, sum
+//     tests/register_cases.py): two v_sad_u8 against 0 (the byte sums) and three v_dot4_u32_u8 (sum a^2, sum b^2, sum
 //     ab).  A tile's partials fit 32 bits (the static_assert beside REG_TILE_ROWS_MAX); they go to moments by six 64-bit
 //     vector atomics per (tile, offset).
 // What keeps every instance at the registers and bytes it had as two kernels: profiles/register_family/README.md.

@@ -1,7 +1,7 @@
 // Survey registration, refinement (include/wm_hip.h, "Survey registration, refinement"): around the integer peak of a pair,
 // the normal equations of one Gauss-Newton step of the brightness-constancy equation -- sub-cell shift, yaw, scale, gain and
 // offset -- as 28 integer sums per pair.  No reference behaviour exists; the rule is the header's, and the checker is its
-// sequential restatement refine_sums_oracle in tests/test_register_refine.py.  Every term is an integer, so the kernel equals
+// sequential restatement refine_sums_oracle in tests/register_cases.py.  Every term is an integer, so the kernel equals
 // the oracle bit for bit whatever the order of its additions; the 4 x 4 or 6 x 6 solve is the host's (registration.py).
 //
 // register_refine_kernel: blockIdx.y = pair, blockIdx.x = tile of REFINE_TILE_X x REFINE_TILE_Y cells of A.  The workgroup
