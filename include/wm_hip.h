@@ -47,6 +47,8 @@ extern "C" {
  *    equations of a sub-cell shift, yaw, scale, gain and offset per pair); the number stays 13 for the same reason.
  *    13, also additive: wm_mosaic_blend_plan, wm_mosaic_blend_accum_u8, wm_mosaic_blend_finish_u8 (survey mosaic, blended:
  *    every cell an integer-weighted mean of the exposure-corrected frames that see it); the number stays 13 for the same reason.
+ *    13, also additive: wm_register_reduce_u8, WM_REGISTER_MAX_LEVEL (survey registration, pyramid: rendered planes reduced
+ *    by 2 x 2 rounded means so the refinement converges from far off); the number stays 13 for the same reason.
  * 12: wm_box_outline_rect, wm_draw_boxes_u8, wm_plot_image_u8, WM_DRAW_MAX_WIDTH, WM_DRAW_MAX_PALETTE, WM_PLOT_SCRATCH_BYTES
  *    (survey overlays: detections outlined on frames and tiles, on the GPU); nothing else changed.
  * 11: wm_chip_window, wm_crop_chips_u8, WM_CHIP_MAX_SIDE (survey review chips: one PIL-exact crop per detection, cut on
@@ -622,6 +624,33 @@ int wm_register_search_zncc(const uint8_t* a_dev, const uint8_t* b_dev, const wm
 #define WM_REGISTER_REFINE_SUMS 28
 int wm_register_refine(const uint8_t* a_dev, const uint8_t* b_dev, const wm_register_pair* pairs_dev, int n_pairs, int search,
                        int side, int64_t* sums_dev /* [n_pairs][WM_REGISTER_REFINE_SUMS] */, void* stream);
+
+/* Survey registration, pyramid (tiling.reduce_planes, tiling.refine(levels=L), tiling.register(refine=k, levels=L)): the
+ * refinement above is one linearisation and converges from within about two cells at the patch corners.  A coarser `cell`
+ * widens that basin, but wm_register_render_u8 samples the nearest pixel, so a coarse cell aliases the ground's fine
+ * texture.  This entry reduces planes rendered at the FINE cell by 2 x 2 rounded means, so wm_register_refine can run on
+ * area-averaged planes, coarse to fine, with a `cell` of 2^l times the fine one.
+ * Rule (wm_register_reduce_u8), per plane, all in integers:
+ *     R_0 = in
+ *     R_{k+1}[j][i] = 0 if any of R_k[2j][2i], R_k[2j][2i+1], R_k[2j+1][2i], R_k[2j+1][2i+1] is 0,
+ *                     else (their sum + 2) >> 2
+ *     out = R_level
+ * 0 keeps its meaning "not seen": a coarse cell is seen iff all 4^level fine cells under it are, and a seen cell stays in
+ * 1..255 (four ones give (4 + 2) >> 2 = 1).  The rule is the recursion with its rounding at every level, not the rounded
+ * mean of the 2^level x 2^level block: the 4 x 4 block of the 2 x 2 blocks [1,1,2,2], [1,1,2,2], [1,1,2,2], [1,1,1,2]
+ * gives 2 where the rounded block mean is 1.
+ * in_dev [n_planes][ext][ext] uint8 -> out_dev [n_planes][ext >> level][ext >> level] uint8.  Limits: 1 <= level <=
+ * WM_REGISTER_MAX_LEVEL; 1 <= ext <= WM_REGISTER_MAX_SIDE + 2 * WM_REGISTER_MAX_SEARCH; ext % (1 << level) == 0; 0 <=
+ * n_planes <= WM_REGISTER_MAX_PAIRS; in_dev and out_dev 4-byte aligned, their ranges disjoint.
+ * Ring alignment: plane B of a render with search = 2^l has side + 2^(l+1) cells a side; with side % 2^l == 0 the reduced
+ * B is the reduced A's grid grown by exactly one coarse cell on every side, which is what wm_register_refine needs
+ * (search = 1, side >> l, pairs with gx >> l and gy >> l and the same x0, y0).
+ * One pass: every input byte is read once and only R_level is written.  Asynchronous on `stream`, nothing allocated;
+ * plain vector loads and stores, no atomics.  Bad arguments fail before any HIP call with a message that names the
+ * argument; n_planes == 0 returns 0 before looking at any pointer. */
+#define WM_REGISTER_MAX_LEVEL 6
+int wm_register_reduce_u8(const uint8_t* in_dev /* [n_planes][ext][ext] */, int n_planes, int ext, int level,
+                          uint8_t* out_dev /* [n_planes][ext >> level][ext >> level] */, void* stream);
 
 /* Survey resampling (tiling.detect_frames(scale=..., resize=...)): a frame brought to the scale the checkpoint was trained
  * at (the val transform's long side of 768, dataloader_coco.py:288) before it is tiled.

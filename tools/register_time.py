@@ -30,6 +30,19 @@ wm_register_search_zncc, the correlation) on the same planes, against the host r
       moments, best and peak must equal the restatement of the correlation rule (tests/register_cases.py:
       zncc_search_oracle, zncc_pick_oracle) on the device's planes, peak by its bytes.  The tool asserts both;
       equals_oracle is true where every comparison that ran held.
+  python tools/register_time.py --only pyramid [--reps 20]
+      The pyramid's reduce (wm_register_reduce_u8, one launch): HIP-event min and median of one call on stacks of 64 and 256
+      planes of 512 x 512 (plane A of side 512) and 520 x 520 (plane B of side 512 at search 4) of random 1..255 at levels
+      1, 3 and 6 -- 2^6 does not divide 520, so level 6 runs on 512 x 512 and on 640 x 640, the B plane of search 64 -- with
+      the bytes it must move, n * ext^2 * (1 + 4^-level), as a rate and as a fraction of the 8 TB/s HBM peak (and 1 152
+      planes of 512 x 512 at levels 1 and 3, 302 MB: the stacks above fit the 256 MiB Infinity Cache, this one does not), and
+      the output compared with tests/pyramid_cases.py's reduce_oracle on the first two planes.  Then, on one chunk of 64 and of
+      256 pairs of the f1000 survey at side 512 and search 4, in the same process and alternating: one
+      wm_register_render_u8 call (which writes the very bytes the reduce reads), the reduce of both of its planes by 1 and
+      by 2 (two launches), and one wm_register_refine call on the planes reduced by 2 (search 1, side 128) and on the
+      fine ones; the ratios reduce / render and reduce / refine of the minima.  Last, end to end on test_register_pyramid's
+      far-off scene: the wall clock of tiling.refine(levels=3, iters=3) against tiling.refine(levels=0, iters=12), twelve
+      iterations each, the best of three after one warm-up.
       Prints one JSON line.  No figure is a pass mark: the numbers are records.
 """
 import argparse
@@ -198,6 +211,108 @@ def run(lines, per_line, side, search, pair_chunk, seed, reps, oracle_pairs, znc
     return out
 
 
+HBM_PEAK = 8.0e12                                  # bytes per second, MI355X
+
+
+def run_pyramid(reps):
+    from pyramid_cases import CELL, SIDE, far_scene, reduce_oracle
+    dev = torch.device("cuda:0")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    lib, st = N.lib(), N.stream_ptr(dev)
+    out = {"stacks": {}, "beside_render_and_refine": {}}
+    gen = torch.Generator(device=dev).manual_seed(5)
+    equal = True
+    shapes = ((512, (1, 3, 6)), (520, (1, 3)), (640, (6,)))
+    for n, of in ((64, shapes), (256, shapes), (1152, ((512, (1, 3)),))):     # the last: 302 MB, past the 256 MiB Infinity Cache
+        for ext, levels in of:
+            src = torch.randint(1, 256, (n, ext, ext), device=dev, dtype=torch.uint8, generator=gen)
+            src[:, ext // 3, ::7] = 0
+            for level in levels:
+                oe = ext >> level
+                dst = torch.empty((n, oe, oe), device=dev, dtype=torch.uint8)
+                call = lambda: N.check(lib.wm_register_reduce_u8(N.ptr(src), n, ext, level, N.ptr(dst), st))
+                t_min, t_med = timed(call, reps, warmup=3)
+                moved = n * ext * ext + n * oe * oe
+                ok = bool(np.array_equal(dst[:2].cpu().numpy(), reduce_oracle(src[:2].cpu().numpy(), level)))
+                equal = equal and ok
+                out["stacks"][f"n{n}_ext{ext}_level{level}"] = {
+                    "ms_min": t_min, "ms_median": t_med, "bytes": moved, "bytes_per_s": float(f"{moved / (t_min * 1e-3):.4g}"),
+                    "fraction_of_hbm_peak": round(moved / (t_min * 1e-3) / HBM_PEAK, 4), "equals_oracle": ok}
+            del src
+    # the parent's kernels on the same chunk, in the same process
+    side, search = 512, 4
+    georef, size = make(25, 40, 1)
+    F = georef.shape[0]
+    table = tiling.register_pairs(georef, size, GSD, search, side, MIN_CELLS)
+    g2p = tiling.ground_to_pixel(georef).reshape(-1, 6)
+    for n in (64, 256):
+        chunk = table[:n]
+        needed = sorted(set(chunk["frame_a"].tolist()) | set(chunk["frame_b"].tolist()))
+        pixels = torch.randint(0, 256, (len(needed), H, W, 3), device=dev, dtype=torch.uint8, generator=gen)
+        desc = _frame_descs([pixels[k] for k in range(len(needed))], dev)
+        slot = np.full(F, -1, dtype=np.int32)
+        slot[needed] = np.arange(len(needed), dtype=np.int32)
+        g_d, s_d, slot_d = up(g2p), up(size), up(slot)
+        pairs_d = up(chunk.view(np.uint8).reshape(n, 32))
+        coarse = chunk.copy()
+        coarse["gx"], coarse["gy"] = chunk["gx"] >> 2, chunk["gy"] >> 2
+        coarse_d = up(coarse.view(np.uint8).reshape(n, 32))
+        E = side + 2 * search
+        a = torch.zeros((n, side, side), device=dev, dtype=torch.uint8)
+        b = torch.zeros((n, E, E), device=dev, dtype=torch.uint8)
+        ra = {l: torch.empty((n, side >> l, side >> l), device=dev, dtype=torch.uint8) for l in (1, 2)}
+        rb = {l: torch.empty((n, E >> l, E >> l), device=dev, dtype=torch.uint8) for l in (1, 2)}
+        status = torch.zeros(1, device=dev, dtype=torch.int32)
+        sums = torch.empty((n, N.REGISTER_REFINE_SUMS), device=dev, dtype=torch.int64)
+        render = lambda: N.check(lib.wm_register_render_u8(N.ptr(desc), len(needed), N.ptr(slot_d), N.ptr(g_d), N.ptr(s_d), F, N.ptr(pairs_d), n,
+                                                           GSD, search, side, N.ptr(a), N.ptr(b), N.ptr(status), st))
+
+        def reduce_both(l):
+            N.check(lib.wm_register_reduce_u8(N.ptr(a), n, side, l, N.ptr(ra[l]), st))
+            N.check(lib.wm_register_reduce_u8(N.ptr(b), n, E, l, N.ptr(rb[l]), st))
+
+        calls = {"render": render, "reduce_by_1": lambda: reduce_both(1), "reduce_by_2": lambda: reduce_both(2),
+                 "refine_fine": lambda: N.check(lib.wm_register_refine(N.ptr(a), N.ptr(b), N.ptr(pairs_d), n, search, side, N.ptr(sums), st)),
+                 "refine_reduced_by_2": lambda: N.check(lib.wm_register_refine(N.ptr(ra[2]), N.ptr(rb[2]), N.ptr(coarse_d), n, 1, side >> 2,
+                                                                                N.ptr(sums), st))}
+        for c in calls.values():
+            c(), c()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in calls}
+        for _ in range(reps):                                     # alternating, in one process, on the same chunk
+            for k, c in calls.items():
+                ms[k].append(once(c))
+        mins = {k: float(np.min(v)) for k, v in ms.items()}
+        rec = {f"{k}_ms_min": round(mins[k], 4) for k in calls}
+        rec.update({f"{k}_ms_median": round(float(np.median(v)), 4) for k, v in ms.items()})
+        rec.update({"chunk_frames": len(needed), "plane_bytes": n * (side * side + E * E), "render_status": int(status.item()),
+                    "reduce_by_1_over_render": round(mins["reduce_by_1"] / mins["render"], 3),
+                    "reduce_by_2_over_render": round(mins["reduce_by_2"] / mins["render"], 3),
+                    "reduce_by_1_over_refine_fine": round(mins["reduce_by_1"] / mins["refine_fine"], 3),
+                    "reduce_by_2_over_refine_fine": round(mins["reduce_by_2"] / mins["refine_fine"], 3)})
+        ok = bool(np.array_equal(rb[2][:2].cpu().numpy(), reduce_oracle(b[:2].cpu().numpy(), 2)))
+        equal = equal and ok
+        rec["equals_oracle"] = ok
+        out["beside_render_and_refine"][f"n{n}"] = rec
+        del pixels, desc, a, b, ra, rb
+    # end to end on the far-off scene of tests/test_register_pyramid.py
+    frames, true, pert = far_scene()
+    wall = {}
+    for name, kw in (("levels3_iters3", {"levels": 3, "iters": 3}), ("levels0_iters12", {"levels": 0, "iters": 12})):
+        took = []
+        for _ in range(4):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            tiling.refine(frames, pert, CELL, side=SIDE, fixed=[0], **kw)
+            took.append(time.perf_counter() - t)
+        wall[name + "_s"] = round(min(took[1:]), 4)
+    wall["pyramid_over_plain"] = round(wall["levels3_iters3_s"] / wall["levels0_iters12_s"], 3)
+    out["end_to_end_far_scene"] = wall
+    out["equals_oracle"] = equal
+    assert equal, "the device result differs from reduce_oracle"
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -211,6 +326,8 @@ def main():
     for i, (name, (lines, per_line, side, search, chunk)) in enumerate(settings.items()):
         if a.only in (None, name):
             out[name] = run(lines, per_line, side, search, chunk, i, a.reps, a.oracle_pairs, a.zncc_oracle_pairs, a.refine_oracle_pairs)
+    if a.only == "pyramid":                                       # asked for by name: the two settings above keep their output
+        out["pyramid"] = run_pyramid(a.reps)
     print(json.dumps(out))
 
 

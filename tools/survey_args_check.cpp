@@ -1,8 +1,8 @@
 // Stand-alone check of the host-side argument validation of every survey entry point -- wm_census, wm_coverage_raster,
 // wm_coverage_points, wm_mosaic_plan, wm_mosaic_fill_u8, wm_mosaic_blend_plan, wm_mosaic_blend_accum_u8,
-// wm_mosaic_blend_finish_u8, wm_register_render_u8, wm_register_search, wm_register_search_zncc and wm_register_refine -- for
-// a sanitizer build of the host code (no GPU needed: every call here returns before the first HIP call).  Build and run,
-// from the repository root, as a program of its own:
+// wm_mosaic_blend_finish_u8, wm_register_render_u8, wm_register_search, wm_register_search_zncc, wm_register_refine and
+// wm_register_reduce_u8 -- for a sanitizer build of the host code (no GPU needed: every call here returns before the first
+// HIP call).  Build and run, from the repository root, as a program of its own:
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Wno-unused-value -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-sanitize-recover=undefined -I include tools/survey_args_check.cpp wildlifemapper_amd/csrc/wm_api.hip \
 //         -o survey_args_check && ./survey_args_check
@@ -30,9 +30,9 @@ struct Args {
               status = 0x9000, best = 0xa000, peak = 0xb000, moments = 0xc000, sums = 0xd000, cov = 0xe000, stats = 0xf000, pts = 0x10000,
               labels = 0x11000, seen = 0x12000, cidx = 0x13000, counts = 0x14000, pstats = 0x15000, source = 0x16000, won = 0x17000,
               mosaic = 0x18001, blend_best = 0x19000, cells = 0x1a000, index = 0x1b000, acc = 0x1c000, exposure = 0x1d000, scratch = 0x1e000,
-              buf = 0x20000;
+              buf = 0x20000, in = 0x100000, out = 0x200000;
     int n_frames = 2, n_resident = 2, n_pairs = 3, n_points = 4, search = 4, side = 64, min_cells = 1, gx = 5, gy = 3,
-        mode = WM_MOSAIC_BILINEAR, flags = WM_MOSAIC_NORTH_UP, n = 10, census_frames = 1, census_flags = 0;
+        mode = WM_MOSAIC_BILINEAR, flags = WM_MOSAIC_NORTH_UP, n = 10, census_frames = 1, census_flags = 0, n_planes = 3, ext = 64, level = 2;
     int64_t scratch_bytes = wm_census_scratch_bytes(10);
     double x0 = 0.0, y0 = 0.0, cell = 0.5, band = 8.0, radius = 1.0;
 };
@@ -99,13 +99,16 @@ static int refine(const Args& a) {
                               (int64_t*)a.sums, nullptr);
 }
 
+static int reduce(const Args& a) { return wm_register_reduce_u8((const uint8_t*)a.in, a.n_planes, a.ext, a.level, (uint8_t*)a.out, nullptr); }
+
 // an entry and the name its messages begin with
 struct Entry { int (*call)(const Args&); const char* name; };
 static const Entry CENSUS = {census, "wm_census: "}, RASTER = {raster, "wm_coverage_raster: "}, POINTS = {points, "wm_coverage_points: "},
                    PLAN = {plan, "wm_mosaic_plan: "}, FILL = {fill, "wm_mosaic_fill_u8: "}, BPLAN = {blend_plan, "wm_mosaic_blend_plan: "},
                    ACCUM = {accum, "wm_mosaic_blend_accum_u8: "}, FINISH = {finish, "wm_mosaic_blend_finish_u8: "},
                    RENDER = {render, "wm_register_render_u8: "}, SEARCH = {search, "wm_register_search: "},
-                   ZNCC = {zncc, "wm_register_search_zncc: "}, REFINE = {refine, "wm_register_refine: "};
+                   ZNCC = {zncc, "wm_register_search_zncc: "}, REFINE = {refine, "wm_register_refine: "},
+                   REDUCE = {reduce, "wm_register_reduce_u8: "};
 
 // a bad argument: each of the entries refuses it under its own name with `word` in the message
 template <class F>
@@ -266,6 +269,31 @@ int main() {
     bad({RENDER}, [&](Args& a) { largest(a); a.status = 0; }, "status_dev", "largest shape, null status");
     bad({ZNCC}, [&](Args& a) { largest(a); a.peak = 0; }, "peak_dev", "largest shape, null peak");
     bad({REFINE}, [&](Args& a) { largest(a); a.sums = 0; }, "sums_dev", "largest shape, null sums");
+
+    // ---- registration, pyramid ----
+    const int max_ext = WM_REGISTER_MAX_SIDE + 2 * WM_REGISTER_MAX_SEARCH;
+    expect(WM_REGISTER_MAX_LEVEL == 6, "WM_REGISTER_MAX_LEVEL is 6");
+    for (int np : {-1, imin, WM_REGISTER_MAX_PAIRS + 1, imax}) bad({REDUCE}, [&](Args& a) { a.n_planes = np; }, "n_planes", "n_planes outside 0..the cap");
+    for (int l : {0, -1, imin, WM_REGISTER_MAX_LEVEL + 1, 31, 32, imax}) bad({REDUCE}, [&](Args& a) { a.level = l; }, "level", "level outside 1..the cap");
+    for (int e : {0, -64, imin, max_ext + 1, max_ext + 64, imax}) bad({REDUCE}, [&](Args& a) { a.ext = e; a.level = 1; }, "ext", "ext outside 1..the cap");
+    for (int e : {1, 63, 66, 96, max_ext - 1}) bad({REDUCE}, [&](Args& a) { a.ext = e; a.level = 6; }, "multiple", "ext that 2^level does not divide");
+    bad({REDUCE}, [](Args& a) { a.ext = 66; }, "multiple", "ext 66 at level 2");
+    bad({REDUCE}, [](Args& a) { a.in = 0; }, "null in_dev", "null in");
+    bad({REDUCE}, [](Args& a) { a.out = 0; }, "null out_dev", "null out");
+    for (uintptr_t off : {1, 2, 3}) {
+        bad({REDUCE}, [&](Args& a) { a.in += off; }, "in_dev not 4-byte aligned", "misaligned in");
+        bad({REDUCE}, [&](Args& a) { a.out += off; }, "out_dev not 4-byte aligned", "misaligned out");
+    }
+    // 3 planes of 64 x 64 in, 3 of 16 x 16 out: the two ranges meet from either side or nest
+    const uintptr_t in_bytes = 3 * 64 * 64, out_bytes = 3 * 16 * 16;
+    for (uintptr_t out : {(uintptr_t)0x100000, 0x100000 + in_bytes - 4, 0x100000 - out_bytes + 4, (uintptr_t)0x100400})
+        bad({REDUCE}, [&](Args& a) { a.out = out; }, "overlap", "in and out overlap");
+    fine(REDUCE, [&](Args& a) { a.n_planes = 0; a.in = a.out = 0; a.ext = -1; a.level = 0; }, "reduce: n_planes == 0 returns 0");
+    // the largest legal shape passes every size computation before the pointer checks stop it
+    bad({REDUCE}, [&](Args& a) { a.n_planes = WM_REGISTER_MAX_PAIRS; a.ext = max_ext; a.level = WM_REGISTER_MAX_LEVEL; a.out = 0; }, "out_dev",
+        "largest stack, null out");
+    bad({REDUCE}, [&](Args& a) { a.n_planes = WM_REGISTER_MAX_PAIRS; a.ext = max_ext; a.level = 1; a.in = 0x100000; a.out = 0x100000 + (uintptr_t)max_ext * max_ext; },
+        "overlap", "largest stack: 26.8e9 bytes of input reach over out");
 
     std::printf("survey_args_check: %d checks, ", checks);
     std::printf(failures ? "%d FAILED\n" : "all passed\n", failures);

@@ -27,6 +27,7 @@ MOSAIC_BAD_SLOT, MOSAIC_BAD_SIZE, MOSAIC_BAD_SOURCE = 1, 2, 4          # wm_mosa
 REGISTER_MAX_SIDE, REGISTER_MAX_SEARCH, REGISTER_MAX_PAIRS = 512, 64, 65535
 REGISTER_BAD_SLOT, REGISTER_BAD_SIZE, REGISTER_BAD_PAIR = 1, 2, 4      # wm_register_render_u8's status bits
 REGISTER_REFINE_SUMS = 28                                              # int64 sums per pair of wm_register_refine
+REGISTER_MAX_LEVEL = 6                                                 # wm_register_reduce_u8: 2 x 2 reductions per call
 CFG_FUSE_LN = 1
 CFG_FOLD_LN = 2
 CFG_FOLD_LN_BF16 = 4
@@ -83,6 +84,7 @@ SYMBOLS = {
     "wm_register_search": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "wm_register_search_zncc": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "wm_register_refine": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    "wm_register_reduce_u8": (_I, [_P, _I, _I, _I, _P, _P]),
     "wm_resample_u8": (_I, [_P, _I, _I, _P, _I, _I, _P]),
     "wm_scaled_size": (_I, [_I, _I, C.c_double, C.POINTER(_I), C.POINTER(_I)]),
     "wm_chip_window": (_I, [C.POINTER(_F), _F, _I, _I, C.POINTER(C.c_int32)]),

@@ -8,6 +8,7 @@
 #include "mosaic_blend_kernels.h"
 #include "register_kernels.h"
 #include "register_refine_kernels.h"
+#include "register_pyramid_kernels.h"
 #include "chip_kernels.h"
 #include "overlay_kernels.h"
 #include "host_core.h"
@@ -399,6 +400,38 @@ int launch_register_refine(const uint8_t* a_dev, const uint8_t* b_dev, const wm_
     const int tiles_x = (side + REFINE_TILE_X - 1) / REFINE_TILE_X, tiles_y = (side + REFINE_TILE_Y - 1) / REFINE_TILE_Y;
     hipLaunchKernelGGL(register_refine_kernel, dim3(tiles_x * tiles_y, n_pairs), dim3(REG_THREADS), 0, s, a_dev, b_dev, pairs_dev, search, side,
                        tiles_x, (unsigned long long*)sums_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The pyramid's reduce: one launch, a wave per 64 x 64 tile, LEVEL a template argument so that every level's steps unroll.
+int launch_register_reduce(const uint8_t* in_dev, int n_planes, int ext, int level, uint8_t* out_dev, hipStream_t s) {
+    const char* name = "wm_register_reduce_u8";
+    constexpr int max_ext = WM_REGISTER_MAX_SIDE + 2 * WM_REGISTER_MAX_SEARCH;
+    if (n_planes < 0 || n_planes > WM_REGISTER_MAX_PAIRS) return fail("%s: n_planes %d outside 0..%d", name, n_planes, WM_REGISTER_MAX_PAIRS);
+    if (n_planes == 0) return 0;
+    if (level < 1 || level > WM_REGISTER_MAX_LEVEL) return fail("%s: level %d outside 1..%d", name, level, WM_REGISTER_MAX_LEVEL);
+    if (ext < 1 || ext > max_ext) return fail("%s: ext %d outside 1..%d", name, ext, max_ext);
+    if (ext % (1 << level)) return fail("%s: ext %d is not a multiple of 2^level = %d", name, ext, 1 << level);
+    if (!in_dev) return fail("%s: null in_dev", name);
+    if (!out_dev) return fail("%s: null out_dev", name);
+    if ((uintptr_t)in_dev % 4) return fail("%s: in_dev not 4-byte aligned", name);
+    if ((uintptr_t)out_dev % 4) return fail("%s: out_dev not 4-byte aligned", name);
+    const int oe = ext >> level;
+    const uintptr_t in0 = (uintptr_t)in_dev, in1 = in0 + (size_t)n_planes * ext * ext, out0 = (uintptr_t)out_dev,
+                    out1 = out0 + (size_t)n_planes * oe * oe;
+    if (in0 < out1 && out0 < in1) return fail("%s: in_dev and out_dev overlap", name);
+    const int tiles_x = (ext + REDUCE_TILE - 1) / REDUCE_TILE, waves = REG_THREADS / 64;
+    const dim3 grid((tiles_x * tiles_x + waves - 1) / waves, n_planes);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(REG_THREADS), 0, s, in_dev, ext, tiles_x, out_dev); };
+    switch (level) {
+        case 1: launch(register_reduce_kernel<1>); break;
+        case 2: launch(register_reduce_kernel<2>); break;
+        case 3: launch(register_reduce_kernel<3>); break;
+        case 4: launch(register_reduce_kernel<4>); break;
+        case 5: launch(register_reduce_kernel<5>); break;
+        default: launch(register_reduce_kernel<6>); break;
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }

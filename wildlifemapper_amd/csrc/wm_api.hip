@@ -294,6 +294,10 @@ extern "C" int wm_register_refine(const uint8_t* a_dev, const uint8_t* b_dev, co
     return launch_register_refine(a_dev, b_dev, pairs_dev, n_pairs, search, side, sums_dev, (hipStream_t)stream);
 }
 
+extern "C" int wm_register_reduce_u8(const uint8_t* in_dev, int n_planes, int ext, int level, uint8_t* out_dev, void* stream) {
+    return launch_register_reduce(in_dev, n_planes, ext, level, out_dev, (hipStream_t)stream);
+}
+
 extern "C" int wm_crop_chips_u8(const wm_frame_desc* frames_dev, int n_frames, const float* boxes_dev, const int32_t* box_frame_dev, int n,
                                 int chip, float context, int min_side, int max_side, uint8_t* chips_dev, int32_t* windows_dev,
                                 void* stream) {

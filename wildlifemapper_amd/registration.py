@@ -10,6 +10,8 @@
     from the integer normal equations of one Gauss-Newton step per pair (wm_register_refine; rule: include/wm_hip.h "Survey
     registration, refinement"), iterated; its host parts are refine_solve (the 4 x 4 or 6 x 6 solve per pair),
     adjust_similarity (one similarity per frame, two calls of adjust) and refine_step (both, and the corrected georef);
+  * reduce_planes: rendered planes reduced by 2 x 2 rounded means (wm_register_reduce_u8; rule: include/wm_hip.h "Survey
+    registration, pyramid"); refine(levels=L) runs the same step on them coarse to fine, so it converges from far off;
   * adjust_exposure, exposure_table: one gain and one offset per frame from the pairs' exposure fits, two calls of adjust,
     and the Q12 table of them that mosaic(blend=, exposure=) applies."""
 from __future__ import annotations
@@ -22,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from ._survey import _check_whole, _finite_number, _pinned_upload
+from ._survey import _check_whole, _finite_number, _pinned_upload, _whole_number
 from .ground import (COVERAGE_MAX_FRAMES, _check_cell, _check_georef, _check_sizes, _footprint_extent, _frame_sequence, _frame_tables,
                      _resident_chunk, _survey_device)
 
@@ -31,6 +33,7 @@ REGISTER_MAX_SEARCH = N.REGISTER_MAX_SEARCH   # WM_REGISTER_MAX_SEARCH
 REGISTER_MAX_PAIRS = N.REGISTER_MAX_PAIRS     # WM_REGISTER_MAX_PAIRS, per launch: register() chunks by pair_chunk
 # wm_register_pair, 32 bytes: the patch of a pair is gx x gy cells with south-west corner (x0, y0)
 REGISTER_PAIR = np.dtype([("frame_a", "<i4"), ("frame_b", "<i4"), ("gx", "<i4"), ("gy", "<i4"), ("x0", "<f8"), ("y0", "<f8")])
+REGISTER_MAX_LEVEL = N.REGISTER_MAX_LEVEL     # WM_REGISTER_MAX_LEVEL: 2 x 2 reductions per wm_register_reduce_u8 call
 _REGISTER_FRAMES_RESIDENT = 8                 # frames on the device per render call of register()
 
 
@@ -230,8 +233,52 @@ def _render_chunk(lib, frames, chunk, s, g_d, s_d, cell, search, side, status, d
     return pairs_d, plane_a, plane_b
 
 
+def _check_levels(levels, side: int, what: str) -> int:
+    """levels of refine() and register(): a whole number in 0..REGISTER_MAX_LEVEL (no bool, no float) with side % 2^levels == 0."""
+    levels = _whole_number(levels, what, "levels", 0, REGISTER_MAX_LEVEL, must=f"must be a whole number in 0..{REGISTER_MAX_LEVEL}")
+    if side % (1 << levels):
+        raise ValueError(f"{what}: levels {levels} needs a side that 2^levels = {1 << levels} divides, and side is {side}")
+    return levels
+
+
+def _reduce(lib, planes: torch.Tensor, level: int, dev) -> torch.Tensor:
+    """One wm_register_reduce_u8 call on a checked (P, ext, ext) uint8 stack on dev."""
+    n, ext = planes.shape[0], planes.shape[1]
+    out = torch.empty((n, ext >> level, ext >> level), device=dev, dtype=torch.uint8)
+    N.check(lib.wm_register_reduce_u8(N.ptr(planes), n, ext, level, N.ptr(out), N.stream_ptr(dev)))
+    return out
+
+
+def reduce_planes(planes, level) -> torch.Tensor:
+    """A stack of rendered planes reduced by 2 x 2 rounded means, `level` times (wm_register_reduce_u8; rule: include/wm_hip.h
+    "Survey registration, pyramid").  planes: a contiguous (P, ext, ext) uint8 device tensor, as wm_register_render_u8 writes
+    it, ext <= REGISTER_MAX_SIDE + 2 * REGISTER_MAX_SEARCH and P <= REGISTER_MAX_PAIRS; level a whole number in
+    1..REGISTER_MAX_LEVEL with ext % 2^level == 0.  Per level a cell is 0 -- not seen -- if any of the four cells under it
+    is 0, else (their sum + 2) >> 2, with that rounding at every level.  Everything is validated before any device work.  Runs
+    on the planes' device and its current stream.  No CPU fallback.  Returns a new (P, ext >> level, ext >> level) uint8 tensor
+    on the same device."""
+    what = "reduce_planes"
+    level = _whole_number(level, what, "level", 1, REGISTER_MAX_LEVEL, must=f"must be a whole number in 1..{REGISTER_MAX_LEVEL}")
+    if not isinstance(planes, torch.Tensor) or planes.dtype != torch.uint8 or planes.dim() != 3 or planes.shape[1] != planes.shape[2]:
+        raise ValueError(f"{what}: planes must be a (P, ext, ext) uint8 tensor, as wm_register_render_u8 writes it")
+    P, ext = int(planes.shape[0]), int(planes.shape[1])
+    if ext < 1 or ext > REGISTER_MAX_SIDE + 2 * REGISTER_MAX_SEARCH:
+        raise ValueError(f"{what}: planes: ext {ext} outside 1..{REGISTER_MAX_SIDE + 2 * REGISTER_MAX_SEARCH}")
+    if ext % (1 << level):
+        raise ValueError(f"{what}: planes: ext {ext} is not a multiple of 2^level = {1 << level}")
+    if P > REGISTER_MAX_PAIRS:
+        raise ValueError(f"{what}: planes: {P} planes exceed {REGISTER_MAX_PAIRS}")
+    if not planes.is_contiguous():
+        raise ValueError(f"{what}: planes must be contiguous")
+    if not planes.is_cuda:
+        raise RuntimeError(f"{what}: planes is on {planes.device}; the HIP path needs a ROCm device tensor "
+                           "(there is no CPU fallback in wildlifemapper_amd)")
+    with torch.cuda.device(planes.device):
+        return _reduce(N.lib(), planes, level, planes.device)
+
+
 def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512, min_cells: int = 4096, min_ratio: float = 1.25,
-             pairs=None, fixed=None, pair_chunk: int = 256, metric: str = "sad", min_corr: float = 0.0, refine: int = 0) -> Dict[str, object]:
+             pairs=None, fixed=None, pair_chunk: int = 256, metric: str = "sad", min_corr: float = 0.0, refine: int = 0, levels: int = 0) -> Dict[str, object]:
     """Correct the georeferences of a survey by matching the pixels of its overlapping frames (wm_register_render_u8,
     wm_register_search or wm_register_search_zncc; rule: include/wm_hip.h "Survey registration" and "Survey registration,
     correlation search").  frames as mosaic() takes them: a sequence that is
@@ -257,7 +304,9 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
     itself corrects only a translation per frame, at a resolution of one cell; refine=k > 0 follows it with k iterations of
     refine() on the corrected georef and the same pair table -- the sub-cell shift, the yaw and the scale of every frame,
     with exposure=(metric == "zncc") -- and adds one key, 'refine', its result ('refine'['georef'] is the refined
-    georeference).  With refine=0 nothing changes, neither the keys nor the launches.
+    georeference).  With refine=0 nothing changes, neither the keys nor the launches.  levels=L > 0 is passed to that refine():
+    refine iterations at each of the levels L, L - 1, ... 0 of a pyramid of the planes, for a yaw or a scale that leaves the
+    patch corners more than about two cells off; it needs refine > 0 and side % 2^L == 0, else ValueError.
     Runs on the current device's current stream.  No CPU fallback.  Returns host arrays:
       'georef' (F,2,3) float64 corrected (shift added to a2, a5), 'shift' (F,2) metres, 'pairs' the table,
       'offset' (P,2) int64 cells (dx, dy), 'cells' (P,) int64 n at the best offset (0: none), 'mean' (P,) float64 sad / n
@@ -275,6 +324,9 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
     if pair_chunk > REGISTER_MAX_PAIRS:
         raise ValueError(f"{what}: pair_chunk {pair_chunk} exceeds {REGISTER_MAX_PAIRS}")
     refine = _check_whole(refine, what, "refine", 0)
+    levels = _check_levels(levels, side, what)
+    if levels and not refine:
+        raise ValueError(f"{what}: levels {levels} without refine: the pyramid belongs to the refinement, pass refine >= 1")
     must = "must be a finite number >= 0"
     min_ratio = _finite_number(min_ratio, what, "min_ratio", lambda r: r >= 0.0, must, must, echo_float=True)
     n_given, sizes = _frame_sequence(frames, sizes, what, "the frames of the current chunk of pairs")
@@ -327,7 +379,7 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
            "runner_up": runner, "accepted": accepted, "residual": adj["residual"], "component": adj["component"], "corr": corr}
     if refine:
         out["refine"] = _refine(frames, out_g, cell, sizes=s, pairs=table, side=side, min_cells=min_cells, iters=refine,
-                                exposure=metric == "zncc", fixed=fixed, pair_chunk=pair_chunk)
+                                exposure=metric == "zncc", fixed=fixed, pair_chunk=pair_chunk, levels=levels)
     return out
 
 
@@ -567,28 +619,55 @@ def refine_step(georef, sizes, pairs, sums, cell, exposure: bool = False, min_ce
             "max_corner": float(moved.max()) if moved.size else 0.0}
 
 
+def _coarse_pairs(table: np.ndarray, level: int):
+    """The pair table of refine()'s level `level`: gx >> level, gy >> level, the same frames, x0 and y0.  Returns it twice: as
+    wm_register_refine reads it -- a pair whose gx or gy became 0 keeps all-zero sums there -- and as refine_step reads it, with
+    1 in the place of such a 0: the pair counts no cell, so it is not accepted and has weight 0 whatever its size.  Level 0
+    is the table itself."""
+    if not level:
+        return table, table
+    dev_t = table.copy()
+    dev_t["gx"], dev_t["gy"] = table["gx"] >> level, table["gy"] >> level
+    gone = (dev_t["gx"] < 1) | (dev_t["gy"] < 1)
+    dev_t["gx"][gone], dev_t["gy"][gone] = 0, 0                   # neither axis of such a pair is read
+    host_t = dev_t.copy()
+    host_t["gx"][gone], host_t["gy"][gone] = 1, 1
+    return dev_t, host_t
+
+
 def refine(frames, georef, cell, sizes=None, pairs=None, side: int = 512, min_cells: int = 4096, iters: int = 3, exposure: bool = False,
-           fixed=None, max_step: float = 2.0, pair_chunk: int = 256) -> Dict[str, object]:
+           fixed=None, max_step: float = 2.0, pair_chunk: int = 256, levels: int = 0) -> Dict[str, object]:
     """Refine the georeferences of a survey below one cell: the sub-cell shift, the yaw and the scale of every frame, from the
     planes register() searches (wm_register_render_u8 at search 1, wm_register_refine; rule: include/wm_hip.h "Survey
     registration, refinement").  Arguments as for register(); georef is usually register()'s 'georef' -- the step is one
-    linearisation and converges from within about max_step cells at the patch corners; farther off, run register() first, or
-    refine at a coarser cell.  pairs: the table to use, None for register_pairs(georef, sizes, cell, 1, side, min_cells);
-    it is made once, from the input georef.  Everything is validated before any device work.  Per iteration, for every
-    chunk of pair_chunk pairs: the planes are rendered at the current georef (frames go up as in register(): a frame is read
+    linearisation and converges from within about max_step cells at the patch corners; farther off in translation, run
+    register() first; farther off in yaw or scale, pass levels (below).  pairs: the table to use, None for
+    register_pairs(georef, sizes, cell, 1, side, min_cells); it is made once, from the input georef at the fine cell.
+    Everything is validated before any device work.  Per iteration, for every chunk of pair_chunk pairs: the planes are rendered at the current georef (frames go up as in register(): a frame is read
     only while a pair of the current chunk needs it), one wm_register_refine call gives the chunk's (n,28) sums, and they
     go to the host; then refine_step() solves every pair (refine_solve), solves one similarity per frame
     (adjust_similarity, fixed=fixed) and corrects the georef.  exposure=True also fits a gain and an offset per pair, for
     frames whose exposure differs.  A survey whose planes coincide cell for cell -- cell = gsd = the scene's pixel and frames
     aligned with the axes, so nearest sampling snaps every plane onto one lattice -- shows the step nothing: the planes are
-    identical while the georef is still up to half a cell off.  Runs on the current device's current stream.  No CPU
+    identical while the georef is still up to half a cell off.
+    levels=L in 1..REGISTER_MAX_LEVEL (side % 2^L == 0, else ValueError) runs `iters` iterations at each level l = L, L - 1,
+    ... 0 of a pyramid, (L + 1) * iters in all, which widens the basin to about 2^(L+1) fine cells at the patch corners.  An
+    iteration at level l > 0 renders the planes at the fine cell with a ring of 2^l cells (wm_register_render_u8 at search
+    2^l), reduces both stacks l times by 2 x 2 rounded means (wm_register_reduce_u8, "Survey registration, pyramid": the
+    reduced B is the reduced A's grid grown by one coarse cell), and runs wm_register_refine and refine_step on them with
+    search 1, side >> l, every pair's gx >> l and gy >> l (same x0, y0), the cell cell * 2^l and min_cells max(1, min_cells
+    >> 2l); a pair whose gx >> l or gy >> l is 0 takes no part at that level (weight 0).  The planes are area means of the
+    fine cells, not a point-sampled coarse render, so the ground's fine texture does not alias.  An iteration at level 0 is
+    the iteration described above, and levels=0 is exactly that loop.  Runs on the current device's current stream.  No CPU
     fallback.  Returns host values: 'georef' (F,2,3) refined; 'yaw' (F,) radians counter-clockwise, 'scale' (F,) and 'shift'
     (F,2) metres, the whole correction of each frame -- with M = out 2 x 2 @ inverse(in 2 x 2): atan2(M10, M00), sqrt(det M)
     - 1, and the displacement of the frame centre's ground position; 'pairs' the table; the last iteration's 'param',
     'cells', 'rms' and 'accepted' as refine_solve returns them; 'history', per iteration a dict of 'rms' (refine_step's
-    'weighted_rms' before the step) and 'max_corner' (metres, the largest corner displacement the step applied)."""
+    'weighted_rms' before the step) and 'max_corner' (metres, the largest corner displacement the step applied), and with
+    levels > 0 also 'level'.  'param', 'cells', 'rms' and 'accepted' are then those of the last iteration at level 0."""
     what = "refine"
     side = _check_register_shape(1, side, 1, what)[1]
+    levels = _check_levels(levels, side, what)
     min_cells, max_step, exposure = _check_refine_policy(min_cells, max_step, exposure, what)
     if min_cells >= 2 ** 31:
         raise ValueError(f"{what}: min_cells {min_cells} does not fit int32")
@@ -616,22 +695,27 @@ def refine(frames, georef, cell, sizes=None, pairs=None, side: int = 512, min_ce
         lib = N.lib()
         with torch.cuda.device(dev):
             status = torch.zeros(1, device=dev, dtype=torch.int32)
-            for _ in range(iters):
+            for l in [lv for lv in range(levels, -1, -1) for _ in range(iters)]:
                 g_d, s_d = _frame_tables(cur, s, dev)
                 sums = np.zeros((P, REGISTER_REFINE_SUMS), dtype=np.int64)
+                coarse = _coarse_pairs(table, l)                  # (the table the device reads, the one refine_step reads)
                 for c0 in range(0, P, pair_chunk):
                     chunk = table[c0:c0 + pair_chunk]
                     n = chunk.shape[0]
-                    pairs_d, plane_a, plane_b = _render_chunk(lib, frames, chunk, s, g_d, s_d, cell, 1, side, status, dev, what)
+                    pairs_d, plane_a, plane_b = _render_chunk(lib, frames, chunk, s, g_d, s_d, cell, 1 << l, side, status, dev, what)
+                    if l:
+                        plane_a, plane_b = _reduce(lib, plane_a, l, dev), _reduce(lib, plane_b, l, dev)
+                        pairs_d = _pinned_upload(coarse[0][c0:c0 + n].view(np.uint8).reshape(n, REGISTER_PAIR.itemsize), dev)
                     sums_d = torch.empty((n, REGISTER_REFINE_SUMS), device=dev, dtype=torch.int64)
-                    N.check(lib.wm_register_refine(N.ptr(plane_a), N.ptr(plane_b), N.ptr(pairs_d), n, 1, side, N.ptr(sums_d), N.stream_ptr(dev)))
+                    N.check(lib.wm_register_refine(N.ptr(plane_a), N.ptr(plane_b), N.ptr(pairs_d), n, 1, side >> l, N.ptr(sums_d),
+                                                   N.stream_ptr(dev)))
                     sums[c0:c0 + n] = sums_d.cpu().numpy()
                     del plane_a, plane_b, sums_d, pairs_d
                 bad = int(status.item())
                 if bad:
                     raise RuntimeError(f"{what}: wm_register_render_u8 skipped planes (status {bad}): a resident frame did not match its slot or size")
-                step = refine_step(cur, s, table, sums, cell, exposure, min_cells, max_step, fixed)
-                history.append({"rms": step["weighted_rms"], "max_corner": step["max_corner"]})
+                step = refine_step(cur, s, coarse[1], sums, cell * (1 << l), exposure, max(1, min_cells >> (2 * l)), max_step, fixed)
+                history.append({"rms": step["weighted_rms"], "max_corner": step["max_corner"], **({"level": l} if levels else {})})
                 cur = step["georef"]
     with np.errstate(all="ignore"):
         yaw, scale = np.zeros(F), np.zeros(F)

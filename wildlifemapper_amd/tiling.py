@@ -41,9 +41,9 @@ from ._survey import _as_frame_array, _finite_number, _frame_descs, _frame_index
 from .ground import (CENSUS_CLASSES, CENSUS_MAX_DETS, COVERAGE_MAX_CELLS, COVERAGE_MAX_FRAMES, COVERAGE_MAX_SIDE, MOSAIC_SAMPLES,  # noqa: F401
                      census, coverage, footprint_bounds, ground_to_pixel, mosaic, mosaic_blend_plan, mosaic_plan, nadir_affine,
                      resampled_georef)
-from .registration import (REGISTER_MAX_PAIRS, REGISTER_MAX_SEARCH, REGISTER_MAX_SIDE, REGISTER_METRICS, REGISTER_PAIR,  # noqa: F401
-                           REGISTER_REFINE_SUMS, adjust, adjust_exposure, adjust_similarity, exposure_table, refine, refine_solve, refine_step,
-                           register, register_pairs)
+from .registration import (REGISTER_MAX_LEVEL, REGISTER_MAX_PAIRS, REGISTER_MAX_SEARCH, REGISTER_MAX_SIDE, REGISTER_METRICS,  # noqa: F401
+                           REGISTER_PAIR, REGISTER_REFINE_SUMS, adjust, adjust_exposure, adjust_similarity, exposure_table, reduce_planes,
+                           refine, refine_solve, refine_step, register, register_pairs)
 from .review import (CHIP_MAX_SIDE, DEFAULT_PALETTE, DRAW_MAX_PALETTE, DRAW_MAX_WIDTH, OVERLAY_MAX, OVERLAY_MIN, _check_chip,  # noqa: F401
                      _check_chip_rule, _check_draw_width, _check_overlay, _check_palette, chip_windows, crop_chips, draw_boxes,
                      outline_rects, overlay_size)
