@@ -1,8 +1,9 @@
-"""What the registration tests (tests/test_register.py, test_register_zncc.py, test_register_refine.py) and tools/register_time.py
-share: the sequential oracles of the registration rules (render, search and pick; the correlation search; the refinement's
-sums -- include/wm_hip.h "Survey registration" and the two sections after it), the cases the files build, the thin calls of
-the C-ABI entry points and the end-to-end scene.  The ground rule of render_plane is ground_oracle.py's.  Nothing here asserts
-about a device."""
+"""What the registration tests (tests/test_register.py, test_register_zncc.py, test_register_refine.py, test_register_pyramid.py)
+and tools/register_time.py share: the sequential oracles of the registration rules (render, search and pick; the correlation
+search; the refinement's sums -- include/wm_hip.h "Survey registration" and the two sections after it), the cases the files
+build, the thin calls of the C-ABI entry points, the end-to-end scene of the search and the analytic scene of the refinement
+and the pyramid (near, near with exposure changes, far off).  The ground rule of render_plane is ground_oracle.py's.  Nothing
+here asserts about a device."""
 import numpy as np
 import torch
 
@@ -362,3 +363,88 @@ def _survey():
     displaced[:, 0, 2] += DISPLACED[:, 0]
     displaced[:, 1, 2] += DISPLACED[:, 1]
     return frames, true, displaced
+
+
+# ---- the analytic scene of the refinement and of the pyramid: four yawed frames over a ground of sinusoids ------------------
+
+FRAME_H, FRAME_W, GSD, CELL, SIDE = 320, 400, 0.5, 1.0, 128
+YAWS = (10.0, -20.0, 170.0, 95.0)
+CENTRES = ((1000.3, 2000.7), (1039.1, 2006.4), (1007.8, 2041.2), (1044.6, 2043.9))     # about 40 m apart, off every lattice
+SIZES = [(FRAME_H, FRAME_W)] * 4
+# (east m, north m, yaw degrees, scale) of the error of each georeference; frame 0 is true
+NEAR = ((0.0, 0.0, 0.0, 0.0), (0.4, -0.3, 0.5, -0.004), (-0.3, 0.4, -0.4, 0.003), (0.35, 0.4, 0.3, 0.004))
+FAR = ((0.0, 0.0, 0.0, 0.0), (3.2, -2.4, 2.5, -0.015), (-2.6, 3.1, -2.0, 0.012), (2.8, 3.0, 1.5, 0.015))
+EXPOSURE = ((1.0, 0.0), (0.7, 30.0), (1.2, -25.0), (0.85, 12.0))                       # gain and offset of each frame
+
+
+def _scene_value(X, Y):
+    """24 sinusoids of wave numbers drawn with sigma 0.08 rad/m, at continuous ground coordinates: within about [70, 190]."""
+    rng = np.random.default_rng(24)
+    k = rng.normal(0.0, 0.08, size=(24, 2))
+    ph = rng.uniform(0, 2 * np.pi, size=24)
+    amp = rng.uniform(0.5, 1.0, size=24)
+    v = np.zeros_like(X)
+    for (kx, ky), p, a in zip(k, ph, amp):
+        v += a * np.sin(kx * (X - 1000.0) + ky * (Y - 2000.0) + p)
+    return 130.0 + v * (60.0 / amp.sum() * 2.2)
+
+
+def _fine_value(X, Y):
+    """A second bank of 24 sinusoids, wave numbers drawn with sigma 0.9 rad/m: texture a coarse point-sampled cell aliases."""
+    rng = np.random.default_rng(7)
+    k = rng.normal(0, 0.9, (24, 2))
+    ph = rng.uniform(0, 2 * np.pi, 24)
+    v = np.zeros_like(X)
+    for (kx, ky), p in zip(k, ph):
+        v += np.sin(kx * (X - 1000.0) + ky * (Y - 2000.0) + p)
+    return v
+
+
+def _far_value(X, Y):
+    """The smooth scene at 0.7 of its contrast plus the fine texture."""
+    return 128.0 + 0.7 * (_scene_value(X, Y) - 130.0) + _fine_value(X, Y) * 25.0 / np.sqrt(12.0)
+
+
+def _perturbed(true, f, errors):
+    """The georeference of frame f with errors[f] = (east m, north m, yaw degrees, scale): a similarity about the frame
+    centre's ground position, then a shift."""
+    dx, dy, yaw, sc = errors[f]
+    c = true[f] @ np.array([FRAME_W / 2, FRAME_H / 2, 1.0])
+    th = np.radians(yaw)
+    M = (1.0 + sc) * np.array([[np.cos(th), -np.sin(th)], [np.sin(th), np.cos(th)]])
+    g = np.empty((2, 3))
+    g[:, :2] = M @ true[f][:, :2]
+    g[:, 2] = M @ (true[f][:, 2] - c) + c + np.array([dx, dy])
+    return g
+
+
+# name: the ground's value, the georeferences' errors, each frame's (gain, offset), whether grey levels outside 2..254 are clipped
+# (the fine texture's tails) or refused
+ANALYTIC_SCENES = {"near": (_scene_value, NEAR, ((1.0, 0.0),) * 4, False), "near_exposure": (_scene_value, NEAR, EXPOSURE, False),
+                   "far": (_far_value, FAR, ((1.0, 0.0),) * 4, True)}
+_ANALYTIC = {}
+
+
+def analytic_scene(name):
+    """frames (grey, so the luma is the value), the true georeferences and the perturbed ones of ANALYTIC_SCENES[name].  Built
+    once per name."""
+    if name not in _ANALYTIC:
+        value, errors, exposure, clip = ANALYTIC_SCENES[name]
+        true = np.stack([tiling.nadir_affine(FRAME_H, FRAME_W, c, GSD, yaw) for c, yaw in zip(CENTRES, YAWS)])
+        vv, uu = np.meshgrid(np.arange(FRAME_H) + 0.5, np.arange(FRAME_W) + 0.5, indexing="ij")
+        frames = []
+        for g, (gain, off) in zip(true, exposure):
+            val = value(g[0, 0] * uu + g[0, 1] * vv + g[0, 2], g[1, 0] * uu + g[1, 1] * vv + g[1, 2])    # at every pixel centre
+            val = np.rint(gain * val + off)
+            if clip:
+                val = np.clip(val, 2, 254)
+            assert val.min() >= 2 and val.max() <= 254
+            frames.append(np.repeat(val.astype(np.uint8)[:, :, None], 3, axis=2))
+        _ANALYTIC[name] = (frames, true, np.stack([_perturbed(true, f, errors) for f in range(4)]))
+    return _ANALYTIC[name]
+
+
+def _corner_error(g, true):
+    """The worst ground distance, over every frame's corners, between the georeference g and the true one: metres."""
+    corners = np.array([[0, 0, 1], [FRAME_W, 0, 1], [0, FRAME_H, 1], [FRAME_W, FRAME_H, 1]], dtype=F64)
+    return float(np.linalg.norm(np.einsum("fij,cj->fci", g - true, corners), axis=2).max())

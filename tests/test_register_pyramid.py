@@ -9,9 +9,8 @@ import pytest
 import torch
 
 from ground_cases import _p, entry_is_whole, header, last_error, macro
-from pyramid_cases import (CELL, FAR, REDUCE_SHAPES, SIDE, SIZES, _corner_error, coarse_tables, device_reduce, far_scene, masked_planes,
-                           near_scene, point_sampled_loop, pyramid_loop, reduce_oracle)
-from register_cases import _case, _oracle, _pairs, _planes, _render, _several_pairs
+from pyramid_cases import REDUCE_SHAPES, coarse_tables, device_reduce, masked_planes, oracle_loop, point_sampled_loop, reduce_oracle
+from register_cases import CELL, FAR, SIDE, SIZES, _corner_error, _oracle, _pairs, _planes, _render, _several_pairs, analytic_scene
 from survey_util import DEV, ROOT, _Lazy, _up
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
@@ -61,7 +60,7 @@ def test_oracle_cases_hold_both_kinds_of_cell(ext, level, n_planes):
 # ---- CPU: the far-off scene, on the oracles ------------------------------------------------------------------------------
 
 def test_far_scene_is_what_the_issue_describes():
-    frames, true, pert = far_scene()
+    frames, true, pert = analytic_scene("far")
     lo, hi = min(int(f.min()) for f in frames), max(int(f.max()) for f in frames)
     first = _corner_error(pert, true)
     print("grey levels", lo, hi, "initial worst corner error", first)
@@ -72,8 +71,8 @@ def test_far_scene_is_what_the_issue_describes():
 
 def test_pyramid_loop_on_the_oracle_converges_from_far_off():
     """levels = 3, iters = 3: measured here 2.40, 0.57, 0.21 | 0.075, 0.087, 0.079 | 0.027, 0.045, 0.028 | 0.0137, 0.0105, 0.0106 m."""
-    frames, true, pert = far_scene()
-    loop = pyramid_loop(3, 3)
+    frames, true, pert = analytic_scene("far")
+    loop = oracle_loop("far", 3, 3, False)
     print("pyramid, worst corner error per iteration:", loop["errors"], "levels", loop["levels"])
     assert loop["levels"] == [3] * 3 + [2] * 3 + [1] * 3 + [0] * 3
     assert loop["errors"][-1] <= 0.25 * CELL                                       # the bound the refinement already meets
@@ -84,7 +83,7 @@ def test_pyramid_loop_on_the_oracle_converges_from_far_off():
 def test_plain_loop_on_the_oracle_walks_away():
     """levels = 0, nine iterations from the same start: measured here 9.78, 9.93, ... 11.05 m.  The point-sampled coarse cells
     are records: 8 m ends at 5.45 m, 4 m at 4.16 m."""
-    loop = pyramid_loop(0, 9)
+    loop = oracle_loop("far", 0, 9, False)
     print("plain loop:", loop["errors"])
     assert loop["levels"] == [0] * 9 and loop["errors"][-1] > CELL
     print("point-sampled cell 8 m, side 16:", point_sampled_loop(8.0, 5), "cell 4 m, side 32:", point_sampled_loop(4.0, 5))
@@ -92,10 +91,10 @@ def test_plain_loop_on_the_oracle_walks_away():
 
 def _small_loop():
     """The scene's six pairs and a seventh of 7 x 128 cells, which has no cell at level 3: levels = 3, one iteration each."""
-    frames, true, pert = far_scene()
+    frames, true, pert = analytic_scene("far")
     table = tiling.register_pairs(pert, SIZES, CELL, 1, SIDE, 4096)
     small = np.concatenate([table, _pairs([(0, 1, 7, 128, float(table["x0"][0]), float(table["y0"][0]))])])
-    return small, pyramid_loop(3, 1, table=small, key="small")
+    return small, oracle_loop("far", 3, 1, False, table=small)
 
 
 def test_a_pair_too_small_for_a_level_takes_no_part():
@@ -270,8 +269,8 @@ def _equals_loop(out, want, levels):
 
 @pytest.mark.gpu
 def test_gpu_refine_with_levels_equals_the_oracle_loop_and_converges():
-    frames, true, pert = far_scene()
-    want = pyramid_loop(3, 3)
+    frames, true, pert = analytic_scene("far")
+    want = oracle_loop("far", 3, 3, False)
     out = tiling.refine(frames, pert, CELL, side=SIDE, iters=3, levels=3, fixed=[0])
     _equals_loop(out, want, 3)
     first, err = _corner_error(pert, true), _corner_error(out["georef"], true)
@@ -281,13 +280,13 @@ def test_gpu_refine_with_levels_equals_the_oracle_loop_and_converges():
         assert abs(out["yaw"][f] + np.radians(FAR[f][2])) < 2e-3 and abs((1 + out["scale"][f]) * (1 + FAR[f][3]) - 1) < 2e-3
     # today's loop from the same start, nine iterations: it ends more than a cell off
     plain = tiling.refine(frames, pert, CELL, side=SIDE, iters=9, levels=0, fixed=[0])
-    _equals_loop(plain, pyramid_loop(0, 9), 0)
+    _equals_loop(plain, oracle_loop("far", 0, 9, False), 0)
     assert _corner_error(plain["georef"], true) > CELL
 
 
 @pytest.mark.gpu
 def test_gpu_refine_with_levels_lazy_frames_and_chunks():
-    frames, true, pert = far_scene()
+    frames, true, pert = analytic_scene("far")
     whole = tiling.refine(frames, pert, CELL, side=SIDE, iters=3, levels=3, fixed=[0])
     lazy = _Lazy(frames)
     again = tiling.refine(lazy, pert, CELL, sizes=SIZES, side=SIDE, iters=3, levels=3, fixed=[0], pair_chunk=4)
@@ -299,15 +298,15 @@ def test_gpu_refine_with_levels_lazy_frames_and_chunks():
 
 @pytest.mark.gpu
 def test_gpu_refine_with_levels_and_exposure_equals_its_oracle_loop():
-    frames, true, pert = far_scene()
+    frames, true, pert = analytic_scene("far")
     out = tiling.refine(frames, pert, CELL, side=SIDE, iters=2, levels=2, exposure=True, fixed=[0])
-    _equals_loop(out, pyramid_loop(2, 2, exposure=True), 2)
+    _equals_loop(out, oracle_loop("far", 2, 2, True), 2)
     print("exposure=True, levels=2: worst corner error", _corner_error(out["georef"], true))
 
 
 @pytest.mark.gpu
 def test_gpu_refine_with_a_pair_too_small_for_a_level():
-    frames, true, pert = far_scene()
+    frames, true, pert = analytic_scene("far")
     want = _small_loop()[1]
     out = tiling.refine(frames, pert, CELL, side=SIDE, iters=1, levels=3, fixed=[0], pairs=want["table"])
     _equals_loop(out, want, 3)
@@ -315,7 +314,7 @@ def test_gpu_refine_with_a_pair_too_small_for_a_level():
 
 @pytest.mark.gpu
 def test_gpu_register_passes_levels_to_the_refinement():
-    frames, true, pert = near_scene()                                                 # test_register_refine's small perturbation
+    frames, true, pert = analytic_scene("near")                                       # test_register_refine's small perturbation
     assert 1.4 < _corner_error(pert, true) < 1.8                                      # 1.68 m there
     kw = dict(search=8, side=SIDE, fixed=[0])
     both = tiling.register(frames, pert, CELL, refine=2, levels=2, **kw)

@@ -11,8 +11,9 @@ import pytest
 import torch
 
 from ground_cases import _p, entry_is_whole, header, last_error, macro
-from register_cases import (DISPLACED, F64, INF, NAN, SUMS, _case, _content, _cover, _oracle_sums, _pairs, _planes, _render, _several_pairs,
-                            _survey, per_k_planes, refine_sums_oracle)
+from pyramid_cases import oracle_loop
+from register_cases import (CELL, DISPLACED, F64, FRAME_H, FRAME_W, INF, NAN, NEAR, SIDE, SIZES, SUMS, _case, _content, _corner_error, _cover,
+                            _oracle_sums, _pairs, _planes, _render, _several_pairs, _survey, analytic_scene, per_k_planes, refine_sums_oracle)
 from survey_util import DEV, ROOT, _Lazy, _up
 from wildlifemapper_amd import _native as N
 from wildlifemapper_amd import tiling
@@ -220,87 +221,15 @@ def test_adjust_similarity_components_and_a_frame_without_pairs():
         tiling.adjust_similarity(6, ab, cp, cf, m, [1.0] * 4, fixed=[6])
 
 
-# ---- the analytic scene ----------------------------------------------------------------------------------------------
+# ---- the analytic scene (register_cases.py) and tiling.refine's loop on the oracles (pyramid_cases.py) ----------------
 
-FRAME_H, FRAME_W, GSD, CELL, SIDE = 320, 400, 0.5, 1.0, 128
-YAWS = (10.0, -20.0, 170.0, 95.0)
-CENTRES = ((1000.3, 2000.7), (1039.1, 2006.4), (1007.8, 2041.2), (1044.6, 2043.9))     # about 40 m apart, off every lattice
-# (east m, north m, yaw degrees, scale) of the error of each georeference; frame 0 is true
-PERTURB = ((0.0, 0.0, 0.0, 0.0), (0.4, -0.3, 0.5, -0.004), (-0.3, 0.4, -0.4, 0.003), (0.35, 0.4, 0.3, 0.004))
-EXPOSURE = ((1.0, 0.0), (0.7, 30.0), (1.2, -25.0), (0.85, 12.0))                       # gain and offset of each frame
-SIZES = [(FRAME_H, FRAME_W)] * 4
-
-
-def _scene_value(X, Y):
-    """About 24 sinusoids of wave numbers drawn with sigma 0.08 rad/m, evaluated at continuous ground coordinates: within
-    about [70, 190]."""
-    rng = np.random.default_rng(24)
-    k = rng.normal(0.0, 0.08, size=(24, 2))
-    ph = rng.uniform(0, 2 * np.pi, size=24)
-    amp = rng.uniform(0.5, 1.0, size=24)
-    v = np.zeros_like(X)
-    for (kx, ky), p, a in zip(k, ph, amp):
-        v += a * np.sin(kx * (X - 1000.0) + ky * (Y - 2000.0) + p)
-    return 130.0 + v * (60.0 / amp.sum() * 2.2)
-
-
-def _perturbed(true, f):
-    dx, dy, yaw, sc = PERTURB[f]
-    c = true[f] @ np.array([FRAME_W / 2, FRAME_H / 2, 1.0])
-    th = np.radians(yaw)
-    M = (1.0 + sc) * np.array([[np.cos(th), -np.sin(th)], [np.sin(th), np.cos(th)]])
-    g = np.empty((2, 3))
-    g[:, :2] = M @ true[f][:, :2]
-    g[:, 2] = M @ (true[f][:, 2] - c) + c + np.array([dx, dy])
-    return g
-
-
-_ANALYTIC = {}
-
-
-def _analytic(exposure_changes=False):
-    """frames (grey, so the luma is the value), the true georeferences and the perturbed ones.  Built once per variant."""
-    if exposure_changes not in _ANALYTIC:
-        true = np.stack([tiling.nadir_affine(FRAME_H, FRAME_W, c, GSD, yaw) for c, yaw in zip(CENTRES, YAWS)])
-        vv, uu = np.meshgrid(np.arange(FRAME_H) + 0.5, np.arange(FRAME_W) + 0.5, indexing="ij")
-        frames = []
-        for f, g in enumerate(true):
-            val = _scene_value(g[0, 0] * uu + g[0, 1] * vv + g[0, 2], g[1, 0] * uu + g[1, 1] * vv + g[1, 2])
-            gain, off = EXPOSURE[f] if exposure_changes else (1.0, 0.0)
-            val = np.rint(gain * val + off)
-            assert val.min() >= 2 and val.max() <= 254
-            frames.append(np.repeat(val.astype(np.uint8)[:, :, None], 3, axis=2))
-        _ANALYTIC[exposure_changes] = (frames, true, np.stack([_perturbed(true, f) for f in range(4)]))
-    return _ANALYTIC[exposure_changes]
-
-
-def _corner_error(g, true):
-    """The worst ground distance, over every frame's corners, between the georeference g and the true one: metres."""
-    corners = np.array([[0, 0, 1], [FRAME_W, 0, 1], [0, FRAME_H, 1], [FRAME_W, FRAME_H, 1]], dtype=F64)
-    return float(np.linalg.norm(np.einsum("fij,cj->fci", g - true, corners), axis=2).max())
-
-
-_LOOPS = {}
-
-
-def _oracle_loop(exposure_changes, exposure, start=None, key=None):
-    """tiling.refine's loop with the oracle's sums in the device's place: iters = 3, frame 0 fixed.  Computed once per variant."""
-    key = (exposure_changes, exposure) if key is None else key
-    if key not in _LOOPS:
-        frames, true, pert = _analytic(exposure_changes)
-        cur = pert if start is None else start
-        table = tiling.register_pairs(cur, SIZES, CELL, 1, SIDE, 4096)
-        steps = []
-        for _ in range(3):
-            steps.append(tiling.refine_step(cur, SIZES, table, _oracle_sums(frames, cur, SIZES, table, CELL, SIDE), CELL,
-                                            exposure=exposure, fixed=[0]))
-            cur = steps[-1]["georef"]
-        _LOOPS[key] = {"georef": cur, "table": table, "steps": steps, "errors": [_corner_error(s["georef"], true) for s in steps]}
-    return _LOOPS[key]
+def _near(exposure_changes=False):
+    """The name of the near scene in register_cases.ANALYTIC_SCENES: frames of one exposure, or of EXPOSURE's four."""
+    return "near_exposure" if exposure_changes else "near"
 
 
 def test_analytic_scene_is_what_the_issue_describes():
-    frames, true, pert = _analytic()
+    frames, true, pert = analytic_scene("near")
     first = _corner_error(pert, true)
     print("initial worst corner error:", first)
     assert 1.4 < first < 1.8 and (pert[0] == true[0]).all()                        # the prototype's 1.62 m, frame 0 true
@@ -310,9 +239,9 @@ def test_analytic_scene_is_what_the_issue_describes():
 
 @pytest.mark.parametrize("exposure_changes", (False, True))
 def test_whole_loop_on_the_oracle(exposure_changes):
-    frames, true, pert = _analytic(exposure_changes)
+    frames, true, pert = analytic_scene(_near(exposure_changes))
     first = _corner_error(pert, true)
-    loop = _oracle_loop(exposure_changes, exposure_changes)
+    loop = oracle_loop(_near(exposure_changes), 0, 3, exposure_changes)
     print("worst corner error per iteration:", first, loop["errors"], "accepted:", [s["accepted"].tolist() for s in loop["steps"]])
     # the issue's bound: a quarter of a cell, and a quarter of where it started.  Measured here: 1.678 m -> 0.064, 0.0142,
     # 0.0141 m; with the exposure changes and exposure=True 0.640, 0.196, 0.0330 m (the gain's bias takes an iteration more)
@@ -322,8 +251,8 @@ def test_whole_loop_on_the_oracle(exposure_changes):
 
 
 def test_exposure_changes_need_the_exposure_terms():
-    frames, true, pert = _analytic(True)
-    with_terms, without = _oracle_loop(True, True), _oracle_loop(True, False)
+    frames, true, pert = analytic_scene("near_exposure")
+    with_terms, without = oracle_loop("near_exposure", 0, 3, True), oracle_loop("near_exposure", 0, 3, False)
     print("exposure changes: with the terms", with_terms["errors"], "without", without["errors"])
     # measured here: 0.033 m with the terms, 1.35 m without (1.40, 1.35, 1.35 over the iterations: it does not converge)
     assert without["errors"][-1] > with_terms["errors"][-1]
@@ -555,8 +484,8 @@ def test_gpu_diagonal_mask_edge_and_planes_of_search_5_and_search_1_agree():
 @pytest.mark.gpu
 @pytest.mark.parametrize("exposure_changes", (False, True))
 def test_gpu_refine_equals_the_oracle_loop(exposure_changes):
-    frames, true, pert = _analytic(exposure_changes)
-    want = _oracle_loop(exposure_changes, exposure_changes)
+    frames, true, pert = analytic_scene(_near(exposure_changes))
+    want = oracle_loop(_near(exposure_changes), 0, 3, exposure_changes)
     out = tiling.refine(frames, pert, CELL, side=SIDE, iters=3, exposure=exposure_changes, fixed=[0])
     np.testing.assert_array_equal(out["pairs"], want["table"])
     assert np.abs(out["georef"] - want["georef"]).max() < 1e-9                      # the same integers into the same host code
@@ -571,12 +500,12 @@ def test_gpu_refine_equals_the_oracle_loop(exposure_changes):
     # the whole correction undoes the perturbation: two opposite corners are 256 m apart and each is within 0.25 m, so what is
     # left of yaw and scale is at most 0.5 / 256 = 1.96e-3 (radians; the perturbation's scale enters at second order, 2e-5)
     for f in range(1, 4):
-        assert abs(out["yaw"][f] + np.radians(PERTURB[f][2])) < 2e-3 and abs((1 + out["scale"][f]) * (1 + PERTURB[f][3]) - 1) < 2e-3
+        assert abs(out["yaw"][f] + np.radians(NEAR[f][2])) < 2e-3 and abs((1 + out["scale"][f]) * (1 + NEAR[f][3]) - 1) < 2e-3
 
 
 @pytest.mark.gpu
 def test_gpu_lazy_frames_chunks_and_register_without_refine():
-    frames, true, pert = _analytic()
+    frames, true, pert = analytic_scene("near")
     whole = tiling.refine(frames, pert, CELL, side=SIDE, iters=2, fixed=[0])
     lazy = _Lazy(frames)
     again = tiling.refine(lazy, pert, CELL, sizes=SIZES, side=SIDE, iters=2, fixed=[0], pair_chunk=2)
@@ -603,7 +532,7 @@ def test_gpu_lazy_frames_chunks_and_register_without_refine():
 @pytest.mark.gpu
 def test_gpu_register_zncc_with_refine_fits_the_exposures():
     """metric="zncc" hands exposure=True to the refinement: a gain and an offset per frame, whole cells and the perturbation."""
-    frames, true, pert = _analytic(True)
+    frames, true, pert = analytic_scene("near_exposure")
     displaced = pert.copy()
     displaced[:, 0, 2] += WHOLE_CELLS[:, 0] * CELL
     displaced[:, 1, 2] += WHOLE_CELLS[:, 1] * CELL
@@ -639,7 +568,7 @@ def _detections_through(true):
 
 @pytest.mark.gpu
 def test_gpu_register_with_refine_corrects_the_census():
-    frames, true, pert = _analytic()
+    frames, true, pert = analytic_scene("near")
     displaced = pert.copy()
     displaced[:, 0, 2] += WHOLE_CELLS[:, 0] * CELL
     displaced[:, 1, 2] += WHOLE_CELLS[:, 1] * CELL

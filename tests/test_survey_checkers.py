@@ -1,7 +1,8 @@
 """The survey's checkers are themselves held in shape: the ground rule is restated in one file (tests/ground_oracle.py), its
-shared geometry gives the values worked out by hand below, and no test or tool imports a test module -- what two files share
-lives in a case or oracle module (survey_util.py, ground_cases.py, ground_oracle.py, register_cases.py).  CPU only; the guards
-match patterns in Python sources."""
+shared geometry gives the values worked out by hand below, the analytic scene of the registration tests is written in one file
+(tests/register_cases.py), and no test or tool imports a test module -- what two files share lives in a case or oracle module
+(survey_util.py, ground_cases.py, ground_oracle.py, register_cases.py, pyramid_cases.py).  CPU only; the guards match patterns
+in Python sources."""
 import glob
 import os
 import re
@@ -33,6 +34,12 @@ def test_uv_expression_is_written_in_one_file():
     # (b0 * X + b1 * Y) + b2 with the coefficients indexed from any array, as every oracle used to spell it
     uv_expr = re.compile(r"\+\s*\w+\[[^\]]*1\]\s*\*\s*\w+\s*\)\s*\+\s*\w+\[[^\]]*2\]")
     assert [name for name, src in _sources("tests") if uv_expr.search(src)] == ["tests/ground_oracle.py"]
+
+
+def test_analytic_scene_is_defined_in_one_file():
+    # the ground of the refinement and pyramid tests and the frames' centres: a second copy would drift from the first
+    for written in (r"^\s*def _scene_value\(", r"^\s*CENTRES\s*=\s*\(\("):
+        assert [name for name, src in _sources("tests", "tools") if re.search(written, src, flags=re.M)] == ["tests/register_cases.py"], written
 
 
 def test_shared_geometry_gives_the_hand_values():

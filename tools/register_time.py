@@ -215,7 +215,8 @@ HBM_PEAK = 8.0e12                                  # bytes per second, MI355X
 
 
 def run_pyramid(reps):
-    from pyramid_cases import CELL, SIDE, far_scene, reduce_oracle
+    from pyramid_cases import reduce_oracle
+    from register_cases import CELL, SIDE, analytic_scene
     dev = torch.device("cuda:0")
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     lib, st = N.lib(), N.stream_ptr(dev)
@@ -295,8 +296,8 @@ def run_pyramid(reps):
         rec["equals_oracle"] = ok
         out["beside_render_and_refine"][f"n{n}"] = rec
         del pixels, desc, a, b, ra, rb
-    # end to end on the far-off scene of tests/test_register_pyramid.py
-    frames, true, pert = far_scene()
+    # end to end on the far-off scene of tests/test_register_pyramid.py (tests/register_cases.py: analytic_scene)
+    frames, true, pert = analytic_scene("far")
     wall = {}
     for name, kw in (("levels3_iters3", {"levels": 3, "iters": 3}), ("levels0_iters12", {"levels": 0, "iters": 12})):
         took = []

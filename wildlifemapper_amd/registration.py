@@ -66,6 +66,28 @@ def _check_pair_table(pairs, n_frames: int, side: int, what: str) -> np.ndarray:
     return t
 
 
+def _check_pair_chunk(pair_chunk, what: str) -> int:
+    pair_chunk = _check_whole(pair_chunk, what, "pair_chunk")
+    if pair_chunk > REGISTER_MAX_PAIRS:
+        raise ValueError(f"{what}: pair_chunk {pair_chunk} exceeds {REGISTER_MAX_PAIRS}")
+    return pair_chunk
+
+
+def _pair_frames(pairs, what: str) -> np.ndarray:
+    """(frame_a, frame_b) of a REGISTER_PAIR table or a (P,2) array of whole numbers, as (P,2) int64: adjust()'s check of pairs."""
+    if isinstance(pairs, np.ndarray) and pairs.dtype == REGISTER_PAIR:
+        pairs = np.stack([pairs["frame_a"], pairs["frame_b"]], axis=1) if pairs.size else np.zeros((0, 2), dtype=np.int64)
+    try:
+        ab = np.asarray(pairs)
+        if ab.size == 0:
+            ab = ab.reshape(0, 2)
+        if ab.dtype.kind not in "iu" or ab.ndim != 2 or ab.shape[1] != 2:
+            raise TypeError
+        return ab.astype(np.int64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: pairs must be a REGISTER_PAIR table or a (P,2) array of whole numbers") from None
+
+
 def register_pairs(georef, sizes, cell, search: int = 16, side: int = 512, min_cells: int = 4096) -> np.ndarray:
     """The overlapping pairs of a survey and their ground patches, for register().  Host only, in double.  georef (F,2,3)
     float64 as for census(), sizes (F,2) (height, width), cell metres.  A pair (i < j) is proposed when the axis-aligned
@@ -119,17 +141,7 @@ def adjust(n_frames, pairs, measured, weights, fixed=None) -> Dict[str, np.ndarr
     with no pair of positive weight."""
     what = "adjust"
     F = _check_whole(n_frames, what, "n_frames", 0)
-    if isinstance(pairs, np.ndarray) and pairs.dtype == REGISTER_PAIR:
-        pairs = np.stack([pairs["frame_a"], pairs["frame_b"]], axis=1) if pairs.size else np.zeros((0, 2), dtype=np.int64)
-    try:
-        ab = np.asarray(pairs)
-        if ab.size == 0:
-            ab = ab.reshape(0, 2)
-        if ab.dtype.kind not in "iu" or ab.ndim != 2 or ab.shape[1] != 2:
-            raise TypeError
-        ab = ab.astype(np.int64)
-    except (TypeError, ValueError):
-        raise ValueError(f"{what}: pairs must be a REGISTER_PAIR table or a (P,2) array of whole numbers") from None
+    ab = _pair_frames(pairs, what)
     P = ab.shape[0]
     if P and (ab.min() < 0 or ab.max() >= F or np.any(ab[:, 0] == ab[:, 1])):
         raise ValueError(f"{what}: pairs: frame_a and frame_b must be two different frames in 0..{F - 1}")
@@ -233,6 +245,35 @@ def _render_chunk(lib, frames, chunk, s, g_d, s_d, cell, search, side, status, d
     return pairs_d, plane_a, plane_b
 
 
+def _rendered_chunks(lib, frames, table, pair_chunk, s, g_d, s_d, cell, search, side, status, dev, what):
+    """One pass of register() or refine() over a pair table: yields (c0, n, *_render_chunk(table[c0:c0 + n])) pair_chunk pairs at
+    a time, then reads `status` (one device-to-host copy) and refuses planes the renders skipped.  Nothing yielded is kept here:
+    the caller lets go of a chunk's planes (del) before it asks for the next, so at most one chunk's planes are alive."""
+    for c0 in range(0, table.shape[0], pair_chunk):
+        chunk = table[c0:c0 + pair_chunk]
+        yield (c0, chunk.shape[0], *_render_chunk(lib, frames, chunk, s, g_d, s_d, cell, search, side, status, dev, what))
+    bad = int(status.item())
+    if bad:
+        raise RuntimeError(f"{what}: wm_register_render_u8 skipped planes (status {bad}): a resident frame did not match its slot or size")
+
+
+def _check_survey(frames, georef, cell, sizes, pairs, search, side, min_cells, fixed, what):
+    """What register() and refine() check of a survey after their own arguments, in this order: frames, cell, georef, sizes, the
+    frame count, the pair table (`pairs`, or register_pairs at this search) and fixed=.  Returns (cell, georef, sizes, table)."""
+    n_given, sizes = _frame_sequence(frames, sizes, what, "the frames of the current chunk of pairs")
+    cell = _check_cell(cell, what)
+    g = _check_georef(georef, what)
+    s = _check_sizes(sizes, g.shape[0], what)
+    F = g.shape[0]
+    if F > COVERAGE_MAX_FRAMES:
+        raise ValueError(f"{what}: {F} frames exceed {COVERAGE_MAX_FRAMES}")
+    if n_given != F:
+        raise ValueError(f"{what}: {n_given} frames for {F} georeferences")
+    table = register_pairs(g, s, cell, search, side, min_cells) if pairs is None else _check_pair_table(pairs, F, side, what)
+    adjust(F, np.zeros((0, 2), dtype=np.int64), np.zeros((0, 2)), np.zeros(0), fixed)         # fixed= validated before device work
+    return cell, g, s, table
+
+
 def _check_levels(levels, side: int, what: str) -> int:
     """levels of refine() and register(): a whole number in 0..REGISTER_MAX_LEVEL (no bool, no float) with side % 2^levels == 0."""
     levels = _whole_number(levels, what, "levels", 0, REGISTER_MAX_LEVEL, must=f"must be a whole number in 0..{REGISTER_MAX_LEVEL}")
@@ -320,27 +361,15 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
     min_corr = _finite_number(min_corr, what, "min_corr", lambda r: -1.0 <= r < 1.0, must, must, refuse=bool, echo_float=True)
     entry, table_dtype, table_last, has_peak, none, decode = _REGISTER_METRIC[metric]
     search, side, min_cells = _check_register_shape(search, side, min_cells, what)
-    pair_chunk = _check_whole(pair_chunk, what, "pair_chunk")
-    if pair_chunk > REGISTER_MAX_PAIRS:
-        raise ValueError(f"{what}: pair_chunk {pair_chunk} exceeds {REGISTER_MAX_PAIRS}")
+    pair_chunk = _check_pair_chunk(pair_chunk, what)
     refine = _check_whole(refine, what, "refine", 0)
     levels = _check_levels(levels, side, what)
     if levels and not refine:
         raise ValueError(f"{what}: levels {levels} without refine: the pyramid belongs to the refinement, pass refine >= 1")
     must = "must be a finite number >= 0"
     min_ratio = _finite_number(min_ratio, what, "min_ratio", lambda r: r >= 0.0, must, must, echo_float=True)
-    n_given, sizes = _frame_sequence(frames, sizes, what, "the frames of the current chunk of pairs")
-    cell = _check_cell(cell, what)
-    g = _check_georef(georef, what)
-    s = _check_sizes(sizes, g.shape[0], what)
-    F = g.shape[0]
-    if F > COVERAGE_MAX_FRAMES:
-        raise ValueError(f"{what}: {F} frames exceed {COVERAGE_MAX_FRAMES}")
-    if n_given != F:
-        raise ValueError(f"{what}: {n_given} frames for {F} georeferences")
-    table = register_pairs(g, s, cell, search, side, min_cells) if pairs is None else _check_pair_table(pairs, F, side, what)
-    adjust(F, np.zeros((0, 2), dtype=np.int64), np.zeros((0, 2)), np.zeros(0), fixed)         # fixed= validated before device work
-    P = table.shape[0]
+    cell, g, s, table = _check_survey(frames, georef, cell, sizes, pairs, search, side, min_cells, fixed, what)
+    F, P = g.shape[0], table.shape[0]
     best = np.zeros((P, 8), dtype=np.int32)
     peak = np.full((P, 2), np.nan, dtype=np.float64)                 # (q, q2) of the correlation search
     best[:, 2] = best[:, 6] = none
@@ -350,11 +379,8 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
         with torch.cuda.device(dev):
             g_d, s_d = _frame_tables(g, s, dev)
             status = torch.zeros(1, device=dev, dtype=torch.int32)
-            for c0 in range(0, P, pair_chunk):
-                chunk = table[c0:c0 + pair_chunk]
-                n = chunk.shape[0]
-                pairs_d, plane_a, plane_b = _render_chunk(lib, frames, chunk, s, g_d, s_d, cell, search, side, status, dev, what)
-                best_d = torch.empty((n, 8), device=dev, dtype=torch.int32)
+            for c0, n, pairs_d, plane_a, plane_b in _rendered_chunks(lib, frames, table, pair_chunk, s, g_d, s_d, cell, search, side, status, dev, what):
+                best_d =torch.empty((n, 8), device=dev, dtype=torch.int32)
                 score = torch.empty((n, 2 * search + 1, 2 * search + 1, table_last), device=dev, dtype=table_dtype)
                 peak_d = torch.empty((n, 2), device=dev, dtype=torch.float64) if has_peak else None
                 N.check(getattr(lib, entry)(N.ptr(plane_a), N.ptr(plane_b), N.ptr(pairs_d), n, search, side, min_cells, N.ptr(score),
@@ -362,10 +388,7 @@ def register(frames, georef, cell, sizes=None, search: int = 16, side: int = 512
                 if has_peak:
                     peak[c0:c0 + n] = peak_d.cpu().numpy()
                 best[c0:c0 + n] = best_d.cpu().numpy()
-                del plane_a, plane_b, score, best_d, peak_d, pairs_d
-            bad = int(status.item())
-        if bad:
-            raise RuntimeError(f"{what}: wm_register_render_u8 skipped planes (status {bad}): a resident frame did not match its slot or size")
+                del plane_a, plane_b, score, best_d, peak_d, pairs_d          # before the next chunk renders
     dy, dx, n1 = (best[:, k].astype(np.int64) for k in (0, 1, 3))
     with np.errstate(all="ignore"):
         has, has2, mean, runner, corr, confident = decode(best, peak, min_corr)
@@ -482,10 +505,7 @@ def adjust_similarity(n_frames, pairs, patch_centres, frame_centres, measured, w
                          f"expected ({P}, 4), ({P}, 2) and ({F}, 2)")
     first = adjust(F, pairs, -m[:, 2:4], weights, fixed)                       # validates pairs, weights and fixed
     yaw, scale = first["shift"][:, 0], first["shift"][:, 1]
-    if isinstance(pairs, np.ndarray) and pairs.dtype == REGISTER_PAIR:
-        ab = np.stack([pairs["frame_a"], pairs["frame_b"]], axis=1).astype(np.int64).reshape(-1, 2)
-    else:
-        ab = np.asarray(pairs).astype(np.int64).reshape(-1, 2)
+    ab = _pair_frames(pairs, what)
     a, b = ab[:, 0], ab[:, 1]
 
     def linear(f, v):                                                          # (theta_f J + sigma_f I) v
@@ -539,10 +559,7 @@ def adjust_exposure(n_frames, pairs, param, weights, fixed=None) -> Dict[str, np
     w = np.where(usable, w, np.where(np.isfinite(w) & (w >= 0), 0.0, w))          # a bad weight still reaches adjust()'s check
     first = adjust(F, pairs, np.stack([ln_g, np.zeros(P)], axis=1), w, fixed)     # validates pairs, weights and fixed
     gain = np.exp(first["shift"][:, 0])
-    if isinstance(pairs, np.ndarray) and pairs.dtype == REGISTER_PAIR:
-        ab = np.stack([pairs["frame_a"], pairs["frame_b"]], axis=1).astype(np.int64).reshape(-1, 2)
-    else:
-        ab = np.asarray(pairs).astype(np.int64).reshape(-1, 2)
+    ab = _pair_frames(pairs, what)
     with np.errstate(all="ignore"):
         want_c = np.where(usable, gain[ab[:, 0]] * o, np.nan)
     second = adjust(F, ab, np.stack([want_c, np.zeros(P)], axis=1), w, fixed)
@@ -672,21 +689,9 @@ def refine(frames, georef, cell, sizes=None, pairs=None, side: int = 512, min_ce
     if min_cells >= 2 ** 31:
         raise ValueError(f"{what}: min_cells {min_cells} does not fit int32")
     iters = _check_whole(iters, what, "iters")
-    pair_chunk = _check_whole(pair_chunk, what, "pair_chunk")
-    if pair_chunk > REGISTER_MAX_PAIRS:
-        raise ValueError(f"{what}: pair_chunk {pair_chunk} exceeds {REGISTER_MAX_PAIRS}")
-    n_given, sizes = _frame_sequence(frames, sizes, what, "the frames of the current chunk of pairs")
-    cell = _check_cell(cell, what)
-    g = _check_georef(georef, what)
-    s = _check_sizes(sizes, g.shape[0], what)
-    F = g.shape[0]
-    if F > COVERAGE_MAX_FRAMES:
-        raise ValueError(f"{what}: {F} frames exceed {COVERAGE_MAX_FRAMES}")
-    if n_given != F:
-        raise ValueError(f"{what}: {n_given} frames for {F} georeferences")
-    table = register_pairs(g, s, cell, 1, side, min_cells) if pairs is None else _check_pair_table(pairs, F, side, what)
-    adjust(F, np.zeros((0, 2), dtype=np.int64), np.zeros((0, 2)), np.zeros(0), fixed)         # fixed= validated before device work
-    P = table.shape[0]
+    pair_chunk = _check_pair_chunk(pair_chunk, what)
+    cell, g, s, table = _check_survey(frames, georef, cell, sizes, pairs, 1, side, min_cells, fixed, what)
+    F, P = g.shape[0], table.shape[0]
     cur = g.copy()
     step = refine_step(cur, s, table, np.zeros((0, REGISTER_REFINE_SUMS), dtype=np.int64), cell, exposure, min_cells, max_step, fixed) if not P else None
     history = []
@@ -699,10 +704,7 @@ def refine(frames, georef, cell, sizes=None, pairs=None, side: int = 512, min_ce
                 g_d, s_d = _frame_tables(cur, s, dev)
                 sums = np.zeros((P, REGISTER_REFINE_SUMS), dtype=np.int64)
                 coarse = _coarse_pairs(table, l)                  # (the table the device reads, the one refine_step reads)
-                for c0 in range(0, P, pair_chunk):
-                    chunk = table[c0:c0 + pair_chunk]
-                    n = chunk.shape[0]
-                    pairs_d, plane_a, plane_b = _render_chunk(lib, frames, chunk, s, g_d, s_d, cell, 1 << l, side, status, dev, what)
+                for c0, n, pairs_d, plane_a, plane_b in _rendered_chunks(lib, frames, table, pair_chunk, s, g_d, s_d, cell, 1 << l, side, status, dev, what):
                     if l:
                         plane_a, plane_b = _reduce(lib, plane_a, l, dev), _reduce(lib, plane_b, l, dev)
                         pairs_d = _pinned_upload(coarse[0][c0:c0 + n].view(np.uint8).reshape(n, REGISTER_PAIR.itemsize), dev)
@@ -710,10 +712,7 @@ def refine(frames, georef, cell, sizes=None, pairs=None, side: int = 512, min_ce
                     N.check(lib.wm_register_refine(N.ptr(plane_a), N.ptr(plane_b), N.ptr(pairs_d), n, 1, side >> l, N.ptr(sums_d),
                                                    N.stream_ptr(dev)))
                     sums[c0:c0 + n] = sums_d.cpu().numpy()
-                    del plane_a, plane_b, sums_d, pairs_d
-                bad = int(status.item())
-                if bad:
-                    raise RuntimeError(f"{what}: wm_register_render_u8 skipped planes (status {bad}): a resident frame did not match its slot or size")
+                    del plane_a, plane_b, sums_d, pairs_d                 # before the next chunk renders
                 step = refine_step(cur, s, coarse[1], sums, cell * (1 << l), exposure, max(1, min_cells >> (2 * l)), max_step, fixed)
                 history.append({"rms": step["weighted_rms"], "max_corner": step["max_corner"], **({"level": l} if levels else {})})
                 cur = step["georef"]
