@@ -301,12 +301,7 @@ def test_layernorm_packed_output(prec, C):
 # ---------------------------------------------------------------------------
 # Folded LayerNorm (WM_CFG_FOLD_LN): statistics in the producing GEMM, normalisation in the consuming GEMM
 # ---------------------------------------------------------------------------
-def _outlier_rows(M, C, dev):
-    """Residual-stream-like rows: unit bulk, a per-row offset, two massive channels (~200x) as the outlier weight profile makes."""
-    x = torch.randn(M, C, device=dev) * (0.7 + torch.rand(M, 1, device=dev)) + 0.2 * torch.randn(M, 1, device=dev)
-    x[:, 101] += 190.0
-    x[:, 678 % C] -= 240.0
-    return x
+from layernorm_cases import outlier_rows as _outlier_rows      # the `outlier` family of the row cases (layernorm_cases.py)
 
 
 @pytest.mark.parametrize("prec", ["fp16", "bf16"])

@@ -30,13 +30,24 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         sum += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
     }
     const float mean = wave_sum(sum) * (1.0f / C);
+    // The mean once more, from the residuals: an fp32 mean is off by up to an ulp of itself, which on a row whose spread is 1e-5
+    // of its mean is a percent of the normalised value (tests/test_gpu_layernorm_rows.py, family flat1e-5).  x - mean is exact for
+    // x within a factor 2 of the mean, so the residuals' own mean is the correction to fp32 accuracy RELATIVE TO THE SPREAD.
+    float rs = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[i][j] -= mean;
+        rs += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+    }
+    const float corr = wave_sum(rs) * (1.0f / C);
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float d = v[i][j] - mean;
-            sq += d * d;
+            v[i][j] -= corr;
+            sq += v[i][j] * v[i][j];
         }
     const float var = wave_sum(sq) * (1.0f / C);
     const float rstd = 1.0f / sqrtf(var + eps);
@@ -47,7 +58,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         const f32x4 b = *(const f32x4*)(beta + c0);
         f32x4 y;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) y[j] = (v[i][j] - mean) * rstd * g[j] + b[j];
+        for (int j = 0; j < 4; ++j) y[j] = v[i][j] * rstd * g[j] + b[j];
         if (nchw_hw > 0) {
             const int64_t img = row / nchw_hw, pix = row % nchw_hw;
 #pragma unroll
@@ -66,8 +77,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 
 // ---------------------------------------------------------------------------
 // The transformer blocks' LayerNorm with the column-tiled statistics of wm_common.h (ln_partial16 / ln_combine): the
-// same arithmetic, operation for operation, as the LayerNorm fused into the residual GEMMs (gemm16_v5.h), which only
-// some batch sizes can use -- a tile's result must not depend on its batch neighbours.  One wave per row, 16-lane
+// statistics of the folded LayerNorm's producers (gemm16_v5.h), operation for operation; applied to x - mean with the mean's
+// own rounding removed (see below), which the folded form, holding one fp32 mean per row, cannot do.  One wave per row, 16-lane
 // group k owns column tile k (C = TN * BN, TN <= 4), 16-bit output.  grid (rows / 4), 256 threads.
 // ---------------------------------------------------------------------------
 // store 4 consecutive outputs of type T (16-bit) or, for FP8, as packed e4m3 bytes (wm_common.h)
@@ -117,6 +128,18 @@ __global__ __launch_bounds__(256) void layernorm_tiled_kernel(const float* __res
     }
     float rstd;
     const float mean = ln_combine(mk, qk, ntile, (float)BN, (float)C, eps, rstd);
+    // the mean's fp32 rounding taken out through the residuals' own mean, as in layernorm_kernel above (the variance feels it in
+    // second order only, so rstd stays ln_combine's: the statistics proper are still those of the folded LayerNorm's producers)
+    float rs = 0.f;
+    if (live) {
+#pragma unroll
+        for (int kk = 0; kk < CPT; ++kk) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[kk][j] -= mean;
+            rs += (v[kk][0] + v[kk][1]) + (v[kk][2] + v[kk][3]);
+        }
+    }
+    const float corr = wave_sum(rs) / (float)C;
     if constexpr (!std::is_same<T, FP8>::value) {
         if (packed) {
             // The output is the A operand of a gemm16_v5 launch: LDS-image order (gemm16_v5.h "Operand layout").  A row's 64 bytes
@@ -133,7 +156,7 @@ __global__ __launch_bounds__(256) void layernorm_tiled_kernel(const float* __res
                     const f32x4 b = *(const f32x4*)(beta + c0);
                     typename T::vec4 o;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) o[j] = T::from_f32(ln_apply(v[kk][j], mean, rstd, g[j], b[j]));
+                    for (int j = 0; j < 4; ++j) o[j] = T::from_f32(ln_apply(v[kk][j], corr, rstd, g[j], b[j]));
                     *(typename T::vec4*)(&stage[w][c0]) = o;
                 }
             }
@@ -157,7 +180,7 @@ __global__ __launch_bounds__(256) void layernorm_tiled_kernel(const float* __res
         const f32x4 b = *(const f32x4*)(beta + c0);
         f32x4 y;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) y[j] = ln_apply(v[kk][j], mean, rstd, g[j], b[j]);
+        for (int j = 0; j < 4; ++j) y[j] = ln_apply(v[kk][j], corr, rstd, g[j], b[j]);
         store4_as<T>(out16, row * C + c0, y);
     }
 }

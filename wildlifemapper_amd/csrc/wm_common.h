@@ -205,8 +205,9 @@ __device__ __forceinline__ float ln_combine(const float (&mk)[8], const float (&
     rstd = 1.0f / sqrtf(m2 / n + eps);
     return mean;
 }
-__device__ __forceinline__ float ln_apply(float v, float mean, float rstd, float g, float b) {
-    return fmaf((v - mean) * rstd, g, b);
+// d = x - mean; corr = the mean of the d's (the fp32 mean's own rounding error)
+__device__ __forceinline__ float ln_apply(float d, float corr, float rstd, float g, float b) {
+    return fmaf((d - corr) * rstd, g, b);
 }
 
 // Element index of (row, col) of a [rows][C] 16-bit operand stored in LDS-image order (gemm16_v5.h "Operand layout"):
