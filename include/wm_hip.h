@@ -49,6 +49,8 @@ extern "C" {
  *    every cell an integer-weighted mean of the exposure-corrected frames that see it); the number stays 13 for the same reason.
  *    13, also additive: wm_register_reduce_u8, WM_REGISTER_MAX_LEVEL (survey registration, pyramid: rendered planes reduced
  *    by 2 x 2 rounded means so the refinement converges from far off); the number stays 13 for the same reason.
+ *    13, also additive: wm_undistort_u8 (survey lens: a frame resampled to the pinhole picture of its Brown-Conrady
+ *    calibration, so the affine georeference holds for it); the number stays 13 for the same reason.
  * 12: wm_box_outline_rect, wm_draw_boxes_u8, wm_plot_image_u8, WM_DRAW_MAX_WIDTH, WM_DRAW_MAX_PALETTE, WM_PLOT_SCRATCH_BYTES
  *    (survey overlays: detections outlined on frames and tiles, on the GPU); nothing else changed.
  * 11: wm_chip_window, wm_crop_chips_u8, WM_CHIP_MAX_SIDE (survey review chips: one PIL-exact crop per detection, cut on
@@ -665,6 +667,38 @@ int wm_register_reduce_u8(const uint8_t* in_dev /* [n_planes][ext][ext] */, int 
  * and finite, result sides <= 65536.  Host only. */
 int wm_resample_u8(const uint8_t* in_dev, int height, int width, uint8_t* out_dev, int out_height, int out_width, void* stream);
 int wm_scaled_size(int height, int width, double scale, int* out_h, int* out_w);
+
+/* Survey lens (lens.lens_plan, preprocess.undistort_u8, tiling.undistorted): a frame resampled ONCE to the pinhole picture of
+ * the same camera, so that the one affine per frame of the census, the coverage, the mosaic and the registration is true of
+ * it.  No reference behaviour exists (the reference has no camera model); this rule is the contract, and tests/lens_cases.py
+ * restates it sequentially (lens_oracle).  All arithmetic is IEEE double, every operation correctly rounded on its own (no
+ * contraction), in the order and with the parentheses written.
+ * Camera: camera[9] doubles fx, fy, cx, cy, k1, k2, p1, p2, k3 -- the Brown-Conrady model in OpenCV's order, as every
+ * photogrammetry package exports it.  cx, cy follow OpenCV's convention, pixel CENTRES at integers; the pixel POSITION used
+ * everywhere else in this header (centres at integer + 0.5) is that plus 0.5.
+ * Output: a pinhole picture of out_height x out_width pixels (oh, ow below) with the one focal length f_out and its principal
+ * point at its geometric centre, so tiling.nadir_affine(oh, ow, centre, gsd, yaw) holds for it with gsd = altitude / f_out.
+ * For the output pixel of row j and column i:
+ *     x   = (((double)i + 0.5) - 0.5 * (double)ow) / f_out          y = (((double)j + 0.5) - 0.5 * (double)oh) / f_out
+ *     r2  = x * x + y * y
+ *     rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))
+ *     xd  = x * rad + (((2.0 * p1) * x) * y + p2 * (r2 + 2.0 * (x * x)))
+ *     yd  = y * rad + (p1 * (r2 + 2.0 * (y * y)) + ((2.0 * p2) * x) * y)
+ *     u   = fx * xd + (cx + 0.5)                                    v = fy * yd + (cy + 0.5)
+ * (u, v) is the position in the source frame.  The source pixel is INSIDE iff 0 <= u < width && 0 <= v < height (a NaN is
+ * outside).  Inside, the three bytes are the sample "Survey mosaic" fetches at (u, v): WM_MOSAIC_NEAREST, the pixel
+ * ((int)floor(v), (int)floor(u)), or WM_MOSAIC_BILINEAR, edge replicate, rounded as written there.  Outside, they are the
+ * fill colour.  Every output byte is written by every call.  Shrinking aliases as the mosaic does (no area filter).
+ * wm_undistort_u8: in_dev [height][width][3] uint8 -> out_dev [out_height][out_width][3] uint8; camera and fill_rgb (three
+ * bytes) are read on the host during the call; mode is WM_MOSAIC_NEAREST or WM_MOSAIC_BILINEAR; stats_dev, unless NULL, is
+ * one int64 that receives the number of output pixels that were filled (zeroed on `stream` first, then one 64-bit atomic
+ * per workgroup that filled any).  One launch, a gather: plain loads and stores, no atomics on the picture, nothing
+ * allocated, asynchronous on `stream`.  Limits: all four sides in 1..65536 (wm_resample_u8's); every camera entry finite;
+ * fx, fy, f_out > 0 (f_out finite); stats_dev 8-byte aligned; the ranges of in_dev and out_dev disjoint.  Bad arguments fail
+ * before any HIP call with a message that names the argument. */
+int wm_undistort_u8(const uint8_t* in_dev, int height, int width, const double camera[9], uint8_t* out_dev, int out_height,
+                    int out_width, double f_out, int mode, const uint8_t fill_rgb[3], int64_t* stats_dev /* [1], may be NULL */,
+                    void* stream);
 
 /* Survey review chips (tiling.detect_frames(chips=...), tiling.crop_chips): one chip x chip uint8 crop per detection, each
  * with a window and a scale of its own, in one launch.

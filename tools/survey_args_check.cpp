@@ -1,7 +1,7 @@
 // Stand-alone check of the host-side argument validation of every survey entry point -- wm_census, wm_coverage_raster,
 // wm_coverage_points, wm_mosaic_plan, wm_mosaic_fill_u8, wm_mosaic_blend_plan, wm_mosaic_blend_accum_u8,
 // wm_mosaic_blend_finish_u8, wm_register_render_u8, wm_register_search, wm_register_search_zncc, wm_register_refine and
-// wm_register_reduce_u8 -- for a sanitizer build of the host code (no GPU needed: every call here returns before the first
+// wm_register_reduce_u8, and the lens correction wm_undistort_u8 -- for a sanitizer build of the host code (no GPU needed: every call here returns before the first
 // HIP call).  Build and run, from the repository root, as a program of its own:
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Wno-unused-value -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-sanitize-recover=undefined -I include tools/survey_args_check.cpp wildlifemapper_amd/csrc/wm_api.hip \
@@ -35,6 +35,13 @@ struct Args {
         mode = WM_MOSAIC_BILINEAR, flags = WM_MOSAIC_NORTH_UP, n = 10, census_frames = 1, census_flags = 0, n_planes = 3, ext = 64, level = 2;
     int64_t scratch_bytes = wm_census_scratch_bytes(10);
     double x0 = 0.0, y0 = 0.0, cell = 0.5, band = 8.0, radius = 1.0;
+    // wm_undistort_u8: a 37 x 53 frame at `in` to a 30 x 40 picture at `out`
+    int height = 37, width = 53, out_height = 30, out_width = 40;
+    double camera[9] = {50.0, 51.0, 26.0, 18.0, -0.1, 0.01, 0.001, -0.001, 0.0}, f_out = 50.0;
+    const double* camera_ptr = camera;
+    uint8_t fill_rgb[3] = {9, 8, 7};
+    const uint8_t* fill_ptr = fill_rgb;
+    uintptr_t lens_stats = 0;
 };
 
 static int census(const Args& a) {
@@ -101,6 +108,11 @@ static int refine(const Args& a) {
 
 static int reduce(const Args& a) { return wm_register_reduce_u8((const uint8_t*)a.in, a.n_planes, a.ext, a.level, (uint8_t*)a.out, nullptr); }
 
+static int undistort(const Args& a) {
+    return wm_undistort_u8((const uint8_t*)a.in, a.height, a.width, a.camera_ptr, (uint8_t*)a.out, a.out_height, a.out_width, a.f_out, a.mode,
+                           a.fill_ptr, (int64_t*)a.lens_stats, nullptr);
+}
+
 // an entry and the name its messages begin with
 struct Entry { int (*call)(const Args&); const char* name; };
 static const Entry CENSUS = {census, "wm_census: "}, RASTER = {raster, "wm_coverage_raster: "}, POINTS = {points, "wm_coverage_points: "},
@@ -108,7 +120,7 @@ static const Entry CENSUS = {census, "wm_census: "}, RASTER = {raster, "wm_cover
                    ACCUM = {accum, "wm_mosaic_blend_accum_u8: "}, FINISH = {finish, "wm_mosaic_blend_finish_u8: "},
                    RENDER = {render, "wm_register_render_u8: "}, SEARCH = {search, "wm_register_search: "},
                    ZNCC = {zncc, "wm_register_search_zncc: "}, REFINE = {refine, "wm_register_refine: "},
-                   REDUCE = {reduce, "wm_register_reduce_u8: "};
+                   REDUCE = {reduce, "wm_register_reduce_u8: "}, UNDISTORT = {undistort, "wm_undistort_u8: "};
 
 // a bad argument: each of the entries refuses it under its own name with `word` in the message
 template <class F>
@@ -294,6 +306,35 @@ int main() {
         "largest stack, null out");
     bad({REDUCE}, [&](Args& a) { a.n_planes = WM_REGISTER_MAX_PAIRS; a.ext = max_ext; a.level = 1; a.in = 0x100000; a.out = 0x100000 + (uintptr_t)max_ext * max_ext; },
         "overlap", "largest stack: 26.8e9 bytes of input reach over out");
+
+    // ---- lens ----
+    bad({UNDISTORT}, [](Args& a) { a.in = 0; }, "null in_dev", "lens: null in");
+    bad({UNDISTORT}, [](Args& a) { a.out = 0; }, "null out_dev", "lens: null out");
+    bad({UNDISTORT}, [](Args& a) { a.camera_ptr = nullptr; }, "null camera", "lens: null camera");
+    bad({UNDISTORT}, [](Args& a) { a.fill_ptr = nullptr; }, "null fill_rgb", "lens: null fill");
+    for (int s : {0, -1, imin, 65537, imax}) {
+        bad({UNDISTORT}, [&](Args& a) { a.height = s; }, "1..65536", "lens: height outside 1..65536");
+        bad({UNDISTORT}, [&](Args& a) { a.width = s; }, "1..65536", "lens: width outside 1..65536");
+        bad({UNDISTORT}, [&](Args& a) { a.out_height = s; }, "1..65536", "lens: out_height outside 1..65536");
+        bad({UNDISTORT}, [&](Args& a) { a.out_width = s; }, "1..65536", "lens: out_width outside 1..65536");
+    }
+    const char* const entry[9] = {"camera fx", "camera fy", "camera cx", "camera cy", "camera k1", "camera k2", "camera p1", "camera p2", "camera k3"};
+    for (int k = 0; k < 9; ++k)
+        for (double o : {nan, inf, -inf}) bad({UNDISTORT}, [&](Args& a) { a.camera[k] = o; }, entry[k], "lens: camera entry not finite");
+    for (double o : {0.0, -0.0, -50.0}) {
+        bad({UNDISTORT}, [&](Args& a) { a.camera[0] = o; }, "camera fx", "lens: fx <= 0");
+        bad({UNDISTORT}, [&](Args& a) { a.camera[1] = o; }, "camera fy", "lens: fy <= 0");
+    }
+    for (double o : {0.0, -1.0, nan, inf, -inf}) bad({UNDISTORT}, [&](Args& a) { a.f_out = o; }, "f_out", "lens: f_out not a finite number > 0");
+    for (int m : {-1, 2, imax, imin}) bad({UNDISTORT}, [&](Args& a) { a.mode = m; }, "mode", "lens: unknown mode");
+    for (uintptr_t off : {1, 4, 7}) bad({UNDISTORT}, [&](Args& a) { a.lens_stats = 0xf000 + off; }, "stats_dev not 8-byte aligned", "lens: misaligned stats");
+    // 37 x 53 x 3 bytes in, 30 x 40 x 3 out: the two ranges meet from either side or nest
+    const uintptr_t lens_in = 37 * 53 * 3, lens_out = 30 * 40 * 3;
+    for (uintptr_t out : {(uintptr_t)0x100000, 0x100000 + lens_in - 1, 0x100000 - lens_out + 1, (uintptr_t)0x100100})
+        bad({UNDISTORT}, [&](Args& a) { a.out = out; }, "overlap", "lens: in and out overlap");
+    // the largest legal shape passes every size computation before the overlap check stops it: 12.9e9 bytes of input reach over out
+    bad({UNDISTORT}, [&](Args& a) { a.height = a.width = a.out_height = a.out_width = 65536; a.out = a.in + (uintptr_t)65536 * 65536 * 3 - 1; },
+        "overlap", "lens: largest frames, ranges that touch");
 
     std::printf("survey_args_check: %d checks, ", checks);
     std::printf(failures ? "%d FAILED\n" : "all passed\n", failures);

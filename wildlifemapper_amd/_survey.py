@@ -78,6 +78,17 @@ def _whole_number(value, what: str, name: str, lo: int, hi=None, multiple: int =
     return int(value)
 
 
+def _check_fill(fill, what: str) -> np.ndarray:
+    """fill= of mosaic() and undistort_u8(): three whole numbers in 0..255, as (3,) uint8, before any device work."""
+    try:
+        fill_a = np.asarray(fill)
+        if fill_a.shape != (3,) or fill_a.dtype.kind not in "iuf" or not np.all((fill_a >= 0) & (fill_a <= 255) & (fill_a == np.floor(fill_a))):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: fill {fill!r} must be three whole numbers in 0..255") from None
+    return fill_a.astype(np.uint8)
+
+
 def _check_whole(value, what: str, name: str, lo: int = 1) -> int:
     """A whole number >= lo (an int, or a float without a fraction), before any device work."""
     return _whole_number(value, what, name, lo, must=f"must be a whole number >= {lo}", floats=True)

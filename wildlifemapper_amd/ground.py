@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from ._survey import _as_frame_array, _check_whole, _finite_number, _frame_descs, _frame_index, _pinned_upload
+from ._survey import _as_frame_array, _check_fill, _check_whole, _finite_number, _frame_descs, _frame_index, _pinned_upload
 from .review import _check_draw_width, _check_palette, draw_boxes
 
 # ---- census ----------------------------------------------------------------------------------------------------------
@@ -591,13 +591,7 @@ def mosaic(frames, georef, cell, sizes=None, bounds=None, sample: str = "bilinea
         raise ValueError(f"{what}: exposure needs blend=: the hard-seam mosaic copies pixels as they are")
     if not isinstance(sample, str) or sample not in MOSAIC_SAMPLES:
         raise ValueError(f"{what}: sample {sample!r} must be 'bilinear' or 'nearest'")
-    try:
-        fill_a = np.asarray(fill)
-        if fill_a.shape != (3,) or fill_a.dtype.kind not in "iuf" or not np.all((fill_a >= 0) & (fill_a <= 255) & (fill_a == np.floor(fill_a))):
-            raise TypeError
-    except (TypeError, ValueError):
-        raise ValueError(f"{what}: fill {fill!r} must be three whole numbers in 0..255") from None
-    fill_a = fill_a.astype(np.uint8)
+    fill_a = _check_fill(fill, what)
     chunk = _check_whole(chunk, what, "chunk")
     if (census is None) != (marker is None):
         raise ValueError(f"{what}: marker {marker!r} and census go together: pass both (census= the dict census() returned) or neither")

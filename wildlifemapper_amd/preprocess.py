@@ -33,6 +33,45 @@ def tiles_from_u8(images: torch.Tensor, resize=None) -> torch.Tensor:
     return out
 
 
+def _check_undistort_args(sample, fill, what: str):
+    """(wm_undistort_u8's mode, the three fill bytes) of sample= and fill=, before any device work."""
+    from ._survey import _check_fill
+    from .ground import MOSAIC_SAMPLES
+    if not isinstance(sample, str) or sample not in MOSAIC_SAMPLES:
+        raise ValueError(f"{what}: sample {sample!r} must be 'bilinear' or 'nearest'")
+    return MOSAIC_SAMPLES[sample], _check_fill(fill, what)
+
+
+def undistort_u8(frame: torch.Tensor, plan, sample: str = "bilinear", fill=(0, 0, 0), count: bool = False):
+    """frame (H,W,3) uint8 on a ROCm device -> its pinhole picture (oh,ow,3) uint8 on the same device, by the dict
+    lens.lens_plan() returned (wm_undistort_u8; rule: include/wm_hip.h "Survey lens").  sample: 'bilinear' (pixel centres at
+    integer + 0.5, edge replicate) or 'nearest', the mosaic's sampling; fill: the (r, g, b) of the pixels that look outside
+    the frame.  Every output byte is written.  count=True: returns (picture, filled), filled a device int64 tensor of one
+    element, the number of filled pixels, without a host synchronisation.  A frame whose shape is not plan['size'] is
+    refused.  Runs on the current stream; everything is validated before any device work."""
+    import ctypes as C
+
+    from .lens import _check_plan
+    what = "undistort_u8"
+    pl = _check_plan(plan, what)
+    mode, fill_a = _check_undistort_args(sample, fill, what)
+    if not isinstance(frame, torch.Tensor) or not frame.is_cuda or frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[-1] != 3:
+        got = f"{tuple(frame.shape)} {frame.dtype} on {frame.device}" if isinstance(frame, torch.Tensor) else type(frame).__name__
+        raise RuntimeError(f"{what}: expected an (H,W,3) uint8 ROCm tensor, got {got}")
+    if tuple(frame.shape[:2]) != tuple(pl["size"]):
+        raise ValueError(f"{what}: frame is {tuple(frame.shape[:2])}, the plan was made for {tuple(pl['size'])}")
+    (h, w), (oh, ow) = pl["size"], pl["out_size"]
+    frame = frame.contiguous()
+    cam = (C.c_double * 9)(*[float(v) for v in pl["camera"]])
+    fill_c = (C.c_uint8 * 3)(*[int(v) for v in fill_a])
+    with torch.cuda.device(frame.device):
+        out = torch.empty((oh, ow, 3), device=frame.device, dtype=torch.uint8)
+        filled = torch.empty(1, device=frame.device, dtype=torch.int64) if count else None
+        N.check(N.lib().wm_undistort_u8(N.ptr(frame), h, w, cam, N.ptr(out), oh, ow, float(pl["f_out"]), mode, fill_c, N.ptr(filled),
+                                        N.stream_ptr(frame.device)))
+    return (out, filled) if count else out
+
+
 def scaled_size(height: int, width: int, scale: float):
     """(oh, ow) = (max(1, floor(height * scale + 0.5)), the same for width), in double (wm_scaled_size; host-only call)."""
     import ctypes as C
