@@ -51,6 +51,8 @@ extern "C" {
  *    by 2 x 2 rounded means so the refinement converges from far off); the number stays 13 for the same reason.
  *    13, also additive: wm_undistort_u8 (survey lens: a frame resampled to the pinhole picture of its Brown-Conrady
  *    calibration, so the affine georeference holds for it); the number stays 13 for the same reason.
+ *    13, also additive: wm_rectify_u8 (survey attitude: a tilted frame resampled to the picture of a level camera, by its
+ *    roll and pitch and its calibration in one gather); the number stays 13 for the same reason.
  * 12: wm_box_outline_rect, wm_draw_boxes_u8, wm_plot_image_u8, WM_DRAW_MAX_WIDTH, WM_DRAW_MAX_PALETTE, WM_PLOT_SCRATCH_BYTES
  *    (survey overlays: detections outlined on frames and tiles, on the GPU); nothing else changed.
  * 11: wm_chip_window, wm_crop_chips_u8, WM_CHIP_MAX_SIDE (survey review chips: one PIL-exact crop per detection, cut on
@@ -699,6 +701,43 @@ int wm_scaled_size(int height, int width, double scale, int* out_h, int* out_w);
 int wm_undistort_u8(const uint8_t* in_dev, int height, int width, const double camera[9], uint8_t* out_dev, int out_height,
                     int out_width, double f_out, int mode, const uint8_t fill_rgb[3], int64_t* stats_dev /* [1], may be NULL */,
                     void* stream);
+
+/* Survey attitude (attitude.attitude_rotation, attitude.rectify_plan, preprocess.rectify_u8, tiling.rectified): a frame taken
+ * by a camera that was not level, resampled ONCE to the picture a level (nadir) pinhole camera at the same place would have
+ * taken: the rotation and the lens model of "Survey lens" in one gather, so the frame is neither blurred nor paid for twice.
+ * No reference behaviour exists; this rule is the contract, and tests/attitude_cases.py restates it sequentially
+ * (attitude_oracle).  All arithmetic is IEEE double, every operation correctly rounded on its own (no contraction), in the
+ * order and with the parentheses written.
+ * Rotation: rot[9] doubles r0..r8, row-major, maps a ray of the level camera into the real camera: d_cam = rot * d_nadir.
+ * Both frames have x to the picture's right, y down the picture and z along the optical axis.  Convention of
+ * attitude.attitude_rotation(roll, pitch): the camera is fixed to the airframe, the optical axis points down, the picture's up
+ * direction is the nose and its right the right wing; yaw stays in tiling.nadir_affine.  Pitch t > 0 is nose up (the axis
+ * swings towards the picture's up direction), roll p > 0 is right wing down (the axis swings towards the picture's left).
+ * With P = [[1,0,0],[0,cos t,-sin t],[0,sin t,cos t]] and Q = [[cos p,0,-sin p],[0,1,0],[sin p,0,cos p]], A = P Q maps
+ * airframe to level and rot = A^T; the third column of A, the optical axis in level coordinates, is
+ * (-sin p, -sin t cos p, cos t cos p).  The kernel does not require rot to be orthonormal: the rule is a homography.
+ * Output: as in "Survey lens", out_height x out_width pixels (oh, ow), one focal length f_out, the principal point at the
+ * geometric centre; tiling.nadir_affine(oh, ow, position, altitude / f_out, yaw) holds for it, position the ground point
+ * straight below the camera.  For the output pixel of row j and column i:
+ *     x  = (((double)i + 0.5) - 0.5 * (double)ow) / f_out          y = (((double)j + 0.5) - 0.5 * (double)oh) / f_out
+ *     X  = (r0 * x + r1 * y) + r2
+ *     Y  = (r3 * x + r4 * y) + r5
+ *     Z  = (r6 * x + r7 * y) + r8
+ * The pixel is OUTSIDE unless Z > 0 (a NaN is outside); otherwise
+ *     xn = X / Z                                                   yn = Y / Z
+ * and (xn, yn) goes through exactly the expressions of "Survey lens" in place of its (x, y): its r2 (the squared radius, not
+ * the rotation's entry), rad, xd, yd, u, v.  The source pixel is INSIDE iff Z > 0 && 0 <= u < width && 0 <= v < height; inside,
+ * the three bytes are "Survey mosaic"'s nearest or bilinear sample at (u, v); outside, the fill colour.  Every output byte is
+ * written by every call.  With rot the identity X == x, Y == y and Z == 1 exactly, and the rule equals wm_undistort_u8's bit
+ * for bit.
+ * wm_rectify_u8: the arguments of wm_undistort_u8 and rot, read on the host during the call; stats_dev, unless NULL, is one
+ * int64 that receives the number of output pixels that got the fill colour, those with Z <= 0 included (zeroed on `stream`
+ * first, then one 64-bit atomic per workgroup that filled any).  One launch, a gather: plain loads and stores, no atomics on
+ * the picture, nothing allocated, asynchronous on `stream`.  Limits and checks: wm_undistort_u8's, and every rot entry finite.
+ * Bad arguments fail before any HIP call with a message that names the argument. */
+int wm_rectify_u8(const uint8_t* in_dev, int height, int width, const double camera[9], const double rot[9], uint8_t* out_dev,
+                  int out_height, int out_width, double f_out, int mode, const uint8_t fill_rgb[3],
+                  int64_t* stats_dev /* [1], may be NULL */, void* stream);
 
 /* Survey review chips (tiling.detect_frames(chips=...), tiling.crop_chips): one chip x chip uint8 crop per detection, each
  * with a window and a scale of its own, in one launch.

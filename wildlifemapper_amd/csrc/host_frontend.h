@@ -5,6 +5,7 @@
 #include <climits>
 
 #include "resample_kernels.h"
+#include "attitude_kernels.h"
 #include "lens_kernels.h"
 #include "host_core.h"
 
@@ -234,15 +235,17 @@ int resample_impl(const uint8_t* in_dev, int height, int width, uint8_t* out_dev
     return 0;
 }
 
-// ---- survey lens: a frame -> the pinhole picture of its camera (include/wm_hip.h "Survey lens") ----
+// ---- survey lens and attitude: a frame -> the pinhole picture of its camera (include/wm_hip.h "Survey lens"), or of a level
+// camera at the same place ("Survey attitude") ----
 // Every argument is checked on the host before the first HIP call; one memset of the optional count and one launch.
-int launch_undistort(const uint8_t* in_dev, int height, int width, const double* camera, uint8_t* out_dev, int out_height, int out_width,
-                     double f_out, int mode, const uint8_t* fill_rgb, int64_t* stats_dev, hipStream_t s) {
-    const char* name = "wm_undistort_u8";
+// rot == nullptr: wm_undistort_u8, which has no rotation.
+int check_lens_args(const char* name, const uint8_t* in_dev, int height, int width, const double* camera, const double* rot, bool has_rot,
+                    uint8_t* out_dev, int out_height, int out_width, double f_out, int mode, const uint8_t* fill_rgb, int64_t* stats_dev) {
     static const char* const entry[9] = {"fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3"};
     if (!in_dev) return fail("%s: null in_dev", name);
     if (!out_dev) return fail("%s: null out_dev", name);
     if (!camera) return fail("%s: null camera", name);
+    if (has_rot && !rot) return fail("%s: null rot", name);
     if (!fill_rgb) return fail("%s: null fill_rgb", name);
     for (int v : {height, width, out_height, out_width})
         if (v < 1 || v > RESAMPLE_MAX_SIDE)
@@ -251,12 +254,22 @@ int launch_undistort(const uint8_t* in_dev, int height, int width, const double*
         if (!std::isfinite(camera[k])) return fail("%s: camera %s %g is not finite", name, entry[k], camera[k]);
     if (!(camera[0] > 0.0)) return fail("%s: camera fx %g: need a focal length > 0", name, camera[0]);
     if (!(camera[1] > 0.0)) return fail("%s: camera fy %g: need a focal length > 0", name, camera[1]);
+    if (has_rot)
+        for (int k = 0; k < 9; ++k)
+            if (!std::isfinite(rot[k])) return fail("%s: rot[%d] %g is not finite", name, k, rot[k]);
     if (!(std::isfinite(f_out) && f_out > 0.0)) return fail("%s: f_out %g: need a finite focal length > 0", name, f_out);
     if (mode != WM_MOSAIC_NEAREST && mode != WM_MOSAIC_BILINEAR) return fail("%s: mode %d is neither WM_MOSAIC_NEAREST nor WM_MOSAIC_BILINEAR", name, mode);
     if ((uintptr_t)stats_dev % 8) return fail("%s: stats_dev not 8-byte aligned", name);
     const uintptr_t in0 = (uintptr_t)in_dev, in1 = in0 + (size_t)height * width * 3, out0 = (uintptr_t)out_dev,
                     out1 = out0 + (size_t)out_height * out_width * 3;
     if (in0 < out1 && out0 < in1) return fail("%s: in_dev and out_dev overlap", name);
+    return 0;
+}
+
+int launch_undistort(const uint8_t* in_dev, int height, int width, const double* camera, uint8_t* out_dev, int out_height, int out_width,
+                     double f_out, int mode, const uint8_t* fill_rgb, int64_t* stats_dev, hipStream_t s) {
+    WM_TRY(check_lens_args("wm_undistort_u8", in_dev, height, width, camera, nullptr, false, out_dev, out_height, out_width, f_out, mode, fill_rgb,
+                           stats_dev));
     if (stats_dev) HIP_TRY(hipMemsetAsync(stats_dev, 0, sizeof(int64_t), s));
     const frame_desc in{in_dev, height, width};
     const lens_camera cam{camera[0], camera[1], camera[2], camera[3], camera[4], camera[5], camera[6], camera[7], camera[8]};
@@ -267,6 +280,25 @@ int launch_undistort(const uint8_t* in_dev, int height, int width, const double*
                            (unsigned long long*)stats_dev);
     };
     mode == WM_MOSAIC_NEAREST ? launch(lens_undistort_kernel<WM_MOSAIC_NEAREST>) : launch(lens_undistort_kernel<WM_MOSAIC_BILINEAR>);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_rectify(const uint8_t* in_dev, int height, int width, const double* camera, const double* rot, uint8_t* out_dev, int out_height,
+                   int out_width, double f_out, int mode, const uint8_t* fill_rgb, int64_t* stats_dev, hipStream_t s) {
+    WM_TRY(check_lens_args("wm_rectify_u8", in_dev, height, width, camera, rot, true, out_dev, out_height, out_width, f_out, mode, fill_rgb,
+                           stats_dev));
+    if (stats_dev) HIP_TRY(hipMemsetAsync(stats_dev, 0, sizeof(int64_t), s));
+    const frame_desc in{in_dev, height, width};
+    const lens_camera cam{camera[0], camera[1], camera[2], camera[3], camera[4], camera[5], camera[6], camera[7], camera[8]};
+    const attitude_rot r{rot[0], rot[1], rot[2], rot[3], rot[4], rot[5], rot[6], rot[7], rot[8]};
+    const unsigned int fill = (unsigned int)fill_rgb[0] | (unsigned int)fill_rgb[1] << 8 | (unsigned int)fill_rgb[2] << 16;
+    const dim3 grid((out_width + COV_BLOCK_X - 1) / COV_BLOCK_X, (out_height + MOS_FILL_BLOCK_Y - 1) / MOS_FILL_BLOCK_Y);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(COV_THREADS), 0, s, in, cam, r, f_out, out_height, out_width, fill, out_dev,
+                           (unsigned long long*)stats_dev);
+    };
+    mode == WM_MOSAIC_NEAREST ? launch(attitude_rectify_kernel<WM_MOSAIC_NEAREST>) : launch(attitude_rectify_kernel<WM_MOSAIC_BILINEAR>);
     HIP_TRY(hipGetLastError());
     return 0;
 }

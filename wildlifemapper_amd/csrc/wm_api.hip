@@ -217,6 +217,12 @@ extern "C" int wm_undistort_u8(const uint8_t* in_dev, int height, int width, con
                             (hipStream_t)stream);
 }
 
+extern "C" int wm_rectify_u8(const uint8_t* in_dev, int height, int width, const double camera[9], const double rot[9], uint8_t* out_dev,
+                             int out_height, int out_width, double f_out, int mode, const uint8_t fill_rgb[3], int64_t* stats_dev, void* stream) {
+    return launch_rectify(in_dev, height, width, camera, rot, out_dev, out_height, out_width, f_out, mode, fill_rgb, stats_dev,
+                          (hipStream_t)stream);
+}
+
 extern "C" int wm_chip_window(const float box[4], float context, int min_side, int max_side, int32_t out[3]) {
     if (!box || !out) return fail("wm_chip_window: null argument");
     WM_TRY(check_chip_rule("wm_chip_window", context, min_side, max_side));

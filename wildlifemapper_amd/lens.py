@@ -15,8 +15,9 @@ principal point at its geometric centre, so nadir_affine(oh, ow, centre, gsd, ya
     wm_undistort_u8), which detect_frames, mosaic, register and refine take as they take any sequence.
 The geometry is numpy float64 on the host, in the rule's own expression; only the pixels are touched on the device.
 
-Not here: estimating the coefficients from the survey's own overlaps, vignetting, fisheye and rational (k4..k6) models,
-oblique cameras."""
+Not here: estimating the coefficients from the survey's own overlaps, vignetting, fisheye and rational (k4..k6) models.
+The roll and pitch of near-nadir flight are attitude.py's, which applies them and this model in one resampling; truly oblique
+cameras and terrain relief are covered by neither."""
 from __future__ import annotations
 
 from typing import Dict
@@ -184,21 +185,36 @@ def _largest(ok, n: int) -> int:
         lo = grown
 
 
-def _valid_size(cam: np.ndarray, h: int, w: int, f_out: float, what: str):
-    """keep='valid': pictures of the frame's own aspect are grown about the centre as far as none of their border pixels is
-    filled; then the width, then the height, are grown on their own as far as they go, until neither can."""
+def _grow_valid(none_filled, h: int, w: int):
+    """keep='valid' given none_filled(oh, ow), which holds of (1, 1): pictures of the frame's own aspect are grown about the
+    centre as far as none of their border pixels is filled; then the width, then the height, are grown on their own as far as
+    they go, until neither can."""
     m = max(h, w)
     shape = lambda k: (max(1, k * h // m), max(1, k * w // m))
-    if not _none_filled(cam, h, w, 1, 1, f_out):
-        raise ValueError(f"{what}: keep='valid' is empty: the principal point ({cam[2]!r}, {cam[3]!r}) does not lie in the "
-                         f"{h} x {w} frame, so the picture's centre pixel would already be filled")
-    oh, ow = shape(_largest(lambda k: _none_filled(cam, h, w, *shape(k), f_out), 1))
+    oh, ow = shape(_largest(lambda k: none_filled(*shape(k)), 1))
     while True:
-        ow2 = _largest(lambda n: _none_filled(cam, h, w, oh, n, f_out), ow)
-        oh2 = _largest(lambda n: _none_filled(cam, h, w, n, ow2, f_out), oh)
+        ow2 = _largest(lambda n: none_filled(oh, n), ow)
+        oh2 = _largest(lambda n: none_filled(n, ow2), oh)
         if (oh2, ow2) == (oh, ow):
             return oh, ow
         oh, ow = oh2, ow2
+
+
+def _valid_size(cam: np.ndarray, h: int, w: int, f_out: float, what: str):
+    """keep='valid': the largest centred picture of which no border pixel is filled (_grow_valid)."""
+    if not _none_filled(cam, h, w, 1, 1, f_out):
+        raise ValueError(f"{what}: keep='valid' is empty: the principal point ({cam[2]!r}, {cam[3]!r}) does not lie in the "
+                         f"{h} x {w} frame, so the picture's centre pixel would already be filled")
+    return _grow_valid(lambda oh, ow: _none_filled(cam, h, w, oh, ow, f_out), h, w)
+
+
+def _size_that_holds(x, y, what: str):
+    """The smallest centred (oh, ow) that holds the positions (x, y), pixels from the picture's centre."""
+    side = lambda lo, hi: max(int(np.ceil(2.0 * -lo)), int(np.floor(2.0 * hi)) + 1, 1)     # -side / 2 <= lo, hi < side / 2
+    oh, ow = side(y.min(), y.max()), side(x.min(), x.max())
+    if oh > LENS_MAX_SIDE or ow > LENS_MAX_SIDE:
+        raise ValueError(f"{what}: keep='all' needs {oh} x {ow} pixels, more than {LENS_MAX_SIDE} a side: pass a smaller f_out")
+    return oh, ow
 
 
 def _all_size(cam: np.ndarray, h: int, w: int, f_out: float, what: str):
@@ -211,23 +227,24 @@ def _all_size(cam: np.ndarray, h: int, w: int, f_out: float, what: str):
                          "undistorted position (the iteration did not converge on an orientation-preserving branch)")
     x = (pts[:, 0] - (cam[2] + 0.5)) / cam[0] * f_out
     y = (pts[:, 1] - (cam[3] + 0.5)) / cam[1] * f_out
-    side = lambda lo, hi: max(int(np.ceil(2.0 * -lo)), int(np.floor(2.0 * hi)) + 1, 1)     # -side / 2 <= lo, hi < side / 2
-    oh, ow = side(y.min(), y.max()), side(x.min(), x.max())
-    if oh > LENS_MAX_SIDE or ow > LENS_MAX_SIDE:
-        raise ValueError(f"{what}: keep='all' needs {oh} x {ow} pixels, more than {LENS_MAX_SIDE} a side: pass a smaller f_out")
-    return oh, ow
+    return _size_that_holds(x, y, what)
 
 
-def _check_no_fold(cam: np.ndarray, oh: int, ow: int, f_out: float, what: str) -> None:
+def _check_no_fold(cam: np.ndarray, oh: int, ow: int, f_out: float, what: str, rays=None) -> None:
     """ValueError when the Jacobian determinant of (x, y) -> (xd, yd) is <= 0 (or not finite) on the border of the output or
-    on a coarse grid over its inside: the picture would show parts of the frame twice, mirrored."""
+    on a coarse grid over its inside: the picture would show parts of the frame twice, mirrored.  rays (attitude.py): the
+    map (x, y) -> (xn, yn, in front) that comes before the lens; the Jacobian is then taken at (xn, yn), and a point that is
+    not in front of the camera, which is filled and never sampled, is not looked at."""
     j, i = _border(oh, ow)
     gj, gi = np.meshgrid(np.linspace(0, oh - 1, _FOLD_GRID), np.linspace(0, ow - 1, _FOLD_GRID), indexing="ij")
     j, i = np.concatenate([j, gj.ravel()]), np.concatenate([i, gi.ravel()])
     x, y = ((i + 0.5) - 0.5 * ow) / f_out, ((j + 0.5) - 0.5 * oh) / f_out
     with np.errstate(all="ignore"):
+        front = True
+        if rays is not None:
+            x, y, front = rays(x, y)
         det = _jacobian(cam, x, y)[4]
-    bad = ~(det > 0)
+    bad = ~(det > 0) & front
     if bad.any():
         idx = np.nonzero(bad)[0]
         k = int(idx[np.argmin((x * x + y * y)[idx])])                       # the nearest to the centre
@@ -329,34 +346,41 @@ class undistorted:
     Known limit: detect_frames overlaps a HOST frame's upload with the previous batch on its copy stream; a host frame that
     comes through this wrapper is uploaded and undistorted on the current stream when it is indexed, and is not overlapped."""
 
-    def __init__(self, frames, plan, sample: str = "bilinear", fill=(0, 0, 0)):
-        what = "undistorted"
+    def _take(self, frames, sample, fill) -> None:
+        what = type(self).__name__
         if not (hasattr(frames, "__getitem__") and hasattr(frames, "__len__")):
             raise ValueError(f"{what}: frames must be a sequence that can be indexed (frames[i], len), got {type(frames).__name__}")
         from .preprocess import _check_undistort_args
-        self.plan = _check_plan(plan, what)
         self.sample, self.fill = sample, fill
         _check_undistort_args(sample, fill, what)
         self.frames = frames
+
+    def __init__(self, frames, plan, sample: str = "bilinear", fill=(0, 0, 0)):
+        self._take(frames, sample, fill)
+        self.plan = _check_plan(plan, "undistorted")
         self.sizes = np.tile(np.asarray(self.plan["out_size"], dtype=np.int64), (len(frames), 1)).reshape(-1, 2)
 
     def __len__(self) -> int:
         return len(self.frames)
 
-    def __getitem__(self, i):
-        n = len(self.frames)
-        if isinstance(i, bool) or not isinstance(i, (int, np.integer)):
-            raise TypeError(f"undistorted: index {i!r} is not a whole number")
-        if not -n <= i < n:
-            raise IndexError(f"undistorted: index {i} of {n} frames")
-        i = int(i) % n
+    def _resample(self, frame, i: int):
+        """The device frame i, resampled (attitude.rectified has a plan per frame and another call)."""
         from . import preprocess
+        return preprocess.undistort_u8(frame, self.plan, self.sample, self.fill)
+
+    def __getitem__(self, i):
+        n, who = len(self.frames), type(self).__name__
+        if isinstance(i, bool) or not isinstance(i, (int, np.integer)):
+            raise TypeError(f"{who}: index {i!r} is not a whole number")
+        if not -n <= i < n:
+            raise IndexError(f"{who}: index {i} of {n} frames")
+        i = int(i) % n
         if not torch.cuda.is_available():
-            raise RuntimeError("undistorted: no ROCm device (there is no CPU fallback in wildlifemapper_amd)")
+            raise RuntimeError(f"{who}: no ROCm device (there is no CPU fallback in wildlifemapper_amd)")
         dev = torch.device("cuda", torch.cuda.current_device())
-        on_dev, on_host = _as_frame_array(self.frames[i], i, dev, "undistorted")
+        on_dev, on_host = _as_frame_array(self.frames[i], i, dev, who)
         fr = on_dev if on_dev is not None else _pinned_upload(on_host, dev)
-        return preprocess.undistort_u8(fr, self.plan, self.sample, self.fill)
+        return self._resample(fr, i)
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))

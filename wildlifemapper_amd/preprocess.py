@@ -49,11 +49,25 @@ def undistort_u8(frame: torch.Tensor, plan, sample: str = "bilinear", fill=(0, 0
     the frame.  Every output byte is written.  count=True: returns (picture, filled), filled a device int64 tensor of one
     element, the number of filled pixels, without a host synchronisation.  A frame whose shape is not plan['size'] is
     refused.  Runs on the current stream; everything is validated before any device work."""
-    import ctypes as C
-
     from .lens import _check_plan
     what = "undistort_u8"
-    pl = _check_plan(plan, what)
+    return _resample_by_plan(frame, _check_plan(plan, what), None, sample, fill, count, what)
+
+
+def rectify_u8(frame: torch.Tensor, plan, sample: str = "bilinear", fill=(0, 0, 0), count: bool = False):
+    """frame (H,W,3) uint8 on a ROCm device -> the picture (oh,ow,3) uint8 a level camera at the same place would have taken,
+    by the dict attitude.rectify_plan() returned: the plan's rotation and lens model in one gather (wm_rectify_u8; rule:
+    include/wm_hip.h "Survey attitude").  sample, fill, count, the frame's shape, the stream and the validation are
+    undistort_u8's; the filled pixels include those that look away from the camera's front (Z <= 0)."""
+    from .attitude import _check_rectify_plan
+    what = "rectify_u8"
+    pl = _check_rectify_plan(plan, what)
+    return _resample_by_plan(frame, pl, pl["rotation"], sample, fill, count, what)
+
+
+def _resample_by_plan(frame, pl, rotation, sample, fill, count: bool, what: str):
+    """undistort_u8 (rotation None) and rectify_u8 on a validated plan."""
+    import ctypes as C
     mode, fill_a = _check_undistort_args(sample, fill, what)
     if not isinstance(frame, torch.Tensor) or not frame.is_cuda or frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[-1] != 3:
         got = f"{tuple(frame.shape)} {frame.dtype} on {frame.device}" if isinstance(frame, torch.Tensor) else type(frame).__name__
@@ -67,8 +81,12 @@ def undistort_u8(frame: torch.Tensor, plan, sample: str = "bilinear", fill=(0, 0
     with torch.cuda.device(frame.device):
         out = torch.empty((oh, ow, 3), device=frame.device, dtype=torch.uint8)
         filled = torch.empty(1, device=frame.device, dtype=torch.int64) if count else None
-        N.check(N.lib().wm_undistort_u8(N.ptr(frame), h, w, cam, N.ptr(out), oh, ow, float(pl["f_out"]), mode, fill_c, N.ptr(filled),
-                                        N.stream_ptr(frame.device)))
+        tail = (N.ptr(out), oh, ow, float(pl["f_out"]), mode, fill_c, N.ptr(filled), N.stream_ptr(frame.device))
+        if rotation is None:
+            N.check(N.lib().wm_undistort_u8(N.ptr(frame), h, w, cam, *tail))
+        else:
+            rot = (C.c_double * 9)(*[float(v) for v in rotation.reshape(9)])
+            N.check(N.lib().wm_rectify_u8(N.ptr(frame), h, w, cam, rot, *tail))
     return (out, filled) if count else out
 
 

@@ -24,8 +24,8 @@ match: the checker is oracle/tiling_oracle.py, a numpy restatement of exactly wh
 Frame coordinates are fp32: a box coordinate keeps a fractional resolution below 0.01 px up to 65536 px (ulp 2**-8).
 
 The rest of the survey API lives beside this module and stays importable from it: chips and overlays in review.py, the
-census, coverage and mosaic in ground.py, registration in registration.py, the lens model (lens_plan, undistorted) in lens.py;
-what they all share is in _survey.py.
+census, coverage and mosaic in ground.py, registration in registration.py, the lens model (lens_plan, undistorted) in lens.py,
+roll and pitch (rectify_plan, rectified) in attitude.py; what they all share is in _survey.py.
 """
 from __future__ import annotations
 
@@ -42,6 +42,7 @@ from ._survey import _as_frame_array, _finite_number, _frame_descs, _frame_index
 from .ground import (CENSUS_CLASSES, CENSUS_MAX_DETS, COVERAGE_MAX_CELLS, COVERAGE_MAX_FRAMES, COVERAGE_MAX_SIDE, MOSAIC_SAMPLES,  # noqa: F401
                      census, coverage, footprint_bounds, ground_to_pixel, mosaic, mosaic_blend_plan, mosaic_plan, nadir_affine,
                      resampled_georef)
+from .attitude import MAX_TILT_DEG, attitude_points, attitude_rotation, rectified, rectify_plan  # noqa: F401
 from .lens import CAMERA_ENTRIES, LENS_KEEP, LENS_MAX_SIDE, distort_points, lens_plan, lens_points, undistort_points, undistorted  # noqa: F401
 from .registration import (REGISTER_MAX_LEVEL, REGISTER_MAX_PAIRS, REGISTER_MAX_SEARCH, REGISTER_MAX_SIDE, REGISTER_METRICS,  # noqa: F401
                            REGISTER_PAIR, REGISTER_REFINE_SUMS, adjust, adjust_exposure, adjust_similarity, exposure_table, reduce_planes,
