@@ -859,7 +859,9 @@ int wm_profile_read(wm_handle* h, wm_kclass_stat* out /* [WM_KCLASS_COUNT] */);
 #define WM_GEMM_V5_256_SPLIT 16
 #define WM_GEMM_V3_PATCH 17     /* gemm16v3_kernel AMODE 2: implicit-GEMM 16x16 / stride-16 patch embed (round 4) */
 #define WM_GEMM_FP8_256_PLANES 18 /* gemm8_kernel<256> with the stream as planes of rows (hi, lo) in and out (fp8 blocks' proj / lin2, round 4) */
-#define WM_GEMM_VARIANT_COUNT 19
+#define WM_GEMM_V5_320_WALK 19  /* a gemm16v5_kernel<320> folded-LayerNorm consumer whose workgroups walk several column tiles; counted IN ADDITION to WM_GEMM_V5_320 */
+#define WM_GEMM_V5_256_WALK 20
+#define WM_GEMM_VARIANT_COUNT 21
 int wm_debug_gemm_variant_counts(int64_t* out /* [WM_GEMM_VARIANT_COUNT] */, int n);
 int wm_debug_reset_gemm_variant_counts(void);
 
@@ -932,6 +934,12 @@ int wm_op_fold_weight16(const void* w16_dev, const float* gamma_dev, const float
                         float* c1_dev, float* c2_dev, int N, int K, int precision, void* stream);
 int wm_op_gemm16_folded(const void* x16_dev, const void* wf_dev, const float* c1_dev, const float* c2_dev, const float* stats_dev,
                         float eps, void* out_16_dev, int M, int N, int K, int act, int precision, void* stream);
+/* wm_op_gemm16_folded with the column tiles per workgroup given (csrc/gemm16_v5.h "Column walk"): walk = 0 the launcher's choice (what
+ * wm_op_gemm16_folded and the engine run), 1 one tile per workgroup, T > 1 that many whatever the grid size; a T that does not divide
+ * (N / tile width) / 4 runs as 1.  With walk > 0 the 256-row-tile kernel runs every shape it can (M % 256 == 0, N % 320 or 256 == 0,
+ * K % 32 == 0, K >= 64), also those the dispatch would give to a half-width kernel.  The output bits do not depend on walk. */
+int wm_op_gemm16_folded_walk(const void* x16_dev, const void* wf_dev, const float* c1_dev, const float* c2_dev, const float* stats_dev,
+                             float eps, void* out_16_dev, int M, int N, int K, int act, int walk, int precision, void* stream);
 int wm_op_gemm16_stats(const void* a_dev, const void* w_dev, const float* bias_dev, const float* residual_dev, float* out_f32_dev,
                        void* x16_dev, float* stats_dev, int M, int N, int K, int layout, int precision, void* stream);
 int wm_op_pack16(const void* in_dev, void* out_dev, int64_t rows, int K, void* stream);

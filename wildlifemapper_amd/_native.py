@@ -17,7 +17,8 @@ PREC_BY_NAME = {"bf16": PREC_BF16, "fp16": PREC_FP16, "f16": PREC_FP16, "fp8": P
 NUM_QUERIES, NUM_LOGITS = 51, 8
 KCLASS_NAMES = ("gemm16", "attn_window", "attn_global", "layernorm", "other")
 GEMM_VARIANTS = ("v1_128", "v2_160", "v2_128", "v3_lockstep", "v3_conv3x3", "v5_320", "v5_320_res", "v5_256", "v5_256_res",
-                 "v5_320_lnf", "v5_256_lnf", "fp8_320", "fp8_256", "v5_320_foldp", "v5_256_foldp", "v5_320_split", "v5_256_split", "v3_patch_embed", "fp8_256_planes")
+                 "v5_320_lnf", "v5_256_lnf", "fp8_320", "fp8_256", "v5_320_foldp", "v5_256_foldp", "v5_320_split", "v5_256_split", "v3_patch_embed", "fp8_256_planes",
+                 "v5_320_walk", "v5_256_walk")
 FLAG_CONF, FLAG_SCORE, FLAG_NMS, FLAG_MERGED = 1, 2, 4, 8
 CRITERION_MAX_TARGETS, CRITERION_SUMS, CRITERION_NONFINITE, CRITERION_UNSOLVED = 2048, 8, 1, 2
 CENSUS_MAX_DETS, CENSUS_SAME_CLASS, CENSUS_UNSOLVED = 262144, 1, 1
@@ -123,6 +124,7 @@ SYMBOLS = {
     "wm_stream_overflow": (_I, [_P, _I]),
     "wm_op_fold_weight16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "wm_op_gemm16_folded": (_I, [_P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P]),
+    "wm_op_gemm16_folded_walk": (_I, [_P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _I, _P]),
     "wm_op_gemm16_stats": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "wm_op_gemm8": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "wm_op_stream_rows": (_I, [_P, _P, _P, _L, _I, _I, _I, _P]),

@@ -32,7 +32,8 @@
 namespace wm {
 
 // DBG (dev only, WM_GEMM_DBG=1, see launch_gemm16v5_t): waves 0 and 4 of workgroup 0 record s_memtime at six marks of
-// K-steps 8..17, every workgroup its wall-clock entry / first barrier / loop end / stores-acknowledged stamps, into
+// K-steps 8..17, every workgroup per tile of its walk its wall-clock entry (tile 0) or hand-over barrier (later tiles) / first
+// barrier / loop end / last staging read / stores-acknowledged (last tile only: the wait would serialise fill and drain) stamps, into
 // p.zero_page.  The instrumented instance is a separate kernel; the product instance carries none of it.
 // (LNF, rounds 1-2: the fp32-residual epilogue also LayerNormed the finished rows, the row block's workgroups exchanging their
 // statistics in-kernel: zero net gain, superseded by the folded LayerNorm below; tools/experiments/gemm16_v5_lnf_fused_layernorm.h.)
@@ -65,6 +66,15 @@ namespace wm {
 // (FOLDC, the consumer, is an instance of its own: compiled into the plain instance its extra epilogue state cost that kernel
 // 114 spilled registers.)
 //
+// Column walk (the FOLDC instance, Gemm16Args::walk = T > 1).  One workgroup fills a CU, so the next tile's workgroup is dispatched only
+// after this one has retired, stores acknowledged, and then starts its ring fill cold.  All column tiles of a row block share the A
+// panel, the row statistics and their combination, so a consumer workgroup can compute T column tiles of its row tile in turn
+// (walk_tile_origin, gemm_common.h): after the barrier behind the last epilogue pass's staging reads it zeroes the accumulators, moves
+// n0 on, requests the tile's c1 / c2 and the first AHEAD K-steps and enters the loop again, while the last pass's global stores are
+// still draining.  The statistics piece is fetched and combined once per workgroup (FOLD_MR stays).  Per tile the arithmetic, the
+// accumulation order, the epilogue and the bytes written are those of walk = 1: which workgroup computes a tile, and when, is all
+// that changes.
+//
 // Split stream (round 4).  The FOLDP epilogue moved 10 bytes per element (fp32 residual in, fp32 out, 16-bit copy out) with every
 // CU in the same phase: it is bound by the memory system (proj at 0.31 of peak).  The stream is therefore kept as TWO 16-bit
 // planes in LDS-image order, hi = T(x) and lo = fp16(x - hi): x = hi + lo carries 22 (fp16 hi) / 19 (bf16 hi) significant bits,
@@ -75,7 +85,7 @@ namespace wm {
 // call) the stream stays fp32 and ln_stats_x16_kernel rounds it to hi + lo in place, so a tile's bits do not depend on the batch.
 template <class T, int BN, int NSLOT = 3, bool DBG = false, bool FOLDP = false, bool FOLDC = false, bool SPLIT = false>
 __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
-    static_assert(!(FOLDC && (FOLDP || DBG)), "the folded-LayerNorm consumer is the plain 16-bit-output kernel");
+    static_assert(!(FOLDC && FOLDP), "the folded-LayerNorm consumer is the plain 16-bit-output kernel");
     static_assert(!SPLIT || FOLDP, "the split-stream epilogue is a form of the statistics-producing one");
     using C = G3<BN>;
     constexpr int AHEAD = NSLOT - 1;                       // K-steps of DMA in flight
@@ -86,18 +96,42 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned long long wt0 = 0, wt1 = 0, wt2 = 0, mt1 = 0, mt2 = 0, we[6] = {0, 0, 0, 0, 0, 0};
     if constexpr (DBG) wt0 = wall_clock64();
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 2, wc = wave & 3;               // wave group = wr: rows 0-127 / 128-255
-    const int fr = lane & 15, fq = lane >> 4;
     const int K = p.K, ns = K / C::BK;
     const char* Ab = (const char*)p.A;
     const char* Wb = (const char*)p.W;
 
     const int tilesM = p.M / C::BM, tilesN = p.N / BN, total_tiles = tilesM * tilesN;
-    const TileOrigin o = grouped_tile_origin<C::BM, BN>(tilesM, tilesN, blockIdx.x, total_tiles, p.group_m);
-    const int m0 = o.m0, n0 = o.n0;
+    // column tiles this workgroup walks ("Column walk"): a compile-time 1 for every instance but the consumer
+    const int walk = FOLDC && p.walk > 1 ? p.walk : 1;
+    const TileOrigin o = FOLDC ? walk_tile_origin<C::BM, BN>(tilesM, tilesN, blockIdx.x, total_tiles / walk, p.group_m, walk)
+                               : grouped_tile_origin<C::BM, BN>(tilesM, tilesN, blockIdx.x, total_tiles, p.group_m);
+    int m0 = o.m0, n0 = o.n0;
+    int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
+    // ---- the tiles of this workgroup's walk: one, and no loop at all, in every instance but the consumer.  The walk is rolled (a
+    // run-time count) and the wave-group skew starts from rest in every tile.  In the consumer everything per lane, per wave and per
+    // row tile is derived inside the loop from copies the optimiser cannot see through: hoisted out of the tile loop, the lane
+    // constants, addresses and flag masks of prologue and epilogue stay live across the K loop and spill ("What
+    // to look for in the ISA", item 2).  (The body keeps the indentation it had.)
+    int wt = 0;
+    do {
+    int lane = threadIdx.x & 63;
+    if constexpr (FOLDC) {
+        lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));        // nothing per lane lives from tile to tile
+        asm volatile("" : "+v"(lane));
+        asm volatile("" : "+s"(m0), "+s"(wave));              // nor what is derived from the row tile and the wave's number
+    }
+    const int tid = FOLDC ? wave * 64 + lane : (int)threadIdx.x;
+    // (the launch's flags likewise: hoisted, each test is a 64-bit mask held in SGPRs across the walk, and those spill too)
+    auto per_tile = [](int v) {
+        if constexpr (FOLDC) asm volatile("" : "+s"(v));
+        return v;
+    };
+    // (the consumer's operands are in LDS-image order by definition: x16 is written so, the folded weight is packed with its fold)
+    const bool a_packed = FOLDC || p.a_packed != 0, w_packed = FOLDC || p.w_packed != 0, out_packed = per_tile(p.out_packed) != 0;
+    const int fold_ntile = per_tile(p.fold_ntile);
+    const int wr = wave >> 2, wc = wave & 3;               // wave group = wr: rows 0-127 / 128-255
+    const int fr = lane & 15, fq = lane >> 4;
     const unsigned lane_off = (unsigned)(lane >> 2) * (unsigned)(K * 2) + (unsigned)((((lane & 3) ^ ((0 - (lane >> 4)) & 3))) << 4);
     const size_t row_bytes = (size_t)K * 2;
     // DMA pieces of this wave for K-step s into ring slot `slot`; EXTRA: waves 0-3 also carry the remainder W piece
@@ -116,7 +150,6 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
 #pragma unroll
         for (int i = 0; i < C::A_PIECES; ++i) {
             const int seg = wave * C::A_PIECES + i;
-            const bool a_packed = p.a_packed != 0;
             const char* base = a_packed ? sgpr_ptr(Ab + ((size_t)((m0 + seg * 16) / 16) * (size_t)ns + (size_t)s) * 1024)
                                         : sgpr_ptr(Ab + (size_t)(m0 + seg * 16) * row_bytes + (size_t)s * 64);
             __builtin_amdgcn_global_load_lds(base + (a_packed ? (unsigned)lane * 16u : lane_off), WM_LDS_PTR(smem + slot * C::STAGE + seg * 1024), 16, 0, 0);
@@ -124,9 +157,9 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
 #pragma unroll
         for (int i = 0; i < C::W_LO + (EXTRA ? 1 : 0); ++i) {
             const int seg = i < C::W_LO ? wave * C::W_LO + i : C::WAVES * C::W_LO + wave;
-            const char* base = p.w_packed ? sgpr_ptr(Wb + ((size_t)((n0 + seg * 16) / 16) * (size_t)ns + (size_t)s) * 1024)
+            const char* base = w_packed ? sgpr_ptr(Wb + ((size_t)((n0 + seg * 16) / 16) * (size_t)ns + (size_t)s) * 1024)
                                               : sgpr_ptr(Wb + (size_t)(n0 + seg * 16) * row_bytes + (size_t)s * 64);
-            __builtin_amdgcn_global_load_lds(base + (p.w_packed ? (unsigned)lane * 16u : lane_off), WM_LDS_PTR(smem + slot * C::STAGE + C::A_BYTES + seg * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(base + (w_packed ? (unsigned)lane * 16u : lane_off), WM_LDS_PTR(smem + slot * C::STAGE + C::A_BYTES + seg * 1024), 16, 0, 0);
         }
     };
 
@@ -136,6 +169,14 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
 
     f32x4 acc[C::MT][C::NT];
     typename T::vec8 wf[C::NT], af[C::MT];
+    if constexpr (FOLDC) {
+        // defined at the top of every tile: left undefined, the values waves 4-7 carry from K-step to K-step would be taken from
+        // the previous tile's last step and stay live (52 registers) through its epilogue
+#pragma unroll
+        for (int i = 0; i < C::NT; ++i) wf[i] = typename T::vec8{};
+#pragma unroll
+        for (int i = 0; i < C::MT; ++i) af[i] = typename T::vec8{};
+    }
 
     auto read_frags = [&](int slot) {
         const char* sS = smem + slot * C::STAGE;
@@ -212,24 +253,27 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
         }
     };
 
+    // landing buffer 0 is idle without a residual: raw partials (8 KiB), (mean, rstd) per row (2 KiB), c1 | c2 of the tile's columns
+    constexpr int FOLD_RAW = LDS_TOTAL - RES_BYTES, FOLD_MR = FOLD_RAW + 8192, FOLD_C = FOLD_MR + 2048;
+    static_assert(FOLD_C + 2 * BN * 4 <= LDS_TOTAL, "fold LDS map");
 #pragma unroll
     for (int i = 0; i < C::MT; ++i)
 #pragma unroll
         for (int j = 0; j < C::NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (SPLIT || p.residual) res_dma(0);
-    // landing buffer 0 is idle without a residual: raw partials (8 KiB), (mean, rstd) per row (2 KiB), c1 | c2 of the tile's columns
-    constexpr int FOLD_RAW = LDS_TOTAL - RES_BYTES, FOLD_MR = FOLD_RAW + 8192, FOLD_C = FOLD_MR + 2048;
-    static_assert(FOLD_C + 2 * BN * 4 <= LDS_TOTAL, "fold LDS map");
+    if (SPLIT || (!FOLDC && p.residual)) res_dma(0);
     if constexpr (FOLDC) {
-        // the row block's partial statistics: 256 rows x fold_ntile x (mean, M2), contiguous; one DMA piece per wave
-        if (wave * 1024 < 256 * p.fold_ntile * 8)
-            __builtin_amdgcn_global_load_lds((const char*)(p.fold_stats + (size_t)m0 * p.fold_ntile * 2) + wave * 1024 + lane * 16,
+        // the row block's partial statistics: 256 rows x fold_ntile x (mean, M2), contiguous; one DMA piece per wave.  They belong to
+        // the rows: fetched (and combined, below) for the first tile of a walk only
+        if (wt == 0 && wave * 1024 < 256 * fold_ntile * 8)
+            __builtin_amdgcn_global_load_lds((const char*)(p.fold_stats + (size_t)m0 * fold_ntile * 2) + wave * 1024 + lane * 16,
                                              WM_LDS_PTR(smem + FOLD_RAW + wave * 1024), 16, 0, 0);
         // c1 and c2 (= the bias argument) of this tile's BN columns: 256-byte pieces (4 B per lane: exact, no over-read), into LDS
         // rather than 40 registers per lane -- the epilogue keeps the 160 accumulators live and reads them per column fragment
         constexpr int PC = BN * 4 / 256;
 #pragma unroll
-        for (int pi = wave; pi < 2 * PC; pi += C::WAVES) {
+        for (int j = 0; j < (2 * PC + C::WAVES - 1) / C::WAVES; ++j) {
+            const int pi = wave + j * C::WAVES;
+            if (pi >= 2 * PC) break;
             const float* src = (pi < PC ? p.fold_c1 + n0 + pi * 64 : p.bias + n0 + (pi - PC) * 64) + lane;
             __builtin_amdgcn_global_load_lds(src, WM_LDS_PTR(smem + FOLD_C + (pi < PC ? pi * 256 : BN * 4 + (pi - PC) * 256)), 4, 0, 0);
         }
@@ -295,7 +339,7 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
     // (measured 13 us per 256x320 tile, a quarter of the kernel).  Staged through the (now idle) ring in passes of
     // 128 rows (16-bit output) or 64 rows (fp32 output), each thread then moves 16-byte chunks that are consecutive
     // along the row, and the residual is read the same way.
-    const int act = p.act & 0xff;
+    const int act = per_tile(p.act) & 0xff;
     f32x4 bias_v[FOLDC ? 1 : C::NT];
     if constexpr (!FOLDC) {
 #pragma unroll
@@ -303,16 +347,16 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
             bias_v[ni] = p.bias ? *(const f32x4*)(p.bias + n0 + wc * C::WCOLS + ni * 16 + fq * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
     if constexpr (FOLDC) {
-        if (tid < C::BM) {                                  // one row per thread: Chan combination of its column-tile partials
-            const float2* raw = (const float2*)(smem + FOLD_RAW) + tid * p.fold_ntile;
+        if (wt == 0 && tid < C::BM) {                       // one row per thread: Chan combination of its column-tile partials
+            const float2* raw = (const float2*)(smem + FOLD_RAW) + tid * fold_ntile;
             float mk[8], qk[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 mk[i] = qk[i] = 0.f;
-                if (i < p.fold_ntile) { const float2 t = raw[i]; mk[i] = t.x; qk[i] = t.y; }
+                if (i < fold_ntile) { const float2 t = raw[i]; mk[i] = t.x; qk[i] = t.y; }
             }
             float rstd;
-            const float mean = ln_combine(mk, qk, p.fold_ntile, p.fold_bn, (float)p.K, p.fold_eps, rstd);
+            const float mean = ln_combine(mk, qk, fold_ntile, p.fold_bn, (float)p.K, p.fold_eps, rstd);
             *(float2*)(smem + FOLD_MR + tid * 8) = make_float2(mean, rstd);
         }
     }
@@ -390,7 +434,7 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
                     barrier();
                 }
             }
-        } else if (p.out32 == nullptr && p.residual == nullptr) {
+        } else if (FOLDC || (p.out32 == nullptr && p.residual == nullptr)) {      // (the consumer is this form by definition)
             // 16-bit staging: 2 passes of 4 row-fragments; LDS row = BN * 2 + 16 bytes
             constexpr int ROWB = BN * 2 + 16, CPR = BN * 2 / 16, MTP = 4, ROWS = 2 * MTP * 16;
             static_assert(ROWS * ROWB <= LDS_TOTAL && (ROWS * CPR) % 512 == 0, "epilogue staging");
@@ -432,7 +476,7 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
                 }
                 __syncthreads();
                 if constexpr (DBG) { if (q < 2) we[1 + 2 * q] = wall_clock64(); }
-                if (p.out_packed) {
+                if (out_packed) {
                     // the output is the next GEMM's A operand: written in LDS-image order.  A wave moves one 16 x 32 tile (1 KiB,
                     // contiguous in memory) per iteration: lane l = position l of the piece = row l >> 2, logical chunk
                     // (l & 3) ^ ((-(l >> 4)) & 3) of the staged rows.
@@ -536,25 +580,42 @@ __global__ __launch_bounds__(512, 2) void gemm16v5_kernel(Gemm16Args p) {
     }
     if constexpr (DBG) {
         if (wave == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // C stores of this wave acknowledged
-            const unsigned long long wt3 = wall_clock64();
+            unsigned long long wt3 = 0;
+            if (wt + 1 == walk) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // C stores of this wave acknowledged
+                wt3 = wall_clock64();
+            }
             unsigned hw;
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
             unsigned xcc;
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
             if (lane == 0) {
-                unsigned long long* r = (unsigned long long*)((char*)p.zero_page + 512) + (size_t)blockIdx.x * 5;
-                r[0] = wt0; r[1] = wt1; r[2] = wt2; r[3] = wt3; r[4] = ((unsigned long long)xcc << 32) | hw;
-                if (blockIdx.x < 8) {
+                // one record per tile, in walk order: (workgroup, tile of its walk)
+                unsigned long long* r = (unsigned long long*)((char*)p.zero_page + 512) + ((size_t)blockIdx.x * walk + wt) * 6;
+                r[0] = wt0; r[1] = wt1; r[2] = wt2; r[3] = wt3; r[4] = ((unsigned long long)xcc << 32) | hw; r[5] = we[4];
+                if (blockIdx.x == 0 && wt + 1 == walk) {                         // (the last tile's: wave 4 rewrites its marks every tile)
                     unsigned* e = (unsigned*)p.zero_page + 64 + 40;          // unused tail of the group-1 marks
-                    if (blockIdx.x == 0) {
-                        for (int i = 0; i < 5; ++i) e[i] = (unsigned)(we[i] - wt2);
-                        e[5] = (unsigned)(mt2 - mt1); e[6] = (unsigned)(wt2 - wt1);      // loop: s_memtime counts, 10 ns units
-                    }
+                    for (int i = 0; i < 5; ++i) e[i] = (unsigned)(we[i] - wt2);
+                    e[5] = (unsigned)(mt2 - mt1); e[6] = (unsigned)(wt2 - wt1);      // loop: s_memtime counts, 10 ns units
                 }
             }
         }
     }
+    if constexpr (FOLDC) {
+        if (wt + 1 < walk) {
+            // Hand-over to the next tile of the walk.  The staging area overlays ring slots 0..2, which the fill below overwrites:
+            // every wave's staging reads of the last pass are back (its stores have their data), then the barrier.  Nothing here
+            // waits for the global stores.  vmcnt is one in-order counter and those stores are older than the DMA pieces requested
+            // next, so the new tile's first counted wait (wait_step(0)) is also the wait for the stores: fill and store drain run
+            // side by side, and the c1 / c2 pieces, issued ahead of the ring pieces as in the first tile, leave the counted waits
+            // of steps 0 and 1 (at most P ring pieces of the following step outstanding) as they are.
+            __builtin_amdgcn_s_waitcnt(0xc07f);
+            barrier();
+            n0 += 4 * BN;
+            if constexpr (DBG) wt0 = wall_clock64();
+        }
+    }
+    } while (FOLDC && ++wt < walk);
 }
 
 }  // namespace wm

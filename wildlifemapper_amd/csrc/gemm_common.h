@@ -53,6 +53,9 @@ struct Gemm16Args {
     const u16* res_lo;
     u16* out_lo;
     int* overflow;
+    // Folded-LayerNorm consumer only (gemm16_v5.h "Column walk"): column tiles per workgroup, 0 | 1 = one (the grid is then
+    // tilesM * tilesN workgroups, otherwise tilesM * tilesN / walk; walk divides tilesN / 4, see walk_tile_origin)
+    int walk;
 };
 
 // s_waitcnt vmcnt(N) with N a template argument (the instruction takes an immediate)
@@ -87,6 +90,18 @@ __device__ __forceinline__ TileOrigin grouped_tile_origin(int tilesM, int tilesN
     const int gsz = min(gm, tilesM - first_m);
     const int in_group = t - group * per_group;
     return {(first_m + in_group % gsz) * BM, (in_group / gsz) * BN};
+}
+
+// The same order for workgroups that each walk `walk` column tiles of one row tile (gemm16_v5.h "Column walk").  The tilesN columns
+// are cut into blocks of 4 * walk; a workgroup owns one SLOT = (row tile, column block, lane 0..3 of the block) and its tile at step t of
+// the walk is column (block * walk + t) * 4 + lane: n0 advances by 4 BN per step and m0 stays.  The slots are numbered like the tiles
+// above with tilesN / walk columns, so at every step the 32 consecutive slots of an XCD still cover group_m = 8 row tiles x 4
+// neighbouring column tiles, and over the walk every tile is computed exactly once.  walk == 1 is grouped_tile_origin itself.
+// Needs tilesN % (4 * walk) == 0 for walk > 1 (the launcher checks); nwg = tilesM * tilesN / walk.
+template <int BM, int BN>
+__device__ __forceinline__ TileOrigin walk_tile_origin(int tilesM, int tilesN, int wg, int nwg, int group_m, int walk) {
+    const TileOrigin slot = grouped_tile_origin<BM, 1>(tilesM, tilesN / walk, wg, nwg, group_m);
+    return {slot.m0, (((slot.n0 >> 2) * walk) * 4 + (slot.n0 & 3)) * BN};
 }
 
 // The activation of a GEMM epilogue: GELU (the fast erf form), ReLU or none ...

@@ -16,28 +16,42 @@ void dev_group_m(Gemm16Args& a) {
     if (const char* e = getenv("WM_GEMM_GROUP_M")) { if (atoi(e) > 0) a.group_m = atoi(e); }
 }
 
-// WM_GEMM_DBG: interval timing inside the plain 256 x 320 instance, on its 1st and (after a run of back-to-back launches) 31st launch
+// column tiles per workgroup of the folded-LayerNorm consumer (WM_GEMM_WALK = T; gemm16_v5.h "Column walk"): as if asked for by the caller
+void dev_walk(Gemm16Args& a) {
+    if (const char* e = getenv("WM_GEMM_WALK")) { if (atoi(e) > 0) a.walk = atoi(e); }
+}
+
+static double dev_median(std::vector<double> v) {
+    if (v.empty()) return 0.0;
+    std::sort(v.begin(), v.end());
+    return v[v.size() / 2];
+}
+
+// WM_GEMM_DBG: interval timing inside the plain or the folded-LayerNorm consumer 256 x 320 instance, on its 1st launch and on every 31st
+// (after a run of back-to-back launches).  One record of six stamps per tile, in (workgroup, tile of its walk) order.
 template <class T16, int BN, int NSLOT, bool FOLDP, bool FOLDC>
 int dev_gemm16v5_timeline(hipStream_t s, const Gemm16Args& a, int grid, int lds) {
-    if constexpr (BN == 320 && NSLOT == 3 && !FOLDP && !FOLDC) {
+    if constexpr (BN == 320 && NSLOT == 3 && !FOLDP) {
         static const bool dbg = getenv("WM_GEMM_DBG") != nullptr;
         static int dbg_count = 0;
         if (dbg) ++dbg_count;
-        if (!dbg || (dbg_count != 1 && dbg_count != 31)) return 0;
+        if (!dbg || (dbg_count != 1 && dbg_count % 31 != 0)) return 0;
         static unsigned* buf = nullptr;
-        const size_t bytes = 512 + (size_t)grid * 40;
-        if (!buf) HIP_TRY(hipMalloc((void**)&buf, 512 + 8192 * 40));
-        if (grid > 8192) return fail("dbg grid");
+        const int walk = a.walk > 1 ? a.walk : 1, tiles = grid * walk;
+        const size_t bytes = 512 + (size_t)tiles * 48;
+        if (!buf) HIP_TRY(hipMalloc((void**)&buf, 512 + 8192 * 48));
+        if (tiles > 8192) return fail("dbg grid");
         HIP_TRY(hipMemsetAsync(buf, 0, bytes, s));
         Gemm16Args d = a;
         d.zero_page = (const u16*)buf;
-        WM_TRY(set_max_lds((const void*)gemm16v5_kernel<T16, BN, NSLOT, true>, lds));
-        hipLaunchKernelGGL((gemm16v5_kernel<T16, BN, NSLOT, true>), dim3(grid), dim3(512), lds, s, d);
+        WM_TRY(set_max_lds((const void*)gemm16v5_kernel<T16, BN, NSLOT, true, false, FOLDC>, lds));
+        hipLaunchKernelGGL((gemm16v5_kernel<T16, BN, NSLOT, true, false, FOLDC>), dim3(grid), dim3(512), lds, s, d);
         HIP_TRY(hipStreamSynchronize(s));
         std::vector<unsigned char> hbuf(bytes);
         HIP_TRY(hipMemcpy(hbuf.data(), buf, bytes, hipMemcpyDeviceToHost));
         const unsigned* hb = (const unsigned*)hbuf.data();
-        fprintf(stderr, "[gemm16v5 dbg] M=%d N=%d K=%d  marks relative to group-0 mark 0 of step 8\n", a.M, a.N, a.K);
+        fprintf(stderr, "[gemm16v5 dbg] launch %d  M=%d N=%d K=%d act=%d out_packed=%d foldc=%d walk=%d grid=%d  marks relative to group-0 mark 0 of step 8\n",
+                dbg_count, a.M, a.N, a.K, a.act, a.out_packed, (int)FOLDC, walk, grid);
         for (int g = 0; g < 2; ++g)
             for (int st = 0; st < 10; st += 3) {
                 fprintf(stderr, "  g%d s%2d:", g, st + 8);
@@ -47,33 +61,52 @@ int dev_gemm16v5_timeline(hipStream_t s, const Gemm16Args& a, int grid, int lds)
         fprintf(stderr, "  workgroup 0 epilogue (10 ns units after loop end): ring free %u, pass0 staged %u, pass0 stores issued %u, pass1 staged %u, pass1 stores issued %u\n",
                 hb[104], hb[105], hb[106], hb[107], hb[108]);
         fprintf(stderr, "  workgroup 0 main loop: %u s_memtime counts in %.2f us -> %.0f MHz\n", hb[109], hb[110] * 0.01, hb[109] / (hb[110] * 0.01));
-        // per-workgroup wall-clock stamps (100 MHz): entry, first barrier passed, loop end, stores acknowledged
+        // per-tile wall-clock stamps (100 MHz): [0] entry (first tile of a workgroup) or hand-over barrier passed (later tiles of a walk),
+        // [1] first barrier passed, [2] loop end, [3] stores acknowledged (last tile of a workgroup, else 0), [4] CU, [5] last staging read
         const unsigned long long* r = (const unsigned long long*)(hbuf.data() + 512);
         unsigned long long t_min = ~0ull, t_max = 0;
-        for (int i = 0; i < grid; ++i) { t_min = std::min(t_min, r[i * 5]); t_max = std::max(t_max, r[i * 5 + 3]); }
-        double pro = 0, loop = 0, epi = 0;
-        for (int i = 0; i < grid; ++i) {
-            pro += (double)(r[i * 5 + 1] - r[i * 5]); loop += (double)(r[i * 5 + 2] - r[i * 5 + 1]); epi += (double)(r[i * 5 + 3] - r[i * 5 + 2]);
+        for (int i = 0; i < tiles; ++i) { t_min = std::min(t_min, r[i * 6]); t_max = std::max(t_max, std::max(r[i * 6 + 3], r[i * 6 + 5])); }
+        auto cu_key = [&](int i) { const unsigned long long v = r[i * 6 + 4]; return (v >> 32 << 16) | ((v >> 8) & 0xff) | (((v >> 13) & 7) << 8); };
+        std::vector<int> ids(tiles);
+        for (int i = 0; i < tiles; ++i) ids[i] = i;
+        std::sort(ids.begin(), ids.end(), [&](int x, int y) { return cu_key(x) != cu_key(y) ? cu_key(x) < cu_key(y) : r[x * 6] < r[y * 6]; });
+        // the boundaries between successive tiles of one CU.  Between workgroups: hand-over = the next one's entry - the last one's stores
+        // acknowledged, fill = entry -> first barrier.  Inside a walk: hand-over = last staging read -> hand-over barrier passed, fill = from
+        // there to the first barrier (it includes the drain of the stores, which nothing waits for separately).
+        std::vector<double> ho_wg, fill_wg, fill_later, ho_in, fill_in, loop, epi, drain, period, gap_wg, gap_in;
+        for (int k = 0; k < tiles; ++k) {
+            const int i = ids[k];
+            const bool first = i % walk == 0, last = i % walk == walk - 1;
+            (first ? fill_wg : fill_in).push_back((double)(r[i * 6 + 1] - r[i * 6]) * 0.01);
+            loop.push_back((double)(r[i * 6 + 2] - r[i * 6 + 1]) * 0.01);
+            epi.push_back((double)(r[i * 6 + 5] - r[i * 6 + 2]) * 0.01);
+            if (last) drain.push_back((double)(r[i * 6 + 3] - r[i * 6 + 5]) * 0.01);
+            if (k == 0 || cu_key(ids[k - 1]) != cu_key(i)) continue;
+            const int j = ids[k - 1];
+            period.push_back((double)(r[i * 6 + 1] - r[j * 6 + 1]) * 0.01);
+            if (first) {
+                ho_wg.push_back(((double)r[i * 6] - (double)r[j * 6 + 3]) * 0.01);
+                gap_wg.push_back(((double)r[i * 6 + 1] - (double)r[j * 6 + 5]) * 0.01);
+                fill_later.push_back((double)(r[i * 6 + 1] - r[i * 6]) * 0.01);
+            } else {
+                ho_in.push_back(((double)r[i * 6] - (double)r[j * 6 + 5]) * 0.01);
+                gap_in.push_back(((double)r[i * 6 + 1] - (double)r[j * 6 + 5]) * 0.01);
+            }
         }
-        fprintf(stderr, "  span %.2f us; per workgroup avg: prologue %.2f us, loop %.2f us, epilogue %.2f us\n", (t_max - t_min) * 0.01,
-                pro / grid * 0.01, loop / grid * 0.01, epi / grid * 0.01);
-        // timeline of the workgroups that ran on the CU of workgroup 0 (same XCC + HW_ID CU/SE bits)
-        auto cu_key = [&](int i) { const unsigned long long v = r[i * 5 + 4]; return (v >> 32 << 16) | ((v >> 8) & 0xff) | (((v >> 13) & 7) << 8); };
-        for (int probe : {0, 1}) {
-            fprintf(stderr, "  workgroups sharing the CU of workgroup %d (entry, barrier0, loop end, done; us from first entry):\n", probe);
-            std::vector<int> ids;
-            for (int i = 0; i < grid; ++i) if (cu_key(i) == cu_key(probe)) ids.push_back(i);
-            std::sort(ids.begin(), ids.end(), [&](int x, int y) { return r[x * 5] < r[y * 5]; });
-            for (int i : ids)
-                fprintf(stderr, "    wg %4d: %7.2f %7.2f %7.2f %7.2f\n", i, (r[i * 5] - t_min) * 0.01, (r[i * 5 + 1] - t_min) * 0.01,
-                        (r[i * 5 + 2] - t_min) * 0.01, (r[i * 5 + 3] - t_min) * 0.01);
+        fprintf(stderr, "  span %.2f us, %d tiles on %d workgroups; medians per tile [us]: loop %.2f, loop end -> last staging read %.2f, last staging read -> stores acknowledged %.2f (n=%zu), first barrier -> next tile's first barrier on the CU %.2f\n",
+                (t_max - t_min) * 0.01, tiles, grid, dev_median(loop), dev_median(epi), dev_median(drain), drain.size(), dev_median(period));
+        fprintf(stderr, "  boundary between workgroups (n=%zu): hand-over (stores acknowledged -> next entry) %.2f, fill (entry -> first barrier) %.2f [all first tiles: %.2f], last staging read -> next first barrier %.2f\n",
+                ho_wg.size(), dev_median(ho_wg), dev_median(fill_later), dev_median(fill_wg), dev_median(gap_wg));
+        fprintf(stderr, "  boundary inside a walk (n=%zu): hand-over (last staging read -> barrier passed) %.2f, fill and store drain (-> first barrier) %.2f, last staging read -> next first barrier %.2f\n",
+                ho_in.size(), dev_median(ho_in), dev_median(fill_in), dev_median(gap_in));
+        // timeline of the tiles that ran on the CU of tile 0
+        fprintf(stderr, "  tiles on the CU of workgroup 0 (entry, barrier0, loop end, last staging read, stores acknowledged; us from first entry):\n");
+        for (int k = 0; k < tiles; ++k) {
+            const int i = ids[k];
+            if (cu_key(i) != cu_key(0)) continue;
+            fprintf(stderr, "    wg %4d tile %d: %7.2f %7.2f %7.2f %7.2f %7.2f\n", i / walk, i % walk, (r[i * 6] - t_min) * 0.01, (r[i * 6 + 1] - t_min) * 0.01,
+                    (r[i * 6 + 2] - t_min) * 0.01, (r[i * 6 + 5] - t_min) * 0.01, r[i * 6 + 3] ? (r[i * 6 + 3] - t_min) * 0.01 : 0.0);
         }
-        // distribution of entry times
-        std::vector<double> ent(grid), fin(grid);
-        for (int i = 0; i < grid; ++i) { ent[i] = (r[i * 5] - t_min) * 0.01; fin[i] = (r[i * 5 + 3] - t_min) * 0.01; }
-        std::sort(ent.begin(), ent.end()); std::sort(fin.begin(), fin.end());
-        fprintf(stderr, "  entry times: min %.2f p25 %.2f p50 %.2f p75 %.2f max %.2f; done: min %.2f p50 %.2f max %.2f\n", ent[0], ent[grid / 4], ent[grid / 2],
-                ent[3 * grid / 4], ent[grid - 1], fin[0], fin[grid / 2], fin[grid - 1]);
         return 1;
     }
     return 0;

@@ -43,6 +43,20 @@ int launch_gemm16v2_t(wm_handle* h, hipStream_t s, const Gemm16Args& a) {
 
 // The 256-row-tile kernel (gemm16_v5.h); FOLDP / FOLDC / SPLIT / NSLOT are the kernel's own flags: the folded LayerNorm's producer
 // (statistics out; SPLIT: the stream as two 16-bit planes) and consumer (normalisation in the epilogue), ring slots.
+// Column tiles per workgroup of the folded-LayerNorm consumer (gemm16_v5.h "Column walk"), by the launch's column tiles: the T that
+// measured fastest at the block shapes (profiles/gemm_walk/kernel_ab.txt; qkv has 12 column tiles of 320, lin1 16).
+static int gemm16_walk_table(int tilesN) { return tilesN == 12 ? 3 : tilesN == 16 ? 4 : 1; }
+// What a launch walks.  `asked` > 0 (the op-level entry) is taken as it is, 0 asks the table, and the table's T holds only while the
+// walking grid is still at least two rounds of 256 workgroups (8 ViT-H tiles per call; measured at 16 = four rounds): a smaller call
+// keeps one tile per workgroup, so that no CU goes idle, and the launch plans recorded for 1 to 4 tiles per call
+// (tests/encoder_cases.py) stay what they are.  Any T that does not divide tilesN / 4 (walk_tile_origin) falls back to 1.
+static int gemm16_walk_for(int tilesM, int tilesN, int asked) {
+    int t = asked > 0 ? asked : gemm16_walk_table(tilesN);
+    if (asked <= 0 && t > 1 && (long)tilesM * tilesN / t < 2 * 256) t = 1;
+    if (t > 1 && (tilesN % 4 || (tilesN / 4) % t)) t = 1;
+    return t;
+}
+
 template <class T16, int BN, bool FOLDP, bool FOLDC, bool SPLIT, int NSLOT = 3>
 int launch_gemm16v5_t(wm_handle* h, hipStream_t s, const Gemm16Args& a_in) {
     using G = G3<BN>;
@@ -53,11 +67,14 @@ int launch_gemm16v5_t(wm_handle* h, hipStream_t s, const Gemm16Args& a_in) {
     count_variant(SPLIT   ? (BN == 320 ? WM_GEMM_V5_320_SPLIT : WM_GEMM_V5_256_SPLIT)
                   : FOLDP ? (BN == 320 ? WM_GEMM_V5_320_FOLDP : WM_GEMM_V5_256_FOLDP)
                   : BN == 320 ? (a_in.residual ? WM_GEMM_V5_320_RES : WM_GEMM_V5_320) : (a_in.residual ? WM_GEMM_V5_256_RES : WM_GEMM_V5_256));
-    const int grid = (a_in.M / 256) * (a_in.N / BN);
     Gemm16Args a = a_in;
 #if WM_DEV_TIMELINE
     dev_group_m(a);
+    if (FOLDC) dev_walk(a);
 #endif
+    a.walk = FOLDC ? gemm16_walk_for(a.M / 256, a.N / BN, a.walk) : 1;
+    if (a.walk > 1) count_variant(BN == 320 ? WM_GEMM_V5_320_WALK : WM_GEMM_V5_256_WALK);       // a walking consumer: under its own name too
+    const int grid = (a.M / 256) * (a.N / BN) / a.walk;
     // a producer's bytes: operands + the stream in and out (split: 2 + 2 B in, 2 + 2 B out; fp32: 4 in, 4 + 2 out, or 2 + 2 out with a lo plane)
     const double stream_bytes = SPLIT ? 8.0 : 4.0 + (a.out32 ? 4.0 : 0.0) + 2.0 + (a.out_lo ? 2.0 : 0.0);
     Bracket br(h, s, WM_KCLASS_GEMM16, gemm16_flops(a),
@@ -80,8 +97,11 @@ static double round_eff(long tiles, long slots) { return (double)tiles / (double
 // The staggered 256 x 320 / 256 x 256 kernel (gemm16_v5.h) serves the shape: the only kernel that reads operands in
 // LDS-image order and writes its 16-bit output in it.  Few tiles (one or two image tiles per call): the half-width
 // 256 x 160 / 128 kernel fills more CUs; cost model from tools/gemm_bench.py --batch 1: rounds of 256 workgroups x (1.0 | 0.6) per tile.
+static bool gemm16_v5_serves(int M, int N, int K) {          // what the kernel can run at all
+    return M > 0 && M % 256 == 0 && K > 0 && K % 32 == 0 && K / 32 >= 2 && N > 0 && (N % 320 == 0 || N % 256 == 0);
+}
 static bool gemm16_takes_v5(int M, int N, int K) {
-    if (M <= 0 || M % 256 || K % G16_BK || K / 32 < 2) return false;
+    if (!gemm16_v5_serves(M, N, K) || K % G16_BK) return false;
     auto prefer_half = [&](int bn) {
         const long t = (long)(M / 256) * (N / bn);
         return (double)((2 * t + 255) / 256) * 0.6 < (double)((t + 255) / 256);
@@ -95,7 +115,8 @@ static bool gemm16_takes_v5(int M, int N, int K) {
 //   Wp: the weight in LDS-image order (or null); a_packed / out_packed: A is / the 16-bit output shall be in that order;
 //   st_stats: folded-LayerNorm PRODUCER (fp32 + residual form): per-row partial statistics out, out16 = 16-bit copy of the
 //             rows in LDS-image order;
-//   fold_stats / fold_c1 / fold_eps: folded-LayerNorm CONSUMER (16-bit-only form): A = such a copy, W = gamma (.) W, bias = c2.
+//   fold_stats / fold_c1 / fold_eps: folded-LayerNorm CONSUMER (16-bit-only form): A = such a copy, W = gamma (.) W, bias = c2;
+//             walk: its column tiles per workgroup (0 = the launcher's choice).
 //   res_hi / res_lo / out_lo: split stream (gemm16_v5.h "Split stream"): with st_stats, the residual as two 16-bit planes in
 //             (res_hi, res_lo; no fp32 residual) and out (out16 = hi, out_lo); out_lo alone: the fp32-residual producer also
 //             writes the lo plane (and no fp32 output when out32 is null).
@@ -110,6 +131,7 @@ struct GemmExtra {
     const void* res_lo = nullptr;
     void* out_lo = nullptr;
     int* overflow = nullptr;
+    int walk = 0;          // consumer: column tiles per workgroup, 0 = the launcher's table (gemm16_walk_for)
 };
 static GemmExtra GX(const void* Wp, int a_packed = 0, int out_packed = 0) {
     GemmExtra x;
@@ -122,13 +144,15 @@ int launch_gemm16(wm_handle* h, hipStream_t s, int prec, const void* A, const vo
                   const GemmExtra& x = GemmExtra{}) {
     const void* Wp = x.Wp;
     const int a_packed = x.a_packed, out_packed = x.out_packed;
-    if (M <= 0 || N <= 0 || K <= 0 || M % G16_BM || N % G16_BN || K % G16_BK)
+    // a caller that names the consumer's walk (the op-level entry) has chosen the 256-row-tile kernel, whose K-step is 32
+    const bool v5_asked = x.walk > 0 && x.fold_stats && gemm16_v5_serves(M, N, K);
+    if (!v5_asked && (M <= 0 || N <= 0 || K <= 0 || M % G16_BM || N % G16_BN || K % G16_BK))
         return fail("gemm16: shape M=%d N=%d K=%d must be multiples of %d/%d/%d", M, N, K, G16_BM, G16_BN, G16_BK);
     if (!out32 && !out16) return fail("gemm16: no output");
     Gemm16Args a{};
     a.A = (const u16*)A; a.W = (const u16*)W; a.bias = bias; a.residual = res; a.out32 = out32; a.out16 = (u16*)out16;
     a.M = M; a.N = N; a.K = K; a.res_mod = res_mod; a.act = act;
-    if (gemm16_takes_v5(M, N, K)) {         // staggered wave groups (gemm16_v5.h)
+    if (gemm16_takes_v5(M, N, K) || v5_asked) {         // staggered wave groups (gemm16_v5.h)
         if (Wp) { a.W = (const u16*)Wp; a.w_packed = 1; }
         a.a_packed = a_packed;
         a.out_packed = out_packed;
@@ -144,10 +168,11 @@ int launch_gemm16(wm_handle* h, hipStream_t s, int prec, const void* A, const vo
             return split ? launch_gemm16v5<true, false, true>(h, s, prec, a) : launch_gemm16v5<true, false, false>(h, s, prec, a);
         }
         if (x.fold_stats) {                 // folded LayerNorm, consumer
-            const int bn = fold_bn_for(K);
-            if (out32 || res || !out16 || !x.fold_c1 || !bias || (act != ACT_NONE && act != ACT_GELU) || K % bn || K / bn > 4)
-                return fail("gemm16: the folded-LayerNorm form is 16-bit-only output, act none | GELU, K a multiple of %d with at most 4 tiles", bn);
+            const int bn = K < 256 ? K : fold_bn_for(K);        // (a K shorter than a statistics tile is one tile: op-level tests of short K loops)
+            if (out32 || res || !out16 || !x.fold_c1 || !bias || (act != ACT_NONE && act != ACT_GELU) || K % bn || K / bn > 4 || !Wp || !a_packed)
+                return fail("gemm16: the folded-LayerNorm form is 16-bit-only output, act none | GELU, operands in LDS-image order, K a multiple of %d with at most 4 tiles", bn);
             a.fold_stats = x.fold_stats; a.fold_c1 = x.fold_c1; a.fold_ntile = K / bn; a.fold_bn = (float)bn; a.fold_eps = x.fold_eps;
+            a.walk = x.walk;
             return launch_gemm16v5<false, true, false>(h, s, prec, a);
         }
         return launch_gemm16v5<false, false, false>(h, s, prec, a);

@@ -444,15 +444,21 @@ extern "C" int wm_op_fold_weight16(const void* w16_dev, const float* gamma_dev, 
     return launch_fold_weight((hipStream_t)stream, precision, w16_dev, nullptr, gamma_dev, beta_dev, bias_dev, wf_dev, c1_dev, c2_dev, N, K);
 }
 
-extern "C" int wm_op_gemm16_folded(const void* x16_dev, const void* wf_dev, const float* c1_dev, const float* c2_dev, const float* stats_dev,
-                                   float eps, void* out_16_dev, int M, int N, int K, int act, int precision, void* stream) {
+extern "C" int wm_op_gemm16_folded_walk(const void* x16_dev, const void* wf_dev, const float* c1_dev, const float* c2_dev, const float* stats_dev,
+                                        float eps, void* out_16_dev, int M, int N, int K, int act, int walk, int precision, void* stream) {
     if (!x16_dev || !wf_dev || !c1_dev || !c2_dev || !stats_dev || !out_16_dev) return fail("wm_op_gemm16_folded: null buffer");
+    if (walk < 0 || walk > 8) return fail("wm_op_gemm16_folded_walk: walk = %d (0 = the launcher's choice, 1..8 column tiles per workgroup)", walk);
     const int out_packed = (act & WM_GEMM_OUT_PACKED) != 0;
     act &= ~WM_GEMM_OUT_PACKED;
-    if (!gemm16_takes_v5(M, N, K)) return fail("wm_op_gemm16_folded: M=%d N=%d K=%d is not served by the 256-row-tile kernel", M, N, K);
+    if (!(walk > 0 ? gemm16_v5_serves(M, N, K) : gemm16_takes_v5(M, N, K)))
+        return fail("wm_op_gemm16_folded: M=%d N=%d K=%d is not served by the 256-row-tile kernel", M, N, K);
     GemmExtra x = GX(wf_dev, 1, out_packed);
-    x.fold_stats = stats_dev; x.fold_c1 = c1_dev; x.fold_eps = eps;
+    x.fold_stats = stats_dev; x.fold_c1 = c1_dev; x.fold_eps = eps; x.walk = walk;
     return launch_gemm16(nullptr, (hipStream_t)stream, precision, x16_dev, nullptr, c2_dev, nullptr, 0, nullptr, out_16_dev, M, N, K, act, x);
+}
+extern "C" int wm_op_gemm16_folded(const void* x16_dev, const void* wf_dev, const float* c1_dev, const float* c2_dev, const float* stats_dev,
+                                   float eps, void* out_16_dev, int M, int N, int K, int act, int precision, void* stream) {
+    return wm_op_gemm16_folded_walk(x16_dev, wf_dev, c1_dev, c2_dev, stats_dev, eps, out_16_dev, M, N, K, act, 0, precision, stream);
 }
 
 extern "C" int wm_op_gemm16_stats(const void* a_dev, const void* w_dev, const float* bias_dev, const float* residual_dev, float* out_f32_dev,
