@@ -53,6 +53,8 @@ extern "C" {
  *    calibration, so the affine georeference holds for it); the number stays 13 for the same reason.
  *    13, also additive: wm_rectify_u8 (survey attitude: a tilted frame resampled to the picture of a level camera, by its
  *    roll and pitch and its calibration in one gather); the number stays 13 for the same reason.
+ *    13, also additive: wm_ortho_u8 (survey terrain: a frame resampled onto a ground grid over a height grid, by its pose, the
+ *    terrain's height and its calibration in one gather); the number stays 13 for the same reason.
  * 12: wm_box_outline_rect, wm_draw_boxes_u8, wm_plot_image_u8, WM_DRAW_MAX_WIDTH, WM_DRAW_MAX_PALETTE, WM_PLOT_SCRATCH_BYTES
  *    (survey overlays: detections outlined on frames and tiles, on the GPU); nothing else changed.
  * 11: wm_chip_window, wm_crop_chips_u8, WM_CHIP_MAX_SIDE (survey review chips: one PIL-exact crop per detection, cut on
@@ -738,6 +740,57 @@ int wm_undistort_u8(const uint8_t* in_dev, int height, int width, const double c
 int wm_rectify_u8(const uint8_t* in_dev, int height, int width, const double camera[9], const double rot[9], uint8_t* out_dev,
                   int out_height, int out_width, double f_out, int mode, const uint8_t fill_rgb[3],
                   int64_t* stats_dev /* [1], may be NULL */, void* stream);
+
+/* Survey terrain (terrain.terrain_grid, terrain.camera_pose, terrain.ortho_plan, preprocess.ortho_u8, tiling.orthorectified): a
+ * frame resampled ONCE onto a ground grid, each output pixel's height taken from a digital elevation model (DEM): the
+ * orthophoto, whose affine georeference is exact whatever the relief.  "Survey attitude" takes the ground for the plane of
+ * tiling.nadir_affine; a point z metres above that plane, d from the nadir point of a level camera H above it, is seen at
+ * d * H / (H - z).  Lens, attitude, yaw, position and relief go into one gather, so the frame is neither blurred nor paid for
+ * twice.  No reference behaviour exists; this rule is the contract, and tests/terrain_cases.py restates it sequentially
+ * (terrain_oracle).  All arithmetic is IEEE double, every operation correctly rounded on its own (no contraction), in the
+ * order and with the parentheses written.
+ * DEM: dem_dev [dem_height][dem_width] float32 (dem_h, dem_w below), north-up: row 0 is the northernmost.  Heights are at cell
+ * CENTRES (GeoTIFF's "pixel is area").  dem_geo[3] = (e0, n0, dcell): east and north of the grid's top-left CORNER, and the
+ * post spacing in metres, so post [r][c] stands at (e0 + (c + 0.5) dcell, n0 - (r + 0.5) dcell).  Each float32 height is
+ * converted to double exactly.
+ * Pose: pose[12] = Ce, Cn, Cu, m0..m8.  (Ce, Cn, Cu) is the camera's position: east, north, and height in the DEM's own
+ * vertical datum.  M = m0..m8, row-major, maps a world vector (east, north, up) into the camera frame of "Survey attitude": x
+ * to the picture's right, y down the picture, z along the optical axis.  For a level camera whose picture-up heading is psi
+ * clockwise from north, M = L(psi) = [[c, -s, 0], [-s, -c, 0], [0, 0, -1]] with c = cos psi, s = sin psi (the rows are
+ * tiling.nadir_affine's (a0, a1) and (a3, a4) over the ground sampling distance; the determinant is +1).  With roll and pitch,
+ * M = rot L(psi), rot being "Survey attitude"'s.  The kernel does not require M to be orthonormal.
+ * Output: out_height x out_width pixels (oh, ow), and out_geo[6] = g0..g5, its pixel-to-ground affine exactly as wm_census
+ * takes one.  For the output pixel of row j and column i, with px = (double)i + 0.5 and py = (double)j + 0.5:
+ *     E  = (g0 * px + g1 * py) + g2                                N  = (g3 * px + g4 * py) + g5
+ *     a  = (E - e0) / dcell - 0.5                                  b  = (n0 - N) / dcell - 0.5
+ * The pixel HAS A HEIGHT iff 0 <= a && a <= dem_w - 1 && 0 <= b && b <= dem_h - 1 (a NaN has none).  Then
+ *     ia = min((int)floor(a), dem_w - 2)                           ib = min((int)floor(b), dem_h - 2)
+ *     ta = a - (double)ia                                          tb = b - (double)ib
+ *     z  = (z00 * (1.0 - ta) + z01 * ta) * (1.0 - tb) + (z10 * (1.0 - ta) + z11 * ta) * tb
+ *            with z00 = dem[ib][ia], z01 = dem[ib][ia + 1], z10 = dem[ib + 1][ia], z11 = dem[ib + 1][ia + 1]
+ *     dE = E - Ce                   dN = N - Cn                    dU = z - Cu
+ *     X  = (m0 * dE + m1 * dN) + m2 * dU
+ *     Y  = (m3 * dE + m4 * dN) + m5 * dU
+ *     Z  = (m6 * dE + m7 * dN) + m8 * dU
+ * The pixel is OUTSIDE unless it has a height and Z > 0 (a NaN is outside: a post that is not finite -- nodata -- leaves no
+ * finite (u, v) below); otherwise
+ *     xn = X / Z                                                   yn = Y / Z
+ * and (xn, yn) goes through exactly the expressions of "Survey lens" in place of its (x, y): its r2, rad, xd, yd, u, v.  The
+ * source pixel is INSIDE iff it has a height && Z > 0 && 0 <= u < width && 0 <= v < height; inside, the three bytes are
+ * "Survey mosaic"'s nearest or bilinear sample at (u, v); outside, the fill colour.  Every output byte is written by every
+ * call.  Occlusion is NOT tested: a cell hidden behind a ridge shows the ridge's pixel (no true-ortho visibility).
+ * wm_ortho_u8: in_dev [height][width][3] uint8 -> out_dev [out_height][out_width][3] uint8; camera, pose, dem_geo, out_geo
+ * and fill_rgb are read on the host during the call, dem_dev on the device; mode is WM_MOSAIC_NEAREST or WM_MOSAIC_BILINEAR.
+ * stats_dev, unless NULL, is two int64: [0] the number of output pixels that got the fill colour, [1] how many of those had
+ * no height or a height that is not finite -- the diagnostic for a DEM that is too small (both zeroed on `stream` first, then
+ * at most one 64-bit atomic each per workgroup).  One launch, a gather: plain loads and stores, no atomics on the picture,
+ * nothing allocated, asynchronous on `stream`.  Limits and checks: wm_rectify_u8's on the frame, the camera, the picture's
+ * sides, mode, fill, stats_dev's alignment and the disjoint ranges of in_dev and out_dev; every pose, dem_geo and out_geo entry
+ * finite; dcell > 0; dem_height and dem_width in 2..32768; dem_dev 4-byte aligned, its range disjoint from out_dev's.  Bad
+ * arguments fail before any HIP call with a message that names the argument. */
+int wm_ortho_u8(const uint8_t* in_dev, int height, int width, const double camera[9], const double pose[12], const float* dem_dev,
+                int dem_height, int dem_width, const double dem_geo[3], uint8_t* out_dev, int out_height, int out_width,
+                const double out_geo[6], int mode, const uint8_t fill_rgb[3], int64_t* stats_dev /* [2], may be NULL */, void* stream);
 
 /* Survey review chips (tiling.detect_frames(chips=...), tiling.crop_chips): one chip x chip uint8 crop per detection, each
  * with a window and a scale of its own, in one launch.

@@ -90,6 +90,8 @@ SYMBOLS = {
     "wm_scaled_size": (_I, [_I, _I, C.c_double, C.POINTER(_I), C.POINTER(_I)]),
     "wm_undistort_u8": (_I, [_P, _I, _I, C.POINTER(C.c_double), _P, _I, _I, C.c_double, _I, C.POINTER(C.c_uint8), _P, _P]),
     "wm_rectify_u8": (_I, [_P, _I, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _I, _I, C.c_double, _I, C.POINTER(C.c_uint8), _P, _P]),
+    "wm_ortho_u8": (_I, [_P, _I, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _I, _I, C.POINTER(C.c_double), _P, _I, _I,
+                         C.POINTER(C.c_double), _I, C.POINTER(C.c_uint8), _P, _P]),
     "wm_chip_window": (_I, [C.POINTER(_F), _F, _I, _I, C.POINTER(C.c_int32)]),
     "wm_crop_chips_u8": (_I, [_P, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P]),
     "wm_box_outline_rect": (_I, [C.POINTER(_F), C.POINTER(C.c_int32)]),

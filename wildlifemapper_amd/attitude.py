@@ -21,9 +21,10 @@ third column of A, the optical axis in level coordinates, is (-sin p, -sin t cos
     one plan per frame.
 The geometry is numpy float64 on the host, in the rule's own expressions; only the pixels are touched on the device.
 
-Not here: truly oblique cameras (a rotation is refused beyond max_tilt_deg, 30 by default), terrain relief (the ground is
-the plane of nadir_affine), estimating the attitude from the survey's own overlaps, and a lever arm or boresight
-misalignment between the log's attitude and the camera (pass the corrected 3 x 3 rotation instead)."""
+Not here: truly oblique cameras (a rotation is refused beyond max_tilt_deg, 30 by default), estimating the attitude from the
+survey's own overlaps, and a lever arm or boresight misalignment between the log's attitude and the camera (pass the corrected
+3 x 3 rotation instead).  The ground is the plane of nadir_affine: over terrain relief use terrain.py instead (ortho_plan,
+orthorectified), which takes the same rotation and applies it, the lens model and a height grid in one resampling."""
 from __future__ import annotations
 
 import math

@@ -6,6 +6,7 @@
 
 #include "resample_kernels.h"
 #include "attitude_kernels.h"
+#include "terrain_kernels.h"
 #include "lens_kernels.h"
 #include "host_core.h"
 
@@ -35,6 +36,7 @@ void resize_coeffs(int in_size, int out_size, std::vector<int>& bounds, std::vec
 
 // ---- what both callers share: the plan slots of a stream, its intermediate image, the horizontal launch ----
 constexpr int RESAMPLE_MAX_SIDE = 65536;       // the merge's fp32 frame coordinates keep sub-0.01 px resolution up to here
+constexpr int TERRAIN_MAX_SIDE = 32768;        // posts a side of wm_ortho_u8's DEM: a post index and a row of posts fit an int
 constexpr int RESAMPLE_PLAN_SLOTS = 8;         // coefficient tables cached per (device, stream), least recently used evicted
 
 // how the horizontal pass of one geometry runs (resample_h_geometry)
@@ -299,6 +301,48 @@ int launch_rectify(const uint8_t* in_dev, int height, int width, const double* c
                            (unsigned long long*)stats_dev);
     };
     mode == WM_MOSAIC_NEAREST ? launch(attitude_rectify_kernel<WM_MOSAIC_NEAREST>) : launch(attitude_rectify_kernel<WM_MOSAIC_BILINEAR>);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- survey terrain: a frame -> its orthophoto over a height grid (include/wm_hip.h "Survey terrain") ----
+// The frame, camera, picture, mode, fill, alignment and overlap checks are check_lens_args' (an orthophoto has no f_out of its
+// own: the output grid is out_geo); then pose, the DEM and out_geo.  One memset of the optional counts and one launch.
+int launch_ortho(const uint8_t* in_dev, int height, int width, const double* camera, const double* pose, const float* dem_dev, int dem_height,
+                 int dem_width, const double* dem_geo, uint8_t* out_dev, int out_height, int out_width, const double* out_geo, int mode,
+                 const uint8_t* fill_rgb, int64_t* stats_dev, hipStream_t s) {
+    const char* name = "wm_ortho_u8";
+    WM_TRY(check_lens_args(name, in_dev, height, width, camera, nullptr, false, out_dev, out_height, out_width, 1.0, mode, fill_rgb, stats_dev));
+    if (!pose) return fail("%s: null pose", name);
+    if (!dem_dev) return fail("%s: null dem_dev", name);
+    if (!dem_geo) return fail("%s: null dem_geo", name);
+    if (!out_geo) return fail("%s: null out_geo", name);
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(pose[k])) return fail("%s: pose[%d] %g is not finite", name, k, pose[k]);
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(dem_geo[k])) return fail("%s: dem_geo[%d] %g is not finite", name, k, dem_geo[k]);
+    for (int k = 0; k < 6; ++k)
+        if (!std::isfinite(out_geo[k])) return fail("%s: out_geo[%d] %g is not finite", name, k, out_geo[k]);
+    if (!(dem_geo[2] > 0.0)) return fail("%s: dem_geo[2] (dcell) %g: need a post spacing > 0", name, dem_geo[2]);
+    if (dem_height < 2 || dem_height > TERRAIN_MAX_SIDE || dem_width < 2 || dem_width > TERRAIN_MAX_SIDE)
+        return fail("%s: dem_height %d, dem_width %d: the DEM's sides must be in 2..%d", name, dem_height, dem_width, TERRAIN_MAX_SIDE);
+    if ((uintptr_t)dem_dev % 4) return fail("%s: dem_dev not 4-byte aligned", name);
+    const uintptr_t dem0 = (uintptr_t)dem_dev, dem1 = dem0 + (size_t)dem_height * dem_width * sizeof(float), out0 = (uintptr_t)out_dev,
+                    out1 = out0 + (size_t)out_height * out_width * 3;
+    if (dem0 < out1 && out0 < dem1) return fail("%s: dem_dev and out_dev overlap", name);
+    if (stats_dev) HIP_TRY(hipMemsetAsync(stats_dev, 0, 2 * sizeof(int64_t), s));
+    const frame_desc in{in_dev, height, width};
+    const lens_camera cam{camera[0], camera[1], camera[2], camera[3], camera[4], camera[5], camera[6], camera[7], camera[8]};
+    const terrain_pose ps{pose[0], pose[1], pose[2], pose[3], pose[4], pose[5], pose[6], pose[7], pose[8], pose[9], pose[10], pose[11]};
+    const terrain_dem dem{dem_dev, dem_height, dem_width, dem_geo[0], dem_geo[1], dem_geo[2]};
+    const terrain_geo geo{out_geo[0], out_geo[1], out_geo[2], out_geo[3], out_geo[4], out_geo[5]};
+    const unsigned int fill = (unsigned int)fill_rgb[0] | (unsigned int)fill_rgb[1] << 8 | (unsigned int)fill_rgb[2] << 16;
+    const dim3 grid((out_width + COV_BLOCK_X - 1) / COV_BLOCK_X, (out_height + MOS_FILL_BLOCK_Y - 1) / MOS_FILL_BLOCK_Y);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(COV_THREADS), 0, s, in, cam, ps, dem, geo, out_height, out_width, fill, out_dev,
+                           (unsigned long long*)stats_dev);
+    };
+    mode == WM_MOSAIC_NEAREST ? launch(terrain_ortho_kernel<WM_MOSAIC_NEAREST>) : launch(terrain_ortho_kernel<WM_MOSAIC_BILINEAR>);
     HIP_TRY(hipGetLastError());
     return 0;
 }

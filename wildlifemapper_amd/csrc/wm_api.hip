@@ -223,6 +223,13 @@ extern "C" int wm_rectify_u8(const uint8_t* in_dev, int height, int width, const
                           (hipStream_t)stream);
 }
 
+extern "C" int wm_ortho_u8(const uint8_t* in_dev, int height, int width, const double camera[9], const double pose[12], const float* dem_dev,
+                           int dem_height, int dem_width, const double dem_geo[3], uint8_t* out_dev, int out_height, int out_width,
+                           const double out_geo[6], int mode, const uint8_t fill_rgb[3], int64_t* stats_dev, void* stream) {
+    return launch_ortho(in_dev, height, width, camera, pose, dem_dev, dem_height, dem_width, dem_geo, out_dev, out_height, out_width, out_geo,
+                        mode, fill_rgb, stats_dev, (hipStream_t)stream);
+}
+
 extern "C" int wm_chip_window(const float box[4], float context, int min_side, int max_side, int32_t out[3]) {
     if (!box || !out) return fail("wm_chip_window: null argument");
     WM_TRY(check_chip_rule("wm_chip_window", context, min_side, max_side));

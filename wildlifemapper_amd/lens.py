@@ -16,8 +16,9 @@ principal point at its geometric centre, so nadir_affine(oh, ow, centre, gsd, ya
 The geometry is numpy float64 on the host, in the rule's own expression; only the pixels are touched on the device.
 
 Not here: estimating the coefficients from the survey's own overlaps, vignetting, fisheye and rational (k4..k6) models.
-The roll and pitch of near-nadir flight are attitude.py's, which applies them and this model in one resampling; truly oblique
-cameras and terrain relief are covered by neither."""
+The roll and pitch of near-nadir flight are attitude.py's, which applies them and this model in one resampling; terrain relief
+is terrain.py's (ortho_plan, orthorectified), which applies all three over a height grid in one resampling; truly oblique
+cameras are covered by none of them."""
 from __future__ import annotations
 
 from typing import Dict

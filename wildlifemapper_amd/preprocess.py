@@ -42,6 +42,15 @@ def _check_undistort_args(sample, fill, what: str):
     return MOSAIC_SAMPLES[sample], _check_fill(fill, what)
 
 
+def _check_plan_frame(frame, pl, what: str) -> None:
+    """The frame of undistort_u8, rectify_u8 and ortho_u8: an (H,W,3) uint8 ROCm tensor of the plan's size."""
+    if not isinstance(frame, torch.Tensor) or not frame.is_cuda or frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[-1] != 3:
+        got = f"{tuple(frame.shape)} {frame.dtype} on {frame.device}" if isinstance(frame, torch.Tensor) else type(frame).__name__
+        raise RuntimeError(f"{what}: expected an (H,W,3) uint8 ROCm tensor, got {got}")
+    if tuple(frame.shape[:2]) != tuple(pl["size"]):
+        raise ValueError(f"{what}: frame is {tuple(frame.shape[:2])}, the plan was made for {tuple(pl['size'])}")
+
+
 def undistort_u8(frame: torch.Tensor, plan, sample: str = "bilinear", fill=(0, 0, 0), count: bool = False):
     """frame (H,W,3) uint8 on a ROCm device -> its pinhole picture (oh,ow,3) uint8 on the same device, by the dict
     lens.lens_plan() returned (wm_undistort_u8; rule: include/wm_hip.h "Survey lens").  sample: 'bilinear' (pixel centres at
@@ -69,11 +78,7 @@ def _resample_by_plan(frame, pl, rotation, sample, fill, count: bool, what: str)
     """undistort_u8 (rotation None) and rectify_u8 on a validated plan."""
     import ctypes as C
     mode, fill_a = _check_undistort_args(sample, fill, what)
-    if not isinstance(frame, torch.Tensor) or not frame.is_cuda or frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[-1] != 3:
-        got = f"{tuple(frame.shape)} {frame.dtype} on {frame.device}" if isinstance(frame, torch.Tensor) else type(frame).__name__
-        raise RuntimeError(f"{what}: expected an (H,W,3) uint8 ROCm tensor, got {got}")
-    if tuple(frame.shape[:2]) != tuple(pl["size"]):
-        raise ValueError(f"{what}: frame is {tuple(frame.shape[:2])}, the plan was made for {tuple(pl['size'])}")
+    _check_plan_frame(frame, pl, what)
     (h, w), (oh, ow) = pl["size"], pl["out_size"]
     frame = frame.contiguous()
     cam = (C.c_double * 9)(*[float(v) for v in pl["camera"]])
@@ -88,6 +93,36 @@ def _resample_by_plan(frame, pl, rotation, sample, fill, count: bool, what: str)
             rot = (C.c_double * 9)(*[float(v) for v in rotation.reshape(9)])
             N.check(N.lib().wm_rectify_u8(N.ptr(frame), h, w, cam, rot, *tail))
     return (out, filled) if count else out
+
+
+def ortho_u8(frame: torch.Tensor, plan, dem, sample: str = "bilinear", fill=(0, 0, 0), count: bool = False):
+    """frame (H,W,3) uint8 on a ROCm device -> its orthophoto (oh,ow,3) uint8 on the same device, by the dict
+    terrain.ortho_plan() returned and the DEM it was made over, a terrain.terrain_grid(): pose, terrain height and lens model
+    in one gather (wm_ortho_u8; rule: include/wm_hip.h "Survey terrain").  The DEM's posts are uploaded once and kept in the
+    dict (terrain.to_device).  sample, fill, the frame's shape, the stream and the validation are undistort_u8's.  count=True:
+    returns (picture, counts), counts a device int64 tensor of two elements, the filled pixels and those of them that had no
+    height or a non-finite one (a DEM that is too small), without a host synchronisation."""
+    import ctypes as C
+    from .terrain import _check_ortho_plan, to_device
+    what = "ortho_u8"
+    pl, d = _check_ortho_plan(plan, dem, what)
+    mode, fill_a = _check_undistort_args(sample, fill, what)
+    _check_plan_frame(frame, pl, what)
+    (h, w), (oh, ow) = pl["size"], pl["out_size"]
+    (dh, dw), (e0, n0) = d["heights"].shape, d["origin"]
+    frame = frame.contiguous()
+    posts = to_device(dem, frame.device)
+    cam = (C.c_double * 9)(*[float(v) for v in pl["camera"]])
+    pose = (C.c_double * 12)(*[float(v) for v in pl["pose"]])
+    dem_geo = (C.c_double * 3)(e0, n0, d["cell"])
+    out_geo = (C.c_double * 6)(*[float(v) for v in pl["georef"].reshape(6)])
+    fill_c = (C.c_uint8 * 3)(*[int(v) for v in fill_a])
+    with torch.cuda.device(frame.device):
+        out = torch.empty((oh, ow, 3), device=frame.device, dtype=torch.uint8)
+        counts = torch.empty(2, device=frame.device, dtype=torch.int64) if count else None
+        N.check(N.lib().wm_ortho_u8(N.ptr(frame), h, w, cam, pose, N.ptr(posts), dh, dw, dem_geo, N.ptr(out), oh, ow, out_geo, mode, fill_c,
+                                    N.ptr(counts), N.stream_ptr(frame.device)))
+    return (out, counts) if count else out
 
 
 def scaled_size(height: int, width: int, scale: float):

@@ -25,7 +25,8 @@ Frame coordinates are fp32: a box coordinate keeps a fractional resolution below
 
 The rest of the survey API lives beside this module and stays importable from it: chips and overlays in review.py, the
 census, coverage and mosaic in ground.py, registration in registration.py, the lens model (lens_plan, undistorted) in lens.py,
-roll and pitch (rectify_plan, rectified) in attitude.py; what they all share is in _survey.py.
+roll and pitch (rectify_plan, rectified) in attitude.py, terrain relief (ortho_plan, orthorectified) in terrain.py; what they all
+share is in _survey.py.
 """
 from __future__ import annotations
 
@@ -47,6 +48,8 @@ from .lens import CAMERA_ENTRIES, LENS_KEEP, LENS_MAX_SIDE, distort_points, lens
 from .registration import (REGISTER_MAX_LEVEL, REGISTER_MAX_PAIRS, REGISTER_MAX_SEARCH, REGISTER_MAX_SIDE, REGISTER_METRICS,  # noqa: F401
                            REGISTER_PAIR, REGISTER_REFINE_SUMS, adjust, adjust_exposure, adjust_similarity, exposure_table, reduce_planes,
                            refine, refine_solve, refine_step, register, register_pairs)
+from .terrain import (TERRAIN_MAX_SIDE, camera_pose, ortho_plan, orthorectified, terrain_grid, terrain_height, terrain_points,  # noqa: F401
+                      to_device)
 from .review import (CHIP_MAX_SIDE, DEFAULT_PALETTE, DRAW_MAX_PALETTE, DRAW_MAX_WIDTH, OVERLAY_MAX, OVERLAY_MIN, _check_chip,  # noqa: F401
                      _check_chip_rule, _check_draw_width, _check_overlay, _check_palette, chip_windows, crop_chips, draw_boxes,
                      outline_rects, overlay_size)
